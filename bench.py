@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py - rendered views/sec of the FORGE reconstruction hot path on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scenes B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scenes B] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,6 +11,8 @@ fusion -> heads -> 64^3 (16+1)-channel volume -> HIP ray-march of 5 views x 128^
 conv_rgb -> 5 RGB 256^2 views + masks, through forge_amd.model.FORGE.forward (GT poses, eval-mode BN,
 fp32). Inputs are resident in HBM before the timed region. Weak scaling: every rank processes its own
 B scenes, no data-path collective (scenes are independent); rank 0 prints ONE JSON line.
+`--steps K` is the number of timed steps in all (after W untimed ones); `ms_per_step` is the time one of them took.
+`--dump-outputs DIR` writes the outputs of the last timed step (the rendered views and masks; `--train`: the loss) as .npy files.
 
 Extra objects on the line:
   roofline        the dominant kernel of the step (conv_igemm_kernel, fp32 MFMA): FLOPs its launches EXECUTE / their HIP-event time
@@ -55,9 +57,9 @@ def main():
                     help="feature grid: 32 = the metric's configuration (64^3 render volume); 64 = BASELINE configs[3]/[4] 128^3-voxel "
                          "scenes: synthetic [b,5,128,64^3] feature volumes through rotate -> fuse -> heads -> ray-march (the encoder cannot produce them)")
     ap.add_argument("--train", action="store_true", help="time the data-parallel training step (SyncBatchNorm + DDP) instead of inference")
-    ap.add_argument("--repeats", type=int, default=10,
-                    help="timed regions of EXACTLY --steps steps each in the same run (each between barrier + synchronize pairs); value = units / the MEDIAN "
-                         "region, min / max reported beside it")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="split the --steps timed steps into this many regions (each between barrier + synchronize pairs); value = units / the MEDIAN "
+                         "region's time per step, min / max reported beside it")
     ap.add_argument("--no-graph", action="store_true", help="launch the step eagerly instead of replaying the captured hipGraph")
     ap.add_argument("--pipeline-depth", type=int, default=4,
                     help="steps in flight: that many hipGraphs of the step replayed round-robin on as many HIP streams (forge_amd.graph.PipelinedForward); "
@@ -74,6 +76,9 @@ def main():
     ap.add_argument("--full-record", default=None, metavar="PATH",
                     help="where the full record goes (default: bench_full.json beside bench.py, and gpurun_out/ when present); "
                          "stdout carries ONE compact strict-JSON line (benchkit/emit.py)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MB in all, "
+                         "benchkit/dump.py; in-tree: bench_outputs/, git-ignored); the inputs are seeded, so the same arguments give the same inputs")
     ap.add_argument("--dry-run", action="store_true", help="CPU/gloo rehearsal of the multi-rank launch path (no HIP work)")
     ap.add_argument("--rehearse-hang", action="store_true", help=argparse.SUPPRESS)       # --dry-run only: one sub-record blocks for ever (the watchdog's test)
     ap.add_argument("--cpu-worker", nargs=3, type=int, metavar=("THREADS", "N", "SEED"), help=argparse.SUPPRESS)

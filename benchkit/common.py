@@ -56,9 +56,15 @@ def _timed(fn, steps, warm=2):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
+def region_sizes(steps, repeats):
+    """`steps` timed steps in all, split into min(repeats, steps) regions as evenly as possible (at least one region)."""
+    r = max(1, min(repeats, steps))
+    return [steps // r + (1 if i < steps % r else 0) for i in range(r)]
+
+
 def timed_region(fn, steps, warmup, repeats=1):
-    """W untimed steps, then `repeats` regions of EXACTLY K timed steps, each between (barrier, synchronize) pairs; a rank that fails keeps
-    the barrier count. Returns (ok, error, last output, [seconds per region])."""
+    """W untimed steps, then EXACTLY K timed steps in all, split into `repeats` regions (region_sizes), each between (barrier, synchronize)
+    pairs; a rank that fails keeps the barrier count. Returns (ok, error, last output, [seconds per region])."""
     good, msg, out, dts = 1.0, None, None, []
     try:
         for _ in range(warmup):
@@ -66,13 +72,13 @@ def timed_region(fn, steps, warmup, repeats=1):
         torch.cuda.synchronize()
     except Exception as e:
         good, msg = 0.0, repr(e)[:400]
-    for _ in range(max(1, repeats)):
+    for n in region_sizes(steps, repeats):
         fdist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         try:
             if good:
-                for _ in range(steps):
+                for _ in range(n):
                     out = fn()
                 torch.cuda.synchronize()
         except Exception as e:
@@ -84,12 +90,16 @@ def timed_region(fn, steps, warmup, repeats=1):
 
 
 def region_stats(dts_max, steps, units_per_step):
-    """dts_max = every region's duration (max over ranks): `value` = units / MEDIAN region; the spread of the same run beside it."""
+    """dts_max = every region's duration (max over ranks) of timed_region(.., steps, .., len(dts_max)): returns the time of `steps` steps at the
+    MEDIAN region's rate per step (`value` = units / that) and the spread of the same run beside it."""
     import statistics
-    med = statistics.median(dts_max)
-    per = lambda d: units_per_step * steps / d if d > 0 else None
-    return med, {"regions": len(dts_max), "steps_per_region": steps, "value_median": per(med), "value_min": per(max(dts_max)), "value_max": per(min(dts_max)),
-                 "ms_per_step_median": med / steps * 1e3, "ms_per_step_min": min(dts_max) / steps * 1e3, "ms_per_step_max": max(dts_max) / steps * 1e3}
+    sizes = region_sizes(steps, len(dts_max))
+    per_step = [d / n if n else 0.0 for d, n in zip(dts_max, sizes)]
+    med = statistics.median(per_step)
+    per = lambda d: units_per_step / d if d > 0 else None
+    return med * steps, {"regions": len(dts_max), "steps_per_region": sizes, "value_median": per(med), "value_min": per(max(per_step)),
+                         "value_max": per(min(per_step)), "ms_per_step_median": med * 1e3, "ms_per_step_min": min(per_step) * 1e3,
+                         "ms_per_step_max": max(per_step) * 1e3}
 
 
 def _bracketed(step, steps, warm, dev):

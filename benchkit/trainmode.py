@@ -4,7 +4,8 @@ import os
 import torch
 
 from forge_amd import dist as fdist, synthetic as syn
-from benchkit.common import T_IN, TRAIN_CAVEATS, region_stats, timed_region
+from benchkit.common import T_IN, TRAIN_CAVEATS, region_sizes, region_stats, timed_region
+from benchkit.dump import dump_outputs, host_copy
 from benchkit.emit import emit
 
 
@@ -42,11 +43,14 @@ def train_bench(args, rank, world, dev, affinity):
         ok, err = 0.0, repr(e)[:400]
         import traceback
         traceback.print_exc()
-    R = max(1, min(args.repeats, 3))                                # bounded: a training region is steps x ~0.2 s
+    R = len(region_sizes(args.steps, args.repeats))
     dts = [0.0] * R
+    dumped = None
     if ok:
         ok, err, lt, dts = timed_region(step, args.steps, args.warmup, R)
         loss = float(lt) if ok else float("nan")
+        if ok and rank == 0 and args.dump_outputs:
+            dumped = host_copy({"loss": lt})
     else:
         for _ in range(2 * R):
             fdist.barrier()
@@ -71,6 +75,7 @@ def train_bench(args, rank, world, dev, affinity):
                                            "this number)") + TRAIN_CAVEATS,
                        "perceptual_term": "excluded", "deterministic": False, "scenes_per_gpu": B, "feature_grid": args.grid,
                        "global_batch": B * world, "parallelism": "dp%d (DDP bucketed RCCL all-reduce of 221 MB fp32 gradients; HIP SyncBatchNorm)" % world,
-                       "rank0_affinity": affinity}}, args.full_record)
+                       "rank0_affinity": affinity},
+            "dump_outputs": dump_outputs(args.dump_outputs, dumped) if dumped is not None else None}, args.full_record)
     fdist.barrier()
     fdist.shutdown()

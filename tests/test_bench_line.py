@@ -77,3 +77,34 @@ def test_oversized_optional_parts_are_dropped_not_the_contract():
     line = emit.dumps(emit.compact(full))
     d = json.loads(line, parse_constant=_refuse)
     assert len(line) < 4096 and "extra" not in d and d["roofline"]["frac"] == 0.659 and d["cpu_baseline"]["value"] == 7.8
+
+
+def test_steps_is_the_number_of_timed_steps():
+    from benchkit.common import region_sizes, region_stats
+    for steps, repeats in ((20, 1), (20, 3), (2, 10), (100, 10), (1, 1)):
+        sizes = region_sizes(steps, repeats)
+        assert sum(sizes) == steps and len(sizes) == min(repeats, steps) and max(sizes) - min(sizes) <= 1
+    dt, rep = region_stats([0.7, 1.4, 0.6], 20, 5.0)                # regions of 7, 7, 6 steps: 0.1, 0.2, 0.1 s per step
+    assert math.isclose(dt, 0.1 * 20) and math.isclose(rep["ms_per_step_median"], 100.0) and rep["steps_per_region"] == [7, 7, 6]
+    assert math.isclose(rep["value_median"], 50.0) and math.isclose(rep["value_min"], 25.0)
+
+
+def test_dump_outputs_float_arrays_within_budget(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    from benchkit import dump
+    outs = {"rgb": torch.rand(5, 3, 64, 64), "masks": torch.rand(5, 1, 64, 64).half(), "loss": torch.tensor(0.5, dtype=torch.float64)}
+    info = dump.dump_outputs(str(tmp_path / "a"), dump.host_copy(outs))
+    for k, v in outs.items():
+        a = np.load(str(tmp_path / "a" / (k + ".npy")))
+        assert a.dtype == (np.float64 if k == "loss" else np.float32) and a.shape == tuple(v.shape) and info["arrays"][k]["sampled_elements"] is None
+        assert np.array_equal(a, v.double().numpy() if k == "loss" else v.float().numpy())
+    monkeypatch.setattr(dump, "MAX_BYTES", 40000)                   # past the budget: a fixed, seeded sample of every array, the same on every call
+    for d in ("b", "c"):
+        dump.dump_outputs(str(tmp_path / d), dump.host_copy(outs))
+    arrays = [np.load(str(tmp_path / "b" / (k + ".npy"))) for k in outs]
+    assert sum(a.nbytes for a in arrays) <= 40000
+    for k in outs:
+        assert np.array_equal(np.load(str(tmp_path / "b" / (k + ".npy"))), np.load(str(tmp_path / "c" / (k + ".npy"))))
+    rgb = np.load(str(tmp_path / "b" / "rgb.npy"))
+    assert np.isin(rgb, outs["rgb"].numpy().reshape(-1)).all()

@@ -331,10 +331,15 @@ def test_pose_estimators_hip_convolutions_vs_float64_and_stock_torch(dev):
     (tools/stock_pose.py): the HIP path has to stay within 3x the stock path's distance (+ 2e-5 of max) in eval mode and within 4x (+ 1e-3) in train
     mode, where the last BatchNorm layers normalise over 2-16 values per channel and amplify any rounding difference chaotically (both paths
     sit 0.3-2e-2 from float64 there). Round 6: eval-mode gradients take the train-mode form of the bound too (single activation-mask flips, see below;
-    MIOpen's per-process solver choice moves the stock yardstick itself between 3e-5 and 1e-3 on the same key)."""
+    MIOpen's per-process solver choice moves the stock yardstick itself between 3e-5 and 1e-3 on the same key). The stock distance is the MEDIAN of
+    STOCK_RUNS evaluations: in train mode one stock evaluation differs from the next in the same process (MIOpen's kernels do not round
+    reproducibly, and the chaotic BatchNorm layers amplify that) - PoseEstimator2D's conv.1.weight gradient drew 2.2e-3 in one process and
+    6.0e-3 .. 1.3e-2 in ten evaluations of two others, while the HIP path sat at 9.9e-3 from float64 in every one."""
     import copy
+    import statistics
     from forge_amd.pose_estimator_2d import PoseEstimator2D
     from forge_amd.pose_estimator_3d import PoseEstimator3D
+    STOCK_RUNS = 5
     torch.manual_seed(3)
     rel = lambda got, want: (got.detach().double().cpu() - want.detach()).abs().max().item() / max(want.detach().abs().max().item(), 1e-30)
 
@@ -371,12 +376,11 @@ def test_pose_estimators_hip_convolutions_vs_float64_and_stock_torch(dev):
             ref = run(ref_mod, x.double(), keys, stock=True)
             g = copy.deepcopy(mod).to(dev)
             hip = run(g, x.to(dev), keys)
-            g2 = copy.deepcopy(mod).to(dev)
-            stock = run(g2, x.to(dev), keys, stock=True)
-            for name, a, b_, r in zip(["features", "d input"] + keys, hip, stock, ref):
+            stocks = [run(copy.deepcopy(mod).to(dev), x.to(dev), keys, stock=True) for _ in range(STOCK_RUNS)]
+            for i, (name, a, r) in enumerate(zip(["features", "d input"] + keys, hip, ref)):
                 if a is None and name == "d input" and isinstance(mod, PoseEstimator2D):
                     continue                                               # the HIP stem gathers its patches from the detached image: no d(image), as in the encoder's trunk
-                eh, es = rel(a, r), rel(b_, r)
+                eh, es = rel(a, r), statistics.median(rel(st[i], r) for st in stocks)
                 if os.environ.get("FORGE_TEST_REPORT"):
                     print("  %-16s %-5s %-52s hip/f64 %.2e  stock/f64 %.2e" % (type(mod).__name__, "train" if train else "eval", name, eh, es))
                 # features: the tight eval bound. Gradients: max-abs of a chain with LeakyReLU / ReLU masks - ONE pre-activation within fp32 noise of zero
