@@ -396,9 +396,7 @@ def _wino_conv(x1, C1, bs1, x2, C2, bs2, U, bias, out, residual, grid, V1=None):
     if V1 is None:
         V1 = wino_input(x1, C1, C1, n, D, H, W, bs=bs1)
     V2 = None if x2 is None else wino_input(x2, C2, C2, n, D, H, W, bs=bs2)
-    R = n * D * (H // 2) * (W // 2)
-    Mm = torch.empty(8 if wino_half_applies(R, Cout, C1 + C2) else 16, R, Cout, dtype=torch.float32, device=out.device)
-    wino_gemm(V1, C1, V2, C2, U, Mm, n, D, H // 2, W // 2, Cout)
+    Mm = wino_gemm(V1, C1, V2, C2, U, None, n, D, H // 2, W // 2, Cout)
     return wino_output(Mm, bias, None, None, 1.0, residual, None, None, out, None, None, n, D, H, W, Cout, Cout, EPI_BIAS)
 
 
@@ -544,17 +542,28 @@ def wino_half_applies(R, Cout, Cin):
 
 @_lib.on_tensor_device
 def wino_gemm(V1, C1, V2, C2, U, Mm, n, D, Ht, Wt, Cout, view=0, views=1, half=None):
-    """Mm[16][n D Ht Wt][Cout] = the 16 point GEMMs. V1 [16][n views D Ht Wt][C1] may hold `views` views per batch element (the
+    """The 16 point GEMMs over R = n D Ht Wt tile rows, returned as the point products [P][R][Cout]: a view of the front of Mm's storage, in the
+    form the inverse transform reads from its shape (wino_output). V1 [16][n views D Ht Wt][C1] may hold `views` views per batch element (the
     transformed inputs of every view of a scene, made by ONE wino_input launch): this call reads view `view`. V2 [16][R][C2] or None.
-    half: Mm receives the 8 planes [2][4][R][Cout] of forge_wino_gemm_half (the first half of a 16-plane buffer) for wino_output(half=True).
-    None = wino_half_applies' rule, which depends on (R, Cout) only - wino_output applies the same rule to ITS row count, so a GEMM / inverse pair over
-    the same rows always agrees; a caller whose products are consumed as the second addend (Mm2) of launches over FEWER rows passes their decision."""
+    half chooses the form - True: P = 8 planes [2][4][R][Cout], the row stage of the inverse transform applied in the GEMM epilogue
+    (forge_wino_gemm_half); False: the P = 16 points; None: wino_half_applies(R, Cout, C1 + C2). A producer whose products another launch adds
+    (wino_output's Mm2) passes that launch's form. Mm: a contiguous float32 buffer of at least P R Cout elements (ValueError otherwise), or None
+    for a new [P][R][Cout] tensor."""
     vol = D * Ht * Wt
+    R = n * vol
     if half is None:
-        half = wino_half_applies(n * vol, Cout, C1 + C2)
+        half = wino_half_applies(R, Cout, C1 + C2)
+    P = 8 if half else 16
     kd = U.shape[1]
     if U.shape != (16, kd, Cout, C1 + C2) or kd not in (1, 3):
         raise ValueError("transformed weight %s does not match Cout=%d Cin=%d" % (tuple(U.shape), Cout, C1 + C2))
+    if Mm is None:
+        Mm = torch.empty(P, R, Cout, dtype=torch.float32, device=V1.device)
+    if not (Mm.is_contiguous() and Mm.dtype == torch.float32 and Mm.numel() >= P * R * Cout):
+        raise ValueError("point-product buffer %s %s%s cannot hold %d x %d x %d float32" % (
+            tuple(Mm.shape), Mm.dtype, "" if Mm.is_contiguous() else " (not contiguous)", P, R, Cout))
+    if Mm.shape != (P, R, Cout):
+        Mm = Mm.as_strided((P, R, Cout), (R * Cout, Cout, 1))
     p1 = ctypes.c_void_p(V1.data_ptr() + 4 * view * vol * C1)
     if half:
         _lib.check(_lib.lib().forge_wino_gemm_half(p1, C1, C1, views * vol if views > 1 else 0, V1.shape[1] * C1, _lib.ptr(V2), C2, C2, 0,
@@ -563,7 +572,7 @@ def wino_gemm(V1, C1, V2, C2, U, Mm, n, D, Ht, Wt, Cout, view=0, views=1, half=N
         return Mm
     _lib.check(_lib.lib().forge_wino_gemm(p1, C1, C1, views * vol if views > 1 else 0, V1.shape[1] * C1, _lib.ptr(V2), C2, C2, 0,
                                           0 if V2 is None else V2.shape[1] * C2, _lib.ptr(U), _lib.ptr(Mm), n, D, Ht, Wt, Cout, kd,
-                                          ord(wino_gemm_tile(n * vol, Cout, C1 + C2)), _lib.current_stream()),
+                                          ord(wino_gemm_tile(R, Cout, C1 + C2)), _lib.current_stream()),
                "forge_wino_gemm")
     return Mm
 
@@ -577,23 +586,22 @@ def wino_gemm_tile(R, Cout, Cin):
 
 
 @_lib.on_tensor_device
-def wino_output(Mm, bias, scale, shift, slope, residual, aux_h, aux_z, out, out2, out3, n, D, H, W, Cout, ldo, epilogue, Mm2=None, view=0, views=1, half=None):
-    """out = epilogue(A^T (Mm + Mm2) A): the element-wise tails of conv_igemm (EPI_*) on the inverse-transformed tiles. Mm2 (optional)
-    [16][n views D H/2 W/2][Cout]: point products of the input half for `views` views per batch element; this call adds view `view`.
-    half: Mm (and Mm2) hold wino_gemm(half=True)'s 8 planes (column stage only); None = the rule wino_gemm applied to make them."""
+def wino_output(Mm, bias, scale, shift, slope, residual, aux_h, aux_z, out, out2, out3, n, D, H, W, Cout, ldo, epilogue, Mm2=None, view=0, views=1):
+    """out = epilogue(A^T (Mm + Mm2) A): the element-wise tails of conv_igemm (EPI_*) on the inverse-transformed tiles. Mm: the point products
+    wino_gemm returned, [P][n D H/2 W/2][Cout]; their form is P - 16 points, or 8 planes whose row stage the GEMM epilogue has applied
+    (forge_wino_output_half then runs the column stage). Mm2 (optional) [P][n views D H/2 W/2][Cout], the same form: point products of the input
+    half for `views` views per batch element; this call adds view `view`. Any other shape raises ValueError."""
     vol = D * (H // 2) * (W // 2)
-    if half is None:
-        half = wino_half_applies(n * vol, Cout, 0)
-    if half:                                                            # Mm2 (if any) is in the 8-plane form too
-        p2 = None if Mm2 is None else ctypes.c_void_p(Mm2.data_ptr() + 4 * view * vol * Cout)
-        _lib.check(_lib.lib().forge_wino_output_half(_lib.ptr(Mm), p2, views * vol, 0 if Mm2 is None else Mm2.shape[1] * Cout, _lib.ptr(bias), _lib.ptr(scale), _lib.ptr(shift), float(slope), _lib.ptr(residual),
-                                                     _lib.ptr(aux_h), _lib.ptr(aux_z), _lib.ptr(out), _lib.ptr(out2), _lib.ptr(out3), n, D, H, W, Cout, ldo,
-                                                     epilogue, _lib.current_stream()), "forge_wino_output_half")
-        return out
+    P = Mm.shape[0] if Mm.dim() == 3 else 0
+    if P not in (8, 16) or Mm.shape[1:] != (n * vol, Cout) or not Mm.is_contiguous():
+        raise ValueError("point products %s do not match [8 | 16][%d][%d]" % (tuple(Mm.shape), n * vol, Cout))
+    if Mm2 is not None and (Mm2.shape != (P, n * views * vol, Cout) or not Mm2.is_contiguous()):
+        raise ValueError("second addend %s does not match [%d][%d][%d] (the form of Mm)" % (tuple(Mm2.shape), P, n * views * vol, Cout))
     p2 = None if Mm2 is None else ctypes.c_void_p(Mm2.data_ptr() + 4 * view * vol * Cout)
-    _lib.check(_lib.lib().forge_wino_output(_lib.ptr(Mm), p2, views * vol, 0 if Mm2 is None else Mm2.shape[1] * Cout, _lib.ptr(bias), _lib.ptr(scale), _lib.ptr(shift), float(slope), _lib.ptr(residual),
-                                            _lib.ptr(aux_h), _lib.ptr(aux_z), _lib.ptr(out), _lib.ptr(out2), _lib.ptr(out3), n, D, H, W, Cout, ldo,
-                                            epilogue, _lib.current_stream()), "forge_wino_output")
+    fn, name = (_lib.lib().forge_wino_output_half, "forge_wino_output_half") if P == 8 else (_lib.lib().forge_wino_output, "forge_wino_output")
+    _lib.check(fn(_lib.ptr(Mm), p2, views * vol, 0 if Mm2 is None else Mm2.shape[1] * Cout, _lib.ptr(bias), _lib.ptr(scale), _lib.ptr(shift), float(slope),
+                  _lib.ptr(residual), _lib.ptr(aux_h), _lib.ptr(aux_z), _lib.ptr(out), _lib.ptr(out2), _lib.ptr(out3), n, D, H, W, Cout, ldo, epilogue,
+                  _lib.current_stream()), name)
     return out
 
 

@@ -425,8 +425,7 @@ class Encoder3D(co.PackedModule):
             y2 = torch.empty(N, Ho, Wo, P, dtype=torch.float32, device=dev)
             if b["u2"] is not None and co.wino_enabled() and H % 2 == 0 and W % 2 == 0:
                 V = co.wino_input(y1, P, P, N, 1, H, W)
-                Mm = torch.empty(16, N * (H // 2) * (W // 2), P, dtype=torch.float32, device=dev)
-                co.wino_gemm(V, P, None, 0, b["u2"], Mm, N, 1, H // 2, W // 2, P)
+                Mm = co.wino_gemm(V, P, None, 0, b["u2"], None, N, 1, H // 2, W // 2, P)
                 co.wino_output(Mm, None, b["a2"][0], b["a2"][1], 0.0, None, None, None, y2, None, None, N, 1, H, W, P, P, co.EPI_AFFINE_ACT)
             else:
                 co.conv_igemm(y1, P, P, None, 0, 0, b["w2"], None, b["a2"][0], b["a2"][1], 0.0, None, None, None, y2, None,
@@ -458,10 +457,7 @@ class Encoder3D(co.PackedModule):
         out = torch.empty(n, D, H, W, 128, dtype=torch.float32, device=vol_rows.device)
         if co.wino_applies(co.TAPS_3x3x3, 1, n, D, H, W, C, 0, 128):       # Winograd F(2x2,3x3) x 3 depth taps, BN + LeakyReLU in the inverse transform
             V = co.wino_input(vol_rows, C, C, n, D, H, W)
-            R = n * D * (H // 2) * (W // 2)
-            hf = co.wino_half_applies(R, 128, C)                        # row stage of the inverse transform in the GEMM epilogue: 8 planes instead of 16
-            Mm = torch.empty(8 if hf else 16, R, 128, dtype=torch.float32, device=vol_rows.device)
-            co.wino_gemm(V, C, None, 0, U, Mm, n, D, H // 2, W // 2, 128)
+            Mm = co.wino_gemm(V, C, None, 0, U, None, n, D, H // 2, W // 2, 128)
             co.wino_output(Mm, bias, sc, sh, 0.01, None, None, None, out, None, None, n, D, H, W, 128, 128, co.EPI_AFFINE_ACT)
         else:
             co.conv_igemm(vol_rows, C, C, None, 0, 0, w, bias, sc, sh, 0.01, None, None, None, out, None,

@@ -100,8 +100,7 @@ def run_layer(L, x, residual=None):
         residual = residual.contiguous()
     if L["U"] is not None and co.wino_applies(L["taps"], 1, n, D, H, W, C, 0, Cout):
         V = co.wino_input(x, C, C, n, D, H, W)
-        Mm = torch.empty(16, n * D * (H // 2) * (W // 2), Cout, dtype=torch.float32, device=x.device)
-        co.wino_gemm(V, C, None, 0, L["U"], Mm, n, D, H // 2, W // 2, Cout)
+        Mm = co.wino_gemm(V, C, None, 0, L["U"], None, n, D, H // 2, W // 2, Cout)
         co.wino_output(Mm, L["bias"], L["sc"], L["sh"], L["slope"], residual, None, None, out, None, None, n, D, H, W, Cout, Cout, epi)
     else:
         co.conv_igemm(x, C, C, None, 0, 0, L["wp"], L["bias"], L["sc"], L["sh"], L["slope"], residual, None, None, out, None,

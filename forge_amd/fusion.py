@@ -237,6 +237,13 @@ def bn_act_rows(bn, rows, slope=1.0, residual=None, stats=None):
     raise RuntimeError("forge_amd: unsupported BatchNorm configuration %r" % (bn,))
 
 
+def _step_scratch(R, C, dev):
+    """One buffer for the point products of a GRU step's 2C-column (gates) and C-column (state, fusion_conv) launches over R tile rows, sized for the
+    larger of their forms: convops.wino_gemm returns each launch's products as a view of its front."""
+    P2, P1 = (8 if co.wino_half_applies(R, c, C) else 16 for c in (2 * C, C))
+    return torch.empty(max(P2 * 2 * C, P1 * C) * R, dtype=torch.float32, device=dev)
+
+
 def require_hip_input(what, x, channels=None):
     """The product has ONE implementation per op - the HIP kernels. Anything they cannot take is an error, never a silent stock-PyTorch
     detour (north_star: no dual code paths)."""
@@ -406,38 +413,37 @@ class _FuseFrozen(torch.autograd.Function):
             R = b * D * Ht * Wt
             Vx = co.wino_input(xr, C, C, b * t, D, H, W)
             Vh = torch.empty(16, R, C, dtype=torch.float32, device=dev)
-            Mm = torch.empty(16, R, 2 * C, dtype=torch.float32, device=dev)
-            Mc = Mm.view(-1)[:16 * R * C].view(16, R, C)
-            gru._wino_h0(p, xr, grid, Vh, Mc, t0, h, nsum=t, sum_stride=vol, bs=t * vol)
+            Mm = _step_scratch(R, C, dev)
+            gru._wino_h0(p, xr, grid, Vh, Mm, t0, h, nsum=t, sum_stride=vol, bs=t * vol)
             # const0 (a dict the caller keeps across calls; with skip_dx0): view 0 holds the SAME values in every call (the un-warped reference
             # view of frozen features, kubric_eval.py:456-470) - the point products of its input halves, V_x0 (x) U_x of both GRU convolutions,
             # are made once and added inside the inverse transforms of step 0, whose GEMMs then contract the hidden-state half only (K = 3 C
             # instead of 6 C). Same arithmetic up to the order of the fp32 additions (the halves meet before A^T . A instead of inside the K loop).
+            # The products keep the form of step 0's hidden-half launches (same rows and columns); one made under another plan (force_plan) is
+            # refused by the inverse transform that would add it.
             hoist = const0 is not None and skip_dx0
             if hoist:
                 ps = gru._packed_wino_halves()
                 if "MXg0" not in const0:
                     Vx0 = co.wino_input(xr[:, 0], C, C, b, D, H, W, bs=t * vol)
-                    const0["MXg0"] = torch.empty(16, R, 2 * C, dtype=torch.float32, device=dev)
-                    const0["MXc0"] = torch.empty(16, R, C, dtype=torch.float32, device=dev)
-                    co.wino_gemm(Vx0, C, None, 0, ps["gate_Ux"], const0["MXg0"], b, D, Ht, Wt, 2 * C)
-                    co.wino_gemm(Vx0, C, None, 0, ps["out_Ux"], const0["MXc0"], b, D, Ht, Wt, C)
+                    const0["MXg0"] = co.wino_gemm(Vx0, C, None, 0, ps["gate_Ux"], None, b, D, Ht, Wt, 2 * C)
+                    const0["MXc0"] = co.wino_gemm(Vx0, C, None, 0, ps["out_Ux"], None, b, D, Ht, Wt, C)
             for ti in range(t):
                 z, hr, r, hn, cand = new(), new(), new(), new(), new()
                 first = hoist and ti == 0
                 co.wino_input(h, C, C, b, D, H, W, out=Vh)
                 if first:
-                    co.wino_gemm(Vh, C, None, 0, ps["gate_Uh"], Mm, b, D, Ht, Wt, 2 * C)
+                    G = co.wino_gemm(Vh, C, None, 0, ps["gate_Uh"], Mm, b, D, Ht, Wt, 2 * C)
                 else:
-                    co.wino_gemm(Vx, C, Vh, C, p["gate_U"], Mm, b, D, Ht, Wt, 2 * C, view=ti, views=t)
-                co.wino_output(Mm, p["gate_b"], None, None, 1.0, None, h, None, z, hr, r, *grid, 2 * C, C, co.EPI_GRU_GATES,
+                    G = co.wino_gemm(Vx, C, Vh, C, p["gate_U"], Mm, b, D, Ht, Wt, 2 * C, view=ti, views=t)
+                co.wino_output(G, p["gate_b"], None, None, 1.0, None, h, None, z, hr, r, *grid, 2 * C, C, co.EPI_GRU_GATES,
                                Mm2=const0["MXg0"] if first else None)
                 co.wino_input(hr, C, C, b, D, H, W, out=Vh)
                 if first:
-                    co.wino_gemm(Vh, C, None, 0, ps["out_Uh"], Mc, b, D, Ht, Wt, C)
+                    S = co.wino_gemm(Vh, C, None, 0, ps["out_Uh"], Mm, b, D, Ht, Wt, C)
                 else:
-                    co.wino_gemm(Vx, C, Vh, C, p["out_U"], Mc, b, D, Ht, Wt, C, view=ti, views=t)
-                co.wino_output(Mc, p["out_b"], p["norm"][0], p["norm"][1], 1.0, None, h, z, hn, out if ti == t - 1 else None, cand, *grid, C, C,
+                    S = co.wino_gemm(Vx, C, Vh, C, p["out_U"], Mm, b, D, Ht, Wt, C, view=ti, views=t)
+                co.wino_output(S, p["out_b"], p["norm"][0], p["norm"][1], 1.0, None, h, z, hn, out if ti == t - 1 else None, cand, *grid, C, C,
                                co.EPI_GRU_OUT, Mm2=const0["MXc0"] if first else None)
                 steps.append((h, z, r, cand))
                 h = hn
@@ -579,12 +585,10 @@ class _FuseGroupsTrain(torch.autograd.Function):
                  "f0": pk(w0), "f3": pk(w3)}
         U = {k: co.wino_pack_packed(v) for k, v in packs.items()}
         Vx = co.wino_input(xr, C, C, b * t, D, H, W)                         # [16][b t R1][C]: all views of all scenes
-        MXg, MXc = newV(b * t * R1, 2 * C), newV(b * t * R1, C)
-        hx = co.wino_half_applies(R, C, C)                                   # the form (8 / 16 planes) of the per-step launches that consume MXg / MXc as second addends
-        co.wino_gemm(Vx, C, None, 0, U["gx"], MXg, b * t, D, Ht, Wt, 2 * C, half=hx)
-        co.wino_gemm(Vx, C, None, 0, U["ox"], MXc, b * t, D, Ht, Wt, C, half=hx)
-        Mm = newV(R, 2 * C)
-        Mc = Mm.view(-1)[:16 * R * C].view(16, R, C)                         # the C-column problems reuse the front of the buffer
+        # in the form (8 / 16 planes) of the per-step launches over R rows that add them as second addends
+        MXg = co.wino_gemm(Vx, C, None, 0, U["gx"], None, b * t, D, Ht, Wt, 2 * C, half=co.wino_half_applies(R, 2 * C, C))
+        MXc = co.wino_gemm(Vx, C, None, 0, U["ox"], None, b * t, D, Ht, Wt, C, half=co.wino_half_applies(R, C, C))
+        Mm = _step_scratch(R, C, dev)
         bnargs = lambda m: bn_module_args(m)
         outs, saved_groups = [], []
         for grp in groups:
@@ -596,26 +600,26 @@ class _FuseGroupsTrain(torch.autograd.Function):
             else:
                 co.wino_input(torch.stack([xr[:, ti] for ti in grp], dim=1).mean(dim=1).reshape(M, C), C, C, b, D, H, W, out=Vm)
             a0 = new()
-            co.wino_gemm(Vm, C, None, 0, U["f0"], Mc, b, D, Ht, Wt, C)
-            co.wino_output(Mc, b0, None, None, 1.0, None, None, None, a0, None, None, *geo, C, C, co.EPI_BIAS)
+            Mp = co.wino_gemm(Vm, C, None, 0, U["f0"], Mm, b, D, Ht, Wt, C)
+            co.wino_output(Mp, b0, None, None, 1.0, None, None, None, a0, None, None, *geo, C, C, co.EPI_BIAS)
             rm, rv, mom, eps, nbt, group = bnargs(fc[1])
             t0, sv1 = bn_rows_fwd(a0, g1, be1, rm, rv, mom, eps, 0.01, None, nbt, group)
             Vt0 = co.wino_input(t0, C, C, b, D, H, W)
             a1 = new()
-            co.wino_gemm(Vt0, C, None, 0, U["f3"], Mc, b, D, Ht, Wt, C)
-            co.wino_output(Mc, b3, None, None, 1.0, None, None, None, a1, None, None, *geo, C, C, co.EPI_BIAS)
+            Mp = co.wino_gemm(Vt0, C, None, 0, U["f3"], Mm, b, D, Ht, Wt, C)
+            co.wino_output(Mp, b3, None, None, 1.0, None, None, None, a1, None, None, *geo, C, C, co.EPI_BIAS)
             rm, rv, mom, eps, nbt, group = bnargs(fc[4])
             h, sv4 = bn_rows_fwd(a1, g4, be4, rm, rv, mom, eps, 0.01, None, nbt, group)
             steps = []
             for ti in grp:
                 Vh = co.wino_input(h, C, C, b, D, H, W)
-                co.wino_gemm(Vh, C, None, 0, U["gh"], Mm, b, D, Ht, Wt, 2 * C)
+                G = co.wino_gemm(Vh, C, None, 0, U["gh"], Mm, b, D, Ht, Wt, 2 * C)
                 z, hr, r = new(), new(), new()
-                co.wino_output(Mm, bg, None, None, 1.0, None, h, None, z, hr, r, *geo, 2 * C, C, co.EPI_GRU_GATES, Mm2=MXg, view=ti, views=t)
+                co.wino_output(G, bg, None, None, 1.0, None, h, None, z, hr, r, *geo, 2 * C, C, co.EPI_GRU_GATES, Mm2=MXg, view=ti, views=t)
                 Vhr = co.wino_input(hr, C, C, b, D, H, W)
-                co.wino_gemm(Vhr, C, None, 0, U["oh"], Mc, b, D, Ht, Wt, C)
+                S = co.wino_gemm(Vhr, C, None, 0, U["oh"], Mm, b, D, Ht, Wt, C)
                 hn, cand = new(), new()
-                co.wino_output(Mc, bo, None, None, 1.0, None, h, z, hn, None, cand, *geo, C, C, co.EPI_GRU_OUT, Mm2=MXc, view=ti, views=t)
+                co.wino_output(S, bo, None, None, 1.0, None, h, z, hn, None, cand, *geo, C, C, co.EPI_GRU_OUT, Mm2=MXc, view=ti, views=t)
                 steps.append((ti, h, z, r, cand, Vh, Vhr))
                 h = hn
             rm, rv, mom, eps, nbt, group = bnargs(norm)
@@ -644,8 +648,7 @@ class _FuseGroupsTrain(torch.autograd.Function):
         newV = lambda rows, c: torch.empty(16, rows, c, dtype=torch.float32, device=dev)
         UT = {k: co.wino_pack_packed(v, transpose=True) for k, v in packs.items()}     # Winograd-domain data-gradient weights [16][3][Cin][Cout]
         dU = {k: co.grad_zeros((16, 3, v.shape[1], v.shape[2]), dev, scratch=True) for k, v in packs.items()}
-        Mm = newV(R, 2 * C)
-        Mc = Mm.view(-1)[:16 * R * C].view(16, R, C)
+        Mc = newV(R, C)                                                      # the data-gradient launches' products (C columns, either form)
 
         def both(dy, Cdy, Vin, wkey, dkey, dst, residual=None):
             """One pass over dy [M, Cdy] for both of its Winograd forms (forge_wino_input_dy), then
@@ -654,8 +657,8 @@ class _FuseGroupsTrain(torch.autograd.Function):
             V, dM = co.wino_input_dy(dy, Cdy, b, D, H, W)
             _lib.check(L.forge_wino_wgrad(p(dM), p(Vin), C, 0, 0, None, 0, 0, 0, p(dU[wkey]), b, D, Ht, Wt, Cdy, 3, st()), "forge_wino_wgrad")
             del dM
-            co.wino_gemm(V, Cdy, None, 0, UT[dkey], Mc, b, D, Ht, Wt, C)
-            co.wino_output(Mc, None, None, None, 1.0, residual, None, None, dst, None, None, *geo, C, C, co.EPI_BIAS)
+            Mp = co.wino_gemm(V, Cdy, None, 0, UT[dkey], Mc, b, D, Ht, Wt, C)
+            co.wino_output(Mp, None, None, None, 1.0, residual, None, None, dst, None, None, *geo, C, C, co.EPI_BIAS)
             return dst
 
         dg_acc = torch.empty(b, t, D, H, W, 2 * C, dtype=torch.float32, device=dev)     # d (gate pre-activations) summed per view over the groups
@@ -703,14 +706,14 @@ class _FuseGroupsTrain(torch.autograd.Function):
         # the shared input halves, once for all views: weight gradients against V_x, data gradient = conv^T(dg, Wg_x) + conv^T(dc, Wo_x)
         nbt_, Rall = b * t, b * t * R1
         dx = torch.empty(b, t, D, H, W, C, dtype=torch.float32, device=dev)
-        MA, MB = newV(Rall, C), newV(Rall, C)
-        for acc, Cacc, key, Mout in ((dg_acc, 2 * C, "gx", MA), (dc_acc, C, "ox", MB)):
+        Mx = {}
+        for acc, Cacc, key in ((dg_acc, 2 * C, "gx"), (dc_acc, C, "ox")):
             Va, dMa = co.wino_input_dy(acc.reshape(-1, Cacc), Cacc, nbt_, D, H, W)
             _lib.check(L.forge_wino_wgrad(p(dMa), p(Vx), C, 0, 0, None, 0, 0, 0, p(dU[key]), nbt_, D, Ht, Wt, Cacc, 3, st()), "forge_wino_wgrad")
             del dMa
-            co.wino_gemm(Va, Cacc, None, 0, UT[key], Mout, nbt_, D, Ht, Wt, C)
+            Mx[key] = co.wino_gemm(Va, Cacc, None, 0, UT[key], None, nbt_, D, Ht, Wt, C)
             del Va
-        co.wino_output(MA, None, None, None, 1.0, None, None, None, dx, None, None, nbt_, D, H, W, C, C, co.EPI_BIAS, Mm2=MB, view=0, views=1)
+        co.wino_output(Mx["gx"], None, None, None, 1.0, None, None, None, dx, None, None, nbt_, D, H, W, C, C, co.EPI_BIAS, Mm2=Mx["ox"], view=0, views=1)
         for grp, dmean in dmeans:                                            # d mean / d x_ti = 1 / |group|
             dm = dmean.reshape(b, 1, D, H, W, C)
             if grp == list(range(grp[0], grp[0] + len(grp))):
@@ -891,17 +894,17 @@ class ConvGRU_3D(co.PackedModule):
         return p
 
     @staticmethod
-    def _wino_h0(p, src, geo, Vh, Mc, t0, h, nsum=1, sum_stride=0, bs=0):
+    def _wino_h0(p, src, geo, Vh, Mm, t0, h, nsum=1, sum_stride=0, bs=0):
         """h = fusion_conv(mean of the nsum view tensors starting at `src`, sum_stride rows apart): two Winograd convolutions with the folded
-        BatchNorm + LeakyReLU tail (scratch Vh / Mc / t0); the view mean of models/encoder.py:62 is taken inside the first input transform."""
+        BatchNorm + LeakyReLU tail (scratch Vh / Mm / t0); the view mean of models/encoder.py:62 is taken inside the first input transform."""
         b, D, H, W = geo
         C = h.shape[-1]
         co.wino_input(src, C, C, b, D, H, W, bs=bs, out=Vh, nsum=nsum, sum_stride=sum_stride)
-        co.wino_gemm(Vh, C, None, 0, p["fc0_U"], Mc, b, D, H // 2, W // 2, C)
-        co.wino_output(Mc, p["fc0_b"], p["bn1"][0], p["bn1"][1], 0.01, None, None, None, t0, None, None, b, D, H, W, C, C, co.EPI_AFFINE_ACT)
+        Mp = co.wino_gemm(Vh, C, None, 0, p["fc0_U"], Mm, b, D, H // 2, W // 2, C)
+        co.wino_output(Mp, p["fc0_b"], p["bn1"][0], p["bn1"][1], 0.01, None, None, None, t0, None, None, b, D, H, W, C, C, co.EPI_AFFINE_ACT)
         co.wino_input(t0, C, C, b, D, H, W, out=Vh)
-        co.wino_gemm(Vh, C, None, 0, p["fc3_U"], Mc, b, D, H // 2, W // 2, C)
-        co.wino_output(Mc, p["fc3_b"], p["bn4"][0], p["bn4"][1], 0.01, None, None, None, h, None, None, b, D, H, W, C, C, co.EPI_AFFINE_ACT)
+        Mp = co.wino_gemm(Vh, C, None, 0, p["fc3_U"], Mm, b, D, H // 2, W // 2, C)
+        co.wino_output(Mp, p["fc3_b"], p["bn4"][0], p["bn4"][1], 0.01, None, None, None, h, None, None, b, D, H, W, C, C, co.EPI_AFFINE_ACT)
 
     def _fuse_wino(self, xr, h0=None):
         """fuse_hip with every 3x3x3 convolution as Winograd F(2x2, 3x3) x 3 depth taps (csrc/winograd.hip): 2.25x fewer MFMA FLOPs.
@@ -917,23 +920,22 @@ class ConvGRU_3D(co.PackedModule):
         geo = (b, D, H, W)
         Vx = co.wino_input(xr, C, C, b * t, D, H, W)                       # [16][b t D Ht Wt][C]: all views of all scenes
         Vh = torch.empty(16, R, C, dtype=torch.float32, device=dev)
-        Mm = torch.empty(16, R, 2 * C, dtype=torch.float32, device=dev)
-        Mc = Mm.view(-1)[:16 * R * C].view(16, R, C)                        # the C-column problems reuse the front of the buffer
+        Mm = _step_scratch(R, C, dev)
         t0, h = new(), new()
         vol = D * H * W
         if h0 is None:
-            self._wino_h0(p, xr, geo, Vh, Mc, t0, h, nsum=t, sum_stride=vol, bs=t * vol)
+            self._wino_h0(p, xr, geo, Vh, Mm, t0, h, nsum=t, sum_stride=vol, bs=t * vol)
         else:
             h.copy_(h0.permute(0, 2, 3, 4, 1).reshape(M, C))
         z, hr, h2, out = new(), new(), t0, new()
         for ti in range(t):
             co.wino_input(h, C, C, b, D, H, W, out=Vh)
-            co.wino_gemm(Vx, C, Vh, C, p["gate_U"], Mm, b, D, Ht, Wt, 2 * C, view=ti, views=t)
-            co.wino_output(Mm, p["gate_b"], None, None, 1.0, None, h, None, z, hr, None, *geo, 2 * C, C, co.EPI_GRU_GATES)
+            G = co.wino_gemm(Vx, C, Vh, C, p["gate_U"], Mm, b, D, Ht, Wt, 2 * C, view=ti, views=t)
+            co.wino_output(G, p["gate_b"], None, None, 1.0, None, h, None, z, hr, None, *geo, 2 * C, C, co.EPI_GRU_GATES)
             co.wino_input(hr, C, C, b, D, H, W, out=Vh)
-            co.wino_gemm(Vx, C, Vh, C, p["out_U"], Mc, b, D, Ht, Wt, C, view=ti, views=t)
+            S = co.wino_gemm(Vx, C, Vh, C, p["out_U"], Mm, b, D, Ht, Wt, C, view=ti, views=t)
             last = ti == t - 1
-            co.wino_output(Mc, p["out_b"], p["norm"][0], p["norm"][1], 1.0, None, h, z, h2, out if last else None, None, *geo, C, C, co.EPI_GRU_OUT)
+            co.wino_output(S, p["out_b"], p["norm"][0], p["norm"][1], 1.0, None, h, z, h2, out if last else None, None, *geo, C, C, co.EPI_GRU_OUT)
             h, h2 = h2, h
         return out.reshape(b, D, H, W, C).permute(0, 4, 1, 2, 3)
 
@@ -953,16 +955,12 @@ class ConvGRU_3D(co.PackedModule):
         geo = (b, D, H, W)
         Vx = co.wino_input(xr, C, C, b * t, D, H, W)
         # 8-plane form (row stage of the inverse transform in the GEMM epilogue, convops.wino_half_applies) for the launches on the 64 x 128 tile: the
-        # shared input-half products and the per-step hidden-half products are then row-combined separately and added in the column-stage kernel
-        hx = co.wino_half_applies(R, C, C)                            # decided by the per-step launches (R rows); the all-view launches follow it
-        P = 8 if hx else 16
-        MXg = torch.empty(P, b * t * R1, 2 * C, dtype=torch.float32, device=dev)
-        MXc = torch.empty(P, b * t * R1, C, dtype=torch.float32, device=dev)
-        co.wino_gemm(Vx, C, None, 0, p["gate_Ux"], MXg, b * t, D, Ht, Wt, 2 * C, half=hx)
-        co.wino_gemm(Vx, C, None, 0, p["out_Ux"], MXc, b * t, D, Ht, Wt, C, half=hx)
+        # shared input-half products and the per-step hidden-half products are then row-combined separately and added in the column-stage kernel.
+        # Each all-view launch takes the form of the per-step launches (R rows, the same columns) that add its products.
+        MXg = co.wino_gemm(Vx, C, None, 0, p["gate_Ux"], None, b * t, D, Ht, Wt, 2 * C, half=co.wino_half_applies(R, 2 * C, C))
+        MXc = co.wino_gemm(Vx, C, None, 0, p["out_Ux"], None, b * t, D, Ht, Wt, C, half=co.wino_half_applies(R, C, C))
         Vh = torch.empty(16, R, C, dtype=torch.float32, device=dev)
-        Mm = torch.empty(P, R, 2 * C, dtype=torch.float32, device=dev)
-        Mc = Mm.view(-1)[:P * R * C].view(P, R, C)
+        Mm = _step_scratch(R, C, dev)
         outs = []
         for grp in groups:
             grp = list(grp)
@@ -970,18 +968,18 @@ class ConvGRU_3D(co.PackedModule):
             mean = None if run else torch.stack([xr[:, ti] for ti in grp], dim=1).mean(dim=1).reshape(M, C)
             t0, h = new(), new()
             if run:
-                self._wino_h0(p, xr[:, grp[0]:], geo, Vh, Mc, t0, h, nsum=len(grp), sum_stride=D * H * W, bs=t * D * H * W)
+                self._wino_h0(p, xr[:, grp[0]:], geo, Vh, Mm, t0, h, nsum=len(grp), sum_stride=D * H * W, bs=t * D * H * W)
             else:
-                self._wino_h0(p, mean, geo, Vh, Mc, t0, h)
+                self._wino_h0(p, mean, geo, Vh, Mm, t0, h)
             z, hr, h2, out = new(), new(), t0, new()
             for k, ti in enumerate(grp):
                 co.wino_input(h, C, C, b, D, H, W, out=Vh)
-                co.wino_gemm(Vh, C, None, 0, p["gate_Uh"], Mm, b, D, Ht, Wt, 2 * C)
-                co.wino_output(Mm, p["gate_b"], None, None, 1.0, None, h, None, z, hr, None, *geo, 2 * C, C, co.EPI_GRU_GATES, Mm2=MXg, view=ti, views=t)
+                G = co.wino_gemm(Vh, C, None, 0, p["gate_Uh"], Mm, b, D, Ht, Wt, 2 * C)
+                co.wino_output(G, p["gate_b"], None, None, 1.0, None, h, None, z, hr, None, *geo, 2 * C, C, co.EPI_GRU_GATES, Mm2=MXg, view=ti, views=t)
                 co.wino_input(hr, C, C, b, D, H, W, out=Vh)
-                co.wino_gemm(Vh, C, None, 0, p["out_Uh"], Mc, b, D, Ht, Wt, C)
+                S = co.wino_gemm(Vh, C, None, 0, p["out_Uh"], Mm, b, D, Ht, Wt, C)
                 last = k == len(grp) - 1
-                co.wino_output(Mc, p["out_b"], p["norm"][0], p["norm"][1], 1.0, None, h, z, h2, out if last else None, None, *geo, C, C,
+                co.wino_output(S, p["out_b"], p["norm"][0], p["norm"][1], 1.0, None, h, z, h2, out if last else None, None, *geo, C, C,
                                co.EPI_GRU_OUT, Mm2=MXc, view=ti, views=t)
                 h, h2 = h2, h
             outs.append(out.reshape(b, D, H, W, C).permute(0, 4, 1, 2, 3))

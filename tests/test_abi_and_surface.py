@@ -345,6 +345,29 @@ def test_modules_refuse_cpu_tensors_instead_of_falling_back():
                 call()
 
 
+def test_wino_point_products_are_checked_before_any_launch(monkeypatch):
+    """convops.wino_gemm / wino_output refuse point-product buffers that do not fit the form (8 or 16 planes) with ValueError before the library
+    is touched. Meta tensors (data_ptr() 0): even a missed check could not hand a kernel a host pointer."""
+    from forge_amd import convops as co
+    monkeypatch.setattr(_lib, "lib", lambda: pytest.fail("the library was called"))
+    meta = lambda *s: torch.empty(*s, device="meta")
+    n, D, H, W, C, Cout = 1, 2, 8, 8, 32, 64
+    R = n * D * (H // 2) * (W // 2)
+    out = meta(n * D * H * W, Cout)
+    wino_output = lambda Mm, Mm2=None, views=1: co.wino_output(Mm, None, None, None, 1.0, None, None, None, out, None, None, n, D, H, W, Cout, Cout,
+                                                               co.EPI_BIAS, Mm2=Mm2, views=views)
+    for Mm, Mm2, views in ((meta(8, R, Cout), meta(16, R, Cout), 1), (meta(16, R, Cout), meta(8, 3 * R, Cout), 3),
+                           (meta(16, R + 1, Cout), None, 1), (meta(8, R, Cout), meta(8, 2 * R, Cout), 3), (meta(12, R, Cout), None, 1),
+                           (meta(16, Cout, R).transpose(1, 2), None, 1)):
+        with pytest.raises(ValueError):
+            wino_output(Mm, Mm2, views)
+    V, U = meta(16, R, C), meta(16, 3, Cout, C)
+    for Mm, half in ((meta(8, R, Cout), False), (meta(8 * R * Cout - 1), True), (meta(16, Cout, R).transpose(1, 2), True),
+                     (meta(16, R, Cout).double(), True)):
+        with pytest.raises(ValueError):
+            co.wino_gemm(V, C, None, 0, U, Mm, n, D, H // 2, W // 2, Cout, half=half)
+
+
 def test_grad_zero_arena_never_hands_out_memory_twice():
     """convops.grad_zeros (one zero-filled arena per backward pass for the atomically accumulated weight gradients): plain torch.zeros outside
     a backward pass; inside one, slices of ONE buffer sized by the previous pass; a pass that dies with an exception, or a nested backward,

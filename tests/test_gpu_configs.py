@@ -865,6 +865,27 @@ def test_fuse_groups_inference_shares_input_halves(dev):
             assert (s - sep).abs().max().item() < 2e-4 * scale and (s.cpu() - ref).abs().max().item() < 2e-4 * scale
 
 
+@pytest.mark.parametrize("C", [64, 128])
+def test_fuse_groups_inference_8_plane_form_equals_separate_fusions(dev, C):
+    """test_fuse_groups_inference_shares_input_halves at 2 scenes = 2048 tile rows per GRU step, where the point products take the 8-plane form
+    (convops.wino_half_applies): at C = 64 the gates' (2 C columns) but not the state's (C columns), so the shared input-half products of the two
+    GRU convolutions come in different forms. ConvGRU_3D.fuse_groups_hip against independent fuse_hip calls, the same bound."""
+    from forge_amd import convops as co
+    from forge_amd.fusion import ConvGRU_3D
+    R = 2 * 16 * 8 * 8
+    assert co.wino_half_applies(R, 2 * C, C) and co.wino_half_applies(R, C, C) == (C > 64)
+    gru = ConvGRU_3D(syn.kubric_config(), n_layers=1, input_size=C, hidden_size=C)
+    gru.load_state_dict(syn.seeded_state_dict(gru.state_dict(), 3))
+    gru = gru.to(dev).eval()
+    x = (torch.randn(2, 5, C, 16, 16, 16, generator=torch.Generator().manual_seed(21)) * 0.5).to(dev)
+    groups = [[0, 1, 2], [3, 4], [0, 1, 2, 3, 4]]
+    with torch.no_grad():
+        shared = gru.fuse_groups_hip(x, groups)
+        for g, s in zip(groups, shared):
+            sep = gru.fuse_hip(x[:, g])
+            assert (s - sep).abs().max().item() < 2e-4 * max(1.0, sep.abs().max().item()), g
+
+
 def test_conv_wgrad_batch_chunking(dev, monkeypatch):
     """convops.conv_wgrad accumulates batches whose operands exceed the kernel's 2 GiB buffer range in batch chunks (needed by the
     128^3-voxel training step at 4 scenes per GPU): with the limit lowered so that 5 volumes split 2 + 2 + 1, the weight gradient equals

@@ -317,19 +317,32 @@ def test_fuse_groups_shared_inputs_equals_separate_fusions(dev):
     """FORGE_poseEstimator3D's three fusions (views (0,1,2), (3,4), (0..4) of the same rotated features) with the input halves of the GRU
     convolutions computed once per view (fuse_groups_autograd_hip) against three independent fuse_autograd_hip calls: outputs, input
     gradient and parameter gradients. Stated tolerance: 2e-4 of the respective max magnitude (fp32 summation order, atomics in wgrad)."""
-    import copy
-    from forge_amd.fusion import ConvGRU_3D
     # Seed: the two paths order their fp32 sums differently (K = 3 x 128 halves + residual vs K = 3 x 256), so a LeakyReLU argument of
     # fusion_conv that lies within rounding of zero can take the other slope in one of them; that single activation then moves its 5^3
     # neighbourhood of dx and the fusion_conv weight gradients by ~1e-3 of their max - a property of LeakyReLU, not of either path.
     # tools/debug/groups_grad_noise.py lists the agreement per seed (8e-7 relative L2 without such an event, 2e-4 with one: seed 11 on
     # the Winograd kernels); this seed has none on either kernel family, so the tight bounds below test the arithmetic.
-    torch.manual_seed(12)
-    a = ConvGRU_3D(syn.kubric_config(), n_layers=1, input_size=128, hidden_size=128).to(dev).train()
+    _groups_vs_separate_fusions_autograd(dev, 1, 128, 12)
+
+
+def test_fuse_groups_shared_inputs_equals_separate_fusions_8_plane_form(dev):
+    """The same comparison and bounds at 2 scenes = 2048 tile rows per GRU step, where every point GEMM of the hand-scheduled node takes the
+    8-plane form (convops.wino_half_applies). (Training needs C a multiple of 128: the weight gradients of the two-input convolutions.)
+    The seed has no LeakyReLU sign flip, as above."""
+    from forge_amd import convops as co
+    assert co.wino_half_applies(2 * 16 * 8 * 8, 256, 128) and co.wino_half_applies(2 * 16 * 8 * 8, 128, 128)
+    _groups_vs_separate_fusions_autograd(dev, 2, 128, 12)
+
+
+def _groups_vs_separate_fusions_autograd(dev, b, C, seed):
+    import copy
+    from forge_amd.fusion import ConvGRU_3D
+    torch.manual_seed(seed)
+    a = ConvGRU_3D(syn.kubric_config(), n_layers=1, input_size=C, hidden_size=C).to(dev).train()
     bmod = copy.deepcopy(a)
-    x = (torch.randn(1, 5, 128, 16, 16, 16) * 0.5).to(dev)
+    x = (torch.randn(b, 5, C, 16, 16, 16) * 0.5).to(dev)
     groups = [[0, 1, 2], [3, 4], [0, 1, 2, 3, 4]]
-    ws = [torch.randn(1, 128, 16, 16, 16, device=dev) for _ in groups]
+    ws = [torch.randn(b, C, 16, 16, 16, device=dev) for _ in groups]
     xa = x.clone().requires_grad_(True)
     outs_a = a.fuse_groups_autograd_hip(xa, groups)
     sum((o * w).sum() for o, w in zip(outs_a, ws)).backward()

@@ -1,5 +1,6 @@
 """Winograd F(2x2, 3x3) x 3-depth-tap path of the fused ConvGRU convolutions (csrc/winograd.hip, forge_wino_*) against a float64
 torch convolution, the direct implicit-GEMM kernel and the oracle's fusion."""
+import contextlib
 import os
 import sys
 
@@ -27,8 +28,8 @@ def _conv_wino(x, x2, w, bias, epilogue=0, **kw):
     V1 = co.wino_input(x, C1, C1, n, D, H, W)
     V2 = None if x2 is None else co.wino_input(x2, C2, C2, n, D, H, W)
     R = n * D * (H // 2) * (W // 2)
-    Mm = torch.empty(16, R, Cout, device=x.device)
-    co.wino_gemm(V1, C1, V2, C2, co.wino_pack_weight(w), Mm, n, D, H // 2, W // 2, Cout)
+    Mm = co.wino_gemm(V1, C1, V2, C2, co.wino_pack_weight(w), torch.empty(16, R, Cout, device=x.device), n, D, H // 2, W // 2, Cout)
+    assert Mm.shape == (8 if co.wino_half_applies(R, Cout, C1 + C2) else 16, R, Cout)          # the form the rule chose, read by wino_output
     out = torch.empty(n * D * H * W, Cout, device=x.device)
     co.wino_output(Mm, bias, kw.get("scale"), kw.get("shift"), kw.get("slope", 1.0), kw.get("residual"), None, None, out, None, None, n, D, H, W, Cout, Cout,
                    epilogue)
@@ -215,6 +216,33 @@ def test_frozen_fusion_hoisted_reference_view_equals_the_plain_frozen_fusion():
         assert rel(outs[0][1], outs[1][1]) < 1e-3, it      # (LeakyReLU arguments within rounding of zero may take the other slope, as above)
 
 
+def test_frozen_fusion_const0_of_another_plan_is_refused():
+    """const0's point products keep the form they were made in (8 planes at 2048 tile rows by default, 16 under a forced plan): reusing them
+    under the other plan raises instead of reading them in the wrong form - in both directions, before the fusion returns anything."""
+    from forge_amd import synthetic as syn
+    from forge_amd.fusion import ConvGRU_3D
+    from forge_amd import convops as co
+    dev = _dev()
+    gru = ConvGRU_3D(syn.kubric_config(), n_layers=1, input_size=128, hidden_size=128)
+    gru.load_state_dict(syn.seeded_state_dict(gru.state_dict(), 3))
+    gru = gru.to(dev).eval()
+    for p_ in gru.parameters():
+        p_.requires_grad_(False)
+    x = (torch.randn(2, 3, 128, 16, 16, 16, generator=torch.Generator().manual_seed(5)) * 0.5).to(dev)
+    R = 2 * 16 * 8 * 8
+    assert co.wino_half_applies(R, 256, 128) and co.wino_half_applies(R, 128, 128)
+    forced = lambda: co.force_plan(tile="B")                          # the default rule's tile, in the 16-plane form
+    with torch.no_grad():
+        for fill, reuse, P in ((contextlib.nullcontext, forced, 8), (forced, contextlib.nullcontext, 16)):
+            const0 = {}
+            with fill():
+                gru.fuse_frozen_hip(x, skip_dx0=True, const0=const0)
+            assert const0["MXg0"].shape == (P, R, 256) and const0["MXc0"].shape == (P, R, 128)
+            with reuse(), pytest.raises(ValueError):
+                gru.fuse_frozen_hip(x, skip_dx0=True, const0=const0)
+        torch.cuda.synchronize()
+
+
 @pytest.mark.parametrize("n,D,H,W,C", [(2, 3, 8, 12, 128), (1, 1, 32, 32, 512), (3, 5, 6, 4, 36)])
 def test_wino_input_dy_equals_the_two_separate_transforms(n, D, H, W, C):
     """forge_wino_input_dy (one pass over an upstream gradient for both of its Winograd forms) == forge_wino_input and forge_wino_dy, bit for bit."""
@@ -328,6 +356,7 @@ def test_half_inverse_transform_in_the_gemm_epilogue_is_bitwise_the_two_launch_f
     Mm, Mm8 = torch.empty(16, R, Cout, device=dev), torch.full((8, R, Cout), float("nan"), device=dev)
     co.wino_gemm(V1, C1, V2, C2, U, Mm, n, D, H // 2, W // 2, Cout, half=False)
     co.wino_gemm(V1, C1, V2, C2, U, Mm8, n, D, H // 2, W // 2, Cout, half=True)
+    assert co.wino_gemm(V1, C1, V2, C2, U, None, n, D, H // 2, W // 2, Cout).shape == (8, R, Cout)       # the rule's choice here
     s0 = (Mm[0:4] + Mm[4:8]) + Mm[8:12]                              # rows of A^T M over the point index i (p = 4 i + j)
     s1 = (Mm[4:8] - Mm[8:12]) - Mm[12:16]
     assert torch.equal(Mm8[0:4], s0) and torch.equal(Mm8[4:8], s1)
@@ -335,18 +364,16 @@ def test_half_inverse_transform_in_the_gemm_epilogue_is_bitwise_the_two_launch_f
     res = torch.randn(M, Cout, device=dev, generator=g)
     for epi, kw in ((co.EPI_BIAS, {}), (co.EPI_AFFINE_ACT, dict(scale=sc, shift=sh, slope=0.01, residual=res))):
         a, b = torch.empty(M, Cout, device=dev), torch.empty(M, Cout, device=dev)
-        co.wino_output(Mm, bias, kw.get("scale"), kw.get("shift"), kw.get("slope", 1.0), kw.get("residual"), None, None, a, None, None, n, D, H, W, Cout, Cout, epi,
-                       half=False)
-        co.wino_output(Mm8, bias, kw.get("scale"), kw.get("shift"), kw.get("slope", 1.0), kw.get("residual"), None, None, b, None, None, n, D, H, W, Cout, Cout, epi,
-                       half=True)
+        co.wino_output(Mm, bias, kw.get("scale"), kw.get("shift"), kw.get("slope", 1.0), kw.get("residual"), None, None, a, None, None, n, D, H, W, Cout, Cout, epi)
+        co.wino_output(Mm8, bias, kw.get("scale"), kw.get("shift"), kw.get("slope", 1.0), kw.get("residual"), None, None, b, None, None, n, D, H, W, Cout, Cout, epi)
         assert torch.equal(a, b)
     # a second addend (the shared input halves of the grouped fusions) in the same 8-plane form: row-combined before the addition - not the same
     # order of fp32 additions as the 16-plane kernel's (m + m2 first), so equal to rounding only
     Mx = torch.randn(16, R, Cout, device=dev, generator=g)
     Mx8 = torch.cat([(Mx[0:4] + Mx[4:8]) + Mx[8:12], (Mx[4:8] - Mx[8:12]) - Mx[12:16]])
     a, b = torch.empty(M, Cout, device=dev), torch.empty(M, Cout, device=dev)
-    co.wino_output(Mm, bias, None, None, 1.0, None, None, None, a, None, None, n, D, H, W, Cout, Cout, co.EPI_BIAS, Mm2=Mx, half=False)
-    co.wino_output(Mm8, bias, None, None, 1.0, None, None, None, b, None, None, n, D, H, W, Cout, Cout, co.EPI_BIAS, Mm2=Mx8, half=True)
+    co.wino_output(Mm, bias, None, None, 1.0, None, None, None, a, None, None, n, D, H, W, Cout, Cout, co.EPI_BIAS, Mm2=Mx)
+    co.wino_output(Mm8, bias, None, None, 1.0, None, None, None, b, None, None, n, D, H, W, Cout, Cout, co.EPI_BIAS, Mm2=Mx8)
     assert (a - b).abs().max().item() <= 4e-6 * a.abs().max().item()
     if Cout % 2 == 0:                                                 # the GRU tails: gates (z | r -> h r) on Cout = 2 Ch columns, state update on Cout columns
         Ch = Cout // 2
@@ -354,14 +381,14 @@ def test_half_inverse_transform_in_the_gemm_epilogue_is_bitwise_the_two_launch_f
         outs = []
         for half in (False, True):
             z, hr, r = (torch.empty(M, Ch, device=dev) for _ in range(3))
-            co.wino_output(Mm8 if half else Mm, bias, None, None, 1.0, None, h, None, z, hr, r, n, D, H, W, Cout, Ch, co.EPI_GRU_GATES, half=half)
+            co.wino_output(Mm8 if half else Mm, bias, None, None, 1.0, None, h, None, z, hr, r, n, D, H, W, Cout, Ch, co.EPI_GRU_GATES)
             outs.append((z, hr, r))
         assert all(torch.equal(u, v) for u, v in zip(*outs))
     hfull, zfull = torch.randn(M, Cout, device=dev, generator=g), torch.rand(M, Cout, device=dev, generator=g)
     outs = []
     for half in (False, True):
         hn, hb, cand = (torch.empty(M, Cout, device=dev) for _ in range(3))
-        co.wino_output(Mm8 if half else Mm, bias, sc, sh, 1.0, None, hfull, zfull, hn, hb, cand, n, D, H, W, Cout, Cout, co.EPI_GRU_OUT, half=half)
+        co.wino_output(Mm8 if half else Mm, bias, sc, sh, 1.0, None, hfull, zfull, hn, hb, cand, n, D, H, W, Cout, Cout, co.EPI_GRU_OUT)
         outs.append((hn, hb, cand))
     assert all(torch.equal(u, v) for u, v in zip(*outs))
 
@@ -384,6 +411,6 @@ def test_half_form_one_depth_tap_2d_launches_bitwise():
     ref = torch.einsum("prc,poc->pro", V.double(), U[:, 0].double())
     assert (Mm.double() - ref).abs().max().item() < 2e-5 * ref.abs().max().item()
     a, b = torch.empty(M, Cout, device=dev), torch.empty(M, Cout, device=dev)
-    co.wino_output(Mm, None, sc, sh, 0.0, None, None, None, a, None, None, n, 1, H, W, Cout, Cout, co.EPI_AFFINE_ACT, half=False)
-    co.wino_output(Mm8, None, sc, sh, 0.0, None, None, None, b, None, None, n, 1, H, W, Cout, Cout, co.EPI_AFFINE_ACT, half=True)
+    co.wino_output(Mm, None, sc, sh, 0.0, None, None, None, a, None, None, n, 1, H, W, Cout, Cout, co.EPI_AFFINE_ACT)
+    co.wino_output(Mm8, None, sc, sh, 0.0, None, None, None, b, None, None, n, 1, H, W, Cout, Cout, co.EPI_AFFINE_ACT)
     assert torch.equal(a, b)

@@ -14,10 +14,10 @@ Mm, MmB = torch.empty(16, R, 256, device=dev), torch.empty(16, R, 256, device=de
 h, z, hr = torch.randn(M, C, device=dev), torch.empty(M, C, device=dev), torch.empty(M, C, device=dev)
 Vh = torch.empty(16, R, C, device=dev)
 bias = torch.zeros(256, device=dev)
-MmT = torch.randn(16, R, 256, device=dev)
 s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
 flops = 2.0 * 16 * R * 256 * 3 * 2 * C
 gemm = lambda out: co.wino_gemm(V1, C, V2, C, U, out, B, D, 16, 16, 256)
+MmT = gemm(torch.empty(16, R, 256, device=dev))                       # products in the form the inverse transform reads
 
 
 def transforms():

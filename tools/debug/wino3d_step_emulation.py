@@ -22,22 +22,22 @@ steps, depth = int(os.environ.get("PROBE_STEPS", "60")), int(os.environ.get("PRO
 TWICE_IN, TWICE_OUT = int(os.environ.get("EMU_IN", "2")), int(os.environ.get("EMU_OUT", "2"))     # 1 = keep the 2-D form's transform bytes (GEMM change alone)
 
 
-def emu_h0(p, src, geo, Vh, Mc, t0, h, nsum=1, sum_stride=0, bs=0):
+def emu_h0(p, src, geo, Vh, Mm, t0, h, nsum=1, sum_stride=0, bs=0):
     b, D, H, W = geo
     C = h.shape[-1]
     U0, U3 = p["fc0_U1"], p["fc3_U1"]
     for _ in range(TWICE_IN):
         co.wino_input(src, C, C, b, D, H, W, bs=bs, out=Vh, nsum=nsum, sum_stride=sum_stride)
     for _ in range(2):
-        co.wino_gemm(Vh, C, None, 0, U0, Mc, b, D, H // 2, W // 2, C)
+        Mp = co.wino_gemm(Vh, C, None, 0, U0, Mm, b, D, H // 2, W // 2, C)
     for _ in range(TWICE_OUT):
-        co.wino_output(Mc, p["fc0_b"], p["bn1"][0], p["bn1"][1], 0.01, None, None, None, t0, None, None, b, D, H, W, C, C, co.EPI_AFFINE_ACT)
+        co.wino_output(Mp, p["fc0_b"], p["bn1"][0], p["bn1"][1], 0.01, None, None, None, t0, None, None, b, D, H, W, C, C, co.EPI_AFFINE_ACT)
     for _ in range(TWICE_IN):
         co.wino_input(t0, C, C, b, D, H, W, out=Vh)
     for _ in range(2):
-        co.wino_gemm(Vh, C, None, 0, U3, Mc, b, D, H // 2, W // 2, C)
+        Mp = co.wino_gemm(Vh, C, None, 0, U3, Mm, b, D, H // 2, W // 2, C)
     for _ in range(TWICE_OUT):
-        co.wino_output(Mc, p["fc3_b"], p["bn4"][0], p["bn4"][1], 0.01, None, None, None, h, None, None, b, D, H, W, C, C, co.EPI_AFFINE_ACT)
+        co.wino_output(Mp, p["fc3_b"], p["bn4"][0], p["bn4"][1], 0.01, None, None, None, h, None, None, b, D, H, W, C, C, co.EPI_AFFINE_ACT)
 
 
 def emu_fuse(self, xr, h0=None):
@@ -55,25 +55,24 @@ def emu_fuse(self, xr, h0=None):
         Vx = co.wino_input(xr, C, C, b * t, D, H, W)
     Vh = torch.zeros(16, R, C, dtype=torch.float32, device=dev_)
     Mm = torch.zeros(16, R, 2 * C, dtype=torch.float32, device=dev_)
-    Mc = Mm.view(-1)[:16 * R * C].view(16, R, C)
     t0, h = new(), new()
     vol = D * H * W
-    emu_h0(p, xr, geo, Vh, Mc, t0, h, nsum=t, sum_stride=vol, bs=t * vol)
+    emu_h0(p, xr, geo, Vh, Mm, t0, h, nsum=t, sum_stride=vol, bs=t * vol)
     z, hr, h2, out = new(), new(), t0, new()
     for ti in range(t):
         for _ in range(TWICE_IN):
             co.wino_input(h, C, C, b, D, H, W, out=Vh)
         for _ in range(2):
-            co.wino_gemm(Vx, C, Vh, C, p["gate_U1"], Mm, b, D, Ht, Wt, 2 * C, view=ti, views=t)
+            G = co.wino_gemm(Vx, C, Vh, C, p["gate_U1"], Mm, b, D, Ht, Wt, 2 * C, view=ti, views=t)
         for _ in range(TWICE_OUT):
-            co.wino_output(Mm, p["gate_b"], None, None, 1.0, None, h, None, z, hr, None, *geo, 2 * C, C, co.EPI_GRU_GATES)
+            co.wino_output(G, p["gate_b"], None, None, 1.0, None, h, None, z, hr, None, *geo, 2 * C, C, co.EPI_GRU_GATES)
         for _ in range(TWICE_IN):
             co.wino_input(hr, C, C, b, D, H, W, out=Vh)
         for _ in range(2):
-            co.wino_gemm(Vx, C, Vh, C, p["out_U1"], Mc, b, D, Ht, Wt, C, view=ti, views=t)
+            S = co.wino_gemm(Vx, C, Vh, C, p["out_U1"], Mm, b, D, Ht, Wt, C, view=ti, views=t)
         last = ti == t - 1
         for _ in range(TWICE_OUT):
-            co.wino_output(Mc, p["out_b"], p["norm"][0], p["norm"][1], 1.0, None, h, z, h2, out if last else None, None, *geo, C, C, co.EPI_GRU_OUT)
+            co.wino_output(S, p["out_b"], p["norm"][0], p["norm"][1], 1.0, None, h, z, h2, out if last else None, None, *geo, C, C, co.EPI_GRU_OUT)
         h, h2 = h2, h
     return out.reshape(b, D, H, W, C).permute(0, 4, 1, 2, 3)
 

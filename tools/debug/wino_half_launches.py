@@ -37,7 +37,8 @@ for name, (n, D, H, W, C1, C2, Cout) in (("gates [x|h] -> 256", (1, 32, 32, 32, 
     res = {}
     for half in (False, True):
         tg = timed(lambda: co.wino_gemm(V1, C1, V2, C2, U, Mm, n, D, H // 2, W // 2, Cout, half=half))
-        to = timed(lambda: co.wino_output(Mm, bias, None, None, 1.0, None, None, None, out, None, None, n, D, H, W, Cout, Cout, co.EPI_BIAS, half=half))
+        Mp = co.wino_gemm(V1, C1, V2, C2, U, Mm, n, D, H // 2, W // 2, Cout, half=half)
+        to = timed(lambda: co.wino_output(Mp, bias, None, None, 1.0, None, None, None, out, None, None, n, D, H, W, Cout, Cout, co.EPI_BIAS))
         res[half] = (tg, to)
     print("%-26s 16 planes: GEMM %7.1f us + inverse %6.1f us = %7.1f | 8 planes: GEMM %7.1f us + inverse %6.1f us = %7.1f  (x%.3f)" %
           (name, res[False][0], res[False][1], sum(res[False]), res[True][0], res[True][1], sum(res[True]), sum(res[False]) / sum(res[True])), flush=True)

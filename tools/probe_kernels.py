@@ -75,9 +75,9 @@ if "wino" in which:
     for _ in range(iters):
         co.wino_input(h, Cc, Cc, 1, D, D, D, out=Vh)
     for _ in range(iters):
-        co.wino_gemm(Vx, Cc, Vh, Cc, U, Mm, 1, D, D // 2, D // 2, 256)
+        Mp = co.wino_gemm(Vx, Cc, Vh, Cc, U, Mm, 1, D, D // 2, D // 2, 256)
     for _ in range(iters):
-        co.wino_output(Mm, bias, None, None, 1.0, None, h, None, z, hr, None, 1, D, D, D, 256, Cc, co.EPI_GRU_GATES)
+        co.wino_output(Mp, bias, None, None, 1.0, None, h, None, z, hr, None, 1, D, D, D, 256, Cc, co.EPI_GRU_GATES)
 if "render_bwd" in which:
     # the ray-march backward (round 4: ray pass -> per-sample scalars in the workspace, voxel-parallel gather): 10 views of ONE 64^3 x 16 volume,
     # 128^2 rays x 64 samples, camera gradients on (the refinement / joint-training form) - forge_render_bwd through the C-ABI
