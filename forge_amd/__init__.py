@@ -18,7 +18,7 @@ def invalidate_packed(module):
 
 def install_reference_aliases():
     """Make `from models.model import FORGE` (the import lines of kubric_train_*.py, demo.py,
-    kubric_eval.py) resolve to this package: registers forge_amd's modules under the reference's
+    kubric_eval.py) and `from models.perceptual_loss import VGGPerceptualLoss` resolve to this package: registers forge_amd's modules under the reference's
     `models.*` names in sys.modules. Call once before importing the reference's entry scripts."""
     import importlib
     import sys
@@ -27,7 +27,7 @@ def install_reference_aliases():
     pkg.__path__ = []
     sys.modules["models"] = pkg
     for name in ("model", "model_single_pose_estimator", "encoder", "fusion", "rotate", "volume_render",
-                 "pose_estimator_3d", "pose_estimator_2d"):
-        mod = importlib.import_module("forge_amd." + name)
+                 "pose_estimator_3d", "pose_estimator_2d", "perceptual_loss"):
+        mod = importlib.import_module("forge_amd." + ("perceptual" if name == "perceptual_loss" else name))
         sys.modules["models." + name] = mod
         setattr(pkg, name, mod)

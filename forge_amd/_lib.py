@@ -72,6 +72,11 @@ SIGNATURES = {
     "forge_attention_fwd": [_P, _P, _P, _LL, _P, _I, _I, _I, _I, _P],
     "forge_im2col_nchw": [_P, _P] + [_I] * 9 + [_P],
     "forge_maxpool2d_nhwc": [_P, _P] + [_I] * 7 + [_P],
+    "forge_vgg_prep_fwd": [_P, _LL, _LL, _LL, _LL, _P, _LL, _LL, _LL, _LL, _P, _P, _P] + [_I] * 7 + [_P],
+    "forge_vgg_prep_bwd": [_P, _I, _P, _P, _LL, _LL, _LL, _LL] + [_I] * 7 + [_P],
+    "forge_l1_partial_blocks": [],
+    "forge_l1_partial": [_P, _P, _LL, _P, _P],
+    "forge_vgg_tap_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "forge_ncdhw_to_ndhwc": [_P, _P, _I, _I, _LL, _P],
     "forge_ndhwc_to_ncdhw": [_P, _P, _I, _I, _LL, _P],
 }

@@ -52,6 +52,16 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
     return base + k;
 }
 
+// ATen's source index / weights of a bilinear resize with align_corners = False (area_pixel_compute_source_index + upsample_bilinear2d_out_frame):
+//   src = max(scale (dst + 0.5) - 0.5, 0), scale = in / out;  i1 = (int)src, ip = i1 < in - 1, l1 = src - i1, l0 = 1 - l1
+__device__ __forceinline__ void bilinear_src(int dst, float scale, int n_in, int& i1, int& ip, float& l0, float& l1) {
+    const float src = fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.f);
+    i1 = (int)src;
+    ip = (i1 < n_in - 1) ? 1 : 0;
+    l1 = src - (float)i1;
+    l0 = 1.f - l1;
+}
+
 __device__ __forceinline__ float4 f4_fma(float w, float4 v, float4 a) {
     a.x = fmaf(w, v.x, a.x);
     a.y = fmaf(w, v.y, a.y);

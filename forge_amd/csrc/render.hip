@@ -547,13 +547,7 @@ __global__ __launch_bounds__(256) void render_bwd_voxels_kernel(const float* __r
 // i.e. align_corners=False). ATen's arithmetic, expression for expression (area_pixel_compute_source_index + upsample_bilinear2d_out_frame):
 //   src = max(scale (dst + 0.5) - 0.5, 0), scale = in / out;  i1 = (int)src, i1p = i1 < in - 1, l1 = src - i1, l0 = 1 - l1
 //   out = h0 (w0 v[h1][w1] + w1l v[h1][w1 + w1p]) + h1l (w0 v[h1 + h1p][w1] + w1l v[h1 + h1p][w1 + w1p])
-__device__ __forceinline__ void bilinear_src(int dst, float scale, int n_in, int& i1, int& ip, float& l0, float& l1) {
-    const float src = fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.f);
-    i1 = (int)src;
-    ip = (i1 < n_in - 1) ? 1 : 0;
-    l1 = src - (float)i1;
-    l0 = 1.f - l1;
-}
+// (bilinear_src: common.h, shared with perceptual.hip's image preparation)
 
 __global__ __launch_bounds__(256) void resize_bilinear_fwd_kernel(const float* __restrict__ in, float* __restrict__ out, int P, int Hi, int Wi, int Ho, int Wo,
                                                                   float sh, float sw) {

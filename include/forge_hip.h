@@ -436,6 +436,33 @@ int forge_adam_small(float* param, const float* grad, float* exp_avg, float* exp
                      float eps, forge_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * f3  VGG-16 perceptual loss (models/perceptual_loss.py:23-44: repeat to 3 channels, (x - mean) / std, bilinear resize to 224^2,
+ * VGG-16 features[:23] with an L1 term at relu1_2 / relu2_2 / relu3_3 / relu4_3). The ten 3x3 convolutions run on forge_conv_igemm /
+ * forge_wino_*, the max-pools on forge_maxpool2d_nhwc, the ReLU masks inside a block on forge_affine_act_bwd; these entries are the rest.
+ *   prep_fwd  rows [(b ? 2N : N) Ho Wo][32] = conv1_1's patch rows (forge_im2col_nchw's k-order, k = (ky*3 + kx)*3 + c, 3x3 pad 1,
+ *             zero for k >= 27) of the prepared images: images a[0..N) then b[0..N), each [N][C][Hi][Wi] read through element strides
+ *             (C = 1 is repeated to 3), normalised by the DEVICE scalars mean[3] / std[3], resized with ATen's bilinear arithmetic
+ *             (align_corners = False) when resize = 1 (else Ho = Hi, Wo = Wi). b nullable.
+ *   prep_bwd  the adjoint: din [N][C][Hi][Wi] (element strides sn..sw) from g, the gradient of the prepared image as channels-last rows
+ *             [N][Ho][Wo][ldg] (channel c at column c); a deterministic gather per source pixel, divided by std, summed over the three
+ *             repeated channels when C = 1.
+ *   l1        partial [forge_l1_partial_blocks()] = per-workgroup sums of |x - y| over n floats (x, y 16-byte aligned); fixed reduction
+ *             tree, the caller adds the rows in a fixed order.
+ *   tap_bwd   d_pre = (maxpool2x2_bwd(g_next) + coef[0] sign(x - y)) * (x > 0) on channels-last rows [N][H][W][C], x = the tap's
+ *             post-ReLU output. The pool backward recomputes each window's winner from x (ATen: first maximum in row-major order, NaN
+ *             wins); g_next [N][H/2][W/2][C] nullable (no following block), coef nullable (no L1 term at this tap; y is then unused).
+ */
+int forge_vgg_prep_fwd(const float* a, long long a_sn, long long a_sc, long long a_sh, long long a_sw, const float* b, long long b_sn,
+                       long long b_sc, long long b_sh, long long b_sw, const float* mean, const float* std, float* rows, int N, int C,
+                       int Hi, int Wi, int Ho, int Wo, int resize, forge_stream_t stream);
+int forge_vgg_prep_bwd(const float* g, int ldg, const float* std, float* din, long long sn, long long sc, long long sh, long long sw,
+                       int N, int C, int Hi, int Wi, int Ho, int Wo, int resize, forge_stream_t stream);
+int forge_l1_partial_blocks(void);
+int forge_l1_partial(const float* x, const float* y, long long n, float* partial, forge_stream_t stream);
+int forge_vgg_tap_bwd(const float* x, const float* y, const float* g_next, const float* coef, float* d_pre, int N, int H, int W, int C,
+                      forge_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * layout helpers: NCDHW <-> channels-last for callers that hold plain-contiguous volumes.
  *   src [n][C][P] -> dst [n][P][C]   (P = D*H*W)   and back.
  */
