@@ -16,6 +16,25 @@ def invalidate_packed(module):
     _inv(module)
 
 
+def set_deterministic(mode):
+    """True / False / None (default: follow torch.are_deterministic_algorithms_enabled()): the bitwise-reproducible kernels for the weight
+    gradients and the pose gradient (forge_amd/determinism.py)."""
+    from .determinism import set_deterministic as _set
+    _set(mode)
+
+
+def is_deterministic():
+    """The effective deterministic mode (forge_amd/determinism.py)."""
+    from .determinism import is_deterministic as _is
+    return _is()
+
+
+def deterministic(mode=True):
+    """`with forge_amd.deterministic(True): ...` - the mode inside the block, the previous setting restored on exit."""
+    from .determinism import deterministic as _ctx
+    return _ctx(mode)
+
+
 def install_reference_aliases():
     """Make `from models.model import FORGE` (the import lines of kubric_train_*.py, demo.py,
     kubric_eval.py) and `from models.perceptual_loss import VGGPerceptualLoss` resolve to this package: registers forge_amd's modules under the reference's

@@ -77,12 +77,23 @@ SIGNATURES = {
     "forge_l1_partial_blocks": [],
     "forge_l1_partial": [_P, _P, _LL, _P, _P],
     "forge_vgg_tap_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "forge_conv_wgrad_det": [_P, _I, _P, _I, _I, _LL, _P, _I, _I, _LL, _P] + [_I] * 9 + [_P, _I, _I, _P, _LL, _P],
+    "forge_conv_wgrad_det_ws_bytes": [_I] * 11 + [_P, _I],
+    "forge_wino_wgrad_det": [_P, _P, _I, _LL, _LL, _P, _I, _LL, _LL, _P, _I, _I, _I, _I, _I, _I, _I, _P, _LL, _P],
+    "forge_wino_wgrad_det_ws_bytes": [_I] * 8,
+    "forge_conv_direct_wgrad_det": [_P, _I, _P, _I, _P] + [_I] * 6 + [_P, _I, _I, _P, _LL, _P],
+    "forge_conv_direct_wgrad_det_ws_bytes": [_I] * 7,
+    "forge_rotate_bwd_det": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _LL, _P],
+    "forge_rotate_bwd_det_ws_bytes": [_I] * 5,
+    "forge_rotate_bwd_slots_det": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _LL, _P],
+    "forge_rotate_bwd_slots_det_ws_bytes": [_I] * 5,
     "forge_ncdhw_to_ndhwc": [_P, _P, _I, _I, _LL, _P],
     "forge_ndhwc_to_ncdhw": [_P, _P, _I, _I, _LL, _P],
 }
 
 
-_LL_RESULTS = ("forge_render_bwd_ws_bytes",)       # byte counts: long long results
+_LL_RESULTS = ("forge_render_bwd_ws_bytes", "forge_conv_wgrad_det_ws_bytes", "forge_wino_wgrad_det_ws_bytes",     # byte counts: long long results
+               "forge_conv_direct_wgrad_det_ws_bytes", "forge_rotate_bwd_det_ws_bytes", "forge_rotate_bwd_slots_det_ws_bytes")
 
 
 def lib():

@@ -8,7 +8,7 @@ import ctypes
 
 import torch
 
-from . import _lib
+from . import _lib, determinism
 
 EPI_BIAS, EPI_AFFINE_ACT, EPI_GRU_GATES, EPI_GRU_OUT = 0, 1, 2, 3
 
@@ -456,7 +456,8 @@ def conv3_wgrad(dy, x1, C1, x2, C2, dwp, grid, Cout, bs1=0, taps=None, dM=None):
         dM = torch.empty(16, R, Cout, dtype=torch.float32, device=dev)
         _lib.check(L.forge_wino_dy(_lib.ptr(dy), dy.shape[-1], _lib.ptr(dM), n, D, H, W, Cout, st), "forge_wino_dy")
     dU = grad_zeros((16, kd, Cout, C1 + C2), dev, scratch=True)
-    _lib.check(L.forge_wino_wgrad(_lib.ptr(dM), _lib.ptr(V1), C1, 0, 0, _lib.ptr(V2), C2, 0, 0, _lib.ptr(dU), n, D, Ht, Wt, Cout, kd, st), "forge_wino_wgrad")
+    determinism.launch("forge_wino_wgrad", (_lib.ptr(dM), _lib.ptr(V1), C1, 0, 0, _lib.ptr(V2), C2, 0, 0, _lib.ptr(dU), n, D, Ht, Wt, Cout, kd),
+                       (C1, C2, n, D, Ht, Wt, Cout, kd), dev)
     _lib.check(L.forge_wino_dw(_lib.ptr(dU), _lib.ptr(dwp), Cout, C1 + C2, kd, st), "forge_wino_dw")
     return dwp
 
@@ -624,11 +625,12 @@ def conv_wgrad(dy, x1, C1, x2, C2, dwp, grid, in_grid, Cout, taps, istride=1, bs
                       or (x2 is not None and span(nc, b2, ld2, in_rows) > MAX_OPERAND_BYTES)):
         nc = (nc + 1) // 2
     off = lambda t, floats: None if t is None else ctypes.c_void_p(t.data_ptr() + 4 * floats)
-    for s0 in range(0, n, nc):
+    ta = _taps_array(taps)
+    for s0 in range(0, n, nc):               # deterministic mode: the batch chunks accumulate (out = prior + S) in order on this stream
         k = min(nc, n - s0)
-        _lib.check(_lib.lib().forge_conv_wgrad(off(dy, s0 * out_rows * ldy), ldy, off(x1, s0 * b1 * ld1), C1, ld1, int(bs1), off(x2, s0 * b2 * ld2), C2, ld2,
-                                               int(bs2), _lib.ptr(dwp), k, D, H, W, istride, Di, Hi, Wi, Cout, _taps_array(taps), len(taps),
-                                               _lib.current_stream()), "forge_conv_wgrad")
+        determinism.launch("forge_conv_wgrad", (off(dy, s0 * out_rows * ldy), ldy, off(x1, s0 * b1 * ld1), C1, ld1, int(bs1), off(x2, s0 * b2 * ld2), C2, ld2,
+                                                int(bs2), _lib.ptr(dwp), k, D, H, W, istride, Di, Hi, Wi, Cout, ta, len(taps)),
+                           (C1, C2, k, D, H, W, istride, Di, Hi, Wi, Cout, ta, len(taps)), dwp.device)
     return dwp
 
 
@@ -903,8 +905,8 @@ class _ConvDirectRows(torch.autograd.Function):
                                                           _taps_array(taps), T, _lib.current_stream()), "forge_conv_direct_dgrad")
         if ctx.needs_input_grad[1]:
             dwp = grad_zeros(wp.shape, wp.device)
-            _lib.check(_lib.lib().forge_conv_direct_wgrad(_lib.ptr(dy), Cout, _lib.ptr(x), Cin, _lib.ptr(dwp), n, D, H, W, Cin, Cout,
-                                                          _taps_array(taps), T, _lib.current_stream()), "forge_conv_direct_wgrad")
+            determinism.launch("forge_conv_direct_wgrad", (_lib.ptr(dy), Cout, _lib.ptr(x), Cin, _lib.ptr(dwp), n, D, H, W, Cin, Cout, _taps_array(taps), T),
+                               (n, D, H, W, Cin, Cout, T), dwp.device)
         if has_bias and ctx.needs_input_grad[2]:
             db = colsum(dy.reshape(-1, Cout))
         return dx, dwp, db, None

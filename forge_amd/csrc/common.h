@@ -70,6 +70,14 @@ __device__ __forceinline__ float4 f4_fma(float w, float4 v, float4 a) {
     return a;
 }
 
+// Deterministic mode (the *_det entry points): kernels that would add partial sums with fp32 atomics store them into slabs of the caller's
+// workspace instead, and det_reduce sums the slabs in slab order:
+//   out[o][e] = (accumulate ? out[o][e] : 0) + S,  S = sum_{s = 0..nslab-1} ws[o outer + s slab + e]  (float64, in s order, rounded once)
+// e < E; E, slab and outer multiples of 4 floats, ws / out 16-byte aligned. DET_SLAB_BYTES caps one launch's slab set (a plan rule on shapes).
+constexpr long long DET_SLAB_BYTES = 64ll << 20;
+int det_reduce(const float* ws, long long nslab, long long slab, long long nouter, long long outer, long long E, float* out, int accumulate,
+               hipStream_t stream, const char* fn);
+
 // hardware fp32 atomic add (global_atomic_add_f32), no CAS loop
 __device__ __forceinline__ void atomic_add_f32(float* p, float v) { unsafeAtomicAdd(p, v); }
 

@@ -87,7 +87,9 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const DirectArgs a) {
 // 5 taps 630 / -, 4 taps 592 / 170, 3 taps - / 187, 2 taps 407 / -, 1 tap 477 / -: occupancy beats the re-reads of dy.
 __host__ __device__ constexpr int wg_taps(int ci, int co) { return 48 / (ci * co) > 4 ? 4 : (48 / (ci * co) < 1 ? 1 : 48 / (ci * co)); }
 
-template <int CI4, int CO>
+// DET = true (forge_conv_direct_wgrad_det): a.o is the slab set [gridDim.x][ntaps][CO][CI]; the workgroup stores its partial sums (zeros
+// included) into slab blockIdx.x and det_reduce sums the slabs in order. The DET = false instantiations compile exactly as before the switch.
+template <int CI4, int CO, bool DET = false>
 __global__ __launch_bounds__(256) void conv_direct_wgrad_kernel(const DirectArgs a) {
     constexpr int CI = CI4 * 4, WG_TAPS = wg_taps(CI, CO), NACC = WG_TAPS * CO * CI;
     __shared__ float red[4][NACC];
@@ -146,7 +148,8 @@ __global__ __launch_bounds__(256) void conv_direct_wgrad_kernel(const DirectArgs
     __syncthreads();
     for (int i = threadIdx.x; i < nt * CO * CI; i += 256) {
         const float s = red[0][i] + red[1][i] + red[2][i] + red[3][i];
-        if (s != 0.f) atomic_add_f32(a.o + (long long)t0 * CO * CI + i, s);
+        if constexpr (DET) a.o[((long long)blockIdx.x * a.ntaps + t0) * CO * CI + i] = s;
+        else if (s != 0.f) atomic_add_f32(a.o + (long long)t0 * CO * CI + i, s);
     }
 }
 
@@ -210,19 +213,59 @@ extern "C" int forge_conv_direct_dgrad(const float* dy, int ld_dy, const float* 
     return 0;
 }
 
-extern "C" int forge_conv_direct_wgrad(const float* dy, int ld_dy, const float* x, int ld_x, float* dw,
-                                       int n, int D, int H, int W, int Cin, int Cout, const int* taps, int ntaps, forge_stream_t stream) {
-    FORGE_REQUIRE(dy && x && dw, FORGE_EINVAL, "forge_conv_direct_wgrad: null pointer argument");
-    DirectArgs a;
-    if (int rc = fill_direct("forge_conv_direct_wgrad", a, n, D, H, W, Cin, Cout, taps, ntaps)) return rc;
-    FORGE_REQUIRE(ld_dy >= Cout && ld_x >= Cin && ld_x % 4 == 0, FORGE_ESHAPE, "forge_conv_direct_wgrad: bad row strides");
-    a.a = dy; a.b = x; a.o = dw; a.w = nullptr; a.bias = nullptr; a.slope = 1.f; a.lda = ld_dy; a.ldb = ld_x; a.ldo = 0;
-    const long long M = (long long)n * D * H * W;
+// det: plan (and, when launching, check the workspace); the slab count is the grid's x extent, capped at DET_SLAB_BYTES
+static long long direct_wgrad_grid(long long M, int Cin, int Cout, int ntaps, bool det) {
     long long gx = (M + 255) / 256;
     if (gx > 2048) gx = 2048;                                     // grid-stride: every workgroup ends with a reduction + atomics
+    if (det) {
+        long long cap = DET_SLAB_BYTES / ((long long)ntaps * Cout * Cin * 4);
+        if (cap < 1) cap = 1;
+        if (gx > cap) gx = cap;
+    }
+    return gx;
+}
+
+static int conv_direct_wgrad_run(const float* dy, int ld_dy, const float* x, int ld_x, float* dw, int n, int D, int H, int W, int Cin, int Cout,
+                                 const int* taps, int ntaps, forge_stream_t stream, int det, int accumulate, void* ws, long long ws_bytes) {
+    const char* fn = det ? "forge_conv_direct_wgrad_det" : "forge_conv_direct_wgrad";
+    FORGE_REQUIRE(dy && x && dw, FORGE_EINVAL, "%s: null pointer argument", fn);
+    DirectArgs a;
+    if (int rc = fill_direct(fn, a, n, D, H, W, Cin, Cout, taps, ntaps)) return rc;
+    FORGE_REQUIRE(ld_dy >= Cout && ld_x >= Cin && ld_x % 4 == 0, FORGE_ESHAPE, "%s: bad row strides", fn);
+    a.a = dy; a.b = x; a.o = dw; a.w = nullptr; a.bias = nullptr; a.slope = 1.f; a.lda = ld_dy; a.ldb = ld_x; a.ldo = 0;
+    const long long M = (long long)n * D * H * W;
+    const long long gx = direct_wgrad_grid(M, Cin, Cout, ntaps, det != 0);
     const int tg = wg_taps(Cin, Cout);
     const dim3 grid((unsigned)gx, (unsigned)((ntaps + tg - 1) / tg));
+    if (det) {
+        const long long slab = (long long)ntaps * Cout * Cin;
+        FORGE_REQUIRE(accumulate == 0 || accumulate == 1, FORGE_EINVAL, "%s: accumulate must be 0 or 1", fn);
+        FORGE_REQUIRE(ws && ((unsigned long long)ws & 15) == 0 && ws_bytes >= gx * slab * 4, FORGE_EINVAL,
+                      "%s: null / unaligned workspace or %lld bytes < %lld", fn, ws_bytes, gx * slab * 4);
+        a.o = (float*)ws;
+        FORGE_DIRECT_DISPATCH(Cin, Cout, hipLaunchKernelGGL((conv_direct_wgrad_kernel<CI4, CO, true>), grid, dim3(256), 0, (hipStream_t)stream, a));
+        FORGE_LAUNCH_CHECK(fn);
+        return det_reduce((const float*)ws, gx, slab, 1, 0, slab, dw, accumulate, (hipStream_t)stream, fn);
+    }
     FORGE_DIRECT_DISPATCH(Cin, Cout, hipLaunchKernelGGL((conv_direct_wgrad_kernel<CI4, CO>), grid, dim3(256), 0, (hipStream_t)stream, a));
-    FORGE_LAUNCH_CHECK("forge_conv_direct_wgrad");
+    FORGE_LAUNCH_CHECK(fn);
     return 0;
+}
+
+extern "C" int forge_conv_direct_wgrad(const float* dy, int ld_dy, const float* x, int ld_x, float* dw,
+                                       int n, int D, int H, int W, int Cin, int Cout, const int* taps, int ntaps, forge_stream_t stream) {
+    return conv_direct_wgrad_run(dy, ld_dy, x, ld_x, dw, n, D, H, W, Cin, Cout, taps, ntaps, stream, 0, 0, nullptr, 0);
+}
+
+extern "C" int forge_conv_direct_wgrad_det(const float* dy, int ld_dy, const float* x, int ld_x, float* dw, int n, int D, int H, int W, int Cin,
+                                           int Cout, const int* taps, int ntaps, int accumulate, void* ws, long long ws_bytes, forge_stream_t stream) {
+    return conv_direct_wgrad_run(dy, ld_dy, x, ld_x, dw, n, D, H, W, Cin, Cout, taps, ntaps, stream, 1, accumulate, ws, ws_bytes);
+}
+
+extern "C" long long forge_conv_direct_wgrad_det_ws_bytes(int n, int D, int H, int W, int Cin, int Cout, int ntaps) {
+    FORGE_REQUIRE(n > 0 && D > 0 && H > 0 && W > 0 && ntaps > 0 && ntaps <= 64, FORGE_EINVAL, "forge_conv_direct_wgrad_det_ws_bytes: bad dims");
+    FORGE_REQUIRE((Cin == 4 || Cin == 8 || Cin == 16) && Cout >= 1 && Cout <= 4, FORGE_ESHAPE,
+                  "forge_conv_direct_wgrad_det_ws_bytes: Cin=%d Cout=%d outside the direct kernels' range (Cin 4/8/16, Cout 1..4)", Cin, Cout);
+    const long long M = (long long)n * D * H * W;
+    return direct_wgrad_grid(M, Cin, Cout, ntaps, true) * ntaps * Cout * Cin * 4;
 }

@@ -50,7 +50,10 @@ constexpr int WT = 128, WK = 16, WJ = WK / 8;  // tile 128 x 128, K-step 16 voxe
 // channel c % CIW - so a narrow-input problem with many taps (the heads' ConvTranspose3d(128, 32, 4, s2): 64 taps x 32 channels; conv1: 27 x 64)
 // runs the full 128 x 128 tile with its 32 MFMAs per wave and K-step instead of 8 / 16 (4 / 2 x the matrix work per barrier and per staged
 // dY row): a thread's staged chunk simply gathers at ITS tap's offset.
-template <int CIW, int TG = 1>
+// DET = true (forge_conv_wgrad_det / forge_wino_wgrad_det, all kernels of this file): a.dw is the slab set [nchunk][ntaps][Cout][Cin] and the
+// epilogue STORES the partial tile into slab `chunk` - every in-range element, zeros included - instead of adding it to dW with atomics;
+// det_reduce (det_reduce.hip) then sums the slabs in chunk order. The DET = false instantiations compile exactly as before the switch.
+template <int CIW, int TG = 1, bool DET = false>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
     constexpr int NWID = CIW * TG;                                  // used columns of the B image
     static_assert(NWID <= 128 && (TG == 1 || NWID == 128), "tap groups fill the 128-column tile");
@@ -181,7 +184,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
             for (int r = 0; r < 16; ++r) {
                 const int i = (r & 3) + 8 * (r >> 2) + 4 * half;
                 const int co = co0 + (P == 2 ? wm * 64 + 2 * i + p : wm * 32 + i);
-                if (co < a.Cout) atomic_add_f32(a.dw + ((long long)te * a.Cout + co) * Cin + ci, acc[p][q][r]);
+                if constexpr (DET) {
+                    if (co < a.Cout) a.dw[(((long long)chunk * a.ntaps + te) * a.Cout + co) * Cin + ci] = acc[p][q][r];
+                } else {
+                    if (co < a.Cout) atomic_add_f32(a.dw + ((long long)te * a.Cout + co) * Cin + ci, acc[p][q][r]);
+                }
             }
     }
 }
@@ -192,6 +199,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
 // a group of up to 4 taps and a chunk of voxels, and feeds the 32x32x2 MFMA straight from global memory (lane l loads
 // dY[row][l & 31] and X[row + tap][l & 31], i.e. each half-wave reads one coalesced 128-byte row per operand per MFMA; the dY
 // element is shared by the wave's taps). Partial 32x32 tiles are added to dW with fp32 atomics.
+template <bool DET = false>
 __global__ __launch_bounds__(256) void conv_wgrad_small_kernel(const WgradArgs a, int tap_groups, int rows_per_wave) {
     const int lane = threadIdx.x & 63, l31 = lane & 31, half = lane >> 5;
     const long long wave_id = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -250,7 +258,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_small_kernel(const WgradArgs a
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int co = (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (co < a.Cout) atomic_add_f32(a.dw + ((long long)(t0 + q) * a.Cout + co) * Cin + l31, acc[q][r]);
+            if constexpr (DET) {                                   // slab = this wave's voxel chunk
+                if (co < a.Cout) a.dw[(((wave_id / tap_groups) * a.ntaps + t0 + q) * a.Cout + co) * Cin + l31] = acc[q][r];
+            } else {
+                if (co < a.Cout) atomic_add_f32(a.dw + ((long long)(t0 + q) * a.Cout + co) * Cin + l31, acc[q][r]);
+            }
         }
     }
 }
@@ -269,6 +281,7 @@ constexpr int LSEG = 32, LMAXL = 9, LMAXR = 3, LROWS = LSEG + 2 * LMAXR, LTAPS =
 
 struct LineTable { signed char dz[LMAXL], dy[LMAXL]; int nlines, rx; };
 
+template <bool DET = false>
 __global__ __launch_bounds__(256) void conv_wgrad_lines_kernel(const WgradArgs a, const LineTable lt) {
     extern __shared__ __attribute__((aligned(16))) float smem[];   // dYs [LSEG][32] | Xs [nlines][LSEG + 2 rx][32]
     float* dYs = smem;
@@ -358,7 +371,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_lines_kernel(const WgradArgs a
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int co = (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (co < a.Cout && acc[j][r] != 0.f) atomic_add_f32(a.dw + ((long long)t * a.Cout + co) * Cin + l31, acc[j][r]);
+            if constexpr (DET) {                                   // slab = this workgroup
+                if (co < a.Cout) a.dw[(((long long)blockIdx.x * a.ntaps + t) * a.Cout + co) * Cin + l31] = acc[j][r];
+            } else {
+                if (co < a.Cout && acc[j][r] != 0.f) atomic_add_f32(a.dw + ((long long)t * a.Cout + co) * Cin + l31, acc[j][r]);
+            }
         }
     }
 }
@@ -375,7 +392,7 @@ typedef __attribute__((ext_vector_type(4))) float f32x4w;
 // NWV = waves per workgroup: 4, or 8 for CIT = 32 (the heads' 32 -> 16 / 32 -> 8 layers): with 4 waves that instantiation needs 189 VGPRs
 // (7 taps x 2 accumulators per wave + 11 staging passes), i.e. spills at 3 workgroups per CU and runs 1.5x slower at 2 (1124 vs 732 us);
 // 8 waves share one staged segment with 4 taps and 6 staging passes each.
-template <int CIT, int IS = 1, int LT = LTAPS, int NWV = 4>
+template <int CIT, int IS = 1, int LT = LTAPS, int NWV = 4, bool DET = false>
 __global__ __launch_bounds__(64 * NWV, NWV == 8 ? 2 : ((CIT == 16 && IS == 1) ? 4 : 3)) void conv_wgrad_lines16_kernel(const WgradArgs a, const LineTable lt) {
     constexpr int NT = CIT / 16, NTHR = 64 * NWV;
     extern __shared__ __attribute__((aligned(16))) float smem[];   // dYs [LSEG][16] | Xs [nlines][LSEG + 2 rx][CIT]
@@ -479,7 +496,11 @@ __global__ __launch_bounds__(64 * NWV, NWV == 8 ? 2 : ((CIT == 16 && IS == 1) ? 
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int co = 4 * kq + r;
-                if (co < a.Cout && acc[j][n][r] != 0.f) atomic_add_f32(a.dw + ((long long)t * a.Cout + co) * Cin + ci, acc[j][n][r]);
+                if constexpr (DET) {
+                    if (co < a.Cout) a.dw[(((long long)blockIdx.x * a.ntaps + t) * a.Cout + co) * Cin + ci] = acc[j][n][r];
+                } else {
+                    if (co < a.Cout && acc[j][n][r] != 0.f) atomic_add_f32(a.dw + ((long long)t * a.Cout + co) * Cin + ci, acc[j][n][r]);
+                }
             }
         }
     }
@@ -489,8 +510,41 @@ __global__ __launch_bounds__(64 * NWV, NWV == 8 ? 2 : ((CIT == 16 && IS == 1) ? 
 
 using namespace forge;
 
+// Deterministic mode (the _det entry points): the kernels store per-chunk partial tiles into slabs of the caller's workspace, and det_reduce
+// (det_reduce.hip) sums the slabs in chunk order. The plan - kernel, split and so the order of every addition - is a function of the shape
+// arguments alone; the slab set of a launch is capped at DET_SLAB_BYTES by lowering the chunk count. DetPlan::launch = false plans only
+// (the _det_ws_bytes queries: same code path, nothing touches the device).
+struct DetPlan {
+    bool launch;
+    void* ws; long long ws_bytes; int accumulate;
+    float* out;                  // the caller's dW (the kernels' a.dw points at the slabs)
+    long long nslab, slab;       // out: slab count and floats per slab
+};
+
+// Point the kernel at the slabs, after checking the workspace (launch) - or only record the plan. Returns > 0 when nothing is to be launched.
+static int det_prepare(WgradArgs& a, DetPlan& d, long long nslab, const char* fn) {
+    d.slab = (long long)a.ntaps * a.Cout * (a.C1 + a.C2);
+    d.nslab = nslab;
+    if (!d.launch) return 1;
+    FORGE_REQUIRE(d.accumulate == 0 || d.accumulate == 1, FORGE_EINVAL, "%s: accumulate must be 0 or 1", fn);
+    FORGE_REQUIRE(d.ws && ((unsigned long long)d.ws & 15) == 0, FORGE_EINVAL, "%s: null or unaligned workspace (16 bytes)", fn);
+    FORGE_REQUIRE(d.ws_bytes >= nslab * d.slab * 4, FORGE_EINVAL, "%s: workspace of %lld bytes, the plan needs %lld", fn, d.ws_bytes, nslab * d.slab * 4);
+    d.out = a.dw;
+    a.dw = (float*)d.ws;
+    return 0;
+}
+
+static int det_finish(const DetPlan& d, hipStream_t stream, const char* fn) {
+    return det_reduce((const float*)d.ws, d.nslab, d.slab, 1, 0, d.slab, d.out, d.accumulate, stream, fn);
+}
+
+static long long det_cap(long long slab_floats) {
+    const long long c = DET_SLAB_BYTES / (slab_floats * 4);
+    return c < 1 ? 1 : c;
+}
+
 // conv_wgrad_kernel<ciw> over (taps x Cout tiles x Cin tiles x voxel chunks) workgroups.
-static int launch_wgrad_tiles(WgradArgs& a, int ciw, hipStream_t stream) {
+static int launch_wgrad_tiles(WgradArgs& a, int ciw, hipStream_t stream, DetPlan* det) {
     const long long M = (long long)a.n * a.D * a.H * a.W;
     const int Cin = a.C1 + a.C2, Cout = a.Cout, ntaps = a.ntaps;
     // narrow single inputs with several taps: TG taps share one 128-column tile (kernel header)
@@ -511,16 +565,25 @@ static int launch_wgrad_tiles(WgradArgs& a, int ciw, hipStream_t stream) {
         if (nchunk > M / 256) nchunk = M / 256;
         if (nchunk < 1) nchunk = 1;
     }
+    if (det && nchunk > det_cap((long long)ntaps * Cout * Cin)) nchunk = det_cap((long long)ntaps * Cout * Cin);
     long long mchunk = ((M + nchunk - 1) / nchunk + WK - 1) / WK * WK;
     a.mchunk = (int)mchunk;
     nchunk = (M + mchunk - 1) / mchunk;
     const long long grid = tiles * nchunk;
     FORGE_REQUIRE(grid < (1ll << 31), FORGE_ESHAPE, "forge_conv_wgrad: grid too large");
+    if (det) {
+        if (int rc = det_prepare(a, *det, nchunk, "forge_conv_wgrad_det")) return rc < 0 ? rc : 0;
+    }
     const size_t lds = 2 * 2 * WK * WT * sizeof(float);     // 32 KiB
+#define FORGE_LAUNCH_WGRAD_K(DETv, CIWv, TGv)                                                                                           \
+    do {                                                                                                                             \
+        FORGE_SET_MAX_LDS_ONCE((conv_wgrad_kernel<CIWv, TGv, DETv>), lds);                                                                                 \
+        hipLaunchKernelGGL((conv_wgrad_kernel<CIWv, TGv, DETv>), dim3((unsigned)grid), dim3(256), lds, stream, a);                                         \
+    } while (0)
 #define FORGE_LAUNCH_WGRAD(CIWv, TGv)                                                                                                \
     do {                                                                                                                             \
-        FORGE_SET_MAX_LDS_ONCE((conv_wgrad_kernel<CIWv, TGv>), lds);                                                                 \
-        hipLaunchKernelGGL((conv_wgrad_kernel<CIWv, TGv>), dim3((unsigned)grid), dim3(256), lds, stream, a);           \
+        if (det) FORGE_LAUNCH_WGRAD_K(true, CIWv, TGv);                                                             \
+        else FORGE_LAUNCH_WGRAD_K(false, CIWv, TGv);                                                                     \
     } while (0)
     if (ciw == 32 && tg == 4) FORGE_LAUNCH_WGRAD(32, 4);
     else if (ciw == 64 && tg == 2) FORGE_LAUNCH_WGRAD(64, 2);
@@ -528,13 +591,14 @@ static int launch_wgrad_tiles(WgradArgs& a, int ciw, hipStream_t stream) {
     else if (ciw == 64) FORGE_LAUNCH_WGRAD(64, 1);
     else FORGE_LAUNCH_WGRAD(128, 1);
 #undef FORGE_LAUNCH_WGRAD
+#undef FORGE_LAUNCH_WGRAD_K
     FORGE_LAUNCH_CHECK("forge_conv_wgrad");
-    return 0;
+    return det ? det_finish(*det, stream, "forge_conv_wgrad_det") : 0;
 }
 
-extern "C" int forge_conv_wgrad(const float* dy, int ldy, const float* x1, int C1, int ld1, long long bs1, const float* x2, int C2, int ld2,
-                                long long bs2, float* dw, int n, int D, int H, int W, int is, int Di, int Hi, int Wi, int Cout,
-                                const int* taps, int ntaps, forge_stream_t stream) {
+static int conv_wgrad_run(const float* dy, int ldy, const float* x1, int C1, int ld1, long long bs1, const float* x2, int C2, int ld2,
+                          long long bs2, float* dw, int n, int D, int H, int W, int is, int Di, int Hi, int Wi, int Cout,
+                          const int* taps, int ntaps, forge_stream_t stream, DetPlan* det) {
     FORGE_REQUIRE(dy && x1 && dw && taps, FORGE_EINVAL, "forge_conv_wgrad: null pointer argument");
     FORGE_REQUIRE(n > 0 && D > 0 && H > 0 && W > 0 && Cout > 0 && ntaps > 0 && ntaps <= 64 && is >= 1 && Di > 0 && Hi > 0 && Wi > 0, FORGE_EINVAL,
                   "forge_conv_wgrad: bad dims");
@@ -582,36 +646,63 @@ extern "C" int forge_conv_wgrad(const float* dy, int ldy, const float* x1, int C
         if (ok) {
             const long long nseg = (long long)n * D * H * ((W + LSEG - 1) / LSEG);
             const size_t lds = (size_t)(LSEG * 32 + lt.nlines * (LSEG + 2 * lt.rx) * 32) * sizeof(float);
-            FORGE_SET_MAX_LDS_ONCE(conv_wgrad_lines_kernel, (LSEG * 32 + LMAXL * LROWS * 32) * sizeof(float));
+            if (!det || det->launch) FORGE_SET_MAX_LDS_ONCE(conv_wgrad_lines_kernel<>, (LSEG * 32 + LMAXL * LROWS * 32) * sizeof(float));
             a.mchunk = 0;
+            // det: one slab per workgroup (each walks its own segments), at most det_cap slabs
+            const long long cap = det ? det_cap((long long)ntaps * Cout * Cin) : (1ll << 40);
+            auto clamp_grid = [&](long long g) { g = nseg < g ? nseg : g; return g < cap ? g : cap; };
             if (lines_s2) {
                 const size_t lds16 = (size_t)(LSEG * 16 + lt.nlines * (2 * LSEG - 1 + 2 * lt.rx) * 16) * sizeof(float);
-                const long long grid16 = nseg < 768 ? nseg : 768;                   // 3 resident workgroups per CU
-                FORGE_SET_MAX_LDS_ONCE((conv_wgrad_lines16_kernel<16, 2, 9>), (LSEG * 16 + 6 * (2 * LSEG - 1 + 2 * LMAXR) * 16) * sizeof(float));
-                hipLaunchKernelGGL((conv_wgrad_lines16_kernel<16, 2, 9>), dim3((unsigned)grid16), dim3(256), lds16, (hipStream_t)stream, a, lt);
+                const long long grid16 = clamp_grid(768);                           // 3 resident workgroups per CU
+                if (det) { if (int rc = det_prepare(a, *det, grid16, "forge_conv_wgrad_det")) return rc < 0 ? rc : 0; }
+                if (det) {
+                    FORGE_SET_MAX_LDS_ONCE((conv_wgrad_lines16_kernel<16, 2, 9, 4, true>), (LSEG * 16 + 6 * (2 * LSEG - 1 + 2 * LMAXR) * 16) * sizeof(float));
+                    hipLaunchKernelGGL((conv_wgrad_lines16_kernel<16, 2, 9, 4, true>), dim3((unsigned)grid16), dim3(256), lds16, (hipStream_t)stream, a, lt);
+                } else {
+                    FORGE_SET_MAX_LDS_ONCE((conv_wgrad_lines16_kernel<16, 2, 9>), (LSEG * 16 + 6 * (2 * LSEG - 1 + 2 * LMAXR) * 16) * sizeof(float));
+                    hipLaunchKernelGGL((conv_wgrad_lines16_kernel<16, 2, 9>), dim3((unsigned)grid16), dim3(256), lds16, (hipStream_t)stream, a, lt);
+                }
                 FORGE_LAUNCH_CHECK("forge_conv_wgrad");
-                return 0;
+                return det ? det_finish(*det, (hipStream_t)stream, "forge_conv_wgrad_det") : 0;
             }
             if (Cout <= 16) {
                 // narrow outputs: the 16x16x4 MFMA tile (no 32-row padding); 4 workgroups per CU walk the segments
                 const int cit = Cin <= 16 ? 16 : 32;
                 const size_t lds16 = (size_t)(LSEG * 16 + lt.nlines * (LSEG + 2 * lt.rx) * cit) * sizeof(float);
-                const long long grid16 = nseg < (cit == 16 ? 1024 : 768) ? nseg : (cit == 16 ? 1024 : 768);    // 4 / 3 resident workgroups per CU (108 / ~150 VGPRs)
+                const long long grid16 = clamp_grid(cit == 16 ? 1024 : 768);        // 4 / 3 resident workgroups per CU (108 / ~150 VGPRs)
                 if (cit == 16) {
-                    FORGE_SET_MAX_LDS_ONCE(conv_wgrad_lines16_kernel<16>, (LSEG * 16 + LMAXL * LROWS * 16) * sizeof(float));
-                    hipLaunchKernelGGL(conv_wgrad_lines16_kernel<16>, dim3((unsigned)grid16), dim3(256), lds16, (hipStream_t)stream, a, lt);
+                    if (det) { if (int rc = det_prepare(a, *det, grid16, "forge_conv_wgrad_det")) return rc < 0 ? rc : 0; }
+                    if (det) {
+                        FORGE_SET_MAX_LDS_ONCE((conv_wgrad_lines16_kernel<16, 1, LTAPS, 4, true>), (LSEG * 16 + LMAXL * LROWS * 16) * sizeof(float));
+                        hipLaunchKernelGGL((conv_wgrad_lines16_kernel<16, 1, LTAPS, 4, true>), dim3((unsigned)grid16), dim3(256), lds16, (hipStream_t)stream, a, lt);
+                    } else {
+                        FORGE_SET_MAX_LDS_ONCE(conv_wgrad_lines16_kernel<16>, (LSEG * 16 + LMAXL * LROWS * 16) * sizeof(float));
+                        hipLaunchKernelGGL(conv_wgrad_lines16_kernel<16>, dim3((unsigned)grid16), dim3(256), lds16, (hipStream_t)stream, a, lt);
+                    }
                 } else {
-                    const long long grid32 = nseg < 512 ? nseg : 512;      // 8-wave workgroups, 2 per CU
-                    FORGE_SET_MAX_LDS_ONCE((conv_wgrad_lines16_kernel<32, 1, 4, 8>), (LSEG * 16 + LMAXL * LROWS * 32) * sizeof(float));
-                    hipLaunchKernelGGL((conv_wgrad_lines16_kernel<32, 1, 4, 8>), dim3((unsigned)grid32), dim3(512), lds16, (hipStream_t)stream, a, lt);
+                    const long long grid32 = clamp_grid(512);              // 8-wave workgroups, 2 per CU
+                    if (det) { if (int rc = det_prepare(a, *det, grid32, "forge_conv_wgrad_det")) return rc < 0 ? rc : 0; }
+                    if (det) {
+                        FORGE_SET_MAX_LDS_ONCE((conv_wgrad_lines16_kernel<32, 1, 4, 8, true>), (LSEG * 16 + LMAXL * LROWS * 32) * sizeof(float));
+                        hipLaunchKernelGGL((conv_wgrad_lines16_kernel<32, 1, 4, 8, true>), dim3((unsigned)grid32), dim3(512), lds16, (hipStream_t)stream, a, lt);
+                    } else {
+                        FORGE_SET_MAX_LDS_ONCE((conv_wgrad_lines16_kernel<32, 1, 4, 8>), (LSEG * 16 + LMAXL * LROWS * 32) * sizeof(float));
+                        hipLaunchKernelGGL((conv_wgrad_lines16_kernel<32, 1, 4, 8>), dim3((unsigned)grid32), dim3(512), lds16, (hipStream_t)stream, a, lt);
+                    }
                 }
                 FORGE_LAUNCH_CHECK("forge_conv_wgrad");
-                return 0;
+                return det ? det_finish(*det, (hipStream_t)stream, "forge_conv_wgrad_det") : 0;
             }
-            const long long grid = nseg < 512 ? nseg : 512;          // 2 workgroups per CU (244 VGPRs), each walking its share of the segments
-            hipLaunchKernelGGL(conv_wgrad_lines_kernel, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, a, lt);
+            const long long grid = clamp_grid(512);                  // 2 workgroups per CU (244 VGPRs), each walking its share of the segments
+            if (det) {
+                if (int rc = det_prepare(a, *det, grid, "forge_conv_wgrad_det")) return rc < 0 ? rc : 0;
+                FORGE_SET_MAX_LDS_ONCE(conv_wgrad_lines_kernel<true>, (LSEG * 32 + LMAXL * LROWS * 32) * sizeof(float));
+                hipLaunchKernelGGL(conv_wgrad_lines_kernel<true>, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, a, lt);
+            } else {
+                hipLaunchKernelGGL(conv_wgrad_lines_kernel<>, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, a, lt);
+            }
             FORGE_LAUNCH_CHECK("forge_conv_wgrad");
-            return 0;
+            return det ? det_finish(*det, (hipStream_t)stream, "forge_conv_wgrad_det") : 0;
         }
         for (int t = 0; t < ntaps; ++t) a.tap[t][3] = 0;
     }
@@ -621,20 +712,54 @@ extern "C" int forge_conv_wgrad(const float* dy, int ldy, const float* x1, int C
         long long rows = (M * tap_groups + 4095) / 4096;            // ~4096 waves
         rows = (rows + 1) / 2 * 2;
         if (rows < 256) rows = 256;
+        if (det) {                                                  // one slab per voxel chunk: at most det_cap chunks
+            const long long cap = det_cap((long long)ntaps * Cout * Cin);
+            if ((M + rows - 1) / rows > cap) rows = ((M + cap - 1) / cap + 1) / 2 * 2;
+        }
         a.mchunk = (int)rows;
         const long long waves = ((M + rows - 1) / rows) * tap_groups;
-        hipLaunchKernelGGL(conv_wgrad_small_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a, tap_groups, (int)rows);
+        if (det) {
+            if (int rc = det_prepare(a, *det, (M + rows - 1) / rows, "forge_conv_wgrad_det")) return rc < 0 ? rc : 0;
+            hipLaunchKernelGGL(conv_wgrad_small_kernel<true>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a, tap_groups, (int)rows);
+        } else {
+            hipLaunchKernelGGL(conv_wgrad_small_kernel<>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a, tap_groups, (int)rows);
+        }
         FORGE_LAUNCH_CHECK("forge_conv_wgrad");
-        return 0;
+        return det ? det_finish(*det, (hipStream_t)stream, "forge_conv_wgrad_det") : 0;
     }
-    return launch_wgrad_tiles(a, (x2 == nullptr && Cin <= 32) ? 32 : (x2 == nullptr && Cin <= 64) ? 64 : WT, (hipStream_t)stream);
+    return launch_wgrad_tiles(a, (x2 == nullptr && Cin <= 32) ? 32 : (x2 == nullptr && Cin <= 64) ? 64 : WT, (hipStream_t)stream, det);
+}
+
+extern "C" int forge_conv_wgrad(const float* dy, int ldy, const float* x1, int C1, int ld1, long long bs1, const float* x2, int C2, int ld2,
+                                long long bs2, float* dw, int n, int D, int H, int W, int is, int Di, int Hi, int Wi, int Cout,
+                                const int* taps, int ntaps, forge_stream_t stream) {
+    return conv_wgrad_run(dy, ldy, x1, C1, ld1, bs1, x2, C2, ld2, bs2, dw, n, D, H, W, is, Di, Hi, Wi, Cout, taps, ntaps, stream, nullptr);
+}
+
+extern "C" int forge_conv_wgrad_det(const float* dy, int ldy, const float* x1, int C1, int ld1, long long bs1, const float* x2, int C2, int ld2,
+                                    long long bs2, float* dw, int n, int D, int H, int W, int is, int Di, int Hi, int Wi, int Cout,
+                                    const int* taps, int ntaps, int accumulate, void* ws, long long ws_bytes, forge_stream_t stream) {
+    DetPlan d = {true, ws, ws_bytes, accumulate, nullptr, 0, 0};
+    return conv_wgrad_run(dy, ldy, x1, C1, ld1, bs1, x2, C2, ld2, bs2, dw, n, D, H, W, is, Di, Hi, Wi, Cout, taps, ntaps, stream, &d);
+}
+
+// Placeholder operand addresses for the plan-only pass of the _det_ws_bytes queries: never dereferenced, nothing is launched.
+static const float* plan_ptr() { static const float dummy[4] = {}; return dummy; }
+
+extern "C" long long forge_conv_wgrad_det_ws_bytes(int C1, int C2, int n, int D, int H, int W, int is, int Di, int Hi, int Wi, int Cout,
+                                                   const int* taps, int ntaps) {
+    DetPlan d = {false, nullptr, 0, 0, nullptr, 0, 0};
+    const float* p = plan_ptr();
+    const int rc = conv_wgrad_run(p, Cout, p, C1, C1, 0, C2 > 0 ? p : nullptr, C2, C2, 0, (float*)p, n, D, H, W, is, Di, Hi, Wi, Cout, taps, ntaps,
+                                  nullptr, &d);
+    return rc != 0 ? (rc < 0 ? rc : FORGE_EINVAL) : d.nslab * d.slab * 4;
 }
 
 // Weight gradient in the Winograd domain (csrc/winograd.hip): dU[p][kd][co][ci] = sum_r dMm[p][r][co] (V1 | V2)[p][r + kd plane][ci] for the 16
 // points in ONE launch of conv_wgrad_kernel - 16 kd "taps" whose operands advance by one point every kd taps. dU [16][kd][Cout][C1+C2] must
 // be zero-filled (fp32 atomics over voxel chunks). 2.25x fewer FLOPs than forge_conv_wgrad on the same convolution.
-extern "C" int forge_wino_wgrad(const float* dMm, const float* V1, int C1, long long bs1, long long pt1, const float* V2, int C2, long long bs2,
-                                long long pt2, float* dU, int n, int D, int Ht, int Wt, int Cout, int kd, forge_stream_t stream) {
+static int wino_wgrad_run(const float* dMm, const float* V1, int C1, long long bs1, long long pt1, const float* V2, int C2, long long bs2,
+                          long long pt2, float* dU, int n, int D, int Ht, int Wt, int Cout, int kd, forge_stream_t stream, DetPlan* det) {
     FORGE_REQUIRE(dMm && V1 && dU && (kd == 1 || kd == 3), FORGE_EINVAL, "forge_wino_wgrad: null pointer argument / kd not 1 or 3");
     FORGE_REQUIRE(n > 0 && D > 0 && Ht > 0 && Wt > 0 && Cout > 0 && Cout % 4 == 0 && C1 > 0 && C1 % 4 == 0 && C2 >= 0 && C2 % 4 == 0 &&
                   (C2 == 0) == (V2 == nullptr) && (C2 == 0 || C1 % WT == 0), FORGE_ESHAPE,
@@ -653,5 +778,24 @@ extern "C" int forge_wino_wgrad(const float* dMm, const float* V1, int C1, long 
     a.tpp = kd; a.pty = R * Cout; a.pt1 = pt1 > 0 ? pt1 : R * C1; a.pt2 = V2 ? (pt2 > 0 ? pt2 : R * C2) : 0;
     for (int t = 0; t < 16 * kd; ++t) a.tap[t][0] = (signed char)(kd == 3 ? t % 3 - 1 : 0);
     const int Cin = C1 + C2;
-    return launch_wgrad_tiles(a, (V2 == nullptr && Cin <= 32) ? 32 : (V2 == nullptr && Cin <= 64) ? 64 : WT, (hipStream_t)stream);
+    return launch_wgrad_tiles(a, (V2 == nullptr && Cin <= 32) ? 32 : (V2 == nullptr && Cin <= 64) ? 64 : WT, (hipStream_t)stream, det);
+}
+
+extern "C" int forge_wino_wgrad(const float* dMm, const float* V1, int C1, long long bs1, long long pt1, const float* V2, int C2, long long bs2,
+                                long long pt2, float* dU, int n, int D, int Ht, int Wt, int Cout, int kd, forge_stream_t stream) {
+    return wino_wgrad_run(dMm, V1, C1, bs1, pt1, V2, C2, bs2, pt2, dU, n, D, Ht, Wt, Cout, kd, stream, nullptr);
+}
+
+extern "C" int forge_wino_wgrad_det(const float* dMm, const float* V1, int C1, long long bs1, long long pt1, const float* V2, int C2, long long bs2,
+                                    long long pt2, float* dU, int n, int D, int Ht, int Wt, int Cout, int kd, int accumulate, void* ws, long long ws_bytes,
+                                    forge_stream_t stream) {
+    DetPlan d = {true, ws, ws_bytes, accumulate, nullptr, 0, 0};
+    return wino_wgrad_run(dMm, V1, C1, bs1, pt1, V2, C2, bs2, pt2, dU, n, D, Ht, Wt, Cout, kd, stream, &d);
+}
+
+extern "C" long long forge_wino_wgrad_det_ws_bytes(int C1, int C2, int n, int D, int Ht, int Wt, int Cout, int kd) {
+    DetPlan d = {false, nullptr, 0, 0, nullptr, 0, 0};
+    const float* p = plan_ptr();
+    const int rc = wino_wgrad_run(p, p, C1, 0, 0, C2 > 0 ? p : nullptr, C2, 0, 0, (float*)p, n, D, Ht, Wt, Cout, kd, nullptr, &d);
+    return rc != 0 ? (rc < 0 ? rc : FORGE_EINVAL) : d.nslab * d.slab * 4;
 }

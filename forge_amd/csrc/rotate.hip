@@ -156,6 +156,9 @@ __global__ __launch_bounds__(256) void rotate_fwd_kernel(const float4* __restric
 // kernel below; its first version scatter-added 8 x C fp32 atomics per voxel from here.)
 constexpr int AFF_ITER = 8;            // (4: 82 us, 8: 78, 16: 80, 32: 129 - too few workgroups)
 
+// DET = true (forge_rotate_bwd_det): dxf is the partial set [n][blocks_per_vol][12]; the workgroup stores its 12 sums (zeros for a mode-0
+// volume) at [n][its block][.] and det_reduce adds them in block order. The DET = false kernel compiles exactly as before the switch.
+template <bool DET = false>
 __global__ __launch_bounds__(256) void rotate_bwd_affine_kernel(const float4* __restrict__ dout, const float4* __restrict__ vox,
                                                          const float* __restrict__ xf, const int* __restrict__ mode,
                                                          const int* __restrict__ src_slot, float* __restrict__ dxf,
@@ -230,8 +233,11 @@ __global__ __launch_bounds__(256) void rotate_bwd_affine_kernel(const float4* __
         __syncthreads();
         if (threadIdx.x < 12) {
             const float s = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
-            atomic_add_f32(dxf + n * 12 + threadIdx.x, s);
+            if constexpr (DET) dxf[((long long)n * blocks_per_vol + bid % blocks_per_vol) * 12 + threadIdx.x] = s;
+            else atomic_add_f32(dxf + n * 12 + threadIdx.x, s);
         }
+    } else if constexpr (DET) {
+        if (threadIdx.x < 12) dxf[((long long)n * blocks_per_vol + bid % blocks_per_vol) * 12 + threadIdx.x] = 0.f;
     }
 }
 
@@ -625,8 +631,15 @@ extern "C" int forge_pose_chain_bwd(const float* jac, const float* dxf, const fl
     return 0;
 }
 
+// workgroups per volume of the affine-gradient kernel (det: partial rows per volume)
+static unsigned rotate_affine_blocks(int C, int D, int H, int W) {
+    const long long per_vol = (long long)D * H * W * (C / 4);
+    return (unsigned)((per_vol + 256 * AFF_ITER - 1) / (256 * AFF_ITER));
+}
+
 static int rotate_bwd_launch(const float* dout, const float* vox, const float* xf, const int* mode, const int* src_slot,
-                             float* dvox, float* dxf, int n, int C, int D, int H, int W, forge_stream_t stream) {
+                             float* dvox, float* dxf, int n, int C, int D, int H, int W, forge_stream_t stream,
+                             int det = 0, int accumulate = 0, void* ws = nullptr, long long ws_bytes = 0) {
     if (int rc = check_rotate_args(dout, xf, mode, dvox ? (const void*)dvox : (const void*)dxf, n, C, D, H, W)) return rc;     // at least one of dvox / dxf
     FORGE_REQUIRE(!dxf || vox, FORGE_EINVAL, "forge_rotate_bwd: dxf requested but vox is NULL");
     const int C4 = C / 4;
@@ -634,6 +647,13 @@ static int rotate_bwd_launch(const float* dout, const float* vox, const float* x
     const unsigned bpv = (unsigned)((per_vol + 255) / 256);
     FORGE_REQUIRE((long long)bpv * n < (1ll << 31), FORGE_ESHAPE, "forge_rotate_bwd: grid too large");
     FORGE_REQUIRE(per_vol < (1ll << 31), FORGE_ESHAPE, "forge_rotate_bwd: a volume holds >= 2^31 float4 elements");
+    const unsigned bpa = rotate_affine_blocks(C, D, H, W);
+    if (det && dxf) {
+        FORGE_REQUIRE(accumulate == 0 || accumulate == 1, FORGE_EINVAL, "forge_rotate_bwd_det: accumulate must be 0 or 1");
+        FORGE_REQUIRE(((unsigned long long)dxf & 15) == 0, FORGE_EINVAL, "forge_rotate_bwd_det: dxf must be 16-byte aligned");
+        FORGE_REQUIRE(ws && ((unsigned long long)ws & 15) == 0 && ws_bytes >= (long long)n * bpa * 12 * 4, FORGE_EINVAL,
+                      "forge_rotate_bwd_det: null / unaligned workspace or %lld bytes < %lld", ws_bytes, (long long)n * bpa * 12 * 4);
+    }
     const int nq = (C4 >= 32 && C4 % 4 == 0) ? 4 : (C4 >= 16 && C4 % 2 == 0) ? 2 : 1;   // the candidate tests are per voxel: amortise them
     const unsigned bpg = (unsigned)((per_vol / nq + 255) / 256);
 #define FORGE_LAUNCH_GATHER(NQv)                                                                                            \
@@ -644,9 +664,14 @@ static int rotate_bwd_launch(const float* dout, const float* vox, const float* x
     else if (nq == 2) FORGE_LAUNCH_GATHER(2);
     else FORGE_LAUNCH_GATHER(1);
 #undef FORGE_LAUNCH_GATHER
+    if (dxf && det) {
+        hipLaunchKernelGGL(rotate_bwd_affine_kernel<true>, dim3(bpa * (unsigned)n), dim3(256), 0, (hipStream_t)stream,
+                           (const float4*)dout, (const float4*)vox, xf, mode, src_slot, (float*)ws, C4, D, H, W, per_vol, bpa);
+        FORGE_LAUNCH_CHECK("forge_rotate_bwd_det");
+        return det_reduce((const float*)ws, bpa, 12, n, (long long)bpa * 12, 12, dxf, accumulate, (hipStream_t)stream, "forge_rotate_bwd_det");
+    }
     if (dxf) {
-        const unsigned bpa = (unsigned)((per_vol + 256 * AFF_ITER - 1) / (256 * AFF_ITER));
-        hipLaunchKernelGGL(rotate_bwd_affine_kernel, dim3(bpa * (unsigned)n), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(rotate_bwd_affine_kernel<>, dim3(bpa * (unsigned)n), dim3(256), 0, (hipStream_t)stream,
                            (const float4*)dout, (const float4*)vox, xf, mode, src_slot, dxf, C4, D, H, W, per_vol, bpa);
     }
     FORGE_LAUNCH_CHECK("forge_rotate_bwd");
@@ -664,3 +689,26 @@ extern "C" int forge_rotate_bwd_slots(const float* dout, const float* vox, const
     FORGE_REQUIRE(src_slot, FORGE_EINVAL, "forge_rotate_bwd_slots: null slot array");
     return rotate_bwd_launch(dout, vox, xf, mode, src_slot, dvox, dxf, n, C, D, H, W, stream);
 }
+
+extern "C" int forge_rotate_bwd_det(const float* dout, const float* vox, const float* xf, const int* mode,
+                                    float* dvox, float* dxf, int n, int C, int D, int H, int W,
+                                    int accumulate, void* ws, long long ws_bytes, forge_stream_t stream) {
+    return rotate_bwd_launch(dout, vox, xf, mode, nullptr, dvox, dxf, n, C, D, H, W, stream, 1, accumulate, ws, ws_bytes);
+}
+
+extern "C" int forge_rotate_bwd_slots_det(const float* dout, const float* vox, const float* xf, const int* mode, const int* src_slot,
+                                          float* dvox, float* dxf, int n, int C, int D, int H, int W,
+                                          int accumulate, void* ws, long long ws_bytes, forge_stream_t stream) {
+    FORGE_REQUIRE(src_slot, FORGE_EINVAL, "forge_rotate_bwd_slots_det: null slot array");
+    return rotate_bwd_launch(dout, vox, xf, mode, src_slot, dvox, dxf, n, C, D, H, W, stream, 1, accumulate, ws, ws_bytes);
+}
+
+extern "C" long long forge_rotate_bwd_det_ws_bytes(int n, int C, int D, int H, int W) {
+    FORGE_REQUIRE(n > 0 && C > 0 && D > 1 && H > 1 && W > 1, FORGE_EINVAL, "forge_rotate_bwd_det_ws_bytes: bad dims (D, H, W > 1)");
+    FORGE_REQUIRE(C % 4 == 0, FORGE_ESHAPE, "forge_rotate_bwd_det_ws_bytes: C must be a multiple of 4");
+    const long long per_vol = (long long)D * H * W * (C / 4);
+    FORGE_REQUIRE(per_vol < (1ll << 31) && ((per_vol + 255) / 256) * n < (1ll << 31), FORGE_ESHAPE, "forge_rotate_bwd_det_ws_bytes: grid too large");
+    return (long long)n * rotate_affine_blocks(C, D, H, W) * 12 * 4;
+}
+
+extern "C" long long forge_rotate_bwd_slots_det_ws_bytes(int n, int C, int D, int H, int W) { return forge_rotate_bwd_det_ws_bytes(n, C, D, H, W); }

@@ -9,7 +9,7 @@ last_state_list, torch.stack of every h) is not reproduced — only the returned
 import torch
 import torch.nn as nn
 
-from . import _lib, convops as co
+from . import _lib, convops as co, determinism
 
 
 def hip_inference(module, x):
@@ -655,7 +655,8 @@ class _FuseGroupsTrain(torch.autograd.Function):
                dU[wkey] += (A dy A^T)^T (x) Vin                                  (weight gradient)
                dst [M, C] = conv^T(dy, weights `dkey`) (+ residual)              (data gradient: point GEMMs on B^T dy B, inverse transform)"""
             V, dM = co.wino_input_dy(dy, Cdy, b, D, H, W)
-            _lib.check(L.forge_wino_wgrad(p(dM), p(Vin), C, 0, 0, None, 0, 0, 0, p(dU[wkey]), b, D, Ht, Wt, Cdy, 3, st()), "forge_wino_wgrad")
+            # deterministic mode: each GRU step's launch accumulates into dU[wkey] (out = prior + S), in step order on this stream
+            determinism.launch("forge_wino_wgrad", (p(dM), p(Vin), C, 0, 0, None, 0, 0, 0, p(dU[wkey]), b, D, Ht, Wt, Cdy, 3), (C, 0, b, D, Ht, Wt, Cdy, 3), dev)
             del dM
             Mp = co.wino_gemm(V, Cdy, None, 0, UT[dkey], Mc, b, D, Ht, Wt, C)
             co.wino_output(Mp, None, None, None, 1.0, residual, None, None, dst, None, None, *geo, C, C, co.EPI_BIAS)
@@ -709,7 +710,7 @@ class _FuseGroupsTrain(torch.autograd.Function):
         Mx = {}
         for acc, Cacc, key in ((dg_acc, 2 * C, "gx"), (dc_acc, C, "ox")):
             Va, dMa = co.wino_input_dy(acc.reshape(-1, Cacc), Cacc, nbt_, D, H, W)
-            _lib.check(L.forge_wino_wgrad(p(dMa), p(Vx), C, 0, 0, None, 0, 0, 0, p(dU[key]), nbt_, D, Ht, Wt, Cacc, 3, st()), "forge_wino_wgrad")
+            determinism.launch("forge_wino_wgrad", (p(dMa), p(Vx), C, 0, 0, None, 0, 0, 0, p(dU[key]), nbt_, D, Ht, Wt, Cacc, 3), (C, 0, nbt_, D, Ht, Wt, Cacc, 3), dev)
             del dMa
             Mx[key] = co.wino_gemm(Va, Cacc, None, 0, UT[key], None, nbt_, D, Ht, Wt, C)
             del Va

@@ -6,7 +6,7 @@ here: calling these ops with CPU tensors (or without the built library) raises.
 """
 import torch
 
-from . import _lib
+from . import _lib, determinism
 
 
 def _require_cuda(*tensors):
@@ -66,12 +66,13 @@ class _RotateWarp(torch.autograd.Function):
         if dvox is None and dxf is None:
             return None, None, None, None
         g_cl = to_channels_last_3d(g)
+        # deterministic mode (forge_amd/determinism.py): the _det entries sum the pose gradient's per-workgroup partials in a fixed order
         if slot is None:
-            _lib.check(_lib.lib().forge_rotate_bwd(_lib.ptr(g_cl), _lib.ptr(vox_cl), _lib.ptr(xf_c), _lib.ptr(mode),
-                                                   _lib.ptr(dvox), _lib.ptr(dxf), n, C, D, H, W, _lib.current_stream()), "forge_rotate_bwd")
+            determinism.launch("forge_rotate_bwd", (_lib.ptr(g_cl), _lib.ptr(vox_cl), _lib.ptr(xf_c), _lib.ptr(mode), _lib.ptr(dvox), _lib.ptr(dxf),
+                                                    n, C, D, H, W), (n, C, D, H, W), g_cl.device)
         else:
-            _lib.check(_lib.lib().forge_rotate_bwd_slots(_lib.ptr(g_cl), _lib.ptr(vox_cl), _lib.ptr(xf_c), _lib.ptr(mode), _lib.ptr(slot),
-                                                         _lib.ptr(dvox), _lib.ptr(dxf), n, C, D, H, W, _lib.current_stream()), "forge_rotate_bwd_slots")
+            determinism.launch("forge_rotate_bwd_slots", (_lib.ptr(g_cl), _lib.ptr(vox_cl), _lib.ptr(xf_c), _lib.ptr(mode), _lib.ptr(slot),
+                                                          _lib.ptr(dvox), _lib.ptr(dxf), n, C, D, H, W), (n, C, D, H, W), g_cl.device)
         return dvox, dxf, None, None
 
 

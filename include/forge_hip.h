@@ -289,7 +289,7 @@ int forge_wino_output(const float* Mm, const float* Mm2, long long bs2, long lon
  *   dw[t][co][ci] += sum_m dy[m][co] * x[voxel(m) + taps[t]][ci]      (x = channel concat of x1 | x2, zero outside the grid)
  * dy [M][ldy] is the upstream gradient of the conv output on the (n,D,H,W) row grid; x1/x2, is, Di.. as in forge_conv_igemm.
  * dw [ntaps][Cout][C1+C2] MUST be zero-filled: partial sums over voxel chunks are accumulated with fp32 atomics (the order of
- * the additions, hence the last bits, is not deterministic). With two inputs C1 must be a multiple of 128.
+ * the additions, hence the last bits, is not deterministic; forge_conv_wgrad_det below is). With two inputs C1 must be a multiple of 128.
  * The data gradient needs no extra entry point: it is forge_conv_igemm on dy with negated taps and wp[t][ci][co] (transposed).
  */
 int forge_conv_wgrad(const float* dy, int ldy, const float* x1, int C1, int ld1, long long bs1, const float* x2, int C2, int ld2,
@@ -312,6 +312,41 @@ int forge_conv_direct_dgrad(const float* dy, int ld_dy, const float* w, float* d
                             int n, int D, int H, int W, int Cin, int Cout, const int* taps, int ntaps, forge_stream_t stream);
 int forge_conv_direct_wgrad(const float* dy, int ld_dy, const float* x, int ld_x, float* dw,
                             int n, int D, int H, int W, int Cin, int Cout, const int* taps, int ntaps, forge_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Deterministic mode: bitwise-reproducible counterparts of the entry points whose partial sums are added with fp32 atomics
+ * (forge_conv_wgrad, forge_wino_wgrad, forge_conv_direct_wgrad, the dxf output of forge_rotate_bwd / forge_rotate_bwd_slots).
+ * Each _det function takes its counterpart's arguments plus (accumulate, ws, ws_bytes) in front of the stream:
+ *   accumulate = 0   the output (dw / dU / dxf) is WRITTEN, every element: no zero-fill needed, prior contents (NaN included) are ignored
+ *   accumulate = 1   out = prior + S with exactly one fp32 add per element, S being what accumulate = 0 writes
+ *   ws, ws_bytes     caller-owned scratch, 16-byte aligned, of at least the matching *_det_ws_bytes(...) bytes (checked: FORGE_EINVAL)
+ * The kernels store per-chunk partial sums into slabs of ws (plain stores, zeros included) and a second launch on the same stream sums
+ * the slabs in chunk order (float64, rounded once). The split - and with it the order of every addition - depends on the shape arguments
+ * only: not on ws_bytes, timing or the device's state; the same inputs give the same bits in any process on any MI355X. One launch's
+ * slab set is capped at 64 MiB by lowering the chunk count. Outputs must be 16-byte aligned (dw, dU: any torch allocation; dxf [n][12]).
+ * The *_det_ws_bytes queries are host-only (no device, no stream) and return < 0 for arguments the launch would reject; the query of
+ * forge_conv_wgrad_det takes the host tap table because the kernel choice depends on the tap geometry. dvox of forge_rotate_bwd_det is the
+ * same deterministic gather as forge_rotate_bwd's; with dxf NULL no workspace is used.
+ */
+int forge_conv_wgrad_det(const float* dy, int ldy, const float* x1, int C1, int ld1, long long bs1, const float* x2, int C2, int ld2,
+                         long long bs2, float* dw, int n, int D, int H, int W, int is, int Di, int Hi, int Wi, int Cout,
+                         const int* taps, int ntaps, int accumulate, void* ws, long long ws_bytes, forge_stream_t stream);
+long long forge_conv_wgrad_det_ws_bytes(int C1, int C2, int n, int D, int H, int W, int is, int Di, int Hi, int Wi, int Cout,
+                                        const int* taps, int ntaps);
+int forge_wino_wgrad_det(const float* dMm, const float* V1, int C1, long long bs1, long long pt1, const float* V2, int C2, long long bs2,
+                         long long pt2, float* dU, int n, int D, int Ht, int Wt, int Cout, int kd, int accumulate, void* ws, long long ws_bytes,
+                         forge_stream_t stream);
+long long forge_wino_wgrad_det_ws_bytes(int C1, int C2, int n, int D, int Ht, int Wt, int Cout, int kd);
+int forge_conv_direct_wgrad_det(const float* dy, int ld_dy, const float* x, int ld_x, float* dw, int n, int D, int H, int W, int Cin, int Cout,
+                                const int* taps, int ntaps, int accumulate, void* ws, long long ws_bytes, forge_stream_t stream);
+long long forge_conv_direct_wgrad_det_ws_bytes(int n, int D, int H, int W, int Cin, int Cout, int ntaps);
+int forge_rotate_bwd_det(const float* dout, const float* vox, const float* xf, const int* mode, float* dvox, float* dxf,
+                         int n, int C, int D, int H, int W, int accumulate, void* ws, long long ws_bytes, forge_stream_t stream);
+long long forge_rotate_bwd_det_ws_bytes(int n, int C, int D, int H, int W);
+int forge_rotate_bwd_slots_det(const float* dout, const float* vox, const float* xf, const int* mode, const int* src_slot,
+                               float* dvox, float* dxf, int n, int C, int D, int H, int W, int accumulate, void* ws, long long ws_bytes,
+                               forge_stream_t stream);
+long long forge_rotate_bwd_slots_det_ws_bytes(int n, int C, int D, int H, int W);
 
 /* ---------------------------------------------------------------------------------------------
  * a4 (training)  element-wise halves of the ConvGRU cell, models/fusion.py:29-35 under autograd. Inference fuses them into
