@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, convops as co
-from .fusion import ConvGRU_3D, affine_act_bwd, bn_act_rows, frozen_eval, hip_inference, require_hip_input
+from .fusion import ConvGRU_3D, affine_act_bwd, bn_act_rows, frozen_eval, hip_inference, require_hip_input, view_run
 
 
 class _Bottleneck(nn.Module):
@@ -268,7 +268,7 @@ class Encoder3D(co.PackedModule):
     def _views(x, g):
         """x[:, g] for a list of view indices - as a slice when they form a run (no index tensor: capturable into a hipGraph)."""
         g = list(g)
-        return x[:, g[0]:g[0] + len(g)] if g == list(range(g[0], g[0] + len(g))) else x[:, g]
+        return x[:, g[0]:g[0] + len(g)] if view_run(g) else x[:, g]
 
     @staticmethod
     def _bn2d_rows(bn, rows, relu=True):

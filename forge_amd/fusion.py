@@ -386,6 +386,184 @@ class _GRUCellPreRows(torch.autograd.Function):
         return (dg if ctx.needs_input_grad[0] else None), (dc if ctx.needs_input_grad[1] else None), dh_total, dwg, dbg, dwo, dbo
 
 
+def view_run(g):
+    """True when the view indices g are consecutive: x[:, g] is then the slice x[:, g[0]:g[0] + len(g)] (no index tensor: capturable into a
+    hipGraph), and the Winograd input transform can take the mean of the views itself."""
+    g = list(g)
+    return g == list(range(g[0], g[0] + len(g)))
+
+
+def _view_mean(xr, grp):
+    """Mean of the views grp of xr [b,t,D,H,W,C] (models/encoder.py:62) as rows [b D H W][C]."""
+    C = xr.shape[-1]
+    if view_run(grp):
+        return xr[:, grp[0]:grp[0] + len(grp)].mean(dim=1).reshape(-1, C)
+    return torch.stack([xr[:, ti] for ti in grp], dim=1).mean(dim=1).reshape(-1, C)
+
+
+def _wino_view_mean(xr, grp, out):
+    """out = the Winograd input transform of the mean of the views grp of xr [b,t,D,H,W,C]; for a run of views the transform takes the mean."""
+    b, t, D, H, W, C = xr.shape
+    vol = D * H * W
+    if view_run(grp):
+        return co.wino_input(xr[:, grp[0]:], C, C, b, D, H, W, bs=t * vol, out=out, nsum=len(grp), sum_stride=vol)
+    return co.wino_input(_view_mean(xr, grp), C, C, b, D, H, W, out=out)
+
+
+def _input_products(Vx, U, n, geo, Cout):
+    """Point products Vx (x) U of the input halves of n scene-views (Vx [16][n D H/2 W/2][C]), made once and added by the inverse transforms of
+    the split steps (_wino_step). They take the form (8 or 16 planes) of the launch that adds them: the hidden-half point GEMM of one step over
+    the b scenes of geo = (b, D, H, W), K = C."""
+    b, D, H, W = geo
+    C = Vx.shape[-1]
+    R = b * D * (H // 2) * (W // 2)
+    return co.wino_gemm(Vx, C, None, 0, U, None, n, D, H // 2, W // 2, Cout, half=co.wino_half_applies(R, Cout, C))
+
+
+def _h0_wino(p, xr, grp, V, Mm, t0, h):
+    """h = fusion_conv(mean of the views grp of xr [b,t,D,H,W,C]): two Winograd convolutions with the folded BatchNorm + LeakyReLU tails
+    (scratch V, Mm, t0)."""
+    b, t, D, H, W, C = xr.shape
+    _wino_view_mean(xr, grp, V)
+    Mp = co.wino_gemm(V, C, None, 0, p["fc0_U"], Mm, b, D, H // 2, W // 2, C)
+    co.wino_output(Mp, p["fc0_b"], *p["bn1"], 0.01, None, None, None, t0, None, None, b, D, H, W, C, C, co.EPI_AFFINE_ACT)
+    co.wino_input(t0, C, C, b, D, H, W, out=V)
+    Mp = co.wino_gemm(V, C, None, 0, p["fc3_U"], Mm, b, D, H // 2, W // 2, C)
+    co.wino_output(Mp, p["fc3_b"], *p["bn4"], 0.01, None, None, None, h, None, None, b, D, H, W, C, C, co.EPI_AFFINE_ACT)
+
+
+def _h0_direct(p, xr, grp, t0, h):
+    """h = fusion_conv(mean of the views grp of xr [b,t,D,H,W,C]): two fused conv + BatchNorm + LeakyReLU launches of the implicit-GEMM kernel."""
+    b, t, D, H, W, C = xr.shape
+    grid, taps = (b, D, H, W), co.TAPS_3x3x3
+    co.conv_igemm(_view_mean(xr, grp), C, C, None, 0, 0, p["fc0_w"], p["fc0_b"], *p["bn1"], 0.01, None, None, None, t0, None, grid, grid[1:], C, C,
+                  taps, epilogue=co.EPI_AFFINE_ACT)
+    co.conv_igemm(t0, C, C, None, 0, 0, p["fc3_w"], p["fc3_b"], *p["bn4"], 0.01, None, None, None, h, None, grid, grid[1:], C, C, taps,
+                  epilogue=co.EPI_AFFINE_ACT)
+
+
+def _wino_step(geo, x, view, views, wg, wo, V, Mm, h, z, hr, hn, out=None, r=None, cand=None):
+    """One ConvGRU step on the Winograd launches over geo = (b, D, H, W): transform h, point GEMMs, inverse transform fused with the gate tail
+    (z, hr = h r; r into `r`); transform hr, point GEMMs, inverse transform fused with tanh / lerp (hn; tanh(c) into `cand`, the fusion_norm
+    folded output into `out`). (Fusing each inverse transform with the next input transform through LDS was built and measured slower -
+    tools/experiments/wino_output_input_kernel.hip.) Two forms:
+      full   x = V_x, the transforms of `views` views per scene: point GEMMs over [V_x of view `view` | V_h], K = 6C, full weights
+      split  x = (MXg, MXc), the input-half products of `views` views per scene (_input_products): point GEMMs over V_h alone, K = 3C,
+             hidden-half weights; the inverse transforms add view `view`'s products
+    wg = (U, bias), wo = (U, bias, scale, shift). V: the buffer of both transforms, or None for a new one each (returned: the training node
+    keeps them for the weight gradient). Mm: the point-product scratch (_step_scratch)."""
+    b, D, H, W = geo
+    C = h.shape[-1]
+    split = isinstance(x, tuple)
+
+    def conv(src, U, Cout, i):
+        Vs = co.wino_input(src, C, C, b, D, H, W, out=V)
+        if split:
+            return Vs, co.wino_gemm(Vs, C, None, 0, U, Mm, b, D, H // 2, W // 2, Cout), dict(Mm2=x[i], view=view, views=views)
+        return Vs, co.wino_gemm(x, C, Vs, C, U, Mm, b, D, H // 2, W // 2, Cout, view=view, views=views), {}
+
+    Vh, G, add = conv(h, wg[0], 2 * C, 0)
+    co.wino_output(G, wg[1], None, None, 1.0, None, h, None, z, hr, r, *geo, 2 * C, C, co.EPI_GRU_GATES, **add)
+    Vhr, S, add = conv(hr, wo[0], C, 1)
+    co.wino_output(S, *wo[1:], 1.0, None, h, z, hn, out, cand, *geo, C, C, co.EPI_GRU_OUT, **add)
+    return Vh, Vhr
+
+
+def _direct_step(grid, x, wg, wo, h, z, hr, hn, out=None, r=None, cand=None, bs=0):
+    """One ConvGRU step on the direct implicit-GEMM kernel (grid = (b, D, H, W)), the same GRU tails and stores as _wino_step in its epilogues:
+    gates (cat / conv / sigmoid / h r), then state (cat / conv / tanh / lerp). Two forms:
+      full   x = x_t, the view's rows with batch stride bs rows: K = 6C over [x_t | h], full packed weights
+      split  x = (gx, cx), the view's input-half products: K = 3C over h, hidden-half weights, gx / cx added as the residual
+    wg = (w, bias), wo = (w, bias, scale, shift)."""
+    C = h.shape[-1]
+    ig, taps = grid[1:], co.TAPS_3x3x3
+    split = isinstance(x, tuple)
+    operands = lambda src, i: ((src, C, C, None, 0, 0), x[i]) if split else ((x, C, C, src, C, C), None)     # (in1, C1, ld1, in2, C2, ld2), residual
+    ops, res = operands(h, 0)
+    co.conv_igemm(*ops, *wg, None, None, 1.0, res, h, None, z, hr, grid, ig, 2 * C, C, taps, epilogue=co.EPI_GRU_GATES, bs1=bs, out3=r)
+    ops, res = operands(hr, 1)
+    co.conv_igemm(*ops, *wo, 1.0, res, h, z, hn, out, grid, ig, C, C, taps, epilogue=co.EPI_GRU_OUT, bs1=bs, out3=cand)
+
+
+def _fuse_eval(gru, xr, groups, wino, split, h0=None, keep=None, const0=None):
+    """The forward of the eval-weight fusions (ConvGRU_3D.fuse_hip, fuse_groups_hip, _FuseFrozen) over xr [b,t,D,H,W,C] rows, on the Winograd
+    launches (wino: the caller has checked wino_fits) or the direct implicit-GEMM kernel. Per group of views: h = fusion_conv(mean of its views)
+    with folded BatchNorm (or the caller's h0 [b,C,D,H,W]), then one full or split step per view, fusion_norm folded into the last one. split:
+    the input halves of both GRU convolutions are made once per view for all groups. Inference ping-pongs h between two buffers and shares the
+    transform / point-product scratch; keep (a list): every step gets new buffers, and keep receives t0 and each step's (h, z, r, tanh(c)) for
+    the backward pass. const0 (Winograd, see ConvGRU_3D.fuse_frozen_hip): step 0 runs split on the cached input-half products of view 0.
+    Returns one [b,C,D,H,W] volume per group."""
+    b, t, D, H, W, C = xr.shape
+    dev, M, vol = xr.device, b * D * H * W, D * H * W
+    geo = (b, D, H, W)
+    new = lambda c=C: torch.empty(M, c, dtype=torch.float32, device=dev)
+    p = gru._packed_halves(wino) if (split or const0 is not None) else gru._packed_wino() if wino else gru._packed()
+    wk = "_U" if wino else "_w"
+    weights = lambda half: ((p["gate" + wk + half], p["gate_b"]), (p["out" + wk + half], p["out_b"], *p["norm"]))
+    wg, wo = weights("h" if split else "")
+    # X, the input side of the steps: V_x (Winograd, full), the products (MXg, MXc) (Winograd, split) or per view (gx, cx) (direct, split)
+    if wino:
+        R = b * D * (H // 2) * (W // 2)
+        X = co.wino_input(xr, C, C, b * t, D, H, W)                       # [16][b t D Ht Wt][C]: all views of all scenes, one launch
+        if split:
+            X = (_input_products(X, p["gate_Ux"], b * t, geo, 2 * C), _input_products(X, p["out_Ux"], b * t, geo, C))
+        V = torch.empty(16, R, C, dtype=torch.float32, device=dev)
+        Mm = _step_scratch(R, C, dev)
+    elif split:                                                            # the input halves once per view (no bias: added with the hidden half)
+        X = {}
+        for ti in sorted({ti for g in groups for ti in g}):
+            X[ti] = (new(2 * C), new())
+            for k, dst in zip(("gate_wx", "out_wx"), X[ti]):
+                co.conv_igemm(xr[:, ti], C, C, None, 0, 0, p[k], None, None, None, 1.0, None, None, None, dst, None, geo, geo[1:], dst.shape[1],
+                              dst.shape[1], co.TAPS_3x3x3, epilogue=co.EPI_BIAS, bs1=t * vol)
+    outs = []
+    for grp in groups:
+        grp = list(grp)
+        t0, h, out = new(), new(), new()
+        if h0 is not None:
+            h.copy_(h0.permute(0, 2, 3, 4, 1).reshape(M, C))
+        elif wino:
+            _h0_wino(p, xr, grp, V, Mm, t0, h)
+        else:
+            _h0_direct(p, xr, grp, t0, h)
+        if keep is not None:
+            keep.append(t0)
+        if const0 is not None and "MXg0" not in const0:
+            # view 0 holds the SAME values in every call (the un-warped reference view of frozen features, kubric_eval.py:456-470): the point
+            # products of its input halves are made once and added inside the inverse transforms of step 0. Same arithmetic up to the order of
+            # the fp32 additions. One made under another plan (force_plan) has another form and is refused by the inverse transform.
+            Vx0 = co.wino_input(xr[:, 0], C, C, b, D, H, W, bs=t * vol)
+            const0["MXg0"], const0["MXc0"] = _input_products(Vx0, p["gate_Ux"], b, geo, 2 * C), _input_products(Vx0, p["out_Ux"], b, geo, C)
+        z, hr, hn, r, cand = new(), new(), t0, None, None                   # t0 is free once h0 is made
+        for k, ti in enumerate(grp):
+            if keep is not None:
+                z, hr, r, hn, cand = new(), new(), new(), new(), new()
+            last = out if k == len(grp) - 1 else None
+            if not wino:
+                _direct_step(geo, X[ti] if split else xr[:, ti], wg, wo, h, z, hr, hn, last, r, cand, bs=0 if split else t * vol)
+            elif const0 is not None and k == 0:
+                _wino_step(geo, (const0["MXg0"], const0["MXc0"]), 0, 1, *weights("h"), V, Mm, h, z, hr, hn, last, r, cand)
+            else:
+                _wino_step(geo, X, ti, t, wg, wo, V, Mm, h, z, hr, hn, last, r, cand)
+            if keep is not None:
+                keep += [h, z, r, cand]
+            h, hn = hn, h
+        outs.append(out.reshape(b, D, H, W, C).permute(0, 4, 1, 2, 3))
+    return outs
+
+
+def _eval_chunks(x, fuse):
+    """Inference over x [b,t,C,D,H,W]: fuse(xr, wino, i, j) on the rows xr [j-i,t,D,H,W,C] of scenes [i, j). Scenes are independent: the Winograd
+    launches run in chunks of wino_scene_chunk scenes (the kernel's 32-bit buffer offsets), the direct kernel (odd H / W, winograd(False)) over
+    the whole batch. Returns fuse's per-group volumes concatenated over the chunks."""
+    b, t, C, D, H, W = x.shape
+    xr = x.permute(0, 1, 3, 4, 5, 2)
+    xr = xr if xr.is_contiguous() else xr.contiguous()
+    nb = co.wino_scene_chunk(b, D, H, W, C, views=t) if co.wino_enabled() else 0
+    parts = [fuse(xr[i:i + (nb or b)], nb > 0, i, i + (nb or b)) for i in range(0, b, nb or b)]
+    return parts[0] if len(parts) == 1 else [torch.cat(o, dim=0) for o in zip(*parts)]
+
+
 class _FuseFrozen(torch.autograd.Function):
     """Encoder3D.fuse for frozen weights (eval mode, gradients only w.r.t. the input views): forward = ConvGRU_3D.fuse_hip - the fused
     conv + BN + LeakyReLU launches of fusion_conv and TWO launches per view (gates: cat / conv / sigmoid / h*r; state: cat / conv /
@@ -401,71 +579,12 @@ class _FuseFrozen(torch.autograd.Function):
         b, t, C, D, H, W = x.shape
         xr = x.permute(0, 1, 3, 4, 5, 2)
         xr = xr if xr.is_contiguous() else xr.contiguous()
-        dev, M, vol = x.device, b * D * H * W, D * H * W
-        grid, ig, taps = (b, D, H, W), (D, H, W), co.TAPS_3x3x3
-        new = lambda c=C: torch.empty(M, c, dtype=torch.float32, device=dev)
-        t0, h = new(), new()
-        wino = co.wino_enabled() and co.wino_fits(b, D, H, W, C, views=t)
-        steps, out = [], new()
-        if wino:                                                             # ConvGRU_3D._fuse_wino with the reset gate / candidate kept
-            p = gru._packed_wino()
-            Ht, Wt = H // 2, W // 2
-            R = b * D * Ht * Wt
-            Vx = co.wino_input(xr, C, C, b * t, D, H, W)
-            Vh = torch.empty(16, R, C, dtype=torch.float32, device=dev)
-            Mm = _step_scratch(R, C, dev)
-            gru._wino_h0(p, xr, grid, Vh, Mm, t0, h, nsum=t, sum_stride=vol, bs=t * vol)
-            # const0 (a dict the caller keeps across calls; with skip_dx0): view 0 holds the SAME values in every call (the un-warped reference
-            # view of frozen features, kubric_eval.py:456-470) - the point products of its input halves, V_x0 (x) U_x of both GRU convolutions,
-            # are made once and added inside the inverse transforms of step 0, whose GEMMs then contract the hidden-state half only (K = 3 C
-            # instead of 6 C). Same arithmetic up to the order of the fp32 additions (the halves meet before A^T . A instead of inside the K loop).
-            # The products keep the form of step 0's hidden-half launches (same rows and columns); one made under another plan (force_plan) is
-            # refused by the inverse transform that would add it.
-            hoist = const0 is not None and skip_dx0
-            if hoist:
-                ps = gru._packed_wino_halves()
-                if "MXg0" not in const0:
-                    Vx0 = co.wino_input(xr[:, 0], C, C, b, D, H, W, bs=t * vol)
-                    const0["MXg0"] = co.wino_gemm(Vx0, C, None, 0, ps["gate_Ux"], None, b, D, Ht, Wt, 2 * C)
-                    const0["MXc0"] = co.wino_gemm(Vx0, C, None, 0, ps["out_Ux"], None, b, D, Ht, Wt, C)
-            for ti in range(t):
-                z, hr, r, hn, cand = new(), new(), new(), new(), new()
-                first = hoist and ti == 0
-                co.wino_input(h, C, C, b, D, H, W, out=Vh)
-                if first:
-                    G = co.wino_gemm(Vh, C, None, 0, ps["gate_Uh"], Mm, b, D, Ht, Wt, 2 * C)
-                else:
-                    G = co.wino_gemm(Vx, C, Vh, C, p["gate_U"], Mm, b, D, Ht, Wt, 2 * C, view=ti, views=t)
-                co.wino_output(G, p["gate_b"], None, None, 1.0, None, h, None, z, hr, r, *grid, 2 * C, C, co.EPI_GRU_GATES,
-                               Mm2=const0["MXg0"] if first else None)
-                co.wino_input(hr, C, C, b, D, H, W, out=Vh)
-                if first:
-                    S = co.wino_gemm(Vh, C, None, 0, ps["out_Uh"], Mm, b, D, Ht, Wt, C)
-                else:
-                    S = co.wino_gemm(Vx, C, Vh, C, p["out_U"], Mm, b, D, Ht, Wt, C, view=ti, views=t)
-                co.wino_output(S, p["out_b"], p["norm"][0], p["norm"][1], 1.0, None, h, z, hn, out if ti == t - 1 else None, cand, *grid, C, C,
-                               co.EPI_GRU_OUT, Mm2=const0["MXc0"] if first else None)
-                steps.append((h, z, r, cand))
-                h = hn
-        else:
-            p = gru._packed()
-            mean = xr.mean(dim=1).reshape(M, C)
-            co.conv_igemm(mean, C, C, None, 0, 0, p["fc0_w"], p["fc0_b"], p["bn1"][0], p["bn1"][1], 0.01, None, None, None, t0, None, grid, ig, C, C, taps,
-                          epilogue=co.EPI_AFFINE_ACT)
-            co.conv_igemm(t0, C, C, None, 0, 0, p["fc3_w"], p["fc3_b"], p["bn4"][0], p["bn4"][1], 0.01, None, None, None, h, None, grid, ig, C, C, taps,
-                          epilogue=co.EPI_AFFINE_ACT)
-            for ti in range(t):
-                xt = xr[:, ti]
-                z, hr, r, hn, cand = new(), new(), new(), new(), new()
-                co.conv_igemm(xt, C, C, h, C, C, p["gate_w"], p["gate_b"], None, None, 1.0, None, h, None, z, hr, grid, ig, 2 * C, C, taps,
-                              epilogue=co.EPI_GRU_GATES, bs1=t * vol, out3=r)
-                co.conv_igemm(xt, C, C, hr, C, C, p["out_w"], p["out_b"], p["norm"][0], p["norm"][1], 1.0, None, h, z, hn, out if ti == t - 1 else None,
-                              grid, ig, C, C, taps, epilogue=co.EPI_GRU_OUT, bs1=t * vol, out3=cand)
-                steps.append((h, z, r, cand))
-                h = hn
+        wino = co.wino_enabled() and co.wino_fits(b, D, H, W, C, views=t)        # the whole batch in one pass: no scene chunks
+        saved = []
+        out = _fuse_eval(gru, xr, [range(t)], wino, False, keep=saved, const0=const0 if (wino and skip_dx0) else None)[0]
         ctx.gru, ctx.shape = gru, (b, t, C, D, H, W)
-        ctx.save_for_backward(t0, *[v for st in steps for v in st])          # per step (h, z, r, cand); steps[0][0] is h0
-        return out.reshape(b, D, H, W, C).permute(0, 4, 1, 2, 3)
+        ctx.save_for_backward(*saved)                                        # t0, then per step (h, z, r, cand); the first h is h0
+        return out
 
     @staticmethod
     @_lib.on_tensor_device
@@ -572,33 +691,25 @@ class _FuseGroupsTrain(torch.autograd.Function):
         b, t, C, D, H, W = x.shape
         xr = x.detach().permute(0, 1, 3, 4, 5, 2)
         xr = xr if xr.is_contiguous() else xr.contiguous()
-        dev, M, vol, Ht, Wt = x.device, b * D * H * W, D * H * W, H // 2, W // 2
+        dev, M, Ht, Wt = x.device, b * D * H * W, H // 2, W // 2
         R1 = D * Ht * Wt
         R = b * R1
         geo = (b, D, H, W)
         fc, norm = gru.fusion_conv, gru.fusion_norm
         new = lambda c=C: torch.empty(M, c, dtype=torch.float32, device=dev)
-        newV = lambda rows, c: torch.empty(16, rows, c, dtype=torch.float32, device=dev)
         pk = lambda w: co.pack_conv3d_weight(w)                              # [27][Cout][Cin]
         wpg, wpo = pk(Wg), pk(Wo)
         packs = {"gx": wpg[:, :, :C].contiguous(), "gh": wpg[:, :, C:].contiguous(), "ox": wpo[:, :, :C].contiguous(), "oh": wpo[:, :, C:].contiguous(),
                  "f0": pk(w0), "f3": pk(w3)}
         U = {k: co.wino_pack_packed(v) for k, v in packs.items()}
         Vx = co.wino_input(xr, C, C, b * t, D, H, W)                         # [16][b t R1][C]: all views of all scenes
-        # in the form (8 / 16 planes) of the per-step launches over R rows that add them as second addends
-        MXg = co.wino_gemm(Vx, C, None, 0, U["gx"], None, b * t, D, Ht, Wt, 2 * C, half=co.wino_half_applies(R, 2 * C, C))
-        MXc = co.wino_gemm(Vx, C, None, 0, U["ox"], None, b * t, D, Ht, Wt, C, half=co.wino_half_applies(R, C, C))
+        MX = (_input_products(Vx, U["gx"], b * t, geo, 2 * C), _input_products(Vx, U["ox"], b * t, geo, C))
         Mm = _step_scratch(R, C, dev)
         bnargs = lambda m: bn_module_args(m)
         outs, saved_groups = [], []
         for grp in groups:
             grp = list(grp)
-            run = grp == list(range(grp[0], grp[0] + len(grp)))
-            Vm = newV(R, C)
-            if run:                                                          # the view mean is taken inside the input transform
-                co.wino_input(xr[:, grp[0]:], C, C, b, D, H, W, bs=t * vol, out=Vm, nsum=len(grp), sum_stride=vol)
-            else:
-                co.wino_input(torch.stack([xr[:, ti] for ti in grp], dim=1).mean(dim=1).reshape(M, C), C, C, b, D, H, W, out=Vm)
+            Vm = _wino_view_mean(xr, grp, torch.empty(16, R, C, dtype=torch.float32, device=dev))
             a0 = new()
             Mp = co.wino_gemm(Vm, C, None, 0, U["f0"], Mm, b, D, Ht, Wt, C)
             co.wino_output(Mp, b0, None, None, 1.0, None, None, None, a0, None, None, *geo, C, C, co.EPI_BIAS)
@@ -612,14 +723,8 @@ class _FuseGroupsTrain(torch.autograd.Function):
             h, sv4 = bn_rows_fwd(a1, g4, be4, rm, rv, mom, eps, 0.01, None, nbt, group)
             steps = []
             for ti in grp:
-                Vh = co.wino_input(h, C, C, b, D, H, W)
-                G = co.wino_gemm(Vh, C, None, 0, U["gh"], Mm, b, D, Ht, Wt, 2 * C)
-                z, hr, r = new(), new(), new()
-                co.wino_output(G, bg, None, None, 1.0, None, h, None, z, hr, r, *geo, 2 * C, C, co.EPI_GRU_GATES, Mm2=MXg, view=ti, views=t)
-                Vhr = co.wino_input(hr, C, C, b, D, H, W)
-                S = co.wino_gemm(Vhr, C, None, 0, U["oh"], Mm, b, D, Ht, Wt, C)
-                hn, cand = new(), new()
-                co.wino_output(S, bo, None, None, 1.0, None, h, z, hn, None, cand, *geo, C, C, co.EPI_GRU_OUT, Mm2=MXc, view=ti, views=t)
+                z, hr, r, hn, cand = new(), new(), new(), new(), new()
+                Vh, Vhr = _wino_step(geo, MX, ti, t, (U["gh"], bg), (U["oh"], bo, None, None), None, Mm, h, z, hr, hn, r=r, cand=cand)
                 steps.append((ti, h, z, r, cand, Vh, Vhr))
                 h = hn
             rm, rv, mom, eps, nbt, group = bnargs(norm)
@@ -717,7 +822,7 @@ class _FuseGroupsTrain(torch.autograd.Function):
         co.wino_output(Mx["gx"], None, None, None, 1.0, None, None, None, dx, None, None, nbt_, D, H, W, C, C, co.EPI_BIAS, Mm2=Mx["ox"], view=0, views=1)
         for grp, dmean in dmeans:                                            # d mean / d x_ti = 1 / |group|
             dm = dmean.reshape(b, 1, D, H, W, C)
-            if grp == list(range(grp[0], grp[0] + len(grp))):
+            if view_run(grp):
                 dx[:, grp[0]:grp[0] + len(grp)].add_(dm, alpha=1.0 / len(grp))
             else:
                 for ti in grp:
@@ -833,44 +938,14 @@ class ConvGRU_3D(co.PackedModule):
         return _FuseFrozen.apply(x, self, bool(skip_dx0), const0)
 
     def fuse_hip(self, x, h0=None):
-        """Encoder3D.fuse on the MI355X: h0 = fusion_conv(mean_t x) as two fused conv+BN+LeakyReLU GEMMs (or the caller's h0
-        [b,C,D,H,W]), then per view two implicit-GEMM launches (gates: cat/conv/sigmoid/h*r fused; state: cat/conv/tanh/lerp fused,
-        the final fusion_norm folded into the last one). x [b,t,C,D,H,W] -> [b,C,D,H,W] (channels-last memory)."""
+        """Encoder3D.fuse on the MI355X: h0 = fusion_conv(mean_t x) as two fused conv+BN+LeakyReLU convolutions (or the caller's h0
+        [b,C,D,H,W]), then per view one full step (gates: cat/conv/sigmoid/h*r fused; state: cat/conv/tanh/lerp fused, the final
+        fusion_norm folded into the last one), on Winograd F(2x2, 3x3) x 3 depth taps where it applies (2.25x fewer MFMA FLOPs).
+        x [b,t,C,D,H,W] -> [b,C,D,H,W] (channels-last memory)."""
         assert self.n_layers == 1 and self.input_size == self.hidden_size
         require_hip_input("ConvGRU_3D.fuse_hip", x, x.shape[2])
-        b, t, C, D, H, W = x.shape
-        xr = x.permute(0, 1, 3, 4, 5, 2)                          # [b,t,D,H,W,C] rows view
-        if not xr.is_contiguous():
-            xr = xr.contiguous()
-        p = self._packed()
-        dev, M, vol = x.device, b * D * H * W, D * H * W
-        nb = co.wino_scene_chunk(b, D, H, W, C, views=t) if co.wino_enabled() else 0
-        if nb:                                                        # scenes are independent: batches beyond the buffer range run in scene chunks
-            if nb >= b:
-                return self._fuse_wino(xr, h0)
-            return torch.cat([self._fuse_wino(xr[i:i + nb], None if h0 is None else h0[i:i + nb]) for i in range(0, b, nb)], dim=0)
-        grid, ig = (b, D, H, W), (D, H, W)
-        new = lambda: torch.empty(M, C, dtype=torch.float32, device=dev)
-        taps = co.TAPS_3x3x3
-        t0, h = new(), new()
-        if h0 is None:
-            mean = xr.mean(dim=1).reshape(M, C)
-            co.conv_igemm(mean, C, C, None, 0, 0, p["fc0_w"], p["fc0_b"], p["bn1"][0], p["bn1"][1], 0.01, None, None, None,
-                          t0, None, grid, ig, C, C, taps, epilogue=co.EPI_AFFINE_ACT)
-            co.conv_igemm(t0, C, C, None, 0, 0, p["fc3_w"], p["fc3_b"], p["bn4"][0], p["bn4"][1], 0.01, None, None, None,
-                          h, None, grid, ig, C, C, taps, epilogue=co.EPI_AFFINE_ACT)
-        else:
-            h.copy_(h0.permute(0, 2, 3, 4, 1).reshape(M, C))
-        z, hr, h2, out = new(), new(), t0, new()
-        for ti in range(t):
-            xt = xr[:, ti]                                        # base pointer of view ti; batch stride t*vol rows
-            co.conv_igemm(xt, C, C, h, C, C, p["gate_w"], p["gate_b"], None, None, 1.0, None, h, None, z, hr,
-                          grid, ig, 2 * C, C, taps, epilogue=co.EPI_GRU_GATES, bs1=t * vol)
-            last = ti == t - 1
-            co.conv_igemm(xt, C, C, hr, C, C, p["out_w"], p["out_b"], p["norm"][0], p["norm"][1], 1.0, None, h, z,
-                          h2, out if last else None, grid, ig, C, C, taps, epilogue=co.EPI_GRU_OUT, bs1=t * vol)
-            h, h2 = h2, h
-        return out.reshape(b, D, H, W, C).permute(0, 4, 1, 2, 3)
+        t = x.shape[1]
+        return _eval_chunks(x, lambda xr, wino, i, j: _fuse_eval(self, xr, [range(t)], wino, False, h0=None if h0 is None else h0[i:j]))[0]
 
     def _packed_wino(self):
         """Winograd-domain weights U = G w G^T [16][3][Cout][Cin] of the four 3x3x3 convolutions (convops.wino_pack_weight)."""
@@ -881,172 +956,30 @@ class ConvGRU_3D(co.PackedModule):
                       "fc0_U": co.wino_pack_weight(fc[0].weight), "fc3_U": co.wino_pack_weight(fc[3].weight)})
         return p
 
-    def _packed_wino_halves(self):
-        """The input (x) and hidden-state (h) halves of the two GRU convolutions as separate Winograd-domain weights [16][3][Cout][C]
-        (the frozen-weight refinement forward with a hoisted reference view, _FuseFrozen)."""
-        p = self._packed_wino()
-        if "gate_Ux" not in p:
+    def _packed_halves(self, wino):
+        """The weights of the split steps: the input (x) and hidden-state (h) halves along Cin of both GRU convolutions, W = (W_x | W_h),
+        sliced from the packed weights [27][Cout][C] (gate_wx, gate_wh, out_wx, out_wh) or, wino, from the Winograd-domain weights
+        [16][3][Cout][C] (gate_Ux, gate_Uh, out_Ux, out_Uh)."""
+        p = self._packed_wino() if wino else self._packed()
+        wk = "_U" if wino else "_w"
+        if "gate" + wk + "x" not in p:
             C = self.hidden_size
-            cell = self.cells[0]
-            for k, w in (("gate", cell.conv_gate.weight), ("out", cell.out_gate.weight)):
-                wp = co.pack_conv3d_weight(w)                                # [27][Cout][2 C]: (x | h) input channels
-                p[k + "_Ux"] = co.wino_pack_packed(wp[:, :, :C].contiguous())
-                p[k + "_Uh"] = co.wino_pack_packed(wp[:, :, C:].contiguous())
+            for k in ("gate", "out"):
+                w = p[k + wk]
+                p[k + wk + "x"], p[k + wk + "h"] = w[..., :C].contiguous(), w[..., C:].contiguous()
         return p
-
-    @staticmethod
-    def _wino_h0(p, src, geo, Vh, Mm, t0, h, nsum=1, sum_stride=0, bs=0):
-        """h = fusion_conv(mean of the nsum view tensors starting at `src`, sum_stride rows apart): two Winograd convolutions with the folded
-        BatchNorm + LeakyReLU tail (scratch Vh / Mm / t0); the view mean of models/encoder.py:62 is taken inside the first input transform."""
-        b, D, H, W = geo
-        C = h.shape[-1]
-        co.wino_input(src, C, C, b, D, H, W, bs=bs, out=Vh, nsum=nsum, sum_stride=sum_stride)
-        Mp = co.wino_gemm(Vh, C, None, 0, p["fc0_U"], Mm, b, D, H // 2, W // 2, C)
-        co.wino_output(Mp, p["fc0_b"], p["bn1"][0], p["bn1"][1], 0.01, None, None, None, t0, None, None, b, D, H, W, C, C, co.EPI_AFFINE_ACT)
-        co.wino_input(t0, C, C, b, D, H, W, out=Vh)
-        Mp = co.wino_gemm(Vh, C, None, 0, p["fc3_U"], Mm, b, D, H // 2, W // 2, C)
-        co.wino_output(Mp, p["fc3_b"], p["bn4"][0], p["bn4"][1], 0.01, None, None, None, h, None, None, b, D, H, W, C, C, co.EPI_AFFINE_ACT)
-
-    def _fuse_wino(self, xr, h0=None):
-        """fuse_hip with every 3x3x3 convolution as Winograd F(2x2, 3x3) x 3 depth taps (csrc/winograd.hip): 2.25x fewer MFMA FLOPs.
-        The views are transformed once, by one launch; the view mean is taken inside the input transform that feeds fusion_conv; per GRU step:
-        transform h, 16 point GEMMs over [V_x | V_h] (K = 3 x 256), inverse transform fused with the gate epilogue; transform h*r, point GEMMs,
-        inverse transform fused with the state update. (Fusing each inverse transform with the next input transform through LDS was built and
-        measured slower - tools/experiments/wino_output_input_kernel.hip.)"""
-        b, t, D, H, W, C = xr.shape
-        p = self._packed_wino()
-        dev, M, Ht, Wt = xr.device, b * D * H * W, H // 2, W // 2
-        R = b * D * Ht * Wt
-        new = lambda c=C: torch.empty(M, c, dtype=torch.float32, device=dev)
-        geo = (b, D, H, W)
-        Vx = co.wino_input(xr, C, C, b * t, D, H, W)                       # [16][b t D Ht Wt][C]: all views of all scenes
-        Vh = torch.empty(16, R, C, dtype=torch.float32, device=dev)
-        Mm = _step_scratch(R, C, dev)
-        t0, h = new(), new()
-        vol = D * H * W
-        if h0 is None:
-            self._wino_h0(p, xr, geo, Vh, Mm, t0, h, nsum=t, sum_stride=vol, bs=t * vol)
-        else:
-            h.copy_(h0.permute(0, 2, 3, 4, 1).reshape(M, C))
-        z, hr, h2, out = new(), new(), t0, new()
-        for ti in range(t):
-            co.wino_input(h, C, C, b, D, H, W, out=Vh)
-            G = co.wino_gemm(Vx, C, Vh, C, p["gate_U"], Mm, b, D, Ht, Wt, 2 * C, view=ti, views=t)
-            co.wino_output(G, p["gate_b"], None, None, 1.0, None, h, None, z, hr, None, *geo, 2 * C, C, co.EPI_GRU_GATES)
-            co.wino_input(hr, C, C, b, D, H, W, out=Vh)
-            S = co.wino_gemm(Vx, C, Vh, C, p["out_U"], Mm, b, D, Ht, Wt, C, view=ti, views=t)
-            last = ti == t - 1
-            co.wino_output(S, p["out_b"], p["norm"][0], p["norm"][1], 1.0, None, h, z, h2, out if last else None, None, *geo, C, C, co.EPI_GRU_OUT)
-            h, h2 = h2, h
-        return out.reshape(b, D, H, W, C).permute(0, 4, 1, 2, 3)
-
-    def _fuse_groups_wino(self, xr, groups):
-        """fuse_groups_hip in the Winograd domain: the views are transformed once and the point products of the INPUT halves of both GRU
-        convolutions are computed once, for all views in one launch each (Mm_x = V_x (x) U_x); every (group, view) step then runs the
-        hidden-state halves only (K = 3 x 128) and the inverse transform adds the view's Mm_x before the fused GRU tail."""
-        b, t, D, H, W, C = xr.shape
-        p = self._packed_wino()
-        if "gate_Ux" not in p:                                         # U = (U_x | U_h) along Cin
-            p.update({"gate_Ux": p["gate_U"][..., :C].contiguous(), "gate_Uh": p["gate_U"][..., C:].contiguous(),
-                      "out_Ux": p["out_U"][..., :C].contiguous(), "out_Uh": p["out_U"][..., C:].contiguous()})
-        dev, M, Ht, Wt = xr.device, b * D * H * W, H // 2, W // 2
-        R1 = D * Ht * Wt
-        R = b * R1
-        new = lambda c=C: torch.empty(M, c, dtype=torch.float32, device=dev)
-        geo = (b, D, H, W)
-        Vx = co.wino_input(xr, C, C, b * t, D, H, W)
-        # 8-plane form (row stage of the inverse transform in the GEMM epilogue, convops.wino_half_applies) for the launches on the 64 x 128 tile: the
-        # shared input-half products and the per-step hidden-half products are then row-combined separately and added in the column-stage kernel.
-        # Each all-view launch takes the form of the per-step launches (R rows, the same columns) that add its products.
-        MXg = co.wino_gemm(Vx, C, None, 0, p["gate_Ux"], None, b * t, D, Ht, Wt, 2 * C, half=co.wino_half_applies(R, 2 * C, C))
-        MXc = co.wino_gemm(Vx, C, None, 0, p["out_Ux"], None, b * t, D, Ht, Wt, C, half=co.wino_half_applies(R, C, C))
-        Vh = torch.empty(16, R, C, dtype=torch.float32, device=dev)
-        Mm = _step_scratch(R, C, dev)
-        outs = []
-        for grp in groups:
-            grp = list(grp)
-            run = grp == list(range(grp[0], grp[0] + len(grp)))       # a run of views: the mean is taken inside the input transform
-            mean = None if run else torch.stack([xr[:, ti] for ti in grp], dim=1).mean(dim=1).reshape(M, C)
-            t0, h = new(), new()
-            if run:
-                self._wino_h0(p, xr[:, grp[0]:], geo, Vh, Mm, t0, h, nsum=len(grp), sum_stride=D * H * W, bs=t * D * H * W)
-            else:
-                self._wino_h0(p, mean, geo, Vh, Mm, t0, h)
-            z, hr, h2, out = new(), new(), t0, new()
-            for k, ti in enumerate(grp):
-                co.wino_input(h, C, C, b, D, H, W, out=Vh)
-                G = co.wino_gemm(Vh, C, None, 0, p["gate_Uh"], Mm, b, D, Ht, Wt, 2 * C)
-                co.wino_output(G, p["gate_b"], None, None, 1.0, None, h, None, z, hr, None, *geo, 2 * C, C, co.EPI_GRU_GATES, Mm2=MXg, view=ti, views=t)
-                co.wino_input(hr, C, C, b, D, H, W, out=Vh)
-                S = co.wino_gemm(Vh, C, None, 0, p["out_Uh"], Mm, b, D, Ht, Wt, C)
-                last = k == len(grp) - 1
-                co.wino_output(S, p["out_b"], p["norm"][0], p["norm"][1], 1.0, None, h, z, h2, out if last else None, None, *geo, C, C,
-                               co.EPI_GRU_OUT, Mm2=MXc, view=ti, views=t)
-                h, h2 = h2, h
-            outs.append(out.reshape(b, D, H, W, C).permute(0, 4, 1, 2, 3))
-        return outs
 
     def fuse_groups_hip(self, x, groups):
         """Several fusions over subsets of the SAME views in inference (FORGE_poseEstimator3D fuses views (0,1,2), (3,4) and (0..4) of
         the same rotated features, models/model_single_pose_estimator.py:108-120): conv([x, h], W) = conv(x, W_x) + conv(h, W_h), so the
-        input halves of both GRU convolutions are computed ONCE per view (two launches per view) and every (group, view) step then runs
-        the hidden-state halves only, the input half entering the fused GRU epilogues as a residual - 25 % fewer GRU FLOPs for the
-        three fusions. Same arithmetic as fuse_hip up to the order of the fp32 additions. Returns one fused volume per group."""
+        input halves of both GRU convolutions are computed ONCE per view and every (group, view) step then runs the hidden-state halves
+        only, the input half entering the fused GRU epilogues as a second addend / residual - 25 % fewer GRU FLOPs for the three fusions.
+        Same arithmetic as fuse_hip up to the order of the fp32 additions. Returns one fused volume per group."""
         assert self.n_layers == 1 and self.input_size == self.hidden_size
         require_hip_input("ConvGRU_3D.fuse_groups_hip", x, x.shape[2])
-        b, t, C, D, H, W = x.shape
-        xr = x.permute(0, 1, 3, 4, 5, 2)
-        xr = xr if xr.is_contiguous() else xr.contiguous()
-        nb = co.wino_scene_chunk(b, D, H, W, C, views=t) if co.wino_enabled() else 0
-        if nb:
-            if nb >= b:
-                return self._fuse_groups_wino(xr, groups)
-            parts = [self._fuse_groups_wino(xr[i:i + nb], groups) for i in range(0, b, nb)]
-            return [torch.cat([p_[g] for p_ in parts], dim=0) for g in range(len(groups))]
-        p = self._packed()
-        if "gate_wx" not in p:                                         # W = (W_x | W_h) along Cin
-            p.update({"gate_wx": p["gate_w"][:, :, :C].contiguous(), "gate_wh": p["gate_w"][:, :, C:].contiguous(),
-                      "out_wx": p["out_w"][:, :, :C].contiguous(), "out_wh": p["out_w"][:, :, C:].contiguous()})
-        dev, M, vol = x.device, b * D * H * W, D * H * W
-        grid, ig, taps = (b, D, H, W), (D, H, W), co.TAPS_3x3x3
-        new = lambda c=C: torch.empty(M, c, dtype=torch.float32, device=dev)
-        used = sorted({ti for g in groups for ti in g})
-        gx, cx = {}, {}
-        for ti in used:                                                # input halves, once per view (no bias: added with the hidden half)
-            gx[ti], cx[ti] = new(2 * C), new()
-            co.conv_igemm(xr[:, ti], C, C, None, 0, 0, p["gate_wx"], None, None, None, 1.0, None, None, None, gx[ti], None, grid, ig, 2 * C, 2 * C, taps,
-                          epilogue=co.EPI_BIAS, bs1=t * vol)
-            co.conv_igemm(xr[:, ti], C, C, None, 0, 0, p["out_wx"], None, None, None, 1.0, None, None, None, cx[ti], None, grid, ig, C, C, taps,
-                          epilogue=co.EPI_BIAS, bs1=t * vol)
-        outs = []
-        for grp in groups:
-            grp = list(grp)
-            if grp == list(range(grp[0], grp[0] + len(grp))):          # a run of views: a slice (no index tensor: capturable into a hipGraph)
-                mean = xr[:, grp[0]:grp[0] + len(grp)].mean(dim=1).reshape(M, C)
-            else:
-                mean = torch.stack([xr[:, ti] for ti in grp], dim=1).mean(dim=1).reshape(M, C)
-            t0, h = new(), new()
-            co.conv_igemm(mean, C, C, None, 0, 0, p["fc0_w"], p["fc0_b"], p["bn1"][0], p["bn1"][1], 0.01, None, None, None, t0, None, grid, ig, C, C, taps,
-                          epilogue=co.EPI_AFFINE_ACT)
-            co.conv_igemm(t0, C, C, None, 0, 0, p["fc3_w"], p["fc3_b"], p["bn4"][0], p["bn4"][1], 0.01, None, None, None, h, None, grid, ig, C, C, taps,
-                          epilogue=co.EPI_AFFINE_ACT)
-            z, hr, h2, out = new(), new(), t0, new()
-            for k, ti in enumerate(grp):
-                co.conv_igemm(h, C, C, None, 0, 0, p["gate_wh"], p["gate_b"], None, None, 1.0, gx[ti], h, None, z, hr, grid, ig, 2 * C, C, taps,
-                              epilogue=co.EPI_GRU_GATES)
-                last = k == len(grp) - 1
-                co.conv_igemm(hr, C, C, None, 0, 0, p["out_wh"], p["out_b"], p["norm"][0], p["norm"][1], 1.0, cx[ti], h, z, h2, out if last else None,
-                              grid, ig, C, C, taps, epilogue=co.EPI_GRU_OUT)
-                h, h2 = h2, h
-            outs.append(out.reshape(b, D, H, W, C).permute(0, 4, 1, 2, 3))
-        return outs
+        return _eval_chunks(x, lambda xr, wino, i, j: _fuse_eval(self, xr, groups, wino, True))
 
     # ---------------------------------------------------------------- HIP training / autograd path
-    @staticmethod
-    def _bn_rows(bn, rows, act=None):
-        """nn.BatchNorm3d / SyncBatchNorm module applied to channels-last rows [b,D,H,W,C] (batch statistics in train mode)."""
-        return bn_act_rows(bn, rows, 1.0 if act is None else act)
-
     def fuse_autograd_hip(self, x):
         """Encoder3D.fuse with an autograd graph (model.train(), or eval-mode pose refinement): the six convolutions per GRU step
         and fusion_conv run on the MFMA implicit-GEMM kernel (forward and data gradient) and the wgrad kernel, the cell's sigmoid /
@@ -1059,8 +992,8 @@ class ConvGRU_3D(co.PackedModule):
         xr = xr if xr.is_contiguous() else xr.contiguous()
         cell, fc = self.cells[0], self.fusion_conv
         lrelu = 0.01
-        h = self._bn_rows(fc[1], co.conv3x3x3_rows(xr.mean(dim=1), None, fc[0].weight, fc[0].bias), lrelu)
-        h = self._bn_rows(fc[4], co.conv3x3x3_rows(h, None, fc[3].weight, fc[3].bias), lrelu)
+        h = bn_act_rows(fc[1], co.conv3x3x3_rows(xr.mean(dim=1), None, fc[0].weight, fc[0].bias), lrelu)
+        h = bn_act_rows(fc[4], co.conv3x3x3_rows(h, None, fc[3].weight, fc[3].bias), lrelu)
         for xv in xr.unbind(1):                       # unbind: ONE stack in backward instead of a zero-filled [b,t,...] scatter per view
             h = gru_cell_rows(xv, h, cell.conv_gate.weight, cell.conv_gate.bias, cell.out_gate.weight, cell.out_gate.bias)
         return bn_act_rows(self.fusion_norm, h).permute(0, 4, 1, 2, 3)
@@ -1096,8 +1029,8 @@ class ConvGRU_3D(co.PackedModule):
         for grp in groups:
             grp = list(grp)
             xm = sum(xviews[ti] for ti in grp) / float(len(grp))
-            h = self._bn_rows(fc[1], co.conv3x3x3_rows(xm, None, fc[0].weight, fc[0].bias), lrelu)
-            h = self._bn_rows(fc[4], co.conv3x3x3_rows(h, None, fc[3].weight, fc[3].bias), lrelu)
+            h = bn_act_rows(fc[1], co.conv3x3x3_rows(xm, None, fc[0].weight, fc[0].bias), lrelu)
+            h = bn_act_rows(fc[4], co.conv3x3x3_rows(h, None, fc[3].weight, fc[3].bias), lrelu)
             for ti in grp:
                 h = _GRUCellPreRows.apply(gx_all[ti], cx_all[ti], h, wgh, cell.conv_gate.bias, woh, cell.out_gate.bias)
             outs.append(bn_act_rows(self.fusion_norm, h).permute(0, 4, 1, 2, 3))

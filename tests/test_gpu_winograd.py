@@ -177,6 +177,8 @@ def test_frozen_fusion_winograd_matches_direct(monkeypatch):
         out = gru.fuse_frozen_hip(xi)
         (out * wgt).sum().backward()
         res[mode] = (out.detach(), xi.grad)
+        with torch.no_grad():
+            assert torch.equal(out.detach(), gru.fuse_hip(x)), mode          # the same forward schedule as inference, bit for bit
     rel = lambda a, b: ((a - b).norm() / b.norm()).item()
     assert rel(res["1"][0], res["0"][0]) < 1e-5
     assert rel(res["1"][1], res["0"][1]) < 1e-3        # sign flips of LeakyReLU arguments within 1e-6 of zero move single elements (test_gpu_configs)
