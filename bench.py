@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py - rendered views/sec of the FORGE reconstruction hot path on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scenes B] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scenes B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,7 +14,9 @@ B scenes, no data-path collective (scenes are independent); rank 0
 `--steps K` is the number of timed steps in all (after W untimed ones); `ms_per_step` is the time one of them took.
 `--dump-outputs DIR` writes the outputs of the last timed step (the rendered views and masks; `--train`: the loss) as .npy files.
 
-Extra objects on the line:
+A plain run does only what the headline figure needs: set-up, W warm-up steps, the K timed steps, the dump, the line. Everything else the
+benchmark measures or checks runs after the timed steps and only with `--full`; `--no-cpu-baseline`, `--no-oracle-check`, `--no-microbench`
+and `--no-extra` leave parts of it out again. With `--full`, extra objects on the line:
   roofline        the dominant kernel of the step (conv_igemm_kernel, fp32 MFMA): FLOPs its launches EXECUTE / their HIP-event time
                   vs the 157.3 TF pipe, plus the whole step against its own executed-FLOP time floor (floor_ms, step_over_floor)
   extra_configs   (N = 1) the other BASELINE configurations, bounded: configs[2] (8 scenes), the 128^3-voxel grid, FORGE_poseEstimator3D
@@ -64,13 +66,15 @@ def main():
     ap.add_argument("--pipeline-depth", type=int, default=4,
                     help="steps in flight: that many hipGraphs of the step replayed round-robin on as many HIP streams (forge_amd.graph.PipelinedForward); "
                          "1 = one stream, back to back")
-    ap.add_argument("--dump-conv", action="store_true", help="print every conv launch of one step (shape, ms, TFLOP/s) to stderr")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure and check everything beyond the headline figure: roofline, "
+                    "per-kernel and per-stage splits, single-stream latency, the CPU baseline and the oracle check, the other configurations; "
+                    "N > 1: strong scaling and the multi-rank sub-records")
+    ap.add_argument("--dump-conv", action="store_true", help="with --full: print every conv launch of one step (shape, ms, TFLOP/s) to stderr")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-oracle-check", action="store_true", help="with --no-cpu-baseline: also skip the one CPU oracle forward the last output is "
             "checked against")
-    ap.add_argument("--min-psnr-db", type=float, default=None, help="exit non-zero unless the last output of the timed region is at least this close to "
-            "the oracle "
-                                                                    "(soak runs: --steps 3000 --no-cpu-baseline --no-extra --min-psnr-db 100)")
+    ap.add_argument("--min-psnr-db", type=float, default=None, help="with --full: exit non-zero unless the last output of the timed region is at least "
+                    "this close to the oracle (soak runs: --steps 3000 --full --no-cpu-baseline --no-extra --min-psnr-db 100)")
     ap.add_argument("--no-microbench", action="store_true", help="skip the per-kernel micro-benchmarks (clean rocprofv3 stats)")
     ap.add_argument("--no-extra", action="store_true", help="skip extra_configs / strong_scaling (the other BASELINE configurations)")
     ap.add_argument("--full-record", default=None, metavar="PATH",
@@ -83,6 +87,9 @@ def main():
     ap.add_argument("--rehearse-hang", action="store_true", help=argparse.SUPPRESS)       # --dry-run only: one sub-record blocks for ever (the watchdog's test)
     ap.add_argument("--cpu-worker", nargs=3, type=int, metavar=("THREADS", "N", "SEED"), help=argparse.SUPPRESS)
     args = ap.parse_args()
+    for flag, given in (("--min-psnr-db", args.min_psnr_db is not None), ("--dump-conv", args.dump_conv)):
+        if given and not args.full:
+            ap.error("%s needs --full (a plain run does not look past the timed steps)" % flag)
     if args.cpu_worker:
         from benchkit.cpu import cpu_worker
         return cpu_worker(*args.cpu_worker)

@@ -45,8 +45,8 @@ def dry_run(args, rank, world):
         lo, hi = fdist.all_reduce_scalars([chk], "cpu", "min")[0], fdist.all_reduce_scalars([chk], "cpu", "max")[0]
         same = abs(hi - lo) < 1e-9 * max(1.0, abs(hi))
     multi = None
-    if world > 1 and not args.train:
-        # the sub-record skeleton of the real multi-rank line (multi_rank_records: watchdog, per-record try block, error gathering) with token
+    if args.full and world > 1 and not args.train:
+        # the sub-record skeleton of the real multi-rank line of a --full run (multi_rank_records: watchdog, per-record try block, error gathering) with token
         # workloads: a DDP step timed with and without no_sync(), a record that FAILS on the last rank (reported, the others carry on), and the
         # differentiable ray-sharded render (all_gather forward, all-reduce backward) on a toy render function
         def token_ddp():

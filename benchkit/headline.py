@@ -1,5 +1,5 @@
-"""The headline measurement: rendered views/sec of the FORGE reconstruction hot path (models/model.py:42-148) on this rank's GPU,
-its dominant-kernel roofline, per-kernel and per-stage splits, parity against the oracle and the CPU baseline beside it."""
+"""The headline measurement: rendered views/sec of the FORGE reconstruction hot path (models/model.py:42-148) on this rank's GPU; with
+`--full` also its dominant-kernel roofline, per-kernel and per-stage splits, parity against the oracle and the CPU baseline beside it."""
 import os
 import sys
 import time
@@ -17,13 +17,33 @@ from benchkit.kernels import kernel_rooflines, pmc_traffic, rocprof_conv_time, s
 from benchkit.multirank import multi_rank_records
 
 
+def describe(grid, B):
+    """(metric, workload, algorithmic GFLOP per step) of the headline configuration: feature grid `grid`, B scenes per GPU."""
+    if grid == 32:
+        metric = "rendered views/sec (5 views, 128^2 px, 64^3 voxel)"
+        workload = ("BASELINE configs[%d]: FORGE hot path, %d scene(s)/GPU x 5 input views 256^2 -> 32^3x128 feature "
+                    "grid -> 64^3 render grid -> 5 views x 128^2 rays x 64 samples -> 5 RGB 256^2; HIP rotate, "
+                    "fp32-MFMA implicit-GEMM ResNet-50 trunk / conv1 / ConvGRU (Winograd F(2x2,3x3) x 3 depth taps) / heads / conv_rgb, HIP ray-march (no "
+                            "MIOpen/rocBLAS kernel in the step); "
+                    "eval BN, random-init seeded weights" % (1 if B == 1 else 2, B))
+        gflop = B * (GF_ENCODER + GF_FUSE + GF_HEADS + GF_CONVRGB)
+    else:
+        metric = "rendered views/sec (5 views, 128^2 px, 128^3 voxel)"
+        workload = ("BASELINE configs[3]/[4] grid (synthetic up-scale, SURVEY.md 8d): %d scene(s)/GPU x 5 synthetic feature volumes "
+                    "[128,64^3] resident in HBM (the encoder cannot produce them from 256^2 images, models/encoder.py:49) -> HIP rotate at "
+                    "D=64 (1.07 GB/scene) -> ConvGRU fusion at M=262144 -> heads -> 128^3 x 17 render volume (142.6 MB) -> 5 views x "
+                    "128^2 rays x 64 samples -> conv_rgb -> 5 RGB 256^2; eval BN, random-init seeded weights" % B)
+        gflop = B * (8 * (GF_FUSE + GF_HEADS) + GF_CONVRGB)
+    return metric, workload, gflop
+
+
 def run_headline(args, rank, world, dev, affinity):
     from forge_amd.model import FORGE
     cfg = syn.kubric_config()
     B = args.scenes
     ok, err = 1.0, None
     graphed = step = eager_step = strong = None
-    B_strong = max(1, 8 // world) if (world > 1 and not args.no_extra and args.grid == 32 and not args.no_graph) else 0
+    B_strong = max(1, 8 // world) if (args.full and world > 1 and not args.no_extra and args.grid == 32 and not args.no_graph) else 0
     try:
         model = FORGE(cfg)
         weights = syn.seeded_state_dict(model.state_dict(), 0)
@@ -93,8 +113,8 @@ def run_headline(args, rank, world, dev, affinity):
     dts = fdist.all_reduce_scalars(dts, dev, "max")                  # every region: the slowest rank's clock
     dt = region_stats(dts, args.steps, 1.0)[0]                      # median region
     # the one exchange of the inference path: (SSE to the target views, pixel count, views rendered) summed over ranks
-    # (RCCL all-reduce of a few doubles) -> whole-job PSNR / view count; ranks_ok rides along
-    if ok:
+    # (RCCL all-reduce of a few doubles) -> whole-job PSNR (--full) / view count; ranks_ok rides along
+    if ok and args.full:
         tgt_dev = sample["images"][:, :V_OUT].reshape(B * V_OUT, 3, 256, 256)
         sse_local, npix_local = float(((out[0] - tgt_dev) ** 2).sum()), float(tgt_dev.numel())
     else:
@@ -122,7 +142,7 @@ def run_headline(args, rank, world, dev, affinity):
     # world > 1: the sub-records whose collectives matter (DDP + SyncBatchNorm training, ray-sharded joint step), bounded and under a watchdog that
     # prints the main line below if they do not come back
     multi = None
-    if world > 1 and not args.no_extra and args.grid == 32:
+    if args.full and world > 1 and not args.no_extra and args.grid == 32:
         metric_main = "rendered views/sec (5 views, 128^2 px, 64^3 voxel)"
         minimal = {"metric": metric_main, "value": (int(views_per_step) * args.steps / dt) if (ok and dt > 0) else None, "unit": "views/s", "n_gpus": world,
                    "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
@@ -143,6 +163,26 @@ def run_headline(args, rank, world, dev, affinity):
         emit({"metric": "rendered views/sec (5 views, 128^2 px, 64^3 voxel)", "value": None, "unit": "views/s", "n_gpus": world, "steps": args.steps,
               "warmup": args.warmup, "ranks_ok": int(ranks_ok), "process_group": pg, "errors": errors, "error": err}, args.full_record)
         return None
+    metric, workload, gflop = describe(args.grid, B)
+    step_ms = dt / args.steps * 1e3
+    result = {
+        "metric": metric, "value": views / dt, "unit": "views/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": step_ms,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "ranks_ok": int(ranks_ok), "errors": errors, "process_group": pg,
+        "repeats": region_stats(dts, args.steps, float(views_per_step))[1],
+        "config": {"workload": workload, "scenes_per_gpu": B, "views_in": T_IN, "views_out": V_OUT, "feature_grid": args.grid,
+                   "render_grid": 2 * args.grid, "rank0_affinity": affinity,
+                   "steps_in_flight": graphed.depth if graphed is not None else 1,
+                   "launch": "eager" if args.no_graph else ("hipGraph replay, %d steps in flight on %d HIP streams" % (graphed.depth, graphed.depth)
+                                                            if (graphed is not None and graphed.depth > 1) else "hipGraph replay"),
+                   "parallelism": "dp%d (scene-sharded, no data-path collective; 4-scalar RCCL all-reduce of SSE/pixels/views/ok for the PSNR report)" % world},
+    }
+    if dumped is not None:
+        result["dump_outputs"] = dump_outputs(args.dump_outputs, dumped)
+    if not args.full:                                                # a plain run: the headline figure and nothing else
+        emit(result, args.full_record)
+        return result
 
     # ---- the same steps with the sample handed over as (pinned) HOST buffers, as a DataLoader would: PCIe-inclusive rate (never `value`)
     pcie_views_per_s = None
@@ -203,7 +243,6 @@ def run_headline(args, rank, world, dev, affinity):
     # 2 x 16 R N kd Cin) / sum of their HIP-event durations. The per-instantiation avg_launch_ms are directly comparable with
     # rocprofv3's per-name AverageNs in profiles/. floor_ms = the same executed FLOPs at the 157.3 TF pipe peak: the step's own time floor.
     convs = {k: v for k, v in conv_launch.items() if k.startswith("conv_igemm_kernel<")}
-    step_ms = dt / args.steps * 1e3
     tot_ms = sum(v["total_ms"] for v in convs.values())
     tot_gf = sum(v["gflop"] for v in convs.values())
     n_launch = sum(v["launches_per_step"] for v in convs.values())
@@ -243,42 +282,14 @@ def run_headline(args, rank, world, dev, affinity):
                         "step). In SURVEY.md 8(d)'s direct-convolution FLOPs the same launches are %.0f GF (the Winograd launches execute 2.25x fewer "
                         "multiplies than the convolutions they replace), so a fraction in those units can exceed 1 and is not reported as one; "
                         "traffic = PMC pass of the fusion's point-GEMM launch (L2 -> fabric bytes, Infinity-Cache hits included)" % alg_gf}
-    if args.grid == 32:
-        metric = "rendered views/sec (5 views, 128^2 px, 64^3 voxel)"
-        workload = ("BASELINE configs[%d]: FORGE hot path, %d scene(s)/GPU x 5 input views 256^2 -> 32^3x128 feature "
-                    "grid -> 64^3 render grid -> 5 views x 128^2 rays x 64 samples -> 5 RGB 256^2; HIP rotate, "
-                    "fp32-MFMA implicit-GEMM ResNet-50 trunk / conv1 / ConvGRU (Winograd F(2x2,3x3) x 3 depth taps) / heads / conv_rgb, HIP ray-march (no "
-                            "MIOpen/rocBLAS kernel in the step); "
-                    "eval BN, random-init seeded weights" % (1 if B == 1 else 2, B))
-        gflop = B * (GF_ENCODER + GF_FUSE + GF_HEADS + GF_CONVRGB)
-    else:
-        metric = "rendered views/sec (5 views, 128^2 px, 128^3 voxel)"
-        workload = ("BASELINE configs[3]/[4] grid (synthetic up-scale, SURVEY.md 8d): %d scene(s)/GPU x 5 synthetic feature volumes "
-                    "[128,64^3] resident in HBM (the encoder cannot produce them from 256^2 images, models/encoder.py:49) -> HIP rotate at "
-                    "D=64 (1.07 GB/scene) -> ConvGRU fusion at M=262144 -> heads -> 128^3 x 17 render volume (142.6 MB) -> 5 views x "
-                    "128^2 rays x 64 samples -> conv_rgb -> 5 RGB 256^2; eval BN, random-init seeded weights" % B)
-        gflop = B * (8 * (GF_FUSE + GF_HEADS) + GF_CONVRGB)
-    result = {
-        "metric": metric, "value": views / dt, "unit": "views/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": step_ms,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "ranks_ok": int(ranks_ok), "errors": errors, "process_group": pg,
-        "repeats": region_stats(dts, args.steps, float(views_per_step))[1],
-        "config": {"workload": workload, "scenes_per_gpu": B, "views_in": T_IN, "views_out": V_OUT, "feature_grid": args.grid,
-                   "render_grid": 2 * args.grid, "rank0_affinity": affinity,
-                   "steps_in_flight": graphed.depth if graphed is not None else 1,
-                   "launch": "eager" if args.no_graph else ("hipGraph replay, %d steps in flight on %d HIP streams" % (graphed.depth, graphed.depth)
-                                                            if (graphed is not None and graphed.depth > 1) else "hipGraph replay"),
-                   "parallelism": "dp%d (scene-sharded, no data-path collective; 4-scalar RCCL all-reduce of SSE/pixels/views/ok for the PSNR report)" % world},
+    result.update({
         "single_stream": single,
         "roofline": roofline, "conv_launches": conv_launch, "kernels": kern, "stages_ms": {k: round(v, 4) for k, v in stages.items()},
         "stages_ms_replay": stages_replay,
         "gflop_per_step_algorithmic": gflop,
         "views_per_s_with_host_to_device_copy": pcie_views_per_s,
         "psnr_to_target_db_all_ranks": fdist.psnr_from_sse(sse, npix),
-    }
-    if dumped is not None:
-        result["dump_outputs"] = dump_outputs(args.dump_outputs, dumped)
+    })
     if strong_res is not None:
         result["strong_scaling"] = strong_res
     if multi is not None:

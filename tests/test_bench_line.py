@@ -79,6 +79,24 @@ def test_oversized_optional_parts_are_dropped_not_the_contract():
     assert len(line) < 4096 and "extra" not in d and d["roofline"]["frac"] == 0.659 and d["cpu_baseline"]["value"] == 7.8
 
 
+def test_plain_run_leaves_the_rest_to_full(tmp_path):
+    """Without --full the benchmark does not look past its timed steps: the 2-rank rehearsal carries no multi-rank sub-records, and the options
+    that need what --full measures refuse to run without it."""
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    full = str(tmp_path / "full.json")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--dry-run", "--full-record", full],
+                       capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    c = json.loads(r.stdout.splitlines()[-1], parse_constant=_refuse)
+    assert c["n_gpus"] == 2 and c["ranks_ok"] == 2 and "multi_rank" not in c
+    assert json.load(open(full))["multi_rank"] is None
+    for flag in (["--min-psnr-db", "100"], ["--dump-conv"]):
+        bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1"] + flag, capture_output=True, text=True, timeout=120,
+                             env=env, cwd=ROOT)
+        assert bad.returncode == 2 and "needs --full" in bad.stderr, (flag, bad.stderr[-500:])
+
+
 def test_steps_is_the_number_of_timed_steps():
     from benchkit.common import region_sizes, region_stats
     for steps, repeats in ((20, 1), (20, 3), (2, 10), (100, 10), (1, 1)):

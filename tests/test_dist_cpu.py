@@ -116,7 +116,8 @@ def test_ray_sharded_render_world2():
 def test_bench_entry_launches_its_own_ranks_dry_run(tmp_path):
     """`python bench.py --gpus 8` (no torchrun environment) must start 8 ranks itself and report n_gpus: 8 - here as the
     CPU/gloo rehearsal of exactly that entry (`--dry-run`: launch, rendezvous on 127.0.0.1, barrier, MAX / SUM reductions, one JSON
-    line from rank 0) - and must FAIL when the launch environment's world size contradicts --gpus."""
+    line from rank 0) - and must FAIL when the launch environment's world size contradicts --gpus. With --full it rehearses the multi-rank sub-records
+    too; a plain run has none."""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
@@ -131,8 +132,8 @@ def test_bench_entry_launches_its_own_ranks_dry_run(tmp_path):
         def refuse(tok):
             raise AssertionError("non-strict JSON token %s" % tok)
         return json.loads(out_lines[-1], parse_constant=refuse)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--scenes", "2", "--dry-run", "--full-record", full],
-                       capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--scenes", "2", "--dry-run", "--full", "--full-record",
+                        full], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     c = strict_line(r.stdout)
     assert c["n_gpus"] == 8 and c["dry_run"] is True and c["ranks_ok"] == 8 and c["full_record"] == full
@@ -148,7 +149,8 @@ def test_bench_entry_launches_its_own_ranks_dry_run(tmp_path):
     assert m["failing_record"]["ranks_ok"] == 7 and len(m["failing_record"]["errors"]) == 1 and "rank 7" in m["failing_record"]["errors"][0]
     assert m["ray_sharded_joint"]["ranks_ok"] == 8 and m["ray_sharded_joint"]["rows"] == 16 and m["ray_sharded_joint"]["d_feat"] == m["ray_sharded_joint"]["expected_d_feat"]
     # a sub-record that never comes back: the watchdog prints the MAIN line and every rank leaves with exit code 0
-    w = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--dry-run", "--rehearse-hang", "--full-record", full],
+    w = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--dry-run", "--full", "--rehearse-hang", "--full-record",
+                        full],
                        capture_output=True, text=True, timeout=300, env=dict(env, FORGE_BENCH_SUBRECORD_DEADLINE_S="3"), cwd=ROOT)
     assert w.returncode == 0, w.stderr[-2000:]
     dw = strict_line(w.stdout)

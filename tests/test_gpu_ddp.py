@@ -206,7 +206,7 @@ def test_bench_entry_two_ranks_on_the_shared_gpu(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     full = str(tmp_path / "full.json")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-microbench", "--full-record", full]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-microbench", "--full-record", full]
     bad = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert bad.returncode != 0 and "GPU(s) visible" in (bad.stderr + bad.stdout)
     ok = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(env, FORGE_BENCH_ALLOW_SHARED_GPUS="1"), cwd=root)
@@ -232,6 +232,31 @@ def test_bench_entry_two_ranks_on_the_shared_gpu(tmp_path):
         assert j["all_reduce_bytes_per_step"] >= vol and j["all_gather_bytes_per_step"] == 10 * 17 * 128 * 128 * 4
     op = m["ray_sharded_joint"]["sharded_render_op"]
     assert all(op["volume_%d_reduce_%s_fwd_bwd_ms" % (D, mode)] > 0 for D in (64, 128) for mode in ("all", "none"))
+
+
+def test_plain_bench_run_is_the_headline_only(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: the contract keys of the headline, the dump of the last timed step, and none of
+    the measurements or checks that --full adds after the timed steps (roofline, per-kernel / per-stage splits, latency, oracle, CPU baseline,
+    other configurations)."""
+    import json
+    import subprocess
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    full, dump = str(tmp_path / "full.json"), str(tmp_path / "dump")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", dump,
+                        "--full-record", full], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    c = _driver_line(r.stdout)
+    assert c["n_gpus"] == 1 and c["steps"] == 3 and c["warmup"] == 1 and c["value"] > 0 and c["unit"] == "views/s" and c["dtype"] == "f32"
+    assert c["higher_is_better"] is True and c["metric"] == "rendered views/sec (5 views, 128^2 px, 64^3 voxel)"
+    assert abs(c["value"] - 5 / (c["ms_per_step"] / 1e3)) < 1e-3 * c["value"]
+    d = json.load(open(full))
+    for k in ("roofline", "conv_launches", "kernels", "stages_ms", "single_stream", "cpu_baseline", "psnr_vs_oracle_db", "extra_configs",
+              "views_per_s_with_host_to_device_copy", "strong_scaling", "multi_rank"):
+        assert k not in d and k not in c, k
+    assert set(d["dump_outputs"]["arrays"]) == {"rgb", "masks"}
+    rgb = np.load(os.path.join(dump, "rgb.npy"))
+    assert rgb.shape == (5, 3, 256, 256) and np.isfinite(rgb).all()
 
 
 def _spawn2(target, args=(), timeout=420):
