@@ -4,6 +4,7 @@ behind the reference's own nn.Module surface. See DESIGN.md / INTEGRATION.md.
 
     from forge_amd.model import FORGE                                   # models.model.FORGE
     from forge_amd.model_single_pose_estimator import FORGE_poseEstimator3D
+    from forge_amd import metrics as lpips; lpips.LPIPS(net="vgg")      # import lpips (kubric_eval.py); metrics.psnr / ssim / image_metrics
 """
 __version__ = "0.2.1"
 

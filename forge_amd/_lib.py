@@ -15,6 +15,7 @@ _lib = None
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _F = ctypes.c_float
+_D = ctypes.c_double
 _LL = ctypes.c_longlong
 
 # name -> argtypes; must list every symbol declared in include/forge_hip.h (tests check this)
@@ -87,6 +88,12 @@ SIGNATURES = {
     "forge_rotate_bwd_det_ws_bytes": [_I] * 5,
     "forge_rotate_bwd_slots_det": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _LL, _P],
     "forge_rotate_bwd_slots_det_ws_bytes": [_I] * 5,
+    "forge_metric_blocks": [],
+    "forge_ssim_tiles": [_I, _I],
+    "forge_psnr": [_P, _LL, _LL, _LL, _LL, _P, _LL, _LL, _LL, _LL, _I, _I, _I, _I, _D, _P, _P, _P],
+    "forge_ssim": [_P, _LL, _LL, _LL, _LL, _P, _LL, _LL, _LL, _LL, _I, _I, _I, _I, _D, _P, _P, _P],
+    "forge_lpips_tap": [_P, _I, _I, _I, _P, _P, _P],
+    "forge_lpips_finalize": [_P, _I, _I, _I, _I, _I, _I, _P, _P],
     "forge_ncdhw_to_ndhwc": [_P, _P, _I, _I, _LL, _P],
     "forge_ndhwc_to_ncdhw": [_P, _P, _I, _I, _LL, _P],
 }

@@ -15,6 +15,7 @@ Backward (input branch only; the weights are frozen, so only data gradients):
   data gradients              transposed Winograd weights (forge_wino_weights(transpose=1)) or negated taps on forge_conv_igemm; conv1_1 as a
                               Cout = 4 (3 padded) launch on the narrow kernel
   prep adjoint                forge_vgg_prep_bwd: deterministic gather per source pixel, / std, summed over the repeated channels
+The forward walk (prep, conv1_1, the blocks with their pools) is `trunk`, shared with LPIPS (forge_amd/metrics.py), which runs it through block 5.
 No atomics anywhere: two calls give bitwise-identical loss and gradient. Everything runs on the caller's current stream (a captured training
 step stays a linear graph).
 
@@ -41,18 +42,22 @@ import torch.nn as nn
 from . import _lib
 from . import convops as co
 
-# VGG-16 configuration D (Simonyan & Zisserman): features[:23] is what the loss uses (four blocks up to relu4_3)
+# VGG-16 configuration D (Simonyan & Zisserman): features[:23] is what the loss uses (four blocks up to relu4_3), features[:30] what LPIPS uses
+# (five blocks up to relu5_3, forge_amd/metrics.py)
 VGG16_CFG = [64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512, 512, "M"]
 BLOCK_SLICES = ((0, 4), (4, 9), (9, 16), (16, 23))
-CONV_IDX = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21)                 # features index of each convolution inside features[:23]
-BLOCK_CONVS = ((0, 1), (2, 3), (4, 5, 6), (7, 8, 9))             # CONV_IDX positions per block; the last one of each block is a tap
-LAYER_NAMES = ("conv1_1", "conv1_2", "conv2_1", "conv2_2", "conv3_1", "conv3_2", "conv3_3", "conv4_1", "conv4_2", "conv4_3")
+TRUNK_SLICES = BLOCK_SLICES + ((23, 30),)
+CONV_IDX = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)     # features index of each convolution inside features[:30]
+BLOCK_CONVS = ((0, 1), (2, 3), (4, 5, 6), (7, 8, 9), (10, 11, 12))  # CONV_IDX positions per block; the last one of each block is a tap
+LAYER_NAMES = ("conv1_1", "conv1_2", "conv2_1", "conv2_2", "conv3_1", "conv3_2", "conv3_3", "conv4_1", "conv4_2", "conv4_3", "conv5_1", "conv5_2",
+               "conv5_3")
 WEIGHTS_FILE = "vgg16-397923af.pth"
 
-# (forward, data gradient) of conv1_2 .. conv4_3: "wino" = F(2x2, 3x3) with one depth tap (forge_wino_input / _gemm / _output), "direct" =
+# (forward, data gradient) of conv1_2 .. conv5_3: "wino" = F(2x2, 3x3) with one depth tap (forge_wino_input / _gemm / _output), "direct" =
 # forge_conv_igemm with 9 taps. Chosen per layer from the A/B of tools/perceptual_probe.py at 10 and 40 pairs (DESIGN.md "VGG-16 perceptual loss",
 # profiles/perceptual_probe.txt): the 64-channel layers at 224^2 / 112^2 are faster direct (K = 64 per Winograd point does not amortise the
-# transforms), every layer from conv2_2 on is faster on Winograd.
+# transforms), every layer from conv2_2 on is faster on Winograd. conv5_x (LPIPS only: forward only, at H/16) from the A/B of
+# tools/metrics_probe.py (DESIGN.md "Evaluation metrics"). A layer whose extent is odd takes the 9-tap GEMM whatever its plan (convops.wino_fits).
 LAYER_PLAN = {name: (("direct", "direct") if name in ("conv1_2", "conv2_1") else ("wino", "wino")) for name in LAYER_NAMES[1:]}
 
 
@@ -108,6 +113,29 @@ def _ref_key(features_key):
     return None
 
 
+def pack_layers(convs, plan, device):
+    """Launch arguments of the VGG convolutions `convs` (conv1_1 first): conv1_1's patch-row weight and its transposed Cout = 4 form, the 9-tap
+    forms of the others (direct forward / data gradient) and their Winograd transforms where plan[i - 1] = (forward, data gradient) takes
+    Winograd (a data gradient of None: forward only)."""
+    layers = []
+    for i, m in enumerate(convs):
+        w = m.weight.detach().to(device=device, dtype=torch.float32)
+        cout, cin = w.shape[:2]
+        L = {"cin": cin, "cout": cout, "bias": m.bias.detach().to(device=device, dtype=torch.float32).contiguous(),
+             "one": torch.ones(cout, device=device), "zero": torch.zeros(cout, device=device)}
+        wp, _ = co.pack_conv2d_weight(w)                                          # [9][Cout][Cin], tap (ky, kx)
+        if i == 0:
+            L["w0"] = co.pad_cin(w.permute(0, 2, 3, 1).reshape(1, cout, 27).contiguous(), 32)      # patch-row order (ky, kx, c)
+            L["wT"] = torch.nn.functional.pad(wp.transpose(1, 2), (0, 0, 0, 1)).contiguous()        # [9][4][64]: Cin 3 -> 4
+        else:
+            L["plan"] = plan[i - 1]
+            L["wp"], L["wT"] = wp, wp.transpose(1, 2).contiguous()
+            L["U"] = co.wino_pack_packed(wp) if plan[i - 1][0] == "wino" else None
+            L["UT"] = co.wino_pack_packed(wp, transpose=True) if plan[i - 1][1] == "wino" else None
+        layers.append(L)
+    return layers
+
+
 class VGGPerceptualLoss(co.PackedModule):
     """models/perceptual_loss.py:7 with the reference's state_dict layout (`blocks.{0..3}.N.{weight,bias}`, `mean`, `std`). See the module
     docstring for the kernels, the weight sources and the deliberate deviations."""
@@ -158,30 +186,11 @@ class VGGPerceptualLoss(co.PackedModule):
         self.plan changed): conv1_1's patch-row weight and its transposed Cout = 4 form, the 9-tap forms of the others (direct forward / data
         gradient) and their Winograd transforms where the plan takes Winograd."""
         convs = self.convs()
-        plan = tuple(self.plan[n] for n in LAYER_NAMES[1:])
+        plan = tuple(self.plan[n] for n in LAYER_NAMES[1:len(convs)])
         if plan != self._plan_key:
             self._packed.clear()
             self._plan_key = plan
-
-        def build():
-            layers = []
-            for i, m in enumerate(convs):
-                w = m.weight.detach().to(device=device, dtype=torch.float32)
-                cout, cin = w.shape[:2]
-                L = {"cin": cin, "cout": cout, "bias": m.bias.detach().to(device=device, dtype=torch.float32).contiguous(),
-                     "one": torch.ones(cout, device=device), "zero": torch.zeros(cout, device=device)}
-                wp, _ = co.pack_conv2d_weight(w)                                          # [9][Cout][Cin], tap (ky, kx)
-                if i == 0:
-                    L["w0"] = co.pad_cin(w.permute(0, 2, 3, 1).reshape(1, cout, 27).contiguous(), 32)      # patch-row order (ky, kx, c)
-                    L["wT"] = torch.nn.functional.pad(wp.transpose(1, 2), (0, 0, 0, 1)).contiguous()        # [9][4][64]: Cin 3 -> 4
-                else:
-                    L["plan"] = plan[i - 1]
-                    L["wp"], L["wT"] = wp, wp.transpose(1, 2).contiguous()
-                    L["U"] = co.wino_pack_packed(wp) if plan[i - 1][0] == "wino" else None
-                    L["UT"] = co.wino_pack_packed(wp, transpose=True) if plan[i - 1][1] == "wino" else None
-                layers.append(L)
-            return layers
-        return self._packed.get([p for m in convs for p in (m.weight, m.bias)], build)
+        return self._packed.get([p for m in convs for p in (m.weight, m.bias)], lambda: pack_layers(convs, plan, device))
 
     _plan_key = None
 
@@ -245,28 +254,27 @@ def _strides(t):
     return [int(s) for s in t.stride()]
 
 
-@_lib.on_tensor_device
-def _forward(input, target, layers, mean, std, resize, only_deepest, save):
-    """(loss, saved) for the batch [input; target]. saved (save=True): the input half of every convolution's post-ReLU output and the target half
-    of every tap, as views of the 2N-image activations."""
+def trunk(a, b, layers, mean, std, resize, Ho, Wo, tap):
+    """The VGG-16 features of the batch [a; b] (2N images, [N, C, Hi, Wi] each): prep (forge_vgg_prep_fwd with the DEVICE scalars mean / std,
+    resized to Ho x Wo when `resize`), conv1_1, then the blocks of BLOCK_CONVS whose convolutions `layers` holds (four for the loss's ten,
+    five for LPIPS's thirteen), each after the first starting with the 2x2 max-pool. tap(block, x) is called on each block's last post-ReLU output [2N, H, W, C] as soon as it is written. Returns the
+    post-ReLU output of every convolution. The caller makes the operands' device current."""
     lib, st = _lib.lib(), _lib.current_stream()
-    N, C, Hi, Wi = input.shape
-    Ho, Wo = (224, 224) if resize else (Hi, Wi)
-    dev = input.device
+    N, C, Hi, Wi = a.shape
+    dev = a.device
     nb = 2 * N
     rows = torch.empty(nb * Ho * Wo, 32, dtype=torch.float32, device=dev)
-    _lib.check(lib.forge_vgg_prep_fwd(_lib.ptr(input), *_strides(input), _lib.ptr(target), *_strides(target), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(rows),
+    _lib.check(lib.forge_vgg_prep_fwd(_lib.ptr(a), *_strides(a), _lib.ptr(b), *_strides(b), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(rows),
                                       N, C, Hi, Wi, Ho, Wo, int(resize), st), "forge_vgg_prep_fwd")
     L0 = layers[0]
     x = torch.empty(nb, Ho, Wo, 64, dtype=torch.float32, device=dev)
     co.conv_igemm(rows, 32, 32, None, 0, 0, L0["w0"], L0["bias"], L0["one"], L0["zero"], 0.0, None, None, None, x, None, (nb, 1, Ho, Wo), (1, Ho, Wo),
                   64, 64, [(0, 0, 0)], epilogue=co.EPI_AFFINE_ACT)
-    acts, taps = [x], []
+    acts = [x]
     H, W = Ho, Wo
-    nblk = lib.forge_l1_partial_blocks()
-    partial = torch.empty(4, nblk, dtype=torch.float32, device=dev)
-    numel = []
-    for b, convs in enumerate(BLOCK_CONVS):
+    for blk, convs in enumerate(BLOCK_CONVS):
+        if convs[-1] >= len(layers):
+            break
         for j in convs:
             if j == 0:
                 continue
@@ -278,12 +286,29 @@ def _forward(input, target, layers, mean, std, resize, only_deepest, save):
             out = torch.empty(nb, H, W, layers[j]["cout"], dtype=torch.float32, device=dev)
             x = _conv(layers[j], x, nb, H, W, out)
             acts.append(x)
+        tap(blk, x)
+    return acts
+
+
+@_lib.on_tensor_device
+def _forward(input, target, layers, mean, std, resize, only_deepest, save):
+    """(loss, saved) for the batch [input; target]. saved (save=True): the input half of every convolution's post-ReLU output and the target half
+    of every tap, as views of the 2N-image activations."""
+    lib, st = _lib.lib(), _lib.current_stream()
+    N, C, Hi, Wi = input.shape
+    Ho, Wo = (224, 224) if resize else (Hi, Wi)
+    nblk = lib.forge_l1_partial_blocks()
+    partial = torch.empty(4, nblk, dtype=torch.float32, device=input.device)
+    numel, taps = [], []
+
+    def l1(b, x):
         half = x.numel() // 2
         numel.append(half)
         taps.append(x)
         if not only_deepest or b == 3:
             flat = x.reshape(-1)
             _lib.check(lib.forge_l1_partial(_lib.ptr(flat), ctypes.c_void_p(flat.data_ptr() + 4 * half), half, _lib.ptr(partial[b]), st), "forge_l1_partial")
+    acts = trunk(input, target, layers, mean, std, resize, Ho, Wo, l1)
     if only_deepest:
         loss = partial[3].sum() / numel[3]
     else:

@@ -498,6 +498,29 @@ int forge_vgg_tap_bwd(const float* x, const float* y, const float* g_next, const
                       forge_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * f4  Image metrics of the evaluation protocol (utils/eval_utils.py:compute_img_metric, kubric_eval.py's lpips.LPIPS(net="vgg")). Images
+ * a, b are [N][C][H][W] float32 read through element strides; image n of a is scored against image n of b. Each entry writes per-workgroup
+ * partial sums into the caller's slab and sums them in a fixed order in a second launch: no atomics, bitwise reproducible, no allocation.
+ *   psnr          out[n] (float64) = 10 log10(data_range^2 / mse), mse over C H W elements in float64; mse = 0 gives +inf.
+ *                 partial: N * forge_metric_blocks() doubles.
+ *   ssim          out[n] (float64) = mean over channels and over all valid 7x7 windows of skimage's SSIM map (uniform window, sample
+ *                 covariance 49/48, K1 = 0.01, K2 = 0.03); H, W >= 7. partial: N * C * forge_ssim_tiles(H, W) doubles.
+ *   ssim_tiles    partials per (image, channel) of forge_ssim, -1 when H or W < 7.
+ *   lpips_tap     one LPIPS tap: f [2N][HW][C] channels-last (image n against image n + N), C in {64, 128, 256, 512}, w [C] the lin weights,
+ *                 f and w 16-byte aligned; partial [N][forge_metric_blocks()] = partial sums over pixels of
+ *                 sum_c w[c] (f0 / (|f0| + 1e-10) - f1 / (|f1| + 1e-10))^2.
+ *   lpips_final   out[n] (float32) = sum over the 5 taps k of (sum of partial[k][n][*]) / hw_k; partial [5][N][forge_metric_blocks()].
+ */
+int forge_metric_blocks(void);
+int forge_ssim_tiles(int H, int W);
+int forge_psnr(const float* a, long long a_sn, long long a_sc, long long a_sh, long long a_sw, const float* b, long long b_sn, long long b_sc,
+               long long b_sh, long long b_sw, int N, int C, int H, int W, double data_range, double* partial, double* out, forge_stream_t stream);
+int forge_ssim(const float* a, long long a_sn, long long a_sc, long long a_sh, long long a_sw, const float* b, long long b_sn, long long b_sc,
+               long long b_sh, long long b_sw, int N, int C, int H, int W, double data_range, double* partial, double* out, forge_stream_t stream);
+int forge_lpips_tap(const float* f, int N, int HW, int C, const float* w, double* partial, forge_stream_t stream);
+int forge_lpips_finalize(const double* partial, int N, int hw0, int hw1, int hw2, int hw3, int hw4, float* out, forge_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * layout helpers: NCDHW <-> channels-last for callers that hold plain-contiguous volumes.
  *   src [n][C][P] -> dst [n][P][C]   (P = D*H*W)   and back.
  */
