@@ -613,7 +613,12 @@ def wino_output(Mm, bias, scale, shift, slope, residual, aux_h, aux_z, out, out2
 @_lib.on_tensor_device
 def conv_wgrad(dy, x1, C1, x2, C2, dwp, grid, in_grid, Cout, taps, istride=1, bs1=0, bs2=0):
     """dwp += weight gradient (forge_conv_wgrad; dwp zero-filled by the caller, accumulated with atomics). Batches whose operands span
-    2 GiB or more (32-bit buffer offsets in the kernel) are accumulated in batch chunks, as conv_igemm launches them."""
+    2 GiB or more (32-bit buffer offsets in the kernel) are accumulated in batch chunks, as conv_igemm launches them. The kernel's 128-wide
+    Cin tiles may not straddle two inputs: with C1 not a multiple of 128 (a ConvGRU cell of hidden size 32 / 64 / 96 / 160, or input width
+    != hidden width) the inputs are concatenated into one first."""
+    if x2 is not None and C1 % 128:
+        x1 = torch.cat([x1[..., :C1], x2[..., :C2]], dim=-1)
+        C1, x2, C2, bs1, bs2 = C1 + C2, None, 0, 0, 0
     n, D, H, W = grid
     Di, Hi, Wi = in_grid
     in_rows, out_rows = Di * Hi * Wi, D * H * W

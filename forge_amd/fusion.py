@@ -258,12 +258,13 @@ class _GRUCellRows(torch.autograd.Function):
     """One ConvGRU step (models/fusion.py:29-35) on channels-last rows with an autograd graph. Both convolutions run on the MFMA
     implicit-GEMM kernel (bias epilogue), data / weight gradients on the same GEMM / the wgrad kernel, and each element-wise half of
     the cell is one HIP kernel per direction (csrc/gru.hip) instead of ~23 generic tensor ops per step.
-      x [b,D,H,W,C] (a view with a batch stride is fine), h [b,D,H,W,C] dense, wg [27][2C][2C], wo [27][C][2C] packed weights."""
+      x [b,D,H,W,Cx] (a view with a batch stride is fine), h [b,D,H,W,C] dense, wg [27][2C][Cx+C], wo [27][C][Cx+C] packed weights."""
 
     @staticmethod
     @_lib.on_tensor_device
     def forward(ctx, x, h, wg, bg, wo, bo):
         b, D, H, W, C = h.shape
+        Cx = x.shape[-1]
         M = b * D * H * W
         dev = h.device
         h = h.contiguous()
@@ -272,12 +273,12 @@ class _GRUCellRows(torch.autograd.Function):
         grid = (b, D, H, W)
         new = lambda c: torch.empty(b, D, H, W, c, dtype=torch.float32, device=dev)
         g = new(2 * C)
-        co.conv3_launch(x, C, h, C, wgc, bg, g, grid, 2 * C, bs1=bsx)
+        co.conv3_launch(x, Cx, h, C, wgc, bg, g, grid, 2 * C, bs1=bsx)
         z, r, hr = new(C), new(C), new(C)
         L, p, st = _lib.lib(), _lib.ptr, _lib.current_stream
         _lib.check(L.forge_gru_gates_fwd(p(g), p(h), p(z), p(r), p(hr), M, C, st()), "forge_gru_gates_fwd")
         cand = new(C)
-        co.conv3_launch(x, C, hr, C, woc, bo, cand, grid, C, bs1=bsx)
+        co.conv3_launch(x, Cx, hr, C, woc, bo, cand, grid, C, bs1=bsx)
         hn = new(C)
         _lib.check(L.forge_gru_state_fwd(p(cand), p(h), p(z), p(hn), M, C, st()), "forge_gru_state_fwd")     # cand <- tanh(conv)
         ctx.save_for_backward(x, h, z, r, hr, cand, wgc, woc)
@@ -289,6 +290,7 @@ class _GRUCellRows(torch.autograd.Function):
     def backward(ctx, dhn):
         x, h, z, r, hr, cand, wg, wo = ctx.saved_tensors
         b, D, H, W, C = h.shape
+        Cx = x.shape[-1]
         M = b * D * H * W
         dev = h.device
         grid = (b, D, H, W)
@@ -299,26 +301,26 @@ class _GRUCellRows(torch.autograd.Function):
         dh, dz, dc = new(C), new(C), new(C)
         _lib.check(L.forge_gru_state_bwd(p(dhn), C, p(h), p(z), p(cand), p(dh), p(dz), p(dc), M, C, None, 0, 0, 0, st()), "forge_gru_state_bwd")
         # candidate conv: c = conv([x | h r], wo)
-        dxh = new(2 * C)                                                                   # (dx | d(h r))
-        co.conv3_launch(dc, C, None, 0, wo, None, dxh, grid, 2 * C, dgrad=True)
+        dxh = new(Cx + C)                                                                  # (dx | d(h r))
+        co.conv3_launch(dc, C, None, 0, wo, None, dxh, grid, Cx + C, dgrad=True)
         dwo = dbo = dwg = dbg = None
         if ctx.needs_input_grad[4]:
             dwo = co.grad_zeros(wo.shape, wo.device)
-            co.conv3_wgrad(dc, x, C, hr, C, dwo, grid, C, bs1=bsx)
+            co.conv3_wgrad(dc, x, Cx, hr, C, dwo, grid, C, bs1=bsx)
         if ctx.has_bias[1] and ctx.needs_input_grad[5]:
             dbo = co.colsum(dc.reshape(M, C))
         # gates: g = conv([x | h], wg); z = sigmoid(g[:C]), r = sigmoid(g[C:]), hr = h r
         dg = new(2 * C)
-        _lib.check(L.forge_gru_gates_bwd(p(dz), _lib.ptr(dxh[..., C:]), 2 * C, p(h), p(z), p(r), p(dg), p(dh), None, 0, M, C, None, 0, 0, 0, st()), "forge_gru_gates_bwd")
-        dxh2 = new(2 * C)
-        co.conv3_launch(dg, 2 * C, None, 0, wg, None, dxh2, grid, 2 * C, dgrad=True)
+        _lib.check(L.forge_gru_gates_bwd(p(dz), _lib.ptr(dxh[..., Cx:]), Cx + C, p(h), p(z), p(r), p(dg), p(dh), None, 0, M, C, None, 0, 0, 0, st()), "forge_gru_gates_bwd")
+        dxh2 = new(Cx + C)
+        co.conv3_launch(dg, 2 * C, None, 0, wg, None, dxh2, grid, Cx + C, dgrad=True)
         if ctx.needs_input_grad[2]:
             dwg = co.grad_zeros(wg.shape, wg.device)
-            co.conv3_wgrad(dg, x, C, h, C, dwg, grid, 2 * C, bs1=bsx)
+            co.conv3_wgrad(dg, x, Cx, h, C, dwg, grid, 2 * C, bs1=bsx)
         if ctx.has_bias[0] and ctx.needs_input_grad[3]:
             dbg = co.colsum(dg.reshape(M, 2 * C))
-        dx = (dxh[..., :C] + dxh2[..., :C]) if ctx.needs_input_grad[0] else None
-        dh_total = (dh + dxh2[..., C:]) if ctx.needs_input_grad[1] else None
+        dx = (dxh[..., :Cx] + dxh2[..., :Cx]) if ctx.needs_input_grad[0] else None
+        dh_total = (dh + dxh2[..., Cx:]) if ctx.needs_input_grad[1] else None
         return dx, dh_total, dwg, dbg, dwo, dbo
 
 
