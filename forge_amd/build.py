@@ -14,6 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libforge_hip.so")
 ARCH = "gfx950"
+FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function", "-DNDEBUG"]
 
 
 def sources():
@@ -46,8 +47,7 @@ def build(force=False, verbose=True):
     objdir = os.path.join(HERE, "csrc", "_obj")
     os.makedirs(objdir, exist_ok=True)
     cc = hipcc()
-    flags = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
-             "-Wall", "-Wno-unused-function", "-DNDEBUG"]
+    flags = FLAGS
     objs = []
     procs = []
     for src in sources():

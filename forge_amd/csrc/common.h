@@ -108,6 +108,10 @@ __device__ __forceinline__ void lds_dma16(const forge_v4i32& rsrc, unsigned voff
 
 __device__ __forceinline__ void lds_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
+// lds_dma_wait + barrier as ONE statement, for a K loop that also has ordinary stores in flight: the wave's LDS-DMA loads and stores have
+// completed and its own LDS reads have returned, then s_barrier - nothing is scheduled between the wait and the barrier.
+__device__ __forceinline__ void lds_dma_wait_barrier() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
 __device__ __forceinline__ unsigned lds_addr(const void* smem_ptr) {                             // LDS byte address of a __shared__ pointer
     return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const char*)smem_ptr;
 }

@@ -73,6 +73,8 @@ struct ConvArgs {
 };
 
 constexpr int BK = 32, NTHREADS = 512;
+constexpr int RS_STAGES = 2;               // LDS stages of the four-point form (RS = 1): the launcher's dynamic LDS is RS_STAGES x 24 KB, and three such
+                                           // workgroups are resident per CU (80 VGPRs = 6 waves per SIMD; tests/test_conv_igemm_resources.py holds both)
 
 #ifdef FORGE_CONV_TIMING   // debug build (tools/debug/conv_timing.py): per-workgroup clock stamps at entry / first barrier / loop end / exit
 __device__ long long g_conv_stamp[8192 * 4];
@@ -98,14 +100,17 @@ __device__ __forceinline__ int lds_off(int row, int chunk) {   // float offset o
 // lost 2-6 % to that); here the loads of step s+1 are issued at the top of step s, fly under its 16 MFMAs per accumulator, and the hand-placed
 // `s_waitcnt vmcnt(0)` sits directly in front of the step's closing barrier. Against the register-staged loop this kernel replaced (same K
 // order, bitwise the same results): +5..21 % per launch (profiles/TUNING_LOG.md, round 3: 64x128 tile 106 -> 129 TF on the Winograd gates
-// GEMM, 128x128 tile 112 -> 135 TF on the K = 6912 direct launch). A third LDS stage (loads two steps ahead) was slower than two: the extra
-// LDS costs a resident workgroup per CU.
+// GEMM, 128x128 tile 112 -> 135 TF on the K = 6912 direct launch). A third LDS stage (loads two steps ahead) was slower than two: on the
+// single-point tiles the extra LDS costs a resident workgroup per CU; on the four-point form (below), where it does not, a three-stage ring with a
+// counted vmcnt was still 1-3 % slower than two stages (profiles/TUNING_LOG.md, round 7).
 //
 // RS = 1 (forge_wino_gemm_half, 64x128 tile): one workgroup runs the FOUR Winograd points i = 0..3 of a point column j on its tile, one K loop after
-// the other into four accumulator sets (the first stage of the next point is loaded under the last step of the current one), and its epilogue
-// applies the ROW stage of the inverse transform A^T M A in registers - the same lane holds element (row, col) of all four points:
-// s0 = (m0 + m1) + m2, s1 = (m1 - m2) - m3, wino_output_kernel's own operations in its own order - and stores 2 planes instead of 4:
-// Mm8 [2][4][R][Cout]. The point products then cross HBM as 2x instead of 4x the output tensor, written here and read by the inverse transform.
+// the other (the first stage of the next point is loaded under the last step of the current one), and applies the ROW stage of the inverse
+// transform A^T M A in registers - the same lane holds element (row, col) of all four points: s0 = (m0 + m1) + m2, s1 = (m1 - m2) - m3,
+// wino_output_kernel's own operations in its own order - and stores 2 planes instead of 4: Mm8 [2][4][R][Cout]. The point products then cross HBM
+// as 2x instead of 4x the output tensor, written here and read by the inverse transform. s0 is stored as soon as point 2 is done, under point 3's
+// K loop, so three accumulator sets are live, not four: 80 VGPRs = 6 waves per SIMD = THREE resident workgroups per CU (3 x 48 KB of LDS;
+// with four sets and 96 VGPRs it was two - 512 slots chip-wide, not the 640 an earlier note assumed).
 template <int BM, int BN, int NW, int MT = 1, int RS = 0>
 __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
     constexpr int NP = RS ? 4 : 1;                   // points per workgroup
@@ -116,7 +121,7 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
     constexpr int RPP = NW * 8;                     // tile rows staged per pass (8 threads per 128-byte row)
     constexpr int ACH = BM / RPP, BCH = BN / RPP;   // 16-byte chunks per thread per K-step
     static_assert(ACH >= 1 && BCH >= 1, "tile too small for the workgroup");
-    extern __shared__ __attribute__((aligned(16))) float smem[];   // [2][A_FLOATS + B_FLOATS]
+    extern __shared__ __attribute__((aligned(16))) float smem[];   // [2][A_FLOATS + B_FLOATS] (RS: RS_STAGES of them)
 
     FORGE_STAMP(0);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -255,9 +260,10 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
 #pragma unroll
         for (int j = 0; j < BCH; ++j) lds_dma16(ww, boff[j] + wbase, stage + (unsigned)(A_FLOATS * 4 + j * NW * 1024));
     };
-    f32x16 accs[NP][MT][NT];
+    constexpr int NACC = RS ? 3 : 1;                               // accumulator sets (RS: the row stage frees one after point 2)
+    f32x16 accs[NACC][MT][NT];
 #pragma unroll
-    for (int q = 0; q < NP; ++q)
+    for (int q = 0; q < NACC; ++q)
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -284,11 +290,13 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
             if (++kc == kchunks) { kc = 0; ++t; prep_tap(t); }
         }
     };
-    prep_tap(t);
-    issue_step(t, kc, 0);
-    lds_dma_wait();
-    __syncthreads();
-    FORGE_STAMP(1);
+    if constexpr (!RS) {
+        prep_tap(t);
+        issue_step(t, kc, 0);
+        lds_dma_wait();
+        __syncthreads();
+        FORGE_STAMP(1);
+    }
     // One K-step = 4 MFMA groups of 8 k-values. (A/B in round 1: issuing the next tile's global loads after group 0 and its LDS
     // writes after group 2, pinned with sched_barrier, changed nothing: 127.3 vs 126.3 TF on the ConvGRU gates shape.)
     auto mfma_group = [&](f32x16 (&acc)[MT][NT], const float* sa, const float* sb, int g) {
@@ -314,6 +322,7 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
 #pragma unroll
             for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].w, fb[j].w, acc[i][j], 0, 0, 0);
     };
+    if constexpr (!RS) {
     int buf = 0;
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
@@ -323,14 +332,6 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
             if (s + 1 < nsteps) {                                 // the other stage was last read in step s - 1: every wave is past that barrier
                 advance();
                 issue_step(t, kc, buf ^ 1);                       // in flight under this step's MFMAs
-            } else if (q + 1 < NP) {                              // RS: the next point's first stage, in flight under this point's last step
-                const long long pn = pb + 4 * (q + 1);
-                w1 = make_rsrc_words(a.in1 + pn * a.pt1, a.span1);
-                w2 = make_rsrc_words(a.in2 ? a.in2 + pn * a.pt2 : a.in1, a.in2 ? a.span2 : 0);
-                ww = make_rsrc_words(a.wp + pn * a.ptw, (long long)a.ntaps * a.Cout * Cin * 4);
-                t = s_begin / kchunks; kc = s_begin - t * kchunks; t += t_lo;
-                prep_tap(t);
-                issue_step(t, kc, buf ^ 1);
             }
 #pragma unroll
             for (int g = 0; g < 4; ++g) mfma_group(accs[q], sa, sb, g);
@@ -338,6 +339,90 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
             __syncthreads();                                      // ... and so is everybody else's
             buf ^= 1;
         }
+    }
+    } else {
+        // Four points, one K loop after the other. An issue cursor (point iq, tap it, chunk ikc) runs one step ahead of the MFMAs and walks straight
+        // over the point switches (descriptors re-made there): the next point's first stage flies under the current point's last step.
+        constexpr int STAGE = A_FLOATS + B_FLOATS;
+        // Depth taps that are zero for the WHOLE tile are not walked: when all valid rows of the tile lie in one depth plane z and z + dz is
+        // outside the grid, that tap's Cin / 32 K-steps multiply DMA'd zeros. Workgroup-uniform. Bitwise neutral for finite weights: an
+        // accumulator that starts at +0 never becomes -0, and x + (+-0) = x. Only leading / trailing taps are trimmed (the K order stays).
+        int t_first = 0, t_end = a.tpp;
+        const unsigned HW = (unsigned)(a.H * a.W);
+        const long long mlast = (m0 + BM < M ? m0 + BM : M) - 1;
+        const unsigned p0 = (unsigned)m0 / HW, p1 = (unsigned)mlast / HW;
+        if (p0 == p1) {
+            const int z = (int)(p0 % (unsigned)a.D) * a.is;
+            while (t_first < t_end - 1 && (unsigned)(z + a.tap[t_first][0]) >= (unsigned)a.Di) ++t_first;
+            while (t_end - 1 > t_first && (unsigned)(z + a.tap[t_end - 1][0]) >= (unsigned)a.Di) --t_end;
+        }
+        const int nst = (t_end - t_first) * kchunks;               // K-steps per point
+        int iq = 0, it = t_first, ikc = 0, ibuf = 0;
+        auto issue_next = [&]() {
+            if (iq >= NP) return;
+            issue_step(it, ikc, ibuf);
+            ibuf = ibuf + 1 == RS_STAGES ? 0 : ibuf + 1;
+            if (++ikc == kchunks) {
+                ikc = 0;
+                if (++it == t_end) {
+                    it = t_first;
+                    if (++iq < NP) {                                // pb = the point column j; the workgroup's points are pb, pb + 4, pb + 8, pb + 12
+                        const long long pn = pb + 4 * iq;
+                        w1 = make_rsrc_words(a.in1 + pn * a.pt1, a.span1);
+                        w2 = make_rsrc_words(a.in2 ? a.in2 + pn * a.pt2 : a.in1, a.in2 ? a.span2 : 0);
+                        ww = make_rsrc_words(a.wp + pn * a.ptw, (long long)a.ntaps * a.Cout * Cin * 4);
+                    }
+                }
+                if (iq < NP) prep_tap(it);
+            }
+        };
+        prep_tap(t_first);
+        issue_next();
+        lds_dma_wait_barrier();
+        FORGE_STAMP(1);
+        // Row stage of A^T M A over the four points, two planes stored (identity rows, no bias): s0 = (m0 + m1) + m2, s1 = (m1 - m2) - m3,
+        // wino_output_kernel's own operations in its own order. Stores go through a buffer descriptor of the plane: rows beyond M lie beyond
+        // its num_records and columns beyond Cout are sent to OOB - dropped by the hardware, no branch (plane < 2 GiB: checked on the host).
+        const int ocol = n0 + wn * (BN / WN) + l31;
+        const unsigned ldo4 = (unsigned)a.ldo * 4u;
+        const unsigned ovb = ocol < a.Cout ? (unsigned)(((int)m0 + wm * 32 + 4 * half) * a.ldo + ocol) * 4u : OOB;
+        auto store_plane = [&](int plane, auto&& val) {
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(a.out + (pb + 4 * plane) * a.pto, 0, (int)(M * a.ldo * 4), 0x00020000);
+            unsigned vb = ovb;
+            asm volatile("" : "+v"(vb));                             // keeps the 16 row offsets from being computed ahead of the K loops and held in registers
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val(r)), rs, (int)(vb + (unsigned)((r & 3) + 8 * (r >> 2)) * ldo4), 0, 0);
+        };
+        static_assert(NT == 1, "the row stage is written for one 32-column MFMA tile per wave");
+        int buf = 0;
+#pragma unroll
+        for (int q = 0; q < NP; ++q) {
+            f32x16 (&aq)[MT][NT] = accs[q == 3 ? 0 : q];
+            for (int s = 0; s < nst; ++s) {
+                const float* sa = smem + buf * STAGE;
+                const float* sb = sa + A_FLOATS;
+                issue_next();                                      // into the stage read in step s - 1: every wave is past that barrier
+#pragma unroll
+                for (int g = 0; g < 4; ++g) mfma_group(aq, sa, sb, g);
+                lds_dma_wait_barrier();                            // the next step's stage is in LDS, this wave's part and everybody else's
+                buf = buf + 1 == RS_STAGES ? 0 : buf + 1;
+            }
+            // s0 is complete after point 2: its stores fly under point 3's K loop (they count in vmcnt like the loads: the first wait of that loop
+            // covers them, a whole K-step later) and point 3 accumulates into the freed set - three sets live instead of four.
+            if (q == 1) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) accs[0][0][0][r] = accs[0][0][0][r] + accs[1][0][0][r];              // t = m0 + m1
+            } else if (q == 2) {
+                store_plane(0, [&](int r) { return accs[0][0][0][r] + accs[2][0][0][r]; });                       // s0 = t + m2
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { accs[1][0][0][r] = accs[1][0][0][r] - accs[2][0][0][r]; accs[0][0][0][r] = 0.f; }   // u = m1 - m2
+            }
+        }
+        FORGE_STAMP(2);
+        store_plane(1, [&](int r) { return accs[1][0][0][r] - accs[0][0][0][r]; });                               // s1 = u - m3
+        FORGE_STAMP(3);
+        return;
     }
 
     FORGE_STAMP(2);
@@ -451,26 +536,6 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
             }
         }
     };
-    if constexpr (RS) {                                             // row stage of A^T M A over the four points, two planes stored (identity rows, no bias)
-        float* const o0 = a.out + pb * a.pto;                        // plane (i' = 0, j)
-        float* const o1 = a.out + (pb + 4) * a.pto;                  // plane (i' = 1, j)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const int col = n0 + wn * (BN / WN) + j * 32 + l31;
-            if (col < a.Cout) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const long long orow = s_row[wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half];
-                    if (orow >= 0) {
-                        const float m0 = accs[0][0][j][r], m1 = accs[1][0][j][r], m2 = accs[NP - 2][0][j][r], m3 = accs[NP - 1][0][j][r];
-                        o0[orow * a.ldo + col] = (m0 + m1) + m2;
-                        o1[orow * a.ldo + col] = (m1 - m2) - m3;
-                    }
-                }
-            }
-        }
-        return;
-    }
     if (a.ksplit > 1) {                                             // raw partial sums; conv_splitk_epilogue_kernel finishes the job
         float* wsl = a.ws + (long long)ks * M * a.Cout;
 #pragma unroll
@@ -897,7 +962,8 @@ static int launch_conv_tile(const ConvArgs& a, char tile, hipStream_t st, bool r
     if (row_stage) {                                                 // forge_wino_gemm_half: a.nbat = 4 point columns, four points per workgroup
         const long long grid = nblk(64, 128) * a.nbat;
         FORGE_REQUIRE(grid < (1ll << 31), FORGE_ESHAPE, "forge_wino_gemm_half: grid too large");
-        const size_t lds = 2 * (64 * BK + 128 * BK) * sizeof(float);
+        FORGE_REQUIRE(M * a.ldo * 4 < (1ll << 31), FORGE_ESHAPE, "forge_wino_gemm_half: an output plane spans >= 2 GiB (32-bit buffer offsets); split the batch");
+        const size_t lds = RS_STAGES * (64 * BK + 128 * BK) * sizeof(float);
         FORGE_SET_MAX_LDS_ONCE((conv_igemm_kernel<64, 128, 8, 1, 1>), lds);
         hipLaunchKernelGGL((conv_igemm_kernel<64, 128, 8, 1, 1>), dim3((unsigned)grid), dim3(8 * 64), lds, st, a);
         return 0;

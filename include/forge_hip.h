@@ -274,7 +274,8 @@ int forge_wino_gemm(const float* V1, int C1, int ld1, long long bs1, long long p
  * one workgroup runs the four points (i = 0..3, j) of a point column on its 64 x 128 tile and stores s0 = (m0 + m1) + m2, s1 = (m1 - m2) - m3 - the
  * operations forge_wino_output performs first, in its order - as Mm8 [2][4][R][Cout]: the point products cross HBM as 2x instead of 4x the output
  * tensor. forge_wino_output_half runs the column stage + the same fused tails on Mm8. Without a second addend the results are bitwise those of
- * forge_wino_gemm + forge_wino_output; a second addend (the shared input halves) arrives in the same 8-plane form and is added after the row stage. For the launches forge_wino_gemm_tile answers with 'B' (R >= 2048 tile rows, Cout > 64). */
+ * forge_wino_gemm + forge_wino_output; a second addend (the shared input halves) arrives in the same 8-plane form and is added after the row stage. For the launches forge_wino_gemm_tile answers with 'B' (R >= 2048 tile rows, Cout > 64).
+ * One output plane (R x Cout floats) must stay below 2 GiB (FORGE_ESHAPE otherwise): the planes are stored through 32-bit buffer offsets. */
 int forge_wino_gemm_half(const float* V1, int C1, int ld1, long long bs1, long long pt1, const float* V2, int C2, int ld2, long long bs2,
                          long long pt2, const float* U, float* Mm8, int n, int D, int Ht, int Wt, int Cout, int kd, forge_stream_t stream);
 int forge_wino_output_half(const float* Mm8, const float* Mm2_8 /* nullable second addend, 8 planes too */, long long bs2, long long pt2, const float* bias, const float* scale,

@@ -1,0 +1,81 @@
+"""The register / LDS budget the implicit-GEMM launches are scheduled for, checked on the compiler's own resource remarks (no GPU needed, only hipcc).
+
+The four-point Winograd form (conv_igemm_kernel<64, 128, 8, 1, 1>, forge_wino_gemm_half) is launched with RS_STAGES x 24 KB of dynamic LDS and
+is meant to run THREE workgroups per CU: that needs 6 waves per SIMD (at most 80 VGPRs), no scratch, and 3 x its LDS within the CU's 160 KB.
+Tile B (<64, 128, 8, 1, 0>) keeps three 48 KB workgroups per CU (plan_conv's occupancy 3)."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "forge_amd", "csrc", "conv_igemm.hip")
+LDS_PER_CU = 160 * 1024
+WAVES_PER_WORKGROUP, SIMDS = 8, 4
+
+
+def _hipcc():
+    from forge_amd import build
+    try:
+        return build.hipcc()
+    except RuntimeError:
+        return shutil.which("hipcc")
+
+
+@pytest.fixture(scope="module")
+def remarks(tmp_path_factory):
+    cc = _hipcc()
+    if not cc:
+        pytest.skip("hipcc not found")
+    from forge_amd import build
+    obj = str(tmp_path_factory.mktemp("res") / "conv_igemm.o")
+    p = subprocess.run([cc] + build.FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-x", "hip", "-c", SRC, "-o", obj],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert p.returncode == 0, p.stdout[-4000:]
+    out, cur = {}, None
+    for line in p.stdout.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            cur = out.setdefault(m.group(1), {})
+            continue
+        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+) \[-Rpass", line)
+        if m and cur is not None:
+            cur[m.group(1).strip()] = int(m.group(2))
+    return out
+
+
+def _kernel(remarks, rs):
+    name = "_ZN5forge17conv_igemm_kernelILi64ELi128ELi8ELi1ELi%dEEEvNS_8ConvArgsE" % rs
+    assert name in remarks, sorted(remarks)
+    return remarks[name]
+
+
+def _constants():
+    src = open(SRC).read()
+    stages = int(re.search(r"constexpr int RS_STAGES = (\d+);", src).group(1))
+    bk = int(re.search(r"constexpr int BK = (\d+),", src).group(1))
+    assert "const size_t lds = RS_STAGES * (64 * BK + 128 * BK) * sizeof(float);" in src      # the launcher sizes its LDS from the same constant
+    return stages, (64 * bk + 128 * bk) * 4
+
+
+def _resident_by_registers(k):
+    return k["Occupancy"] * SIMDS // WAVES_PER_WORKGROUP
+
+
+def test_four_point_form_keeps_three_workgroups_per_cu(remarks):
+    k = _kernel(remarks, 1)
+    stages, stage_bytes = _constants()
+    assert k["ScratchSize"] == 0 and k.get("VGPRs Spill", 0) == 0 and k.get("SGPRs Spill", 0) == 0
+    resident = _resident_by_registers(k)
+    assert resident >= 3, "four-point form: %d VGPRs, %d waves per SIMD" % (k["VGPRs"], k["Occupancy"])
+    assert resident * stages * stage_bytes <= LDS_PER_CU, "the registers admit %d workgroups, the LDS does not" % resident
+
+
+def test_tile_b_keeps_three_48k_workgroups_per_cu(remarks):
+    k = _kernel(remarks, 0)
+    _, stage_bytes = _constants()
+    assert k["ScratchSize"] == 0
+    assert 2 * stage_bytes == 48 * 1024 and 3 * 2 * stage_bytes <= LDS_PER_CU
+    assert _resident_by_registers(k) >= 3
