@@ -1135,7 +1135,8 @@ static int wino_gemm_impl(const float* V1, int C1, int ld1, long long bs1, long 
                   "forge_wino_gemm: an operand spans >= 2 GiB per Winograd point (32-bit buffer offsets); split the batch");
     a.wp = U; a.slope = 1.f; a.out = Mm; a.n = n; a.D = D; a.H = Ht; a.W = Wt; a.is = 1; a.Di = D; a.Hi = Ht; a.Wi = Wt;
     a.Cout = Cout; a.ldo = Cout; a.ldr = Cout; a.ntaps = kd; a.os = 1; a.Do = D; a.Ho = Ht; a.Wo = Wt; a.nphase = 1; a.tpp = kd; a.epi = EPI_BIAS;
-    a.ksplit = 1; a.nbat = half ? 4 : 16; a.pt1 = pt1; a.pt2 = pt2; a.ptw = (long long)kd * Cout * (C1 + C2); a.pto = R * Cout;
+    a.ksplit = 1; a.nbat = half ? 4 : 16; a.pt1 = pt1 > 0 ? pt1 : R * ld1; a.pt2 = V2 ? (pt2 > 0 ? pt2 : R * ld2) : 0;   // 0 = dense planes, as forge_wino_wgrad reads it
+    a.ptw = (long long)kd * Cout * (C1 + C2); a.pto = R * Cout;
     if (kd == 3) { a.tap[0][0] = -1; a.tap[2][0] = 1; }                 // depth taps (-1,0,0), (0,0,0), (1,0,0); kd = 1: the 2-D convolution's single tap
     if (int rc = launch_conv_tile(a, (char)(tile ? tile : forge_wino_gemm_tile(R, Cout, C1 + C2)), (hipStream_t)stream, half)) return rc;
     FORGE_LAUNCH_CHECK("forge_wino_gemm");

@@ -12,8 +12,8 @@
 //   wino_output_kernel   y = epilogue(A^T Mm A)               HBM-bound: reads 4x the output size, fuses the same element-wise tails
 //                                                             as the direct kernel (bias, folded BN + LeakyReLU, GRU gates / state update)
 // B^T and A^T hold only 0 / +-1: the transforms are exact additions; the only extra rounding relative to the direct kernel is in
-// U = G w G^T (rounded once, on the host, from a float64 product) and in the order of the fp32 additions. Measured against a float64
-// convolution the fp32 error is 1.4x that of a direct fp32 convolution (tests/test_gpu_winograd.py).
+// U = G w G^T (rounded once from a float64 product) and in the order of the fp32 additions. Measured against a float64 convolution the
+// fp32 error is 0.43-1.47x (maximum) / 0.60-1.51x (rms) that of the direct fp32 kernel (tests/test_gpu_wino_matrix.py, profiles/r11_wino_matrix.txt).
 #include "common.h"
 
 namespace forge {
@@ -415,6 +415,9 @@ static int wino_output_impl(const float* Mm, const float* Mm2, long long bs2, lo
     FORGE_REQUIRE(n > 0 && D > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && Cout > 0 && Cout % 8 == 0 && ldo % 4 == 0, FORGE_ESHAPE,
                   "forge_wino_output: n=%d D=%d H=%d W=%d Cout=%d ldo=%d (H, W even; Cout multiple of 8; ldo of 4)", n, D, H, W, Cout, ldo);
     FORGE_REQUIRE(epilogue >= 0 && epilogue <= 3, FORGE_EINVAL, "forge_wino_output: unknown epilogue %d", epilogue);
+    // ldo: the row stride of out (and of out2 / out3 of the GRU state epilogue). The gate epilogue writes dense rows of Cout / 2 floats and takes no other.
+    FORGE_REQUIRE(epilogue == W_GRU_GATES ? ldo == Cout / 2 : ldo >= Cout, FORGE_ESHAPE,
+                  "forge_wino_output: ldo=%d (epilogues 0, 1, 3: ldo >= Cout=%d; epilogue 2: ldo == Cout / 2)", ldo, Cout);
     FORGE_REQUIRE(epilogue != W_AFFINE_ACT || (scale && shift), FORGE_EINVAL, "forge_wino_output: affine epilogue needs scale/shift");
     FORGE_REQUIRE(epilogue != W_GRU_GATES || (aux_h && out2), FORGE_EINVAL, "forge_wino_output: GRU gate epilogue needs aux_h, out2");
     FORGE_REQUIRE(epilogue != W_GRU_OUT || (aux_h && aux_z && (!out2 || (scale && shift))), FORGE_EINVAL,

@@ -98,10 +98,12 @@ def run_layer(L, x, residual=None):
     epi = co.EPI_AFFINE_ACT if L["sc"] is not None else co.EPI_BIAS
     if residual is not None and not residual.is_contiguous():
         residual = residual.contiguous()
-    if L["U"] is not None and co.wino_applies(L["taps"], 1, n, D, H, W, C, 0, Cout):
+    # a residual goes to the direct kernel: forge_wino_output's affine epilogue adds it BEFORE the affine map (include/forge_hip.h), which is
+    # not the formula above unless scale = 1
+    if L["U"] is not None and residual is None and co.wino_applies(L["taps"], 1, n, D, H, W, C, 0, Cout):
         V = co.wino_input(x, C, C, n, D, H, W)
         Mm = co.wino_gemm(V, C, None, 0, L["U"], None, n, D, H // 2, W // 2, Cout)
-        co.wino_output(Mm, L["bias"], L["sc"], L["sh"], L["slope"], residual, None, None, out, None, None, n, D, H, W, Cout, Cout, epi)
+        co.wino_output(Mm, L["bias"], L["sc"], L["sh"], L["slope"], None, None, None, out, None, None, n, D, H, W, Cout, Cout, epi)
     else:
         co.conv_igemm(x, C, C, None, 0, 0, L["wp"], L["bias"], L["sc"], L["sh"], L["slope"], residual, None, None, out, None,
                       (n, Do, Ho, Wo), (D, H, W), Cout, Cout, L["taps"], istride=s, epilogue=epi)

@@ -239,9 +239,18 @@ int forge_conv_igemm_plan(long long M, int Cout, int Cin, int ntaps, int nphase,
  *   forge_wino_gemm    Mm[p][r][co] = sum_kd sum_ci U[p][kd][co][ci] (V1 | V2)[p][r + kd plane][ci]  for the 16 points in ONE launch of the
  *                      fp32-MFMA implicit-GEMM kernel (forge_conv_igemm's: 3 depth taps over the (n, D, Ht, Wt) tile grid, K = 3 (C1+C2));
  *                      V1 / V2: channel-concatenated operands (V2 nullable with C2 = 0) with row strides ld, batch strides bs rows
- *                      (0 = dense) and point strides pt floats; U [16][3][Cout][C1+C2]; Mm [16][R][Cout] dense. C1, C2 % 32 == 0.
- *   forge_wino_output  y = A^T (Mm + Mm2) A per tile, then forge_conv_igemm's epilogue 0..3 with the same operands (bias, scale/shift/slope,
- *                      residual [rows][Cout] added to the pre-activation, aux_h / aux_z, out / out2 / out3; out rows of ldo floats).
+ *                      (0 = dense) and point strides pt floats (0 = dense planes of R rows, R ld:
+ *                      with a batch stride bs > D Ht Wt the planes are longer than that - pass pt explicitly, here and to forge_wino_wgrad); U [16][kd][Cout][C1+C2]; Mm [16][R][Cout] dense. C1, C2 % 32 == 0,
+ *                      Cout > 16. tile: 0 = forge_wino_gemm_tile's rule (Cout <= 64: 'D' below 2048 tile rows, 'C' from there; wider: 'D' / 'B'), or 'A'..'E'.
+ *   forge_wino_output  y = A^T (Mm + Mm2) A per tile (row stage first: s = A^T m over i as (m0 + m1) + m2 | (m1 - m2) - m3, then the same over j),
+ *                      v = y + bias + residual (residual [rows][Cout] DENSE, nullable, in EVERY epilogue), then the tail on forge_conv_igemm's operands:
+ *                        0  out = v                                  1  out = lrelu(v * scale + shift, slope)
+ *                        2, 3  forge_conv_igemm's GRU gates / state on the pre-activation v (aux_h / aux_z / out2 / out3 as there)
+ *                      Epilogue 1 is NOT forge_conv_igemm's: the residual is added BEFORE the affine map here, after it there; the two agree when
+ *                      scale = 1 (how convops.conv3_launch uses the direct kernel) or without a residual.
+ *                      ldo: row stride in floats of out (epilogues 0, 1, 3; also of out2 / out3 of epilogue 3), ldo >= Cout and a multiple of 4.
+ *                      Epilogue 2 writes out / out2 / out3 as dense rows of Cout / 2 floats and accepts ldo == Cout / 2 only. aux_h / aux_z /
+ *                      residual rows are always dense (Cout, or Cout / 2 for the gates' aux_h). FORGE_ESHAPE otherwise.
  *                      Mm2 (nullable): a second set of point products with batch stride bs2 rows and point stride pt2 floats (0 = as Mm) -
  *                      the input half conv(x, W_x) of conv([x, h], W), computed once per view when several fusions share views.
  *   forge_wino_weights U [16][kd][Cout][Cin] = G w[kd] G^T from forge_conv_igemm's packed weights wp [9 kd][Cout][Cin] (float64 inside, rounded
@@ -250,7 +259,9 @@ int forge_conv_igemm_plan(long long M, int Cout, int Cin, int ntaps, int nphase,
  * kd = 3: 3x3x3 kernels (three depth taps summed inside the point GEMMs); kd = 1: the 3x3 kernels of a 2-D convolution (ResNet
  * bottlenecks: the planes of the (n, D) grid do not mix, so images can sit on either axis).
  * B^T and A^T hold 0 / +-1 only (exact additions); U is rounded once from a float64 product. Not bit-identical to
- * forge_conv_igemm (different order of the fp32 additions); error vs a float64 convolution is ~1.4x the direct fp32 kernel's. */
+ * forge_conv_igemm (different order of the fp32 additions); measured against a float64 convolution in units of u sum |x||w|
+ * (profiles/r11_wino_matrix.txt) the maximum error is 0.43-1.47x and the rms error 0.60-1.51x the direct fp32 kernel's: smaller on the long 3-D reductions (one
+ * fused-multiply-add chain of K = 27 Cin there, 16 chains of 3 Cin here), larger on the 2-D forms and on short reductions, where the transforms' additions dominate. */
 int forge_wino_weights(const float* wp, float* U, int Cout, int Cin, int kd, int transpose, forge_stream_t stream);
 /* Weight gradient of the same convolution in the Winograd domain (training): dMm = A dy A^T (forge_wino_dy, the adjoint of the inverse
  * transform; dM [16][R][Cout]), dU[p][kd][co][ci] = sum_r dMm[p][r][co] (V1 | V2)[p][r + kd plane][ci] (forge_wino_wgrad: the weight-gradient

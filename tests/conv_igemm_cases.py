@@ -328,6 +328,38 @@ def _accumulate(case, d, taps, wp, dtype, grain, ksplit, mut, want_S):
     return acc, S
 
 
+def gru_tail(epi, v, S, rs, h, z, scale, shift, out2):
+    """The GRU epilogues on the pre-activation v [M][Cout] (bias included, residual rs - nullable - not yet): what forge_conv_igemm and forge_wino_output
+    both compute. epi 2: g = sigmoid(v + rs); out = g[:, :Ch], out2 = h g[:, Ch:], out3 = g[:, Ch:]. epi 3: cand = tanh(v + rs), out = h (1 - z) + cand z,
+    out2 (if asked) = out scale + shift, out3 = cand. S: the magnitude sum of v (None: no sigmas). Returns ({outputs}, {sigma_S}, {sigma_A})."""
+    o, oS, oA = {}, {}, {}
+    want_S = S is not None
+    if rs is not None:
+        v = v + rs
+    if epi == 2:
+        Ch = v.shape[1] // 2
+        g = torch.sigmoid(v)
+        o["out"], o["out2"], o["out3"] = g[:, :Ch], h * g[:, Ch:], g[:, Ch:]
+        if want_S:
+            gS, gA = S / 4, (rs.abs() / 4 if rs is not None else 0) + g
+            oS["out"], oA["out"] = gS[:, :Ch], gA[:, :Ch]
+            oS["out2"], oA["out2"] = h.abs() * gS[:, Ch:], h.abs() * gA[:, Ch:]
+            oS["out3"], oA["out3"] = gS[:, Ch:], gA[:, Ch:]
+    else:
+        cand = torch.tanh(v)
+        hn = h * (1 - z) + cand * z
+        o["out"], o["out3"] = hn, cand
+        if out2:
+            o["out2"] = hn * scale + shift
+        if want_S:
+            cS, cA = S, (rs.abs() if rs is not None else 0) + cand.abs()
+            oS["out"], oA["out"] = z.abs() * cS, z.abs() * cA + (h * (1 - z)).abs() + (cand * z).abs()
+            oS["out3"], oA["out3"] = cS, cA
+            if out2:
+                oS["out2"], oA["out2"] = scale.abs() * oS["out"], scale.abs() * oA["out"] + shift.abs()
+    return o, oS, oA
+
+
 def evaluate(case, d, dtype=torch.float64, grain="tap", ksplit=1, mut=None):
     """The contract evaluated in `dtype` on the CPU. Returns {"out" / "out2" / "out3": [rows][width] with NaN in rows the launch does not name,
     "named": bool [rows], "sig_S" / "sig_A": {output: [rows][width]} (float64 evaluation only), "pre": the pre-activations in GEMM-row order}."""
@@ -375,39 +407,9 @@ def evaluate(case, d, dtype=torch.float64, grain="tap", ksplit=1, mut=None):
             if want_S:
                 oS["out"] = L * scale.abs() * S
                 oA["out"] = L * (shift.abs() + (rs.abs() if rs is not None else 0)) + torch.zeros_like(S)
-        elif case.epi == 2:
-            Ch = case.Cout // 2
-            if rs is not None:
-                v = v + rs
-            g = torch.sigmoid(v)
-            h = aux_h[orow]
-            o["out"], o["out2"] = g[:, :Ch], h * g[:, Ch:]
-            if case.out3:
-                o["out3"] = g[:, Ch:]
-            if want_S:
-                gS, gA = S / 4, (rs.abs() / 4 if rs is not None else 0) + g
-                oS["out"], oA["out"] = gS[:, :Ch], gA[:, :Ch]
-                oS["out2"], oA["out2"] = h.abs() * gS[:, Ch:], h.abs() * gA[:, Ch:]
-                oS["out3"], oA["out3"] = gS[:, Ch:], gA[:, Ch:]
         else:
-            if rs is not None:
-                v = v + rs
-            cand = torch.tanh(v)
-            z, h = aux_z[orow], aux_h[orow]
-            if mut == "swap_z":
-                z = 1 - z
-            hn = h * (1 - z) + cand * z
-            o["out"] = hn
-            if case.out2:
-                o["out2"] = hn * scale + shift
-            if case.out3:
-                o["out3"] = cand
-            if want_S:
-                cS, cA = S, (rs.abs() if rs is not None else 0) + cand.abs()
-                oS["out"], oA["out"] = z.abs() * cS, z.abs() * cA + (h * (1 - z)).abs() + (cand * z).abs()
-                oS["out3"], oA["out3"] = cS, cA
-                if case.out2:
-                    oS["out2"], oA["out2"] = scale.abs() * oS["out"], scale.abs() * oA["out"] + shift.abs()
+            z = None if aux_z is None else (1 - aux_z[orow] if mut == "swap_z" else aux_z[orow])
+            o, oS, oA = gru_tail(case.epi, v, S if want_S else None, rs, aux_h[orow], z, scale, shift, case.out2)
         for k in desc:
             val = o[k]
             if mut == "shift_block" and M > 65:                    # rows 32..63 take the values of rows 33..64

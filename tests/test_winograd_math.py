@@ -3,9 +3,7 @@ weight-gradient forms of Winograd F(2x2, 3x3) x 3 depth taps against torch's con
 matrices and index conventions (tile row r = ((n D + z) H/2 + th) W/2 + tw, point p = 4 i + j, patch rows 2 th - 1 .., cols 2 tw - 1 ..)."""
 import torch
 
-BT = torch.tensor([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1.]], dtype=torch.float64)
-G = torch.tensor([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1.]], dtype=torch.float64)
-AT = torch.tensor([[1, 1, 1, 0], [0, 1, -1, -1.]], dtype=torch.float64)
+from wino_cases import AT, BT, G          # the one place the three matrices are written down (tests/wino_cases.py)
 
 
 def _input_transform(x):
