@@ -4,6 +4,8 @@ Host-side plumbing only: layout checks, output allocation, stream hand-off, auto
 All arithmetic of the hot path happens in forge_amd/csrc/*.hip. There is no CPU implementation
 here: calling these ops with CPU tensors (or without the built library) raises.
 """
+import os
+
 import torch
 
 from . import _lib, determinism
@@ -247,3 +249,84 @@ def attention(q, k, v):
     _lib.check(_lib.lib().forge_attention_fwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), 0 if v.shape[0] == 1 and B > 1 else Nk, _lib.ptr(out), B, Nq, Nk, d,
                                               _lib.current_stream()), "forge_attention_fwd")
     return out
+
+
+# ---- differentiable attention (training), opt-in: forge_attention_fwd_lse / forge_attention_bwd. Off by default - with the switch off nothing
+# in the package calls the two entry points and every training attention stays on torch's differentiable ops, bit for bit as before.
+_attention_training = os.environ.get("FORGE_ATTENTION_TRAIN", "0") == "1"          # read once, at import
+
+
+def set_attention_training(flag):
+    """True: attentions inside an autograd graph run ops.attention_train (where attention_train_applies holds); False (the default, or
+    FORGE_ATTENTION_TRAIN unset at import): they keep torch's matmul - softmax - matmul. Returns the previous setting."""
+    global _attention_training
+    if not isinstance(flag, bool):
+        raise TypeError("set_attention_training takes True or False (got %r)" % (flag,))
+    prev, _attention_training = _attention_training, flag
+    return prev
+
+
+def attention_training():
+    """The current setting of set_attention_training()."""
+    return _attention_training
+
+
+def _attention_train_domain(q, k, v):
+    """attention_applies' shape / dtype / device rules without its grad-mode clause, plus: a value table shared by the batch (v [1,Nk,64], B > 1)
+    is a constant - forge_attention_bwd does not sum a gradient over the batch for it."""
+    return (q.is_cuda and k.device == q.device and v.device == q.device
+            and q.dtype == torch.float32 and k.dtype == torch.float32 and v.dtype == torch.float32
+            and q.dim() == 3 and k.dim() == 3 and v.dim() == 3 and q.shape[-1] == 64 and k.shape[-1] == 64 and v.shape[-1] == 64
+            and q.shape[0] == k.shape[0] and v.shape[0] in (1, q.shape[0]) and v.shape[1] == k.shape[1]
+            and q.shape[1] % 64 == 0 and k.shape[1] % 64 == 0 and q.shape[1] > 0 and k.shape[1] > 0
+            and not (v.shape[0] == 1 and q.shape[0] > 1 and v.requires_grad))
+
+
+def attention_train_applies(q, k, v):
+    """ops.attention_train's domain, and the switch (set_attention_training / FORGE_ATTENTION_TRAIN=1) is on."""
+    return _attention_training and _attention_train_domain(q, k, v)
+
+
+class _AttentionTrain(torch.autograd.Function):
+    """forge_attention_fwd_lse / forge_attention_bwd: saved for backward are q, k, v, out and lse [B,Nq] - never a [B,Nq,Nk] matrix."""
+
+    @staticmethod
+    @_lib.on_tensor_device
+    def forward(ctx, q, k, v):
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        B, Nq, d = q.shape
+        Nk = k.shape[1]
+        out = torch.empty(B, Nq, d, dtype=torch.float32, device=q.device)
+        lse = torch.empty(B, Nq, dtype=torch.float32, device=q.device)
+        ctx.v_rows = 0 if v.shape[0] == 1 and B > 1 else Nk
+        _lib.check(_lib.lib().forge_attention_fwd_lse(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), ctx.v_rows, _lib.ptr(out), _lib.ptr(lse), B, Nq, Nk, d,
+                                                      _lib.current_stream()), "forge_attention_fwd_lse")
+        ctx.save_for_backward(q, k, v, out, lse)
+        return out
+
+    @staticmethod
+    @_lib.on_tensor_device
+    def backward(ctx, dout):
+        q, k, v, out, lse = ctx.saved_tensors
+        B, Nq, d = q.shape
+        Nk = k.shape[1]
+        dout = dout.contiguous()
+        dq, dk = torch.empty_like(q), torch.empty_like(k)                       # written in full by the kernels: no zero-fills
+        dv = torch.empty_like(v) if ctx.needs_input_grad[2] and ctx.v_rows else None
+        delta = torch.empty(B, Nq, dtype=torch.float32, device=q.device)
+        _lib.check(_lib.lib().forge_attention_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), ctx.v_rows, _lib.ptr(out), _lib.ptr(lse), _lib.ptr(dout),
+                                                  _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(delta), B, Nq, Nk, d, _lib.current_stream()),
+                   "forge_attention_bwd")
+        return dq, dk, dv
+
+
+def attention_train(q, k, v):
+    """ops.attention inside an autograd graph: softmax(q k^T) v (same kernel, same bits) with a HIP backward that recomputes the softmax from the
+    saved log-sum-exp - no [B,Nq,Nk] matrix forward or backward, no atomics (bitwise reproducible). q [B,Nq,64], k [B,Nk,64], v [B,Nk,64] or a
+    constant [1,Nk,64] shared by the batch. Independent of the switch (that gates attention_train_applies, the models' dispatch); outside the
+    domain it raises."""
+    if not _attention_train_domain(q, k, v):
+        raise RuntimeError("forge_amd: ops.attention_train needs fp32 [B,N,64] tensors on the MI355X with token counts that are multiples of 64, and a "
+                           "value table shared by the batch must not require grad (got q %s, k %s, v %s%s)"
+                           % (tuple(q.shape), tuple(k.shape), tuple(v.shape), ", v.requires_grad" if v.requires_grad else ""))
+    return _AttentionTrain.apply(q, k, v)

@@ -4,8 +4,10 @@ models/pose_estimator_3d.py:9-144 and the Block/Attention/Mlp/positional-embeddi
 
 On the MI355X its eight 3x3x3 convolutions (stride 1 and 2) + BatchNorm + LeakyReLU run on libforge_hip.so (convops.conv3d_rows, bn_act_rows on
 channels-last rows; round 5): in the joint fine-tune step (BASELINE configs[4]) MIOpen served them with its `naive_conv_*` fp32 kernels - 164 ms
-of a 256 ms step (profiles/r05_joint_grid32_kernel_share_before.txt). The attention block (1x1 projections, 4096-token softmax, MLP) stays
-stock torch (rocBLAS GEMMs). CPU tensors run the same modules on torch's own kernels (the architecture pin of tests/test_oracle_golden.py)."""
+of a 256 ms step (profiles/r05_joint_grid32_kernel_share_before.txt). The attention block's 1x1 projections and MLP stay stock torch (rocBLAS
+GEMMs); its 4096-token softmax attentions run on forge_attention_fwd in inference and, in training, on torch's differentiable ops unless
+ops.set_attention_training(True) (or FORGE_ATTENTION_TRAIN=1) routes them to forge_attention_fwd_lse / forge_attention_bwd. CPU tensors run
+the same modules on torch's own kernels (the architecture pin of tests/test_oracle_golden.py)."""
 import math
 
 import torch
@@ -51,6 +53,8 @@ class Attention(nn.Module):
             from . import ops
             if ops.attention_applies(query, key, value):                  # inference on the MI355X: the N x N matrix never leaves registers
                 return ops.attention(query, key, value)
+            if ops.attention_train_applies(query, key, value):            # training, opt-in (ops.set_attention_training): HIP forward + backward
+                return ops.attention_train(query, key, value)
         split = lambda x: x.reshape(B, N, self.num_heads, C // self.num_heads).permute(0, 2, 1, 3)
         q, k, v = split(query), split(key), split(value)
         attn = torch.matmul(q, k.transpose(-2, -1)).softmax(dim=-1)
@@ -109,7 +113,7 @@ class Block(nn.Module):
         from . import ops
         q, k = self.qk_tokens(query, key)
         v = self._lin(self.encode_value, key)
-        x = query + (ops.attention(q, k, v) if ops.attention_applies(q, k, v) else self.attn(query=q, key=k, value=v))
+        x = query + (ops.attention(q, k, v) if ops.attention_applies(q, k, v) else self.attn(query=q, key=k, value=v))    # (attn: the opt-in training kernels)
         return x + self.mlp(self.norm2(x))
 
     def get_attn(self, query, key, query_embed=None, key_embed=None):
@@ -153,7 +157,12 @@ class PoseTransformer(nn.Module):
         from . import ops
         pe = self._pos_embed(q)
         qn, kn = self.cross_transformer.qk_tokens(q, k)
-        coord = ops.attention(qn, kn, pe) if ops.attention_applies(qn, kn, pe) else torch.matmul(self.cross_transformer.attn.get_attn(query=qn, key=kn), pe)
+        if ops.attention_applies(qn, kn, pe):
+            coord = ops.attention(qn, kn, pe)
+        elif ops.attention_train_applies(qn, kn, pe):                     # training, opt-in: the table is a constant shared by the batch (no dv)
+            coord = ops.attention_train(qn, kn, pe)
+        else:
+            coord = torch.matmul(self.cross_transformer.attn.get_attn(query=qn, key=kn), pe)
         return self.self_transformer.forward_tokens(coord, coord)
 
     def forward(self, q, k, q_pe=None, k_pe=None):
@@ -163,6 +172,10 @@ class PoseTransformer(nn.Module):
         if ops.attention_applies(qn, kn, pe):
             # inference on the MI355X: softmax(q k^T) pe in one launch instead of the [B,N,N] matrix + softmax + matmul
             coord = ops.attention(qn, kn, pe).permute(0, 2, 1)            # [B,C,N]
+            return self.self_transformer(query=coord, key=coord)
+        if ops.attention_train_applies(qn, kn, pe):
+            # training, opt-in (ops.set_attention_training): the same launch with its log-sum-exp saved, and a HIP backward that recomputes the softmax
+            coord = ops.attention_train(qn, kn, pe).permute(0, 2, 1)      # [B,C,N]
             return self.self_transformer(query=coord, key=coord)
         attn = self.cross_transformer.attn.get_attn(query=qn, key=kn)    # [B,N,N] (autograd path)
         coord = torch.matmul(attn, pe).permute(0, 2, 1)                  # [B,C,N]

@@ -447,6 +447,27 @@ int forge_affine_act_bwd(const float* dy, int ld_dy, const float* y, int ld_y, c
 int forge_attention_fwd(const float* q, const float* k, const float* v, long long v_batch_rows, float* out, int B, int Nq, int Nk, int d,
                         forge_stream_t stream);
 
+/* The differentiable pair of forge_attention_fwd, for TRAINING the pose estimator (opt-in on the Python side: ops.set_attention_training).
+ * forge_attention_fwd_lse: forge_attention_fwd (same kernel, same launch rule, `out` bit for bit the same) that also writes
+ *   lse[B][Nq] = ln sum_keys exp(q . k), the natural-log sum-exp of the unscaled logits - all the backward needs to recompute the softmax.
+ * forge_attention_bwd: gradients of out = softmax(q k^T) v for the upstream gradient dout [B][Nq][d]. The softmax P = exp(q k^T - lse) is
+ *   recomputed tile by tile from the saved lse; nothing of size Nq x Nk is stored. Three launches on `stream`, no atomics - the results are
+ *   bitwise reproducible from run to run:
+ *     delta_ws[B][Nq] = sum_c dout out          (workspace of B Nq floats owned by the caller; nothing is allocated inside)
+ *     dq = dS k            with dS = P o (dout v^T - delta)          (one wave per 32 queries walks the key tiles)
+ *     dk = dS^T q,  dv = P^T dout                                    (one wave per 32 keys walks the query tiles)
+ *   The dq pass also sums each row of dS (0 in exact arithmetic; with delta taken from the fp32 `out` it is the forward's rounding) and of P,
+ *   accumulates P k, and removes the residual: rho = sum dS / sum P, dq -= rho (P k), delta_ws += rho for the second pass - so that every row of
+ *   dS sums to zero as in a softmax backward that keeps the matrix. 8 contractions of 2 B Nq Nk d FLOPs with dv, 7 without.
+ *   dq [B][Nq][d], dk [B][Nk][d] and dv [B][Nk][d] (dense) are written in full: no pre-zeroing, no accumulation into them.
+ *   dv may be NULL: the dv chain is skipped. With one v shared by the batch (v_batch_rows = 0: the positional table, a constant) dv MUST be
+ *   NULL (FORGE_EINVAL otherwise).
+ * Domain and layouts as forge_attention_fwd: d = 64, Nq and Nk multiples of 64. */
+int forge_attention_fwd_lse(const float* q, const float* k, const float* v, long long v_batch_rows, float* out, float* lse, int B, int Nq, int Nk,
+                            int d, forge_stream_t stream);
+int forge_attention_bwd(const float* q, const float* k, const float* v, long long v_batch_rows, const float* out, const float* lse,
+                        const float* dout, float* dq, float* dk, float* dv, float* delta_ws, int B, int Nq, int Nk, int d, forge_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * a1  ResNet stem helpers (torchvision conv1/bn1/relu/maxpool behind models/encoder.py:71-73).
  * forge_im2col_nchw: img [N][C][H][W] -> patch rows out [N*Ho*Wo][Kpad], k = (ky*kw + kx)*C + c, zeros outside the image and
