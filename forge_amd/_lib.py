@@ -73,6 +73,8 @@ SIGNATURES = {
     "forge_attention_fwd": [_P, _P, _P, _LL, _P, _I, _I, _I, _I, _P],
     "forge_attention_fwd_lse": [_P, _P, _P, _LL, _P, _P, _I, _I, _I, _I, _P],
     "forge_attention_bwd": [_P, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "forge_attention_mh_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I] + [_LL] * 8 + [_F, _P],
+    "forge_attention_mh_bwd": [_P] * 10 + [_I, _I, _I, _I, _I] + [_LL] * 8 + [_F, _P],
     "forge_im2col_nchw": [_P, _P] + [_I] * 9 + [_P],
     "forge_maxpool2d_nhwc": [_P, _P] + [_I] * 7 + [_P],
     "forge_vgg_prep_fwd": [_P, _LL, _LL, _LL, _LL, _P, _LL, _LL, _LL, _LL, _P, _P, _P] + [_I] * 7 + [_P],

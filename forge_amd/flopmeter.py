@@ -1,7 +1,7 @@
 """Executed-FLOP meter for the matrix-core launches of libforge_hip.so (measurement aid for bench.py / tools; not on the product path).
 
 `with FlopMeter() as m: step()` wraps the ctypes entry points whose work runs on the fp32 MFMA pipe - forge_conv_igemm, forge_wino_gemm,
-forge_conv_wgrad, forge_wino_wgrad, forge_attention_fwd / _fwd_lse / _bwd - for the duration of the block and sums the FLOPs each launch EXECUTES, computed from the call's own
+forge_conv_wgrad, forge_wino_wgrad, forge_attention_fwd / _fwd_lse / _bwd / _mh_fwd / _mh_bwd - for the duration of the block and sums the FLOPs each launch EXECUTES, computed from the call's own
 arguments (2 M N taps Cin for a direct / data-gradient / weight-gradient convolution, 2 x 16 R N kd Cin for the 16 Winograd point problems).
 Only eager launches made by this process are seen (a hipGraph replay makes no Python calls): meter one eager pass, time the replay.
 """
@@ -45,8 +45,17 @@ def _attention_bwd(a):  # forge_attention_bwd(q,k,v,v_batch_rows,out,lse,dout,dq
     return (16.0 if dv else 14.0) * _v(a[11]) * _v(a[12]) * _v(a[13]) * _v(a[14])
 
 
+def _attention_mh(a):   # forge_attention_mh_fwd(q,k,v,out,lse,B,H,Nq,Nk,d,<8 strides>,scale,stream): the two contractions, per head
+    return 4.0 * _v(a[5]) * _v(a[6]) * _v(a[7]) * _v(a[8]) * _v(a[9])
+
+
+def _attention_mh_bwd(a):   # forge_attention_mh_bwd(q,k,v,out,lse,dout,dq,dk,dv,delta_ws,B,H,Nq,Nk,d,<8 strides>,scale,stream): as _attention_bwd, per head
+    return (16.0 if _v(a[8]) else 14.0) * _v(a[10]) * _v(a[11]) * _v(a[12]) * _v(a[13]) * _v(a[14])
+
+
 _ENTRIES = {"forge_conv_igemm": _igemm, "forge_wino_gemm": _wino_gemm, "forge_wino_gemm_half": _wino_gemm, "forge_conv_wgrad": _wgrad, "forge_wino_wgrad": _wino_wgrad,
-            "forge_attention_fwd": _attention, "forge_attention_fwd_lse": _attention_lse, "forge_attention_bwd": _attention_bwd}
+            "forge_attention_fwd": _attention, "forge_attention_fwd_lse": _attention_lse, "forge_attention_bwd": _attention_bwd,
+            "forge_attention_mh_fwd": _attention_mh, "forge_attention_mh_bwd": _attention_mh_bwd}
 
 
 class FlopMeter:

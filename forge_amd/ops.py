@@ -4,6 +4,7 @@ Host-side plumbing only: layout checks, output allocation, stream hand-off, auto
 All arithmetic of the hot path happens in forge_amd/csrc/*.hip. There is no CPU implementation
 here: calling these ops with CPU tensors (or without the built library) raises.
 """
+import math
 import os
 
 import torch
@@ -330,3 +331,120 @@ def attention_train(q, k, v):
                            "value table shared by the batch must not require grad (got q %s, k %s, v %s%s)"
                            % (tuple(q.shape), tuple(k.shape), tuple(v.shape), ", v.requires_grad" if v.requires_grad else ""))
     return _AttentionTrain.apply(q, k, v)
+
+
+# ---- multi-head attention (the 2-D pose estimator's six blocks), opt-in: forge_attention_mh_fwd / forge_attention_mh_bwd. Off by default - with
+# the switch off nothing in the package calls the two entry points and MultiHeadAttention runs torch's bmm - softmax - bmm, bit for bit as before.
+# Independent of set_attention_training (which keeps its meaning: the single-head attentions of the 3-D estimator inside an autograd graph).
+_multihead_attention = os.environ.get("FORGE_ATTENTION_MH", "0") == "1"            # read once, at import
+
+
+def set_multihead_attention(flag):
+    """True: MultiHeadAttention (forge_amd/pose_estimator_2d.py) runs ops.attention_mh / ops.attention_mh_train where attention_mh_applies holds;
+    False (the default, or FORGE_ATTENTION_MH unset at import): it keeps torch's head split - bmm - softmax - bmm - head merge. Returns the
+    previous setting."""
+    global _multihead_attention
+    if not isinstance(flag, bool):
+        raise TypeError("set_multihead_attention takes True or False (got %r)" % (flag,))
+    prev, _multihead_attention = _multihead_attention, flag
+    return prev
+
+
+def multihead_attention():
+    """The current setting of set_multihead_attention()."""
+    return _multihead_attention
+
+
+def _mh_strides(t):
+    """(batch stride, row stride) in floats as the kernels take them: a batch of one has no batch stride (torch reports an arbitrary one)."""
+    return (0 if t.shape[0] == 1 else t.stride(0)), t.stride(1)
+
+
+def _attention_mh_domain(q, k, v, num_heads):
+    """The domain of forge_attention_mh_fwd / _bwd: fp32 q [B,Nq,H*64], k / v [B,Nk,H*64] on one HIP device, channel stride 1, the other strides
+    multiples of 4 floats and the storage 16-byte aligned (float4 access), token counts multiples of 64."""
+    if not (isinstance(num_heads, int) and not isinstance(num_heads, bool) and num_heads >= 1):
+        return False
+    if not all(torch.is_tensor(t) and t.dim() == 3 and t.is_cuda and t.dtype == torch.float32 and t.device == q.device and t.shape[-1] == 64 * num_heads
+               for t in (q, k, v)):
+        return False
+    if not (q.shape[0] == k.shape[0] == v.shape[0] and k.shape[1] == v.shape[1] and q.shape[0] > 0
+            and q.shape[1] > 0 and k.shape[1] > 0 and q.shape[1] % 64 == 0 and k.shape[1] % 64 == 0):
+        return False
+    return all(t.stride(2) == 1 and t.data_ptr() % 16 == 0 and all(s >= 0 and s % 4 == 0 for s in _mh_strides(t)) for t in (q, k, v))
+
+
+def attention_mh_applies(q, k, v, num_heads, pad_mask=None, attn_mask=None, dropout_p=0.0, training=False):
+    """The dispatch predicate of MultiHeadAttention: the switch (set_multihead_attention / FORGE_ATTENTION_MH=1) is on, q / k / v are in the
+    kernels' domain (fp32 HIP tensors on one device, heads of 64 channels, token counts multiples of 64, float4-addressable strides), there is no
+    key-padding mask and no attention mask, and dropout is inactive (p == 0, or the module is in eval mode)."""
+    return (_multihead_attention and pad_mask is None and attn_mask is None and (dropout_p == 0 or not training)
+            and _attention_mh_domain(q, k, v, num_heads))
+
+
+def _mh_check(what, q, k, v, num_heads, scale):
+    if (_attention_mh_domain(q, k, v, num_heads) and isinstance(scale, (int, float)) and not isinstance(scale, bool)
+            and math.isfinite(scale) and scale > 0):
+        return
+    desc = lambda t: "%s %s strides %s %s" % (tuple(t.shape), str(t.dtype).replace("torch.", ""), tuple(t.stride()), t.device) if torch.is_tensor(t) else repr(t)
+    raise RuntimeError("forge_amd: ops.%s needs fp32 q [B,Nq,H*64] and k, v [B,Nk,H*64] on the MI355X with heads of 64 channels, token counts that are "
+                       "multiples of 64, channel stride 1, the other strides multiples of 4 floats, 16-byte aligned storage and a finite positive scale "
+                       "(got num_heads %r, scale %r, q %s, k %s, v %s)" % (what, num_heads, scale, desc(q), desc(k), desc(v)))
+
+
+def _mh_forward(q, k, v, num_heads, scale, want_lse):
+    B, Nq, C = q.shape
+    Nk = k.shape[1]
+    out = torch.empty(B, Nq, C, dtype=torch.float32, device=q.device)
+    lse = torch.empty(B, num_heads, Nq, dtype=torch.float32, device=q.device) if want_lse else None
+    _lib.check(_lib.lib().forge_attention_mh_fwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(out), _lib.ptr(lse), B, num_heads, Nq, Nk, 64,
+                                                 *_mh_strides(q), *_mh_strides(k), *_mh_strides(v), *_mh_strides(out), scale, _lib.current_stream()),
+               "forge_attention_mh_fwd")
+    return out, lse
+
+
+@_lib.on_tensor_device
+def attention_mh(q, k, v, num_heads, scale):
+    """softmax(scale q_h k_h^T) v_h for every head h, heads side by side in the channels as the q / k / v projections write them and o_proj reads
+    them: q [B,Nq,H*64], k / v [B,Nk,H*64] -> [B,Nq,H*64], without the head-split and head-merge copies and without the [B*H,Nq,Nk] matrix
+    (forge_attention_mh_fwd). Strided views (slices of a wider projection) are taken as they are. Inference only (no autograd node); independent of
+    the switch (that gates attention_mh_applies, the module's dispatch); outside the domain it raises."""
+    _mh_check("attention_mh", q, k, v, num_heads, scale)
+    return _mh_forward(q.detach(), k.detach(), v.detach(), num_heads, float(scale), False)[0]
+
+
+class _AttentionMHTrain(torch.autograd.Function):
+    """forge_attention_mh_fwd (with lse) / forge_attention_mh_bwd: saved for backward are q, k, v (as they came: views stay views), out and
+    lse [B,H,Nq] - never a [B*H,Nq,Nk] matrix."""
+
+    @staticmethod
+    @_lib.on_tensor_device
+    def forward(ctx, q, k, v, num_heads, scale):
+        out, lse = _mh_forward(q, k, v, num_heads, scale, True)
+        ctx.num_heads, ctx.scale = num_heads, scale
+        ctx.save_for_backward(q, k, v, out, lse)
+        return out
+
+    @staticmethod
+    @_lib.on_tensor_device
+    def backward(ctx, dout):
+        q, k, v, out, lse = ctx.saved_tensors
+        B, Nq, C = q.shape
+        Nk, H = k.shape[1], ctx.num_heads
+        dout = dout.contiguous()
+        mk = lambda n: torch.empty(B, n, C, dtype=torch.float32, device=q.device)     # dense, written in full by the kernels: no zero-fills
+        dq, dk = mk(Nq), mk(Nk)
+        dv = mk(Nk) if ctx.needs_input_grad[2] else None
+        delta = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
+        _lib.check(_lib.lib().forge_attention_mh_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(out), _lib.ptr(lse), _lib.ptr(dout), _lib.ptr(dq),
+                                                     _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(delta), B, H, Nq, Nk, 64, *_mh_strides(q), *_mh_strides(k),
+                                                     *_mh_strides(v), *_mh_strides(out), ctx.scale, _lib.current_stream()), "forge_attention_mh_bwd")
+        return dq, dk, dv, None, None
+
+
+def attention_mh_train(q, k, v, num_heads, scale):
+    """ops.attention_mh inside an autograd graph (same kernel, same bits) with a HIP backward that recomputes the softmax from the saved
+    log-sum-exp: no [B*H,Nq,Nk] matrix forward or backward, no atomics (bitwise reproducible). Independent of the switch; outside the domain it
+    raises."""
+    _mh_check("attention_mh_train", q, k, v, num_heads, scale)
+    return _AttentionMHTrain.apply(q, k, v, num_heads, float(scale))

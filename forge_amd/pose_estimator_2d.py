@@ -4,14 +4,19 @@ blocks of models/model_utils.py:258-427 (einops is not required).
 
 On the MI355X every convolution of the module - the FPN's LeakyReLU ResNet-50, its lateral / top / smoothing layers and the four stride-2
 convolutions of `conv` - runs on libforge_hip.so with HIP BatchNorm (round 5; FPN.forward_rows, PoseEstimator2D._conv_rows; in eval mode without
-an autograd graph as the inference schedule of forge_amd/frozen.py: one launch per convolution, BatchNorm folded); the six attention
-blocks stay stock torch (rocBLAS GEMMs, softmax, LayerNorm). One path: host tensors raise (the stock-torch evaluation of the same modules that
-tests and probes compare against lives in tools/stock_pose.py)."""
+an autograd graph as the inference schedule of forge_amd/frozen.py: one launch per convolution, BatchNorm folded). The six attention
+blocks' projections, LayerNorms and MLPs are stock torch (rocBLAS GEMMs); their softmax attention is stock torch too (head-split copies, bmm,
+softmax over a materialised [B*4,Nq,Nk] matrix, bmm, head-merge copy: eight launches) unless ops.set_multihead_attention(True) (or
+FORGE_ATTENTION_MH=1) routes it to forge_attention_mh_fwd / forge_attention_mh_bwd: one launch forward that reads the heads where the
+projections wrote them, three backward, no N x N matrix. Off by default. One path: host tensors raise (the stock-torch evaluation of the same
+modules that tests and probes compare against lives in tools/stock_pose.py; it calls these attention blocks, so it is stock only with the
+switch off)."""
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import ops as _ops
 from .convops import PackCache as _PackCache, PackedModule as _PackedModule
 
 
@@ -54,7 +59,12 @@ class MultiHeadAttention(nn.Module):
         if attn_mask is not None:
             raise NotImplementedError("attention masks not supported")
         b = x_q.shape[0]
-        q, k, v = self._heads(self.q_proj(x_q)), self._heads(self.k_proj(x_k)), self._heads(self.v_proj(x_v))
+        q, k, v = self.q_proj(x_q), self.k_proj(x_k), self.v_proj(x_v)
+        if _ops.attention_mh_applies(q, k, v, self.num_heads, pad_mask=pad_mask, attn_mask=attn_mask, dropout_p=self.dropout.p, training=self.training):
+            # opt-in (ops.set_multihead_attention; False whenever the switch is off): the kernels read the heads where the projections wrote them
+            attend = _ops.attention_mh_train if torch.is_grad_enabled() else _ops.attention_mh
+            return self.o_proj(attend(q, k, v, self.num_heads, self.dp_scale))
+        q, k, v = self._heads(q), self._heads(k), self._heads(v)
         attn = torch.bmm(q, k.transpose(1, 2)) * self.dp_scale
         if pad_mask is not None:
             mask = pad_mask[:, None, None, :].expand(b, self.num_heads, 1, pad_mask.shape[-1]).reshape(b * self.num_heads, 1, -1)

@@ -468,6 +468,31 @@ int forge_attention_fwd_lse(const float* q, const float* k, const float* v, long
 int forge_attention_bwd(const float* q, const float* k, const float* v, long long v_batch_rows, const float* out, const float* lse,
                         const float* dout, float* dq, float* dk, float* dv, float* delta_ws, int B, int Nq, int Nk, int d, forge_stream_t stream);
 
+/* Multi-head attention out = softmax(scale q k^T) v per head, for the six attention blocks of the 2-D pose estimator
+ * (`MultiHeadAttention`, models/model_utils.py:258-342: 4 heads of 64 channels, scale = 64^-1/2; opt-in on the Python side:
+ * ops.set_multihead_attention). The kernels of the three entry points above with two additions - those entry points are their H = 1, row stride
+ * 64, scale = 1 case, bit for bit:
+ *   head addressing: the projections stay as the Linear layers wrote them, [B][N][H*64] rows. Batch index b*H + h reads row r of q at
+ *     q + b*q_bs + r*q_rs + 64*h, and k (k_bs, k_rs), v (v_bs, v_rs) and out (out_bs, out_rs) alike: no head-split copy, no head-merge copy.
+ *     Strides are in floats, the channel stride is 1; slices of a wider tensor (one fused [B][N][3*H*64] projection) are addressed as they are.
+ *     Every stride must be a non-negative multiple of 4 (FORGE_ESHAPE) and q, k, v, out 16-byte aligned (FORGE_EINVAL): float4 access. Rows of
+ *     out must not overlap (out_rs >= H*64, out_bs >= Nq*out_rs for B > 1).
+ *   scale: a finite positive logit scale (FORGE_EINVAL otherwise), folded into the multiply q gets anyway (q * scale * log2 e); in the backward
+ *     dq and dk carry it, applied after the row-residual correction of the dq pass (dq = scale * (dS k - rho P k)).
+ * Dense buffers: lse [B][H][Nq] and delta_ws [B][H][Nq] (workspace of the caller), dout [B][Nq][H*64], dq [B][Nq][H*64], dk and dv [B][Nk][H*64].
+ * forge_attention_mh_fwd: lse may be NULL (inference: not stored; `out` has the same bits either way).
+ * forge_attention_mh_bwd: dv may be NULL (not wanted: the dv chain is skipped). Three launches, no atomics, bitwise reproducible; dq, dk, dv are
+ *   written in full. FLOPs: 4 B H Nq Nk d forward, 16 (14 without dv) B H Nq Nk d backward.
+ * The two-/four-part launch rule of the single-head entry points applies to B*H batch indices. d = 64, H >= 1, Nq and Nk multiples of 64
+ * (FORGE_ESHAPE); null pointers other than the two named are FORGE_EINVAL. */
+int forge_attention_mh_fwd(const float* q, const float* k, const float* v, float* out, float* lse, int B, int H, int Nq, int Nk, int d,
+                           long long q_bs, long long q_rs, long long k_bs, long long k_rs, long long v_bs, long long v_rs, long long out_bs,
+                           long long out_rs, float scale, forge_stream_t stream);
+int forge_attention_mh_bwd(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* dout, float* dq,
+                           float* dk, float* dv, float* delta_ws, int B, int H, int Nq, int Nk, int d, long long q_bs, long long q_rs,
+                           long long k_bs, long long k_rs, long long v_bs, long long v_rs, long long out_bs, long long out_rs, float scale,
+                           forge_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * a1  ResNet stem helpers (torchvision conv1/bn1/relu/maxpool behind models/encoder.py:71-73).
  * forge_im2col_nchw: img [N][C][H][W] -> patch rows out [N*Ho*Wo][Kpad], k = (ky*kw + kx)*C + c, zeros outside the image and
