@@ -5,6 +5,7 @@ ConvTranspose phase decomposition and the launch wrapper. No arithmetic of the h
 here apart from the one-off weight repacks (cached per parameter version).
 """
 import ctypes
+import os
 
 import torch
 
@@ -234,6 +235,7 @@ class _State:
     """Process-wide measurement switches (defaults = the product). Set through force_plan() / winograd(), or monkeypatched by tests."""
     plan_override = None              # (tile letter or None, ksplit or None): set by force_plan() only (tools/conv_plan_sweep.py, tests)
     winograd = True                   # False: the direct implicit-GEMM kernel for every 3x3(x3) convolution
+    wino_depth_nest = os.environ.get("FORGE_WINO_DEPTH_NEST", "1") != "0"     # False: the eval fusion's GRU launches stay on the four-point form
 
 
 STATE = _State()
@@ -534,6 +536,51 @@ def wino_input(x, C, ld, n, D, H, W, bs=0, out=None, nsum=1, sum_stride=0):
     return V
 
 
+@_lib.on_tensor_device
+def wino_pack_packed_dn(wp):
+    """Packed weights [27][Cout][Cin] -> U' = G_depth (x) (G w G^T), the weights of the depth nest (forge_wino_weights_dn: float64 inside, rounded
+    once): the entry's [16][4][Cout][Cin], returned as [16][2][2][Cout][Cin] - position k = 2 i + j. The fifth dimension is what tells wino_gemm the
+    nest's weights from forge_wino_weights' [16][kd][Cout][Cin], and dimension 1 stays what it is there: the K loops of Cin a launch runs per output
+    plane (2 here: four positions per pair of planes), which is how launch meters count its work."""
+    T, co_, ci_ = wp.shape
+    assert T == 27
+    wp = wp.detach()
+    wp = wp if wp.is_contiguous() else wp.contiguous()
+    U = torch.empty((16, 2, 2, co_, ci_), dtype=torch.float32, device=wp.device)
+    _lib.check(_lib.lib().forge_wino_weights_dn(_lib.ptr(wp), _lib.ptr(U), co_, ci_, _lib.current_stream()), "forge_wino_weights_dn")
+    return U
+
+
+def wino_depth_nest_applies(R, D, Ht, Wt, Cout, Cin):
+    """The three-depth-tap point-GEMM launches that take the depth nest (forge_wino_gemm_dn: a Winograd F(2, 3) over the depth taps inside the GEMM
+    kernel, 2/3 of the matrix-core work, 16 planes out): the entry's own preconditions - D even, Ht Wt a multiple of 64, Cin of 32 - on the launches
+    forge_wino_gemm would give its 64 x 128 tile, with no forced plan, unless switched off (STATE.wino_depth_nest / FORGE_WINO_DEPTH_NEST=0)."""
+    return (STATE.wino_depth_nest and STATE.plan_override is None and D % 2 == 0 and (Ht * Wt) % 64 == 0 and Cin % 32 == 0
+            and R * Cout * 4 <= MAX_OPERAND_BYTES and wino_gemm_tile(R, Cout, Cin) == "B")
+
+
+@_lib.on_tensor_device
+def wino_gemm_dn(V1, C1, V2, C2, Ud, Mm, n, D, Ht, Wt, Cout, view=0, views=1):
+    """wino_gemm's 16 point products [16][R][Cout] through the depth nest (forge_wino_gemm_dn), from Ud [16][2][2][Cout][C1 + C2] (wino_pack_packed_dn).
+    Operands and the buffer Mm as wino_gemm; the caller has checked wino_depth_nest_applies' shape conditions (the entry refuses the others)."""
+    vol = D * Ht * Wt
+    R = n * vol
+    if Ud.shape != (16, 2, 2, Cout, C1 + C2) or not Ud.is_contiguous():
+        raise ValueError("depth-nest weight %s does not match Cout=%d Cin=%d" % (tuple(Ud.shape), Cout, C1 + C2))
+    if Mm is None:
+        Mm = torch.empty(16, R, Cout, dtype=torch.float32, device=V1.device)
+    if not (Mm.is_contiguous() and Mm.dtype == torch.float32 and Mm.numel() >= 16 * R * Cout):
+        raise ValueError("point-product buffer %s %s%s cannot hold 16 x %d x %d float32" % (
+            tuple(Mm.shape), Mm.dtype, "" if Mm.is_contiguous() else " (not contiguous)", R, Cout))
+    if Mm.shape != (16, R, Cout):
+        Mm = Mm.as_strided((16, R, Cout), (R * Cout, Cout, 1))
+    p1 = ctypes.c_void_p(V1.data_ptr() + 4 * view * vol * C1)
+    _lib.check(_lib.lib().forge_wino_gemm_dn(p1, C1, C1, views * vol if views > 1 else 0, V1.shape[1] * C1, _lib.ptr(V2), C2, C2, 0,
+                                             0 if V2 is None else V2.shape[1] * C2, _lib.ptr(Ud), _lib.ptr(Mm), n, D, Ht, Wt, Cout, 3,
+                                             _lib.current_stream()), "forge_wino_gemm_dn")
+    return Mm
+
+
 def wino_half_applies(R, Cout, Cin):
     """The point-GEMM launches whose inverse transform's row stage runs in the GEMM epilogue (forge_wino_gemm_half / forge_wino_output_half: half the
     point-product bytes through HBM; bitwise the same result without a second addend): those forge_wino_gemm would give its 64 x 128 tile - a rule
@@ -549,7 +596,9 @@ def wino_gemm(V1, C1, V2, C2, U, Mm, n, D, Ht, Wt, Cout, view=0, views=1, half=N
     half chooses the form - True: P = 8 planes [2][4][R][Cout], the row stage of the inverse transform applied in the GEMM epilogue
     (forge_wino_gemm_half); False: the P = 16 points; None: wino_half_applies(R, Cout, C1 + C2). A producer whose products another launch adds
     (wino_output's Mm2) passes that launch's form. Mm: a contiguous float32 buffer of at least P R Cout elements (ValueError otherwise), or None
-    for a new [P][R][Cout] tensor."""
+    for a new [P][R][Cout] tensor. U of five dimensions (wino_pack_packed_dn): the depth nest, 16 points (wino_gemm_dn)."""
+    if U.dim() == 5:
+        return wino_gemm_dn(V1, C1, V2, C2, U, Mm, n, D, Ht, Wt, Cout, view=view, views=views)
     vol = D * Ht * Wt
     R = n * vol
     if half is None:

@@ -111,9 +111,17 @@ __device__ __forceinline__ int lds_off(int row, int chunk) {   // float offset o
 // as 2x instead of 4x the output tensor, written here and read by the inverse transform. s0 is stored as soon as point 2 is done, under point 3's
 // K loop, so three accumulator sets are live, not four: 80 VGPRs = 6 waves per SIMD = THREE resident workgroups per CU (3 x 48 KB of LDS;
 // with four sets and 96 VGPRs it was two - 512 slots chip-wide, not the 640 an earlier note assumed).
+//
+// RS = 2 (forge_wino_gemm_dn, 64x128 tile): the depth nest. A Winograd F(2, 3) over the three DEPTH taps on top of the 2-D points: a workgroup owns 64
+// tile rows of an EVEN plane z for one point p and runs four K loops k = 0..3 of K = Cin each (instead of 2 planes x 3 taps = six) on the operands
+//   k = 0: V[z-1] - V[z+1]   k = 1: V[z] + V[z+1]   k = 2: V[z+1] - V[z]   k = 3: V[z] - V[z+2]      (the rows of B^T; planes outside the grid are zero)
+// against U'[p][k] (forge_wino_weights_dn). Both planes of a position are staged as two A images by LDS-DMA (an out-of-grid plane at the out-of-range
+// offset) and combined with one fp32 operation per element on the ds_read_b128 results, in front of the MFMAs. The output side is A^T = [1 1 1 0; 0 1 -1 -1]
+// over the four positions - the four-point form's own skeleton: y_z = (m0 + m1) + m2 stored under k = 3's loop, y_{z+1} = (m1 - m2) - m3 - and the result
+// is the ordinary 16-plane Mm [16][R][Cout] of forge_wino_gemm. 2 x 32 KB of LDS: two workgroups per CU (resources: the remark above forge_wino_gemm_dn).
 template <int BM, int BN, int NW, int MT = 1, int RS = 0>
 __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
-    constexpr int NP = RS ? 4 : 1;                   // points per workgroup
+    constexpr int NP = RS ? 4 : 1;                   // points (RS = 2: depth positions) per workgroup
     constexpr int WM = BM / (32 * MT), WN = NW / WM; // NW waves as WM(M) x WN(N); wave tile (32 MT) x (BN / WN)
     constexpr int NT = BN / (32 * WN);              // 32-col MFMA tiles per wave
     static_assert(NT >= 1 && WM * WN == NW && NT * 32 * WN == BN && WM * 32 * MT == BM, "unsupported tile");
@@ -144,12 +152,21 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
     const int t_lo = phase * a.tpp;
     long long pb = 0;                                               // batched problems: workgroups [p tiles, (p+1) tiles) do problem p, so that (with
     if (a.nbat > 1) {                                               // xcd_remap's contiguous chunks) an XCD's L2 holds the weights of its own problems only
-        const unsigned tiles = (unsigned)((M + BM - 1) / BM) * (unsigned)ntile_n;
+        unsigned tiles = (unsigned)((M + BM - 1) / BM) * (unsigned)ntile_n;
+        if constexpr (RS == 2) tiles = (unsigned)(M / (2 * BM)) * (unsigned)ntile_n;   // depth nest: the tiles of the even planes only
         pb = bid / tiles;
         bid -= (unsigned)pb * tiles;
     }
     float* const outp = a.out + pb * a.pto;
-    const long long m0 = (long long)(bid / ntile_n) * BM;
+    const long long m0 = [&]() -> long long {
+        if constexpr (RS == 2) {                                    // tile ti of the even planes: plane pair ti / (HW / BM) = planes 2 pair, 2 pair + 1 of the
+            const unsigned tpl = (unsigned)(a.H * a.W) / BM;       // flat (n, z) axis (D even: a pair never straddles batch elements)
+            const unsigned ti = bid / ntile_n, pair = ti / tpl;
+            return (long long)(2u * pair * tpl + (ti - pair * tpl)) * BM;
+        } else {
+            return (long long)(bid / ntile_n) * BM;
+        }
+    }();
     const int n0 = (bid % ntile_n) * BN;
     const int Cin = a.C1 + a.C2;
     const int kchunks = Cin / BK;
@@ -340,7 +357,7 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
             buf ^= 1;
         }
     }
-    } else {
+    } else if constexpr (RS == 1) {
         // Four points, one K loop after the other. An issue cursor (point iq, tap it, chunk ikc) runs one step ahead of the MFMAs and walks straight
         // over the point switches (descriptors re-made there): the next point's first stage flies under the current point's last step.
         constexpr int STAGE = A_FLOATS + B_FLOATS;
@@ -421,6 +438,95 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
         }
         FORGE_STAMP(2);
         store_plane(1, [&](int r) { return accs[1][0][0][r] - accs[0][0][0][r]; });                               // s1 = u - m3
+        FORGE_STAMP(3);
+        return;
+    }
+
+    if constexpr (RS == 2) {
+        // Depth nest (see above). All 64 rows of the tile lie in plane (n, z), z even; the host has checked H W % 64 == 0, D even, M H W ldo 4 < 2^31.
+        constexpr int STAGE = 2 * A_FLOATS + B_FLOATS;             // [A image of plane a_k][A image of plane b_k][B]
+        static_assert(ACH == 1 && NT == 1 && MT == 1, "the depth nest is written for the 64 x 128 tile of 8 waves");
+        const unsigned HW = (unsigned)(a.H * a.W);
+        const int z = (int)(((unsigned)m0 / HW) % (unsigned)a.D);  // workgroup-uniform
+        const int sp0 = (az[0] * a.Hi + ay[0]) * a.Wi + ax[0];
+        const unsigned base1 = (unsigned)(((an[0] * (int)a.bs1r + sp0) * a.ld1 + asrc[0]) * 4), base2 = (unsigned)(((an[0] * (int)a.bs2r + sp0) * a.ld2 + asrc[0]) * 4);
+        const int ps1 = (int)HW * a.ld1 * 4, ps2 = (int)HW * a.ld2 * 4;   // bytes from a plane to the next in V1 / V2
+        unsigned ea1, eb1, ea2, eb2;                               // this thread's chunk in planes z + dza / z + dzb of V1 / V2, OOB outside the grid
+        auto prep_pos = [&](int k) {
+            const int dza = k == 0 ? -1 : k == 2 ? 1 : 0, dzb = k == 2 ? 0 : k == 3 ? 2 : 1;
+            const bool oka = (unsigned)(z + dza) < (unsigned)a.D, okb = (unsigned)(z + dzb) < (unsigned)a.D;
+            ea1 = oka ? base1 + (unsigned)(dza * ps1) : OOB; ea2 = oka ? base2 + (unsigned)(dza * ps2) : OOB;
+            eb1 = okb ? base1 + (unsigned)(dzb * ps1) : OOB; eb2 = okb ? base2 + (unsigned)(dzb * ps2) : OOB;
+        };
+        int ik = 0, ikc = 0, ibuf = 0;
+        auto issue_next = [&]() {                                  // the issue cursor runs one step ahead of the MFMAs, straight over the position switches
+            if (ik >= NP) return;
+            const int c0 = ikc * BK;
+            const unsigned stage = lds_wave + (unsigned)ibuf * (unsigned)(STAGE * 4);
+            if (c0 < a.C1) {
+                lds_dma16(w1, ea1 + (unsigned)(c0 * 4), stage);
+                lds_dma16(w1, eb1 + (unsigned)(c0 * 4), stage + (unsigned)(A_FLOATS * 4));
+            } else {
+                lds_dma16(w2, ea2 + (unsigned)((c0 - a.C1) * 4), stage);
+                lds_dma16(w2, eb2 + (unsigned)((c0 - a.C1) * 4), stage + (unsigned)(A_FLOATS * 4));
+            }
+            const unsigned wbase = (unsigned)((ik * a.Cout * Cin + c0) * 4);
+#pragma unroll
+            for (int j = 0; j < BCH; ++j) lds_dma16(ww, boff[j] + wbase, stage + (unsigned)(2 * A_FLOATS * 4 + j * NW * 1024));
+            ibuf ^= 1;
+            if (++ikc == kchunks) {
+                ikc = 0;
+                if (++ik < NP) prep_pos(ik);
+            }
+        };
+        prep_pos(0);
+        issue_next();
+        lds_dma_wait_barrier();
+        FORGE_STAMP(1);
+        const int ocol = n0 + wn * (BN / WN) + l31;
+        const unsigned ldo4 = (unsigned)a.ldo * 4u;
+        const unsigned ovb = ocol < a.Cout ? (unsigned)(((int)m0 + wm * 32 + 4 * half) * a.ldo + ocol) * 4u : OOB;
+        auto store_plane = [&](int plane, auto&& val) {            // the tile's rows of plane z + `plane`: the first plane's plus H W (buffer-descriptor stores, as RS = 1)
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(outp, 0, (int)(M * a.ldo * 4), 0x00020000);
+            unsigned vb = ovb + (unsigned)plane * HW * ldo4;
+            asm volatile("" : "+v"(vb));
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val(r)), rs, (int)(vb + (unsigned)((r & 3) + 8 * (r >> 2)) * ldo4), 0, 0);
+        };
+        int buf = 0;
+#pragma unroll
+        for (int q = 0; q < NP; ++q) {
+            f32x16& aq = accs[q == 3 ? 0 : q][0][0];
+            const float sgn = q == 1 ? 1.f : -1.f;                 // a_k + b_k at k = 1, a_k - b_k elsewhere: fmaf(+-1, b, a) is that one rounded add / sub
+            for (int s = 0; s < kchunks; ++s) {
+                const float* sa = smem + buf * STAGE;
+                const float* sb = sa + 2 * A_FLOATS;
+                issue_next();                                      // into the stage read in step s - 1: every wave is past that barrier
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int ao = lds_off(wm * 32 + l31, 2 * g + half);
+                    const float4 pa = *reinterpret_cast<const float4*>(sa + ao), pq = *reinterpret_cast<const float4*>(sa + A_FLOATS + ao);
+                    const float4 fb = *reinterpret_cast<const float4*>(sb + lds_off(wn * (BN / WN) + l31, 2 * g + half));
+                    aq = __builtin_amdgcn_mfma_f32_32x32x2f32(fmaf(sgn, pq.x, pa.x), fb.x, aq, 0, 0, 0);
+                    aq = __builtin_amdgcn_mfma_f32_32x32x2f32(fmaf(sgn, pq.y, pa.y), fb.y, aq, 0, 0, 0);
+                    aq = __builtin_amdgcn_mfma_f32_32x32x2f32(fmaf(sgn, pq.z, pa.z), fb.z, aq, 0, 0, 0);
+                    aq = __builtin_amdgcn_mfma_f32_32x32x2f32(fmaf(sgn, pq.w, pa.w), fb.w, aq, 0, 0, 0);
+                }
+                lds_dma_wait_barrier();
+                buf ^= 1;
+            }
+            if (q == 1) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) accs[0][0][0][r] = accs[0][0][0][r] + accs[1][0][0][r];              // t = m0 + m1
+            } else if (q == 2) {
+                store_plane(0, [&](int r) { return accs[0][0][0][r] + accs[2][0][0][r]; });                       // y_z = t + m2, in flight under k = 3's loop
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { accs[1][0][0][r] = accs[1][0][0][r] - accs[2][0][0][r]; accs[0][0][0][r] = 0.f; }   // u = m1 - m2
+            }
+        }
+        FORGE_STAMP(2);
+        store_plane(1, [&](int r) { return accs[1][0][0][r] - accs[0][0][0][r]; });                               // y_{z+1} = u - m3
         FORGE_STAMP(3);
         return;
     }
@@ -956,9 +1062,17 @@ static ConvPlan plan_conv(long long M, int Cout, int Cin, int ntaps, bool can_sp
 }
 
 // Launch conv_igemm_kernel with the planned tile: ceil(M / BM) x ceil(Cout / BN) workgroups per (K slice, phase, batched problem).
-static int launch_conv_tile(const ConvArgs& a, char tile, hipStream_t st, bool row_stage = false) {
+static int launch_conv_tile(const ConvArgs& a, char tile, hipStream_t st, int row_stage = 0) {
     const long long M = (long long)a.n * a.D * a.H * a.W;
     auto nblk = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((a.Cout + bn - 1) / bn); };
+    if (row_stage == 2) {                                            // forge_wino_gemm_dn: the tiles of the even planes, 16 points
+        const long long grid = (M / 128) * ((a.Cout + 127) / 128) * a.nbat;
+        FORGE_REQUIRE(grid < (1ll << 31), FORGE_ESHAPE, "forge_wino_gemm_dn: grid too large");
+        const size_t lds = 2 * (2 * 64 * BK + 128 * BK) * sizeof(float);
+        FORGE_SET_MAX_LDS_ONCE((conv_igemm_kernel<64, 128, 8, 1, 2>), lds);
+        hipLaunchKernelGGL((conv_igemm_kernel<64, 128, 8, 1, 2>), dim3((unsigned)grid), dim3(8 * 64), lds, st, a);
+        return 0;
+    }
     if (row_stage) {                                                 // forge_wino_gemm_half: a.nbat = 4 point columns, four points per workgroup
         const long long grid = nblk(64, 128) * a.nbat;
         FORGE_REQUIRE(grid < (1ll << 31), FORGE_ESHAPE, "forge_wino_gemm_half: grid too large");
@@ -1117,7 +1231,8 @@ extern "C" int forge_wino_gemm_tile(long long R, int Cout, int Cin) {
 // transformed weights U[p] [kd depth taps][Cout][C1 + C2] into Mm[p] [rows][Cout] - a kd-tap implicit GEMM over the tile grid, K = kd (C1 + C2);
 // kd = 3 for the 3x3x3 convolutions, kd = 1 for the 3x3 convolutions of a 2-D network (D = 1 or D = images: planes do not mix).
 static int wino_gemm_impl(const float* V1, int C1, int ld1, long long bs1, long long pt1, const float* V2, int C2, int ld2, long long bs2,
-                          long long pt2, const float* U, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, int tile, bool half, forge_stream_t stream) {
+                          long long pt2, const float* U, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, int tile, int form, forge_stream_t stream) {
+    const bool half = form == 1, dn = form == 2;                    // form: 0 = 16 points, 1 = the four-point row stage, 2 = the depth nest
     FORGE_REQUIRE(tile == 0 || (tile >= 'A' && tile <= 'E'), FORGE_EINVAL, "forge_wino_gemm: tile must be 0 (default rule) or 'A'..'E'");
     FORGE_REQUIRE(V1 && U && Mm && (kd == 1 || kd == 3), FORGE_EINVAL, "forge_wino_gemm: null pointer argument / kd not 1 or 3");
     FORGE_REQUIRE(n > 0 && D > 0 && Ht > 0 && Wt > 0 && Cout > 16, FORGE_EINVAL, "forge_wino_gemm: bad dims n=%d D=%d Ht=%d Wt=%d Cout=%d (Cout > 16)", n,
@@ -1125,6 +1240,8 @@ static int wino_gemm_impl(const float* V1, int C1, int ld1, long long bs1, long 
     FORGE_REQUIRE(C1 > 0 && C1 % BK == 0 && C2 >= 0 && C2 % BK == 0 && (C2 == 0) == (V2 == nullptr), FORGE_ESHAPE,
                   "forge_wino_gemm: C1=%d / C2=%d must be multiples of %d, V2 given iff C2 > 0", C1, C2, BK);
     FORGE_REQUIRE(ld1 >= C1 && ld1 % 4 == 0 && (C2 == 0 || (ld2 >= C2 && ld2 % 4 == 0)), FORGE_EINVAL, "forge_wino_gemm: bad row strides");
+    FORGE_REQUIRE(!dn || (kd == 3 && D % 2 == 0 && ((long long)Ht * Wt) % 64 == 0), FORGE_EINVAL,
+                  "forge_wino_gemm_dn: needs three depth taps, an even D and Ht Wt %% 64 == 0 (kd=%d D=%d Ht=%d Wt=%d)", kd, D, Ht, Wt);
     ConvArgs a;
     memset(&a, 0, sizeof(a));
     const long long vol = (long long)D * Ht * Wt, R = (long long)n * vol;
@@ -1137,15 +1254,23 @@ static int wino_gemm_impl(const float* V1, int C1, int ld1, long long bs1, long 
     a.Cout = Cout; a.ldo = Cout; a.ldr = Cout; a.ntaps = kd; a.os = 1; a.Do = D; a.Ho = Ht; a.Wo = Wt; a.nphase = 1; a.tpp = kd; a.epi = EPI_BIAS;
     a.ksplit = 1; a.nbat = half ? 4 : 16; a.pt1 = pt1 > 0 ? pt1 : R * ld1; a.pt2 = V2 ? (pt2 > 0 ? pt2 : R * ld2) : 0;   // 0 = dense planes, as forge_wino_wgrad reads it
     a.ptw = (long long)kd * Cout * (C1 + C2); a.pto = R * Cout;
+    if (dn) {                                                         // U' [16][4][Cout][Cin]: the four depth positions take the place of the taps
+        FORGE_REQUIRE(R * Cout * 4 < (1ll << 31) && 4ll * Cout * (C1 + C2) * 4 < (1ll << 31), FORGE_ESHAPE,
+                      "forge_wino_gemm_dn: an output plane spans >= 2 GiB (32-bit buffer offsets); split the batch");
+        a.ntaps = a.tpp = 4; a.ptw = 4ll * Cout * (C1 + C2);
+        if (int rc = launch_conv_tile(a, 'B', (hipStream_t)stream, 2)) return rc;
+        FORGE_LAUNCH_CHECK("forge_wino_gemm_dn");
+        return 0;
+    }
     if (kd == 3) { a.tap[0][0] = -1; a.tap[2][0] = 1; }                 // depth taps (-1,0,0), (0,0,0), (1,0,0); kd = 1: the 2-D convolution's single tap
-    if (int rc = launch_conv_tile(a, (char)(tile ? tile : forge_wino_gemm_tile(R, Cout, C1 + C2)), (hipStream_t)stream, half)) return rc;
+    if (int rc = launch_conv_tile(a, (char)(tile ? tile : forge_wino_gemm_tile(R, Cout, C1 + C2)), (hipStream_t)stream, half ? 1 : 0)) return rc;
     FORGE_LAUNCH_CHECK("forge_wino_gemm");
     return 0;
 }
 
 extern "C" int forge_wino_gemm(const float* V1, int C1, int ld1, long long bs1, long long pt1, const float* V2, int C2, int ld2, long long bs2,
                                long long pt2, const float* U, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, int tile, forge_stream_t stream) {
-    return wino_gemm_impl(V1, C1, ld1, bs1, pt1, V2, C2, ld2, bs2, pt2, U, Mm, n, D, Ht, Wt, Cout, kd, tile, false, stream);
+    return wino_gemm_impl(V1, C1, ld1, bs1, pt1, V2, C2, ld2, bs2, pt2, U, Mm, n, D, Ht, Wt, Cout, kd, tile, 0, stream);
 }
 
 // forge_wino_gemm with the ROW stage of the inverse transform applied in the GEMM's epilogue (conv_igemm_kernel<..., RS = 1>): Mm8 [2][4][R][Cout],
@@ -1153,5 +1278,16 @@ extern "C" int forge_wino_gemm(const float* V1, int C1, int ld1, long long bs1, 
 // first. forge_wino_output_half finishes the transform. 64 x 128 tile only (the launches forge_wino_gemm_tile gives 'B').
 extern "C" int forge_wino_gemm_half(const float* V1, int C1, int ld1, long long bs1, long long pt1, const float* V2, int C2, int ld2, long long bs2,
                                     long long pt2, const float* U, float* Mm8, int n, int D, int Ht, int Wt, int Cout, int kd, forge_stream_t stream) {
-    return wino_gemm_impl(V1, C1, ld1, bs1, pt1, V2, C2, ld2, bs2, pt2, U, Mm8, n, D, Ht, Wt, Cout, kd, 'B', true, stream);
+    return wino_gemm_impl(V1, C1, ld1, bs1, pt1, V2, C2, ld2, bs2, pt2, U, Mm8, n, D, Ht, Wt, Cout, kd, 'B', 1, stream);
+}
+
+// forge_wino_gemm through the depth nest (conv_igemm_kernel<64, 128, 8, 1, 2>): the same 16 point products Mm [16][R][Cout] of a three-depth-tap problem,
+// made with four K loops of C1 + C2 per plane pair instead of six, against Ud = U' [16][4][Cout][C1 + C2] (forge_wino_weights_dn). Rounded in another
+// order than forge_wino_gemm: not bitwise its result. FORGE_EINVAL unless kd == 3, D is even, Ht Wt % 64 == 0 and C1, C2 are multiples of 32.
+// Code object (hipcc -O3, gfx950): 87 VGPRs, 0 AGPRs, 52 SGPRs, no scratch = 5 waves per SIMD by registers; 2 x 32 KB = 64 KB of dynamic LDS -> TWO workgroups per CU
+// (the LDS binds; the four-point form: 80 VGPRs, 48 KB, three).
+extern "C" int forge_wino_gemm_dn(const float* V1, int C1, int ld1, long long bs1, long long pt1, const float* V2, int C2, int ld2, long long bs2,
+                                  long long pt2, const float* Ud, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, forge_stream_t stream) {
+    FORGE_REQUIRE(C1 > 0 && C1 % BK == 0 && C2 >= 0 && C2 % BK == 0, FORGE_EINVAL, "forge_wino_gemm_dn: C1=%d / C2=%d must be multiples of %d", C1, C2, BK);
+    return wino_gemm_impl(V1, C1, ld1, bs1, pt1, V2, C2, ld2, bs2, pt2, Ud, Mm, n, D, Ht, Wt, Cout, kd, 'B', 2, stream);
 }

@@ -138,6 +138,41 @@ __global__ __launch_bounds__(256) void wino_weight_kernel(const float* __restric
     }
 }
 
+// Weights of the depth nest (forge_wino_gemm_dn): U'[4i+j][k][o][c] = sum_kd Gd[k][kd] (G w[kd] G^T)[i][j] with the depth rows Gd = G: w0, (w0 + w1 + w2) / 2,
+// (w0 - w1 + w2) / 2, w2. One thread per (o, c); float64 (exact: at most 27 fp32 terms with coefficients 1, 1/2, 1/4, 1/8), rounded once.
+__global__ __launch_bounds__(256) void wino_weight_dn_kernel(const float* __restrict__ wp, float* __restrict__ U, int Cout, int Cin) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, per = (long long)Cout * Cin;
+    if (idx >= per) return;
+    double w[3][3][3];
+#pragma unroll
+    for (int t = 0; t < 27; ++t) w[t / 9][(t / 3) % 3][t % 3] = (double)wp[t * per + idx];
+    const long long pt = 4 * per;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        double d[3][3], g[4][3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int b = 0; b < 3; ++b)
+                d[a][b] = k == 0 ? w[0][a][b] : k == 1 ? 0.5 * (w[0][a][b] + w[1][a][b] + w[2][a][b]) : k == 2 ? 0.5 * (w[0][a][b] - w[1][a][b] + w[2][a][b]) : w[2][a][b];
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {                // G d
+            g[0][b] = d[0][b];
+            g[1][b] = 0.5 * (d[0][b] + d[1][b] + d[2][b]);
+            g[2][b] = 0.5 * (d[0][b] - d[1][b] + d[2][b]);
+            g[3][b] = d[2][b];
+        }
+        float* up = U + k * per + idx;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {                // (G d) G^T
+            up[(4 * i + 0) * pt] = (float)g[i][0];
+            up[(4 * i + 1) * pt] = (float)(0.5 * (g[i][0] + g[i][1] + g[i][2]));
+            up[(4 * i + 2) * pt] = (float)(0.5 * (g[i][0] - g[i][1] + g[i][2]));
+            up[(4 * i + 3) * pt] = (float)g[i][2];
+        }
+    }
+}
+
 enum WinoEpilogue : int { W_BIAS = 0, W_AFFINE_ACT = 1, W_GRU_GATES = 2, W_GRU_OUT = 3 };   // = ConvEpilogue of conv_igemm.hip
 
 struct WinoOutArgs {
@@ -369,6 +404,14 @@ extern "C" int forge_wino_weights(const float* wp, float* U, int Cout, int Cin, 
     const long long total = (long long)kd * Cout * Cin;
     hipLaunchKernelGGL(wino_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, wp, U, Cout, Cin, kd, transpose);
     FORGE_LAUNCH_CHECK("forge_wino_weights");
+    return 0;
+}
+
+extern "C" int forge_wino_weights_dn(const float* wp, float* Ud, int Cout, int Cin, forge_stream_t stream) {
+    FORGE_REQUIRE(wp && Ud && Cout > 0 && Cin > 0, FORGE_EINVAL, "forge_wino_weights_dn: bad argument");
+    const long long total = (long long)Cout * Cin;
+    hipLaunchKernelGGL(wino_weight_dn_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, wp, Ud, Cout, Cin);
+    FORGE_LAUNCH_CHECK("forge_wino_weights_dn");
     return 0;
 }
 

@@ -237,10 +237,11 @@ def bn_act_rows(bn, rows, slope=1.0, residual=None, stats=None):
     raise RuntimeError("forge_amd: unsupported BatchNorm configuration %r" % (bn,))
 
 
-def _step_scratch(R, C, dev):
+def _step_scratch(R, C, dev, nest=False):
     """One buffer for the point products of a GRU step's 2C-column (gates) and C-column (state, fusion_conv) launches over R tile rows, sized for the
-    larger of their forms: convops.wino_gemm returns each launch's products as a view of its front."""
-    P2, P1 = (8 if co.wino_half_applies(R, c, C) else 16 for c in (2 * C, C))
+    larger of their forms: convops.wino_gemm returns each launch's products as a view of its front. nest: the step's launches take the depth nest
+    (16 planes)."""
+    P2, P1 = (8 if co.wino_half_applies(R, c, C) and not nest else 16 for c in (2 * C, C))
     return torch.empty(max(P2 * 2 * C, P1 * C) * R, dtype=torch.float32, device=dev)
 
 
@@ -422,15 +423,16 @@ def _input_products(Vx, U, n, geo, Cout):
     return co.wino_gemm(Vx, C, None, 0, U, None, n, D, H // 2, W // 2, Cout, half=co.wino_half_applies(R, Cout, C))
 
 
-def _h0_wino(p, xr, grp, V, Mm, t0, h):
+def _h0_wino(p, xr, grp, V, Mm, t0, h, nest=False):
     """h = fusion_conv(mean of the views grp of xr [b,t,D,H,W,C]): two Winograd convolutions with the folded BatchNorm + LeakyReLU tails
-    (scratch V, Mm, t0)."""
+    (scratch V, Mm, t0). nest: their point GEMMs run the depth nest on p's fc0_Ud / fc3_Ud."""
     b, t, D, H, W, C = xr.shape
+    gemm = lambda k: co.wino_gemm(V, C, None, 0, p[k + ("_Ud" if nest else "_U")], Mm, b, D, H // 2, W // 2, C)
     _wino_view_mean(xr, grp, V)
-    Mp = co.wino_gemm(V, C, None, 0, p["fc0_U"], Mm, b, D, H // 2, W // 2, C)
+    Mp = gemm("fc0")
     co.wino_output(Mp, p["fc0_b"], *p["bn1"], 0.01, None, None, None, t0, None, None, b, D, H, W, C, C, co.EPI_AFFINE_ACT)
     co.wino_input(t0, C, C, b, D, H, W, out=V)
-    Mp = co.wino_gemm(V, C, None, 0, p["fc3_U"], Mm, b, D, H // 2, W // 2, C)
+    Mp = gemm("fc3")
     co.wino_output(Mp, p["fc3_b"], *p["bn4"], 0.01, None, None, None, h, None, None, b, D, H, W, C, C, co.EPI_AFFINE_ACT)
 
 
@@ -444,7 +446,7 @@ def _h0_direct(p, xr, grp, t0, h):
                   epilogue=co.EPI_AFFINE_ACT)
 
 
-def _wino_step(geo, x, view, views, wg, wo, V, Mm, h, z, hr, hn, out=None, r=None, cand=None):
+def _wino_step(geo, x, view, views, wg, wo, V, Mm, h, z, hr, hn, out=None, r=None, cand=None, nest=None):
     """One ConvGRU step on the Winograd launches over geo = (b, D, H, W): transform h, point GEMMs, inverse transform fused with the gate tail
     (z, hr = h r; r into `r`); transform hr, point GEMMs, inverse transform fused with tanh / lerp (hn; tanh(c) into `cand`, the fusion_norm
     folded output into `out`). (Fusing each inverse transform with the next input transform through LDS was built and measured slower -
@@ -453,13 +455,16 @@ def _wino_step(geo, x, view, views, wg, wo, V, Mm, h, z, hr, hn, out=None, r=Non
       split  x = (MXg, MXc), the input-half products of `views` views per scene (_input_products): point GEMMs over V_h alone, K = 3C,
              hidden-half weights; the inverse transforms add view `view`'s products
     wg = (U, bias), wo = (U, bias, scale, shift). V: the buffer of both transforms, or None for a new one each (returned: the training node
-    keeps them for the weight gradient). Mm: the point-product scratch (_step_scratch)."""
+    keeps them for the weight gradient). Mm: the point-product scratch (_step_scratch). nest (full form only) = (Ud_gates, Ud_state): both point
+    GEMMs run the depth nest (convops.wino_gemm with wino_pack_packed_dn's weights) on these weights and hand 16 planes to the same inverse transforms."""
     b, D, H, W = geo
     C = h.shape[-1]
     split = isinstance(x, tuple)
 
     def conv(src, U, Cout, i):
         Vs = co.wino_input(src, C, C, b, D, H, W, out=V)
+        if nest is not None:
+            return Vs, co.wino_gemm(x, C, Vs, C, nest[i], Mm, b, D, H // 2, W // 2, Cout, view=view, views=views), {}
         if split:
             return Vs, co.wino_gemm(Vs, C, None, 0, U, Mm, b, D, H // 2, W // 2, Cout), dict(Mm2=x[i], view=view, views=views)
         return Vs, co.wino_gemm(x, C, Vs, C, U, Mm, b, D, H // 2, W // 2, Cout, view=view, views=views), {}
@@ -503,6 +508,7 @@ def _fuse_eval(gru, xr, groups, wino, split, h0=None, keep=None, const0=None):
     wk = "_U" if wino else "_w"
     weights = lambda half: ((p["gate" + wk + half], p["gate_b"]), (p["out" + wk + half], p["out_b"], *p["norm"]))
     wg, wo = weights("h" if split else "")
+    nest, nest_h0 = None, False
     # X, the input side of the steps: V_x (Winograd, full), the products (MXg, MXc) (Winograd, split) or per view (gx, cx) (direct, split)
     if wino:
         R = b * D * (H // 2) * (W // 2)
@@ -510,7 +516,14 @@ def _fuse_eval(gru, xr, groups, wino, split, h0=None, keep=None, const0=None):
         if split:
             X = (_input_products(X, p["gate_Ux"], b * t, geo, 2 * C), _input_products(X, p["out_Ux"], b * t, geo, C))
         V = torch.empty(16, R, C, dtype=torch.float32, device=dev)
-        Mm = _step_scratch(R, C, dev)
+        # the full steps of the plain eval fusion take the depth nest where both of their launches qualify (K = 2C per depth position)
+        if (not split and keep is None and const0 is None
+                and all(co.wino_depth_nest_applies(R, D, H // 2, W // 2, c, 2 * C) for c in (2 * C, C))):
+            pd = gru._packed_wino_dn()
+            nest = (pd["gate_Ud"], pd["out_Ud"])
+            # fusion_conv's two launches (K = C per position) follow where the rule holds for them (tools/wino_dn_probe.py: 0.90 of the four-point pair)
+            nest_h0 = co.wino_depth_nest_applies(R, D, H // 2, W // 2, C, C)
+        Mm = _step_scratch(R, C, dev, nest is not None)
     elif split:                                                            # the input halves once per view (no bias: added with the hidden half)
         X = {}
         for ti in sorted({ti for g in groups for ti in g}):
@@ -525,7 +538,7 @@ def _fuse_eval(gru, xr, groups, wino, split, h0=None, keep=None, const0=None):
         if h0 is not None:
             h.copy_(h0.permute(0, 2, 3, 4, 1).reshape(M, C))
         elif wino:
-            _h0_wino(p, xr, grp, V, Mm, t0, h)
+            _h0_wino(p, xr, grp, V, Mm, t0, h, nest_h0)
         else:
             _h0_direct(p, xr, grp, t0, h)
         if keep is not None:
@@ -546,7 +559,7 @@ def _fuse_eval(gru, xr, groups, wino, split, h0=None, keep=None, const0=None):
             elif const0 is not None and k == 0:
                 _wino_step(geo, (const0["MXg0"], const0["MXc0"]), 0, 1, *weights("h"), V, Mm, h, z, hr, hn, last, r, cand)
             else:
-                _wino_step(geo, X, ti, t, wg, wo, V, Mm, h, z, hr, hn, last, r, cand)
+                _wino_step(geo, X, ti, t, wg, wo, V, Mm, h, z, hr, hn, last, r, cand, nest=nest)
             if keep is not None:
                 keep += [h, z, r, cand]
             h, hn = hn, h
@@ -956,6 +969,13 @@ class ConvGRU_3D(co.PackedModule):
             cell, fc = self.cells[0], self.fusion_conv
             p.update({"gate_U": co.wino_pack_weight(cell.conv_gate.weight), "out_U": co.wino_pack_weight(cell.out_gate.weight),
                       "fc0_U": co.wino_pack_weight(fc[0].weight), "fc3_U": co.wino_pack_weight(fc[3].weight)})
+        return p
+
+    def _packed_wino_dn(self):
+        """_packed_wino plus the depth-nest weights U' [16][2][2][Cout][Cin] of the four 3x3x3 convolutions (convops.wino_pack_packed_dn)."""
+        p = self._packed_wino()
+        if "gate_Ud" not in p:
+            p.update({k + "_Ud": co.wino_pack_packed_dn(p[k + "_w"]) for k in ("gate", "out", "fc0", "fc3")})
         return p
 
     def _packed_halves(self, wino):

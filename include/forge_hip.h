@@ -292,6 +292,16 @@ int forge_wino_gemm_half(const float* V1, int C1, int ld1, long long bs1, long l
 int forge_wino_output_half(const float* Mm8, const float* Mm2_8 /* nullable second addend, 8 planes too */, long long bs2, long long pt2, const float* bias, const float* scale,
                            const float* shift, float slope, const float* residual, const float* aux_h, const float* aux_z, float* out, float* out2, float* out3,
                            int n, int D, int H, int W, int Cout, int ldo, int epilogue, forge_stream_t stream);
+/* The depth nest: forge_wino_gemm's 16 point products Mm [16][R][Cout] of a THREE-depth-tap problem with a Winograd F(2, 3) over the depth taps
+ * inside the GEMM kernel - four K loops of C1 + C2 per pair of planes (z, z + 1), z even, instead of six. Position k multiplies the operand
+ * V[z-1] - V[z+1] | V[z] + V[z+1] | V[z+1] - V[z] | V[z] - V[z+2] (one fp32 addition of two planes of V, planes outside the grid are zero) with
+ * Ud[p][k]; the pair's rows are (m0 + m1) + m2 and (m1 - m2) - m3. forge_wino_weights_dn makes Ud [16][4][Cout][Cin] = G_depth (x) (G w G^T) from the
+ * packed weights wp [27][Cout][Cin], depth rows w0, (w0 + w1 + w2) / 2, (w0 - w1 + w2) / 2, w2, in float64 and rounded once. The result feeds
+ * forge_wino_output like forge_wino_gemm's; it is rounded in another order and is not bitwise forge_wino_gemm's. Operands as forge_wino_gemm.
+ * FORGE_EINVAL unless kd == 3, D is even, Ht Wt % 64 == 0 and C1, C2 are multiples of 32; one output plane must stay below 2 GiB (FORGE_ESHAPE). */
+int forge_wino_gemm_dn(const float* V1, int C1, int ld1, long long bs1, long long pt1, const float* V2, int C2, int ld2, long long bs2,
+                       long long pt2, const float* Ud, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, forge_stream_t stream);
+int forge_wino_weights_dn(const float* wp, float* Ud, int Cout, int Cin, forge_stream_t stream);
 int forge_wino_gemm_tile(long long R, int Cout, int Cin);   /* the workgroup tile letter ('A'..'E', see forge_conv_igemm_plan) forge_wino_gemm uses for R tile rows per point, Cin = C1 + C2 */
 int forge_wino_output(const float* Mm, const float* Mm2, long long bs2, long long pt2, const float* bias, const float* scale, const float* shift, float slope, const float* residual,
                       const float* aux_h, const float* aux_z, float* out, float* out2, float* out3, int n, int D, int H, int W, int Cout,
