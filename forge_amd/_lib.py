@@ -86,6 +86,7 @@ SIGNATURES = {
     "forge_vgg_tap_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "forge_conv_wgrad_det": [_P, _I, _P, _I, _I, _LL, _P, _I, _I, _LL, _P] + [_I] * 9 + [_P, _I, _I, _P, _LL, _P],
     "forge_conv_wgrad_det_ws_bytes": [_I] * 11 + [_P, _I],
+    "forge_conv_wgrad_plan": [_I] * 11 + [_P, _I, _I, _P],
     "forge_wino_wgrad_det": [_P, _P, _I, _LL, _LL, _P, _I, _LL, _LL, _P, _I, _I, _I, _I, _I, _I, _I, _P, _LL, _P],
     "forge_wino_wgrad_det_ws_bytes": [_I] * 8,
     "forge_conv_direct_wgrad_det": [_P, _I, _P, _I, _P] + [_I] * 6 + [_P, _I, _I, _P, _LL, _P],

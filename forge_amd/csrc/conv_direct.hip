@@ -158,6 +158,8 @@ static int fill_direct(const char* fn, DirectArgs& a, int n, int D, int H, int W
     FORGE_REQUIRE((Cin == 4 || Cin == 8 || Cin == 16) && Cout >= 1 && Cout <= 4, FORGE_ESHAPE,
                   "%s: Cin=%d Cout=%d outside the direct kernels' range (Cin 4/8/16, Cout 1..4)", fn, Cin, Cout);
     a.n = n; a.D = D; a.H = H; a.W = W; a.ntaps = ntaps;
+    for (int k = 0; k < 3 * ntaps; ++k)       // the kernels carry the taps as signed bytes
+        FORGE_REQUIRE(taps[k] >= -128 && taps[k] <= 127, FORGE_EINVAL, "%s: tap %d component %d = %d outside [-128, 127]", fn, k / 3, k % 3, taps[k]);
     for (int t = 0; t < 64; ++t) {
         for (int k = 0; k < 3; ++k) a.tap[t][k] = (signed char)(t < ntaps ? taps[t * 3 + k] : 0);
         a.tap[t][3] = 0;

@@ -1162,6 +1162,8 @@ extern "C" int forge_conv_igemm(const float* in1, int C1, int ld1, long long bs1
         a.tpp = ntaps / a.nphase;
         a.pz = a.py = a.px = 0;
     }
+    for (int k = 0; k < 3 * ntaps; ++k)       // the kernels carry the taps as signed bytes
+        FORGE_REQUIRE(taps[k] >= -128 && taps[k] <= 127, FORGE_EINVAL, "forge_conv_igemm: tap %d component %d = %d outside [-128, 127]", k / 3, k % 3, taps[k]);
     for (int t = 0; t < MAX_TAPS; ++t) {
         for (int k = 0; k < 3; ++k) a.tap[t][k] = (signed char)(t < ntaps ? taps[t * 3 + k] : 0);
         a.tap[t][3] = 0;

@@ -534,6 +534,20 @@ static int det_prepare(WgradArgs& a, DetPlan& d, long long nslab, const char* fn
     return 0;
 }
 
+// What conv_wgrad_run chose (forge_conv_wgrad_plan): recorded by the dispatch itself right where it launches; dry = record and launch nothing.
+struct WgradPlan {
+    bool dry;
+    int family, p1, p2, nwv;     // family 1 tiles (CIW, TG) | 2 small (32, taps per wave) | 3 lines (32, 1) | 4 lines16 (CIT, IS); waves per workgroup
+    long long grid, nchunk;      // workgroups; voxel chunks (tiles, small) or persistent workgroups (lines, lines16) = slabs of the deterministic mode
+    int mchunk, nlines;          // voxels per chunk (0: the line kernels walk segments); (dz, dy) lines
+};
+
+static bool plan_note(WgradPlan* p, int family, int p1, int p2, int nwv, long long grid, long long nchunk, int mchunk, int nlines) {
+    if (!p) return false;
+    p->family = family; p->p1 = p1; p->p2 = p2; p->nwv = nwv; p->grid = grid; p->nchunk = nchunk; p->mchunk = mchunk; p->nlines = nlines;
+    return p->dry;
+}
+
 static int det_finish(const DetPlan& d, hipStream_t stream, const char* fn) {
     return det_reduce((const float*)d.ws, d.nslab, d.slab, 1, 0, d.slab, d.out, d.accumulate, stream, fn);
 }
@@ -544,7 +558,7 @@ static long long det_cap(long long slab_floats) {
 }
 
 // conv_wgrad_kernel<ciw> over (taps x Cout tiles x Cin tiles x voxel chunks) workgroups.
-static int launch_wgrad_tiles(WgradArgs& a, int ciw, hipStream_t stream, DetPlan* det) {
+static int launch_wgrad_tiles(WgradArgs& a, int ciw, hipStream_t stream, DetPlan* det, WgradPlan* plan = nullptr) {
     const long long M = (long long)a.n * a.D * a.H * a.W;
     const int Cin = a.C1 + a.C2, Cout = a.Cout, ntaps = a.ntaps;
     // narrow single inputs with several taps: TG taps share one 128-column tile (kernel header)
@@ -571,6 +585,7 @@ static int launch_wgrad_tiles(WgradArgs& a, int ciw, hipStream_t stream, DetPlan
     nchunk = (M + mchunk - 1) / mchunk;
     const long long grid = tiles * nchunk;
     FORGE_REQUIRE(grid < (1ll << 31), FORGE_ESHAPE, "forge_conv_wgrad: grid too large");
+    if (plan_note(plan, 1, ciw, tg, 4, grid, nchunk, a.mchunk, 0)) return 0;
     if (det) {
         if (int rc = det_prepare(a, *det, nchunk, "forge_conv_wgrad_det")) return rc < 0 ? rc : 0;
     }
@@ -598,7 +613,7 @@ static int launch_wgrad_tiles(WgradArgs& a, int ciw, hipStream_t stream, DetPlan
 
 static int conv_wgrad_run(const float* dy, int ldy, const float* x1, int C1, int ld1, long long bs1, const float* x2, int C2, int ld2,
                           long long bs2, float* dw, int n, int D, int H, int W, int is, int Di, int Hi, int Wi, int Cout,
-                          const int* taps, int ntaps, forge_stream_t stream, DetPlan* det) {
+                          const int* taps, int ntaps, forge_stream_t stream, DetPlan* det, WgradPlan* plan = nullptr) {
     FORGE_REQUIRE(dy && x1 && dw && taps, FORGE_EINVAL, "forge_conv_wgrad: null pointer argument");
     FORGE_REQUIRE(n > 0 && D > 0 && H > 0 && W > 0 && Cout > 0 && ntaps > 0 && ntaps <= 64 && is >= 1 && Di > 0 && Hi > 0 && Wi > 0, FORGE_EINVAL,
                   "forge_conv_wgrad: bad dims");
@@ -617,6 +632,8 @@ static int conv_wgrad_run(const float* dy, int ldy, const float* x1, int C1, int
     a.span2 = x2 ? ((long long)(n - 1) * a.bs2r + (long long)Di * Hi * Wi) * ld2 * 4 : 0;
     FORGE_REQUIRE(a.spany < (1ll << 31) && a.span1 < (1ll << 31) && a.span2 < (1ll << 31), FORGE_ESHAPE,
                   "forge_conv_wgrad: an operand spans >= 2 GiB (32-bit buffer offsets); split the batch");
+    for (int k = 0; k < 3 * ntaps; ++k)       // the kernels carry the taps as signed bytes
+        FORGE_REQUIRE(taps[k] >= -128 && taps[k] <= 127, FORGE_EINVAL, "forge_conv_wgrad: tap %d component %d = %d outside [-128, 127]", k / 3, k % 3, taps[k]);
     for (int t = 0; t < 64; ++t) {
         for (int k = 0; k < 3; ++k) a.tap[t][k] = (signed char)(t < ntaps ? taps[t * 3 + k] : 0);
         a.tap[t][3] = 0;
@@ -646,7 +663,7 @@ static int conv_wgrad_run(const float* dy, int ldy, const float* x1, int C1, int
         if (ok) {
             const long long nseg = (long long)n * D * H * ((W + LSEG - 1) / LSEG);
             const size_t lds = (size_t)(LSEG * 32 + lt.nlines * (LSEG + 2 * lt.rx) * 32) * sizeof(float);
-            if (!det || det->launch) FORGE_SET_MAX_LDS_ONCE(conv_wgrad_lines_kernel<>, (LSEG * 32 + LMAXL * LROWS * 32) * sizeof(float));
+            if ((!det || det->launch) && !(plan && plan->dry)) FORGE_SET_MAX_LDS_ONCE(conv_wgrad_lines_kernel<>, (LSEG * 32 + LMAXL * LROWS * 32) * sizeof(float));
             a.mchunk = 0;
             // det: one slab per workgroup (each walks its own segments), at most det_cap slabs
             const long long cap = det ? det_cap((long long)ntaps * Cout * Cin) : (1ll << 40);
@@ -654,6 +671,7 @@ static int conv_wgrad_run(const float* dy, int ldy, const float* x1, int C1, int
             if (lines_s2) {
                 const size_t lds16 = (size_t)(LSEG * 16 + lt.nlines * (2 * LSEG - 1 + 2 * lt.rx) * 16) * sizeof(float);
                 const long long grid16 = clamp_grid(768);                           // 3 resident workgroups per CU
+                if (plan_note(plan, 4, 16, 2, 4, grid16, grid16, 0, lt.nlines)) return 0;
                 if (det) { if (int rc = det_prepare(a, *det, grid16, "forge_conv_wgrad_det")) return rc < 0 ? rc : 0; }
                 if (det) {
                     FORGE_SET_MAX_LDS_ONCE((conv_wgrad_lines16_kernel<16, 2, 9, 4, true>), (LSEG * 16 + 6 * (2 * LSEG - 1 + 2 * LMAXR) * 16) * sizeof(float));
@@ -671,6 +689,7 @@ static int conv_wgrad_run(const float* dy, int ldy, const float* x1, int C1, int
                 const size_t lds16 = (size_t)(LSEG * 16 + lt.nlines * (LSEG + 2 * lt.rx) * cit) * sizeof(float);
                 const long long grid16 = clamp_grid(cit == 16 ? 1024 : 768);        // 4 / 3 resident workgroups per CU (108 / ~150 VGPRs)
                 if (cit == 16) {
+                    if (plan_note(plan, 4, 16, 1, 4, grid16, grid16, 0, lt.nlines)) return 0;
                     if (det) { if (int rc = det_prepare(a, *det, grid16, "forge_conv_wgrad_det")) return rc < 0 ? rc : 0; }
                     if (det) {
                         FORGE_SET_MAX_LDS_ONCE((conv_wgrad_lines16_kernel<16, 1, LTAPS, 4, true>), (LSEG * 16 + LMAXL * LROWS * 16) * sizeof(float));
@@ -681,6 +700,7 @@ static int conv_wgrad_run(const float* dy, int ldy, const float* x1, int C1, int
                     }
                 } else {
                     const long long grid32 = clamp_grid(512);              // 8-wave workgroups, 2 per CU
+                    if (plan_note(plan, 4, 32, 1, 8, grid32, grid32, 0, lt.nlines)) return 0;
                     if (det) { if (int rc = det_prepare(a, *det, grid32, "forge_conv_wgrad_det")) return rc < 0 ? rc : 0; }
                     if (det) {
                         FORGE_SET_MAX_LDS_ONCE((conv_wgrad_lines16_kernel<32, 1, 4, 8, true>), (LSEG * 16 + LMAXL * LROWS * 32) * sizeof(float));
@@ -694,6 +714,7 @@ static int conv_wgrad_run(const float* dy, int ldy, const float* x1, int C1, int
                 return det ? det_finish(*det, (hipStream_t)stream, "forge_conv_wgrad_det") : 0;
             }
             const long long grid = clamp_grid(512);                  // 2 workgroups per CU (244 VGPRs), each walking its share of the segments
+            if (plan_note(plan, 3, 32, 1, 4, grid, grid, 0, lt.nlines)) return 0;
             if (det) {
                 if (int rc = det_prepare(a, *det, grid, "forge_conv_wgrad_det")) return rc < 0 ? rc : 0;
                 FORGE_SET_MAX_LDS_ONCE(conv_wgrad_lines_kernel<true>, (LSEG * 32 + LMAXL * LROWS * 32) * sizeof(float));
@@ -718,6 +739,7 @@ static int conv_wgrad_run(const float* dy, int ldy, const float* x1, int C1, int
         }
         a.mchunk = (int)rows;
         const long long waves = ((M + rows - 1) / rows) * tap_groups;
+        if (plan_note(plan, 2, 32, 4, 4, (waves + 3) / 4, (M + rows - 1) / rows, (int)rows, 0)) return 0;
         if (det) {
             if (int rc = det_prepare(a, *det, (M + rows - 1) / rows, "forge_conv_wgrad_det")) return rc < 0 ? rc : 0;
             hipLaunchKernelGGL(conv_wgrad_small_kernel<true>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a, tap_groups, (int)rows);
@@ -727,7 +749,7 @@ static int conv_wgrad_run(const float* dy, int ldy, const float* x1, int C1, int
         FORGE_LAUNCH_CHECK("forge_conv_wgrad");
         return det ? det_finish(*det, (hipStream_t)stream, "forge_conv_wgrad_det") : 0;
     }
-    return launch_wgrad_tiles(a, (x2 == nullptr && Cin <= 32) ? 32 : (x2 == nullptr && Cin <= 64) ? 64 : WT, (hipStream_t)stream, det);
+    return launch_wgrad_tiles(a, (x2 == nullptr && Cin <= 32) ? 32 : (x2 == nullptr && Cin <= 64) ? 64 : WT, (hipStream_t)stream, det, plan);
 }
 
 extern "C" int forge_conv_wgrad(const float* dy, int ldy, const float* x1, int C1, int ld1, long long bs1, const float* x2, int C2, int ld2,
@@ -753,6 +775,21 @@ extern "C" long long forge_conv_wgrad_det_ws_bytes(int C1, int C2, int n, int D,
     const int rc = conv_wgrad_run(p, Cout, p, C1, C1, 0, C2 > 0 ? p : nullptr, C2, C2, 0, (float*)p, n, D, H, W, is, Di, Hi, Wi, Cout, taps, ntaps,
                                   nullptr, &d);
     return rc != 0 ? (rc < 0 ? rc : FORGE_EINVAL) : d.nslab * d.slab * 4;
+}
+
+// What forge_conv_wgrad (det = 0) / forge_conv_wgrad_det (det = 1) would launch for dense operands of this shape: conv_wgrad_run itself with
+// the launch switched off. plan[8] = family, CIW | CIT, TG | IS (small: taps per wave), waves per workgroup, workgroups, chunks, mchunk, lines.
+extern "C" int forge_conv_wgrad_plan(int C1, int C2, int n, int D, int H, int W, int is, int Di, int Hi, int Wi, int Cout, const int* taps, int ntaps,
+                                     int det, long long* plan) {
+    FORGE_REQUIRE(plan && (det == 0 || det == 1), FORGE_EINVAL, "forge_conv_wgrad_plan: null plan / det not 0 or 1");
+    DetPlan d = {false, nullptr, 0, 0, nullptr, 0, 0};
+    WgradPlan w = {true, 0, 0, 0, 0, 0, 0, 0, 0};
+    const float* p = plan_ptr();
+    const int rc = conv_wgrad_run(p, Cout, p, C1, C1, 0, C2 > 0 ? p : nullptr, C2, C2, 0, (float*)p, n, D, H, W, is, Di, Hi, Wi, Cout, taps, ntaps,
+                                  nullptr, det ? &d : nullptr, &w);
+    if (rc != 0) return rc < 0 ? rc : FORGE_EINVAL;
+    plan[0] = w.family; plan[1] = w.p1; plan[2] = w.p2; plan[3] = w.nwv; plan[4] = w.grid; plan[5] = w.nchunk; plan[6] = w.mchunk; plan[7] = w.nlines;
+    return 0;
 }
 
 // Weight gradient in the Winograd domain (csrc/winograd.hip): dU[p][kd][co][ci] = sum_r dMm[p][r][co] (V1 | V2)[p][r + kd plane][ci] for the 16

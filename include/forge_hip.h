@@ -174,7 +174,8 @@ int forge_resize_bilinear_bwd(const float* g, float* din, int P, int Hi, int Wi,
  *                               channel slice of a wider tensor can be fed). C1, C2 % 32 == 0. bs1/bs2 = batch
  *                               strides in rows (0 = dense Di Hi Wi): lets view t of a [b][t] stack be fed in place.
  *   wp  [ntaps][Cout][C1+C2]    packed weights: wp[t][co][ci] multiplies in[voxel + taps[t]][ci]
- *   taps [ntaps][3]             HOST array of (dz,dy,dx) input offsets, ntaps <= 27
+ *   taps [ntaps][3]             HOST array of (dz,dy,dx) input offsets, ntaps <= 27, every component in [-128, 127] (FORGE_EINVAL
+ *                               otherwise: the kernels carry taps as signed bytes)
  *   out rows                    output voxel of GEMM-grid voxel (z,y,x) is (z os+pz, y os+py, x os+px)
  *                               in an (n,Do,Ho,Wo) grid; row stride ldo floats.
  *                               plain conv: is=os=1, Di=Do=D..; strided conv: is=2; ConvTranspose phase: os=2.
@@ -313,6 +314,9 @@ int forge_wino_output(const float* Mm, const float* Mm2, long long bs2, long lon
  * dw [ntaps][Cout][C1+C2] MUST be zero-filled: partial sums over voxel chunks are accumulated with fp32 atomics (the order of
  * the additions, hence the last bits, is not deterministic; forge_conv_wgrad_det below is). With two inputs C1 must be a multiple of 128.
  * The data gradient needs no extra entry point: it is forge_conv_igemm on dy with negated taps and wp[t][ci][co] (transposed).
+ * Refusals: FORGE_EINVAL for null pointers, non-positive dims, ntaps outside 1..64, an x2 / C2 mismatch and any tap component outside
+ * [-128, 127] (the kernels carry taps as signed bytes); FORGE_ESHAPE for channel counts or row strides that are no multiple of 4, ld < C,
+ * two inputs with C1 % 128 != 0 and an operand spanning 2 GiB or more.
  */
 int forge_conv_wgrad(const float* dy, int ldy, const float* x1, int C1, int ld1, long long bs1, const float* x2, int C2, int ld2,
                      long long bs2, float* dw, int n, int D, int H, int W, int is, int Di, int Hi, int Wi, int Cout,
@@ -322,7 +326,8 @@ int forge_conv_wgrad(const float* dy, int ldy, const float* x1, int C1, int ld1,
  * a5 / a7  direct convolution for TINY channel counts (Cin in {4, 8, 16}, Cout in 1..4): the last convolutions of the density head
  * (Conv3d(8, 1, 3), models/encoder.py:31) and of conv_rgb (Conv2d(8, 3, 5), models/volume_render.py:36). A matrix-core tile pads such
  * a layer to 16 or 32 channels on both sides (up to 128x the useful FLOPs); these are streaming problems and run on the vector ALUs.
- * Stride-1 "same" geometry on channels-last rows: in [M][ld_in], w [ntaps][Cout][Cin], taps (dz,dy,dx) inside the (n,D,H,W) grid.
+ * Stride-1 "same" geometry on channels-last rows: in [M][ld_in], w [ntaps][Cout][Cin], taps (dz,dy,dx) inside the (n,D,H,W) grid, every
+ * component in [-128, 127] (FORGE_EINVAL otherwise: the kernels carry taps as signed bytes).
  *   fwd    out[m][co] = act(bias[co] + sum_t sum_ci w[t][co][ci] in[m + tap_t][ci])     (bias nullable; act = LeakyReLU(slope):
  *          slope 1 = none, 0 = ReLU - the inference path fuses the layer's trailing ReLU)
  *   dgrad  dx[m][ci]  = sum_t sum_co w[t][co][ci] dy[m - tap_t][co]
@@ -355,6 +360,15 @@ int forge_conv_wgrad_det(const float* dy, int ldy, const float* x1, int C1, int 
                          const int* taps, int ntaps, int accumulate, void* ws, long long ws_bytes, forge_stream_t stream);
 long long forge_conv_wgrad_det_ws_bytes(int C1, int C2, int n, int D, int H, int W, int is, int Di, int Hi, int Wi, int Cout,
                                         const int* taps, int ntaps);
+/* Host-only, like the query above: what forge_conv_wgrad (det = 0) or forge_conv_wgrad_det (det = 1) launches for dense operands of this
+ * shape - the dispatch itself with the launch switched off, refusals included (< 0). plan[8]:
+ *   [0] kernel family  1 conv_wgrad_kernel<CIW, TG>  2 conv_wgrad_small_kernel  3 conv_wgrad_lines_kernel  4 conv_wgrad_lines16_kernel<CIT, IS, .., NWV>
+ *   [1] CIW (128 / 64 / 32) or CIT (16 / 32); 32 for families 2, 3      [2] TG (1 / 2 / 4) or IS (1 / 2); taps per wave (4) for family 2
+ *   [3] waves per workgroup (NWV)                                       [4] workgroups of the launch
+ *   [5] voxel chunks (families 1, 2) or persistent workgroups walking the 32-voxel segments (3, 4): the slab count of the deterministic mode
+ *   [6] mchunk, voxels per chunk (0 for families 3, 4)                  [7] (dz, dy) lines (families 3, 4) */
+int forge_conv_wgrad_plan(int C1, int C2, int n, int D, int H, int W, int is, int Di, int Hi, int Wi, int Cout, const int* taps, int ntaps,
+                          int det, long long* plan);
 int forge_wino_wgrad_det(const float* dMm, const float* V1, int C1, long long bs1, long long pt1, const float* V2, int C2, long long bs2,
                          long long pt2, float* dU, int n, int D, int Ht, int Wt, int Cout, int kd, int accumulate, void* ws, long long ws_bytes,
                          forge_stream_t stream);

@@ -200,6 +200,31 @@ def test_conv_plan_is_host_arithmetic_and_sane():
     assert co.wino_gemm_tile(8192, 256, 256) == "B" and co.wino_gemm_tile(40960, 128, 64) == "B" and co.wino_gemm_tile(320, 256, 256) == "D"
 
 
+def test_conv_wgrad_plan_is_host_arithmetic(built_lib):
+    """forge_conv_wgrad_plan runs without a GPU and answers with the dispatch's own choice: the step's weight-gradient shapes land on the kernels
+    csrc/conv_wgrad.hip names for them, and a rejected shape comes back as the launch's error code."""
+    import ctypes
+    L = _lib.lib()
+    t27 = [(z, y, x) for z in (-1, 0, 1) for y in (-1, 0, 1) for x in (-1, 0, 1)]
+
+    def plan(C1, C2, n, D, H, W, Cout, taps, det=0, istride=1):
+        ta = (ctypes.c_int * (3 * len(taps)))(*[v for t in taps for v in t])
+        out = (ctypes.c_longlong * 8)()
+        rc = L.forge_conv_wgrad_plan(C1, C2, n, D, H, W, istride, D * istride if D > 1 else 1, H * istride, W * istride, Cout, ta, len(taps), det, out)
+        return rc, tuple(out)
+    for det in (0, 1):
+        assert plan(128, 128, 1, 32, 32, 32, 256, t27, det)[1][:4] == (1, 128, 1, 4)          # ConvGRU gates: 128-wide tiles, two inputs
+        assert plan(64, 0, 1, 32, 32, 32, 64, t27, det)[1][:4] == (1, 64, 1, 4)               # below M = 131072: ungrouped
+        assert plan(64, 0, 4, 32, 32, 32, 64, t27, det)[1][:4] == (1, 64, 2, 4)               # conv1 at 4 scenes: two taps per tile
+        assert plan(32, 0, 1, 64, 64, 64, 32, t27, det)[1][:4] == (3, 32, 1, 4)               # heads 32 -> 32: the line kernel
+        assert plan(32, 0, 1, 64, 64, 64, 16, t27, det)[1][:4] == (4, 32, 1, 8)               # heads 32 -> 16: 16 x 16 x 4 MFMA, 8 waves
+        assert plan(16, 0, 1, 64, 64, 64, 8, t27, det)[1][:4] == (4, 16, 1, 4)
+    rc, p = plan(64, 0, 1, 16, 16, 16, 64, t27)
+    assert rc == 0 and p[4] == 27 * p[5] and p[6] % 16 == 0 and p[5] * p[6] >= 4096 > (p[5] - 1) * p[6]     # grid = taps x chunks, chunks cover M
+    assert plan(64, 32, 1, 16, 16, 16, 64, t27)[0] == -2 and plan(64, 0, 0, 16, 16, 16, 64, t27)[0] == -1
+    assert plan(64, 0, 1, 16, 16, 16, 64, [(0, 0, 0), (0, 0, 128)])[0] == -1 and b"outside [-128, 127]" in L.forge_last_error()
+
+
 def test_plan_model_replica_of_the_fitting_tool_matches_the_library():
     """tools/fit_plan_model.py re-fits plan_conv's constants on sweep data with a Python replica of the model; the replica (and the constants it
     starts from) must stay the library's: same (tile, split-K) on a grid of 405 shapes."""

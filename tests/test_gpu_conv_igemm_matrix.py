@@ -306,7 +306,8 @@ def test_refusals_of_the_contract(dev):
                 ("lift with Cout <= 64", dict(epi=1, lift=2, Cout=64, ldo=64), b"lift needs"),
                 ("more K slices than K-steps", dict(taps=cc.T1, ksplit=2, ws=ws), b"ksplit=2 needs"),
                 ("merged phases with ntaps % nphase != 0", dict(ostride=2, ph=(-1, -1, -1), og=(1, 8, 8), taps=cc.T9), b"merged phases need ntaps"),
-                ("a row stride that breaks the 16-byte alignment", dict(ld1=34), b"row strides must")):
+                ("a row stride that breaks the 16-byte alignment", dict(ld1=34), b"row strides must"),
+                ("a tap component outside a signed byte", dict(taps=cc.T9[:8] + [(0, 0, 128)]), b"outside [-128, 127]")):
             rc, msg = call(**kw)
             assert rc == -1 and text in msg, (what, rc, msg)
         rc, msg = call()                                              # the baseline itself is a legal launch
