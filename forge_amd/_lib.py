@@ -77,6 +77,13 @@ SIGNATURES = {
     "forge_attention_bwd": [_P, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "forge_attention_mh_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I] + [_LL] * 8 + [_F, _P],
     "forge_attention_mh_bwd": [_P] * 10 + [_I, _I, _I, _I, _I] + [_LL] * 8 + [_F, _P],
+    "forge_token_linear_fwd": [_P, _LL, _P, _P, _P, _P, _F, _P, _LL, _P, _LL, _P, _P, _I, _I, _I, _I, _P],
+    "forge_layer_norm_fwd": [_P, _LL, _P, _P, _F, _P, _LL, _P, _I, _I, _P],
+    "forge_token_rows_plan": [_I, _I, _I, _P, _P],
+    "forge_token_linear_bwd_ws_bytes": [_I, _I, _I, _I],
+    "forge_token_linear_bwd": [_P, _LL, _P, _LL] + [_P] * 11 + [_LL, _I, _I, _I, _I, _P],
+    "forge_layer_norm_bwd_ws_bytes": [_I, _I],
+    "forge_layer_norm_bwd": [_P, _LL, _P, _LL] + [_P] * 6 + [_LL, _I, _I, _P],
     "forge_im2col_nchw": [_P, _P] + [_I] * 9 + [_P],
     "forge_maxpool2d_nhwc": [_P, _P] + [_I] * 7 + [_P],
     "forge_vgg_prep_fwd": [_P, _LL, _LL, _LL, _LL, _P, _LL, _LL, _LL, _LL, _P, _P, _P] + [_I] * 7 + [_P],
@@ -107,7 +114,8 @@ SIGNATURES = {
 
 
 _LL_RESULTS = ("forge_render_bwd_ws_bytes", "forge_conv_wgrad_det_ws_bytes", "forge_wino_wgrad_det_ws_bytes",     # byte counts: long long results
-               "forge_conv_direct_wgrad_det_ws_bytes", "forge_rotate_bwd_det_ws_bytes", "forge_rotate_bwd_slots_det_ws_bytes")
+               "forge_conv_direct_wgrad_det_ws_bytes", "forge_rotate_bwd_det_ws_bytes", "forge_rotate_bwd_slots_det_ws_bytes",
+               "forge_token_linear_bwd_ws_bytes", "forge_layer_norm_bwd_ws_bytes")
 
 
 def lib():

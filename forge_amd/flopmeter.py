@@ -1,7 +1,7 @@
 """Executed-FLOP meter for the matrix-core launches of libforge_hip.so (measurement aid for bench.py / tools; not on the product path).
 
 `with FlopMeter() as m: step()` wraps the ctypes entry points whose work runs on the fp32 MFMA pipe - forge_conv_igemm, forge_wino_gemm (_half, _dn),
-forge_conv_wgrad, forge_wino_wgrad, forge_attention_fwd / _fwd_lse / _bwd / _mh_fwd / _mh_bwd - for the duration of the block and sums the FLOPs each launch EXECUTES, computed from the call's own
+forge_conv_wgrad, forge_wino_wgrad, forge_attention_fwd / _fwd_lse / _bwd / _mh_fwd / _mh_bwd, forge_token_linear_fwd / _bwd - for the duration of the block and sums the FLOPs each launch EXECUTES, computed from the call's own
 arguments (2 M N taps Cin for a direct / data-gradient / weight-gradient convolution, 2 x 16 R N kd Cin for the 16 Winograd point problems).
 Only eager launches made by this process are seen (a hipGraph replay makes no Python calls): meter one eager pass, time the replay.
 """
@@ -57,9 +57,19 @@ def _attention_mh_bwd(a):   # forge_attention_mh_bwd(q,k,v,out,lse,dout,dq,dk,dv
     return (16.0 if _v(a[8]) else 14.0) * _v(a[10]) * _v(a[11]) * _v(a[12]) * _v(a[13]) * _v(a[14])
 
 
+def _token_fwd(a):      # forge_token_linear_fwd(x,ldx,w,bias,gamma,beta,eps,residual,ldr,y,ldy,pre,stats,R,K,N,act,stream): one R x N x K product
+    return 2.0 * _v(a[13]) * _v(a[14]) * _v(a[15])
+
+
+def _token_bwd(a):      # forge_token_linear_bwd(dy,lddy,x,ldx,w,gamma,beta,stats,pre,dx,dw,dbias,dgamma,dbeta,ws,ws_bytes,R,K,N,act,stream): g W (for dx or
+    dxn = _v(a[9]) or _v(a[12]) or _v(a[13])        # the LayerNorm's gradients) and g^T xn (dw), each R x N x K, each only when asked for
+    return 2.0 * _v(a[16]) * _v(a[17]) * _v(a[18]) * ((1 if dxn else 0) + (1 if _v(a[10]) else 0))
+
+
 _ENTRIES = {"forge_conv_igemm": _igemm, "forge_wino_gemm": _wino_gemm, "forge_wino_gemm_half": _wino_gemm, "forge_wino_gemm_dn": _wino_gemm_dn, "forge_conv_wgrad": _wgrad, "forge_wino_wgrad": _wino_wgrad,
             "forge_attention_fwd": _attention, "forge_attention_fwd_lse": _attention_lse, "forge_attention_bwd": _attention_bwd,
-            "forge_attention_mh_fwd": _attention_mh, "forge_attention_mh_bwd": _attention_mh_bwd}
+            "forge_attention_mh_fwd": _attention_mh, "forge_attention_mh_bwd": _attention_mh_bwd,
+            "forge_token_linear_fwd": _token_fwd, "forge_token_linear_bwd": _token_bwd}
 
 
 class FlopMeter:

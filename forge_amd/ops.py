@@ -448,3 +448,296 @@ def attention_mh_train(q, k, v, num_heads, scale):
     raises."""
     _mh_check("attention_mh_train", q, k, v, num_heads, scale)
     return _AttentionMHTrain.apply(q, k, v, num_heads, float(scale))
+
+
+# ---- token-row layers (LayerNorm / Linear / GELU around the attention kernels of both pose estimators), opt-in: forge_token_linear_fwd / _bwd,
+# forge_layer_norm_fwd / _bwd (csrc/token.hip). Off by default - with the switch off nothing in the package calls the entry points and the blocks
+# run nn.LayerNorm / nn.Linear / nn.GELU, bit for bit as before. Independent of set_attention_training and set_multihead_attention.
+_token_layers = os.environ.get("FORGE_TOKEN_LAYERS", "0") == "1"                   # read once, at import
+
+
+def set_token_layers(flag):
+    """True: the transformer blocks of both pose estimators run their LayerNorm / Linear / GELU chains on ops.token_linear / ops.layer_norm where
+    token_layers_applies holds; False (the default, or FORGE_TOKEN_LAYERS unset at import): they keep torch's modules. Returns the previous setting."""
+    global _token_layers
+    if not isinstance(flag, bool):
+        raise TypeError("set_token_layers takes True or False (got %r)" % (flag,))
+    prev, _token_layers = _token_layers, flag
+    return prev
+
+
+def token_layers():
+    """The current setting of set_token_layers()."""
+    return _token_layers
+
+
+TOKEN_MAX_CHANNELS, TOKEN_MAX_LN_CHANNELS = 1024, 256
+
+
+def _token_rows(t):
+    """(rows view [R,C], row stride in floats) of a [..., C] tensor whose leading dimensions collapse into one row stride, or None."""
+    if not (torch.is_tensor(t) and t.dim() >= 2 and t.is_cuda and t.dtype == torch.float32 and t.stride(-1) == 1 and t.numel() > 0):
+        return None
+    try:
+        v = t.view(-1, t.shape[-1])
+    except RuntimeError:
+        return None
+    ld = v.stride(0) if v.shape[0] > 1 else v.shape[1]
+    if ld % 4 or ld < v.shape[1] or v.data_ptr() % 16 or v.shape[0] >= 1 << 31:
+        return None
+    return v, ld
+
+
+def _token_vec(t, n, dev):
+    return torch.is_tensor(t) and t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.shape == (n,) and t.is_contiguous() and t.data_ptr() % 16 == 0
+
+
+def _layer_norm_domain(x, gamma, beta, eps):
+    rows = _token_rows(x)
+    if rows is None:
+        return False
+    K = x.shape[-1]
+    return (K % 64 == 0 and 64 <= K <= TOKEN_MAX_LN_CHANNELS and _token_vec(gamma, K, x.device) and _token_vec(beta, K, x.device)
+            and isinstance(eps, (int, float)) and not isinstance(eps, bool) and math.isfinite(eps) and eps >= 0)
+
+
+def _token_domain(x, weight, bias=None, ln=None, act=None, residual=None):
+    """The domain of forge_token_linear_fwd / _bwd: fp32 x [...,K] on a HIP device with channel stride 1, leading dimensions that collapse into one
+    row stride (a multiple of 4 floats), 16-byte aligned storage; weight [N,K] contiguous; K and N multiples of 64 up to 1024 (K <= 256 under a
+    LayerNorm prologue ln = (gamma, beta, eps)); act None or "gelu"; bias [N]; residual [...,N] addressed like x."""
+    if _token_rows(x) is None or act not in (None, "gelu"):
+        return False
+    K, dev = x.shape[-1], x.device
+    if not (torch.is_tensor(weight) and weight.dim() == 2 and weight.is_cuda and weight.device == dev and weight.dtype == torch.float32
+            and weight.shape[1] == K and weight.is_contiguous() and weight.data_ptr() % 16 == 0):
+        return False
+    N = weight.shape[0]
+    if K % 64 or N % 64 or not (64 <= K <= TOKEN_MAX_CHANNELS and 64 <= N <= TOKEN_MAX_CHANNELS):
+        return False
+    if bias is not None and not _token_vec(bias, N, dev):
+        return False
+    if ln is not None and not (isinstance(ln, (tuple, list)) and len(ln) == 3 and _layer_norm_domain(x, *ln)):
+        return False
+    if residual is not None and not (_token_rows(residual) is not None and residual.device == dev and residual.shape == x.shape[:-1] + (N,)):
+        return False
+    return True
+
+
+def token_layers_applies(x, weight=None, bias=None, ln=None, act=None, residual=None, dropout_p=0.0, training=False):
+    """The dispatch predicate of the pose estimators' blocks: the switch (set_token_layers / FORGE_TOKEN_LAYERS=1) is on, dropout is inactive
+    (p == 0, or the module is in eval mode) and the arguments are in the kernels' domain - of ops.token_linear, or with weight None of
+    ops.layer_norm (ln = (gamma, beta, eps))."""
+    if not _token_layers or (dropout_p != 0 and training):
+        return False
+    if weight is None:
+        return isinstance(ln, (tuple, list)) and len(ln) == 3 and _layer_norm_domain(x, *ln)
+    return _token_domain(x, weight, bias, ln, act, residual)
+
+
+def _token_desc(t):
+    return "%s %s strides %s %s" % (tuple(t.shape), str(t.dtype).replace("torch.", ""), tuple(t.stride()), t.device) if torch.is_tensor(t) else repr(t)
+
+
+def _token_check(what, x, weight, bias, ln, act, residual):
+    if _token_domain(x, weight, bias, ln, act, residual):
+        return
+    raise RuntimeError("forge_amd: ops.%s needs fp32 x [...,K] and weight [N,K] on the MI355X with K and N multiples of 64 up to %d (K <= %d under a "
+                       "LayerNorm (gamma, beta, eps)), channel stride 1, one row stride that is a multiple of 4 floats, 16-byte aligned storage, act None "
+                       "or 'gelu', bias [N] and residual [...,N] (got act %r, x %s, weight %s, bias %s, ln %s, residual %s)"
+                       % (what, TOKEN_MAX_CHANNELS, TOKEN_MAX_LN_CHANNELS, act, _token_desc(x), _token_desc(weight), _token_desc(bias),
+                          "(%s)" % ", ".join(_token_desc(t) for t in ln) if isinstance(ln, (tuple, list)) else repr(ln), _token_desc(residual)))
+
+
+def _layer_norm_check(what, x, gamma, beta, eps):
+    if _layer_norm_domain(x, gamma, beta, eps):
+        return
+    raise RuntimeError("forge_amd: ops.%s needs fp32 x [...,K] on the MI355X with K a multiple of 64 up to %d, channel stride 1, one row stride that is a "
+                       "multiple of 4 floats, 16-byte aligned storage, gamma / beta [K] and a finite eps >= 0 (got x %s, gamma %s, beta %s, eps %r)"
+                       % (what, TOKEN_MAX_LN_CHANNELS, _token_desc(x), _token_desc(gamma), _token_desc(beta), eps))
+
+
+_TOKEN_ACT = {None: 0, "gelu": 1}
+
+
+def _token_forward(x, weight, bias, ln, act, residual, out, want_saved):
+    """One forge_token_linear_fwd launch. Returns (y, stats or None, pre or None); stats / pre only when want_saved (the autograd form)."""
+    (xr, ldx), N = _token_rows(x), weight.shape[0]
+    R, K = xr.shape
+    y = torch.empty(x.shape[:-1] + (N,), dtype=torch.float32, device=x.device) if out is None else out
+    yr, ldy = _token_rows(y)
+    rr, ldr = _token_rows(residual) if residual is not None else (None, 0)
+    gamma, beta, eps = ln if ln is not None else (None, None, 0.0)
+    stats = torch.empty(R, 2, dtype=torch.float32, device=x.device) if want_saved and ln is not None else None
+    pre = torch.empty(R, N, dtype=torch.float32, device=x.device) if want_saved and act is not None else None
+    _lib.check(_lib.lib().forge_token_linear_fwd(_lib.ptr(xr), ldx, _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(gamma), _lib.ptr(beta), float(eps),
+                                                 _lib.ptr(rr), ldr, _lib.ptr(yr), ldy, _lib.ptr(pre), _lib.ptr(stats), R, K, N, _TOKEN_ACT[act],
+                                                 _lib.current_stream()), "forge_token_linear_fwd")
+    return y, stats, pre
+
+
+@_lib.on_tensor_device
+def token_linear(x, weight, bias=None, ln=None, act=None, residual=None, out=None):
+    """act(LN?(x) weight^T + bias) (+ residual) in one launch (forge_token_linear_fwd): x [...,K], weight [N,K] (nn.Linear's), ln = (gamma, beta,
+    eps) a LayerNorm over the K channels in front of the product, act None or "gelu" (exact erf), residual [...,N] added last -> [...,N]. `out`:
+    a preallocated [...,N] destination, possibly a slice of a wider tensor (a q|k|v slab); the bits do not depend on its strides. Inference only
+    (no autograd node); independent of the switch (that gates token_layers_applies, the modules' dispatch); outside the domain it raises."""
+    _token_check("token_linear", x, weight, bias, ln, act, residual)
+    if out is not None and not (_token_rows(out) is not None and out.device == x.device and out.shape == x.shape[:-1] + (weight.shape[0],)):
+        raise RuntimeError("forge_amd: ops.token_linear: out must be fp32 %s on x's device, addressed like x (got %s)"
+                           % (tuple(x.shape[:-1] + (weight.shape[0],)), _token_desc(out)))
+    det = lambda t: None if t is None else t.detach()
+    y = _token_forward(x.detach(), weight.detach(), det(bias), None if ln is None else (ln[0].detach(), ln[1].detach(), ln[2]), act, det(residual),
+                       det(out), False)[0]
+    return y if out is None else out
+
+
+class _TokenLinearTrain(torch.autograd.Function):
+    """forge_token_linear_fwd / forge_token_linear_bwd: saved for backward are x (as it came), the parameters, stats [R,2] (with a LayerNorm) and the
+    pre-activation (only with GELU) - never the normalised rows."""
+
+    @staticmethod
+    @_lib.on_tensor_device
+    def forward(ctx, x, weight, bias, gamma, beta, residual, eps, act):
+        ln = None if gamma is None else (gamma, beta, eps)
+        y, stats, pre = _token_forward(x, weight, bias, ln, act, residual, None, True)
+        ctx.act, ctx.has_ln = act, ln is not None
+        ctx.save_for_backward(x, weight, gamma, beta, stats, pre)
+        return y
+
+    @staticmethod
+    @_lib.on_tensor_device
+    def backward(ctx, dy):
+        x, weight, gamma, beta, stats, pre = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        (xr, ldx), (N, K) = _token_rows(x), weight.shape
+        R = xr.shape[0]
+        dy = dy.contiguous()
+        dyr = dy.view(R, N)
+        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=x.device)         # written in full by the kernels: no zero-fills
+        dx = new(x.shape) if need[0] else None
+        dw = new(N, K) if need[1] or need[2] else None                                # dbias is a by-product of the dW pass
+        db = new(N) if need[2] else None
+        dg = new(K) if ctx.has_ln and need[3] else None
+        dbt = new(K) if ctx.has_ln and need[4] else None
+        L = _lib.lib()
+        nbytes = L.forge_token_linear_bwd_ws_bytes(R, K, N, int(ctx.has_ln))
+        ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=x.device)
+        _lib.check(L.forge_token_linear_bwd(_lib.ptr(dyr), N, _lib.ptr(xr), ldx, _lib.ptr(weight), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(stats),
+                                            _lib.ptr(pre), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(dg), _lib.ptr(dbt), _lib.ptr(ws), nbytes, R, K, N,
+                                            _TOKEN_ACT[ctx.act], _lib.current_stream()), "forge_token_linear_bwd")
+        return dx, (dw if need[1] else None), db, dg, dbt, (dy if need[5] else None), None, None
+
+
+def token_linear_train(x, weight, bias=None, ln=None, act=None, residual=None):
+    """ops.token_linear inside an autograd graph (same kernel, same bits) with the HIP backward forge_token_linear_bwd: gradients for x, weight,
+    bias, the LayerNorm's gamma / beta and the residual; the normalised rows are recomputed, the sums over rows are chunked in a fixed order (no
+    atomics: bitwise reproducible). Independent of the switch; outside the domain it raises."""
+    _token_check("token_linear_train", x, weight, bias, ln, act, residual)
+    gamma, beta, eps = ln if ln is not None else (None, None, 0.0)
+    return _TokenLinearTrain.apply(x, weight, bias, gamma, beta, residual, float(eps), act)
+
+
+def _layer_norm_forward(x, gamma, beta, eps, want_stats):
+    xr, ldx = _token_rows(x)
+    R, K = xr.shape
+    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    stats = torch.empty(R, 2, dtype=torch.float32, device=x.device) if want_stats else None
+    _lib.check(_lib.lib().forge_layer_norm_fwd(_lib.ptr(xr), ldx, _lib.ptr(gamma), _lib.ptr(beta), float(eps), _lib.ptr(y), K, _lib.ptr(stats), R, K,
+                                               _lib.current_stream()), "forge_layer_norm_fwd")
+    return y, stats
+
+
+@_lib.on_tensor_device
+def layer_norm(x, gamma, beta, eps=1e-5):
+    """F.layer_norm(x, (K,), gamma, beta, eps) over the last dimension of x [...,K] (forge_layer_norm_fwd: the LayerNorm prologue of
+    ops.token_linear stand-alone, same bits). Inference only (no autograd node); independent of the switch; outside the domain it raises."""
+    _layer_norm_check("layer_norm", x, gamma, beta, eps)
+    return _layer_norm_forward(x.detach(), gamma.detach(), beta.detach(), eps, False)[0]
+
+
+class _LayerNormTrain(torch.autograd.Function):
+    """forge_layer_norm_fwd / forge_layer_norm_bwd: saved for backward are x, gamma and stats [R,2]."""
+
+    @staticmethod
+    @_lib.on_tensor_device
+    def forward(ctx, x, gamma, beta, eps):
+        y, stats = _layer_norm_forward(x, gamma, beta, eps, True)
+        ctx.save_for_backward(x, gamma, stats)
+        return y
+
+    @staticmethod
+    @_lib.on_tensor_device
+    def backward(ctx, dy):
+        x, gamma, stats = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        xr, ldx = _token_rows(x)
+        R, K = xr.shape
+        dyr = dy.contiguous().view(R, K)
+        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=x.device)
+        dx, dg, dbt = (new(x.shape) if need[0] else None), (new(K) if need[1] else None), (new(K) if need[2] else None)
+        L = _lib.lib()
+        nbytes = L.forge_layer_norm_bwd_ws_bytes(R, K)
+        ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=x.device)
+        _lib.check(L.forge_layer_norm_bwd(_lib.ptr(dyr), K, _lib.ptr(xr), ldx, _lib.ptr(gamma), _lib.ptr(stats), _lib.ptr(dx), _lib.ptr(dg), _lib.ptr(dbt),
+                                          _lib.ptr(ws), nbytes, R, K, _lib.current_stream()), "forge_layer_norm_bwd")
+        return dx, dg, dbt, None
+
+
+def layer_norm_train(x, gamma, beta, eps=1e-5):
+    """ops.layer_norm inside an autograd graph (same kernel, same bits) with the HIP backward forge_layer_norm_bwd (no atomics: bitwise
+    reproducible). Independent of the switch; outside the domain it raises."""
+    _layer_norm_check("layer_norm_train", x, gamma, beta, eps)
+    return _LayerNormTrain.apply(x, gamma, beta, float(eps))
+
+
+def token_rows_plan(R, K, N):
+    """(chunks, chunk_rows) of forge_token_linear_bwd's sums over rows (dW, dbias): host arithmetic on the shape alone (forge_token_rows_plan)."""
+    import ctypes
+    c, r = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.check(_lib.lib().forge_token_rows_plan(int(R), int(K), int(N), ctypes.byref(c), ctypes.byref(r)), "forge_token_rows_plan")
+    return c.value, r.value
+
+
+def _plain_layer_norm(norm, K):
+    """(gamma, beta, eps) of an nn.LayerNorm over the last K channels with both affine parameters, else None."""
+    if (isinstance(norm, torch.nn.LayerNorm) and tuple(norm.normalized_shape) == (K,) and norm.weight is not None and norm.bias is not None):
+        return norm.weight, norm.bias, norm.eps
+    return None
+
+
+# Call sites that stay on torch even with the switch on (names: the `site` arguments of the modules' dispatch - 2d.proj, 2d.o_proj, 2d.fc1,
+# 2d.fc2, 2d.norm, 3d.qk, 3d.v, 3d.fc1, 3d.fc2). profiles/r16_token_layers_probe.txt: as a hipGraph replay at one scene PoseEstimator3D wins
+# every alternated window with its sites on the kernels, PoseEstimator2D loses every window (2.65 ms against 2.39 ms) - rocBLAS is the faster
+# GEMM at 1024 x 256 rows once the launches cost nothing - so the 2-D estimator's sites are listed here until their kernels win. Tests and
+# tools/token_layers_probe.py empty the set to exercise and measure the 2-D wiring.
+TOKEN_SITES_ON_TORCH = frozenset(("2d.proj", "2d.o_proj", "2d.fc1", "2d.fc2", "2d.norm"))
+
+
+def module_token_linear(x, weight, bias, norm=None, act=None, residual=None, dropout_p=0.0, training=False, site=None):
+    """The modules' dispatch of one `residual + act(linear(norm(x)))` site: the fused launch (ops.token_linear_train inside an autograd graph, else
+    ops.token_linear) when token_layers_applies holds, else None - the caller then runs its stock statements. norm: an nn.LayerNorm or None; act: an
+    nn.GELU (exact erf) or None."""
+    if not _token_layers or site in TOKEN_SITES_ON_TORCH:
+        return None
+    ln = None
+    if norm is not None:
+        ln = _plain_layer_norm(norm, x.shape[-1]) if torch.is_tensor(x) and x.dim() >= 1 else None
+        if ln is None:
+            return None
+    if act is not None and not (isinstance(act, torch.nn.GELU) and getattr(act, "approximate", "none") == "none"):
+        return None
+    a = None if act is None else "gelu"
+    if not token_layers_applies(x, weight, bias, ln, a, residual, dropout_p=dropout_p, training=training):
+        return None
+    fn = token_linear_train if torch.is_grad_enabled() else token_linear
+    return fn(x, weight, bias, ln=ln, act=a, residual=residual)
+
+
+def module_layer_norm(x, norm, site=None):
+    """The modules' dispatch of one stand-alone nn.LayerNorm site: ops.layer_norm(_train) when token_layers_applies holds, else None."""
+    if not _token_layers or site in TOKEN_SITES_ON_TORCH or not torch.is_tensor(x) or x.dim() < 1:
+        return None
+    ln = _plain_layer_norm(norm, x.shape[-1])
+    if ln is None or not token_layers_applies(x, ln=ln):
+        return None
+    return (layer_norm_train if torch.is_grad_enabled() else layer_norm)(x, *ln)

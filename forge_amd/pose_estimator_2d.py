@@ -5,12 +5,15 @@ blocks of models/model_utils.py:258-427 (einops is not required).
 On the MI355X every convolution of the module - the FPN's LeakyReLU ResNet-50, its lateral / top / smoothing layers and the four stride-2
 convolutions of `conv` - runs on libforge_hip.so with HIP BatchNorm (round 5; FPN.forward_rows, PoseEstimator2D._conv_rows; in eval mode without
 an autograd graph as the inference schedule of forge_amd/frozen.py: one launch per convolution, BatchNorm folded). The six attention
-blocks' projections, LayerNorms and MLPs are stock torch (rocBLAS GEMMs); their softmax attention is stock torch too (head-split copies, bmm,
+blocks' projections, LayerNorms and MLPs are stock torch (rocBLAS GEMMs). They are wired to the fused token-row kernels (ops.token_linear /
+ops.layer_norm = forge_token_linear_fwd / _bwd, forge_layer_norm_fwd / _bwd) behind ops.set_token_layers(True) / FORGE_TOKEN_LAYERS=1, but every
+site of this module is listed in ops.TOKEN_SITES_ON_TORCH and stays on torch even with that switch on: as a hipGraph replay the estimator lost with
+them (profiles/r16_token_layers_probe.txt). `out` (Linear + BatchNorm1d on 4 rows) is torch in any case. Their softmax attention is stock torch too (head-split copies, bmm,
 softmax over a materialised [B*4,Nq,Nk] matrix, bmm, head-merge copy: eight launches) unless ops.set_multihead_attention(True) (or
 FORGE_ATTENTION_MH=1) routes it to forge_attention_mh_fwd / forge_attention_mh_bwd: one launch forward that reads the heads where the
 projections wrote them, three backward, no N x N matrix. Off by default. One path: host tensors raise (the stock-torch evaluation of the same
 modules that tests and probes compare against lives in tools/stock_pose.py; it calls these attention blocks, so it is stock only with the
-switch off)."""
+switches off)."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -58,12 +61,16 @@ class MultiHeadAttention(nn.Module):
     def forward(self, x_q, x_k, x_v, pad_mask=None, attn_mask=None):
         if attn_mask is not None:
             raise NotImplementedError("attention masks not supported")
-        b = x_q.shape[0]
-        q, k, v = self.q_proj(x_q), self.k_proj(x_k), self.v_proj(x_v)
-        if _ops.attention_mh_applies(q, k, v, self.num_heads, pad_mask=pad_mask, attn_mask=attn_mask, dropout_p=self.dropout.p, training=self.training):
+        return self.attend(self.q_proj(x_q), self.k_proj(x_k), self.v_proj(x_v), pad_mask=pad_mask)
+
+    def attend(self, q, k, v, pad_mask=None, residual=None):
+        """o_proj(softmax(scale q_h k_h^T) v_h) (+ residual) for the projected q, k, v (forward's second half; the fused token-layer routes of
+        CrossAttention / SelfAttention enter here with their own projections and hand o_proj its residual)."""
+        b = q.shape[0]
+        if _ops.attention_mh_applies(q, k, v, self.num_heads, pad_mask=pad_mask, attn_mask=None, dropout_p=self.dropout.p, training=self.training):
             # opt-in (ops.set_multihead_attention; False whenever the switch is off): the kernels read the heads where the projections wrote them
             attend = _ops.attention_mh_train if torch.is_grad_enabled() else _ops.attention_mh
-            return self.o_proj(attend(q, k, v, self.num_heads, self.dp_scale))
+            return self._out(attend(q, k, v, self.num_heads, self.dp_scale), residual)
         q, k, v = self._heads(q), self._heads(k), self._heads(v)
         attn = torch.bmm(q, k.transpose(1, 2)) * self.dp_scale
         if pad_mask is not None:
@@ -72,7 +79,26 @@ class MultiHeadAttention(nn.Module):
         attn = self.dropout(attn.softmax(dim=-1))
         o = torch.bmm(attn, v)
         o = o.reshape(b, self.num_heads, o.shape[1], -1).permute(0, 2, 1, 3).reshape(b, o.shape[1], -1)
-        return self.o_proj(o)
+        return self._out(o, residual)
+
+    def _out(self, o, residual):
+        if residual is None:
+            return self.o_proj(o)
+        y = _ops.module_token_linear(o, self.o_proj.weight, self.o_proj.bias, residual=residual, site="2d.o_proj")       # opt-in: the residual in o_proj's epilogue
+        return residual + self.o_proj(o) if y is None else y
+
+
+def _linear(x, lin, norm=None, site="2d.proj"):
+    """lin(norm(x)): one LN + Linear launch under ops.set_token_layers where the tensors are in the kernels' domain, else the stock statements."""
+    y = _ops.module_token_linear(x, lin.weight, lin.bias, norm=norm, site=site)
+    if y is not None:
+        return y
+    return lin(x if norm is None else norm(x))
+
+
+def _norm(x, norm):
+    y = _ops.module_layer_norm(x, norm, site="2d.norm")
+    return norm(x) if y is None else y
 
 
 class MLP_attention(nn.Module):
@@ -84,6 +110,11 @@ class MLP_attention(nn.Module):
                                  nn.GELU(), nn.Linear(widening_factor * num_channels, num_channels))
 
     def forward(self, x):
+        if _ops.token_layers():
+            # opt-in: LayerNorm + fc1 + GELU in one launch, fc2 in another (each site falls back to its stock statements outside the kernels' domain)
+            norm, fc1, act, fc2 = self.mlp
+            h = _ops.module_token_linear(x, fc1.weight, fc1.bias, norm=norm, act=act, site="2d.fc1")
+            return _linear(act(fc1(norm(x))) if h is None else h, fc2, site="2d.fc2")
         return self.mlp(x)
 
 
@@ -101,6 +132,14 @@ class CrossAttention(nn.Module):
         self.mlp = MLP_attention(num_q_input_channels, mlp_ratio)
 
     def forward(self, x_q, x_k, x_v, pad_mask=None, attn_mask=None, residual=False):
+        if _ops.token_layers() and attn_mask is None:
+            # opt-in (ops.set_token_layers): q_norm -> q_proj, k_norm -> k_proj, v_norm -> v_proj as three LN + Linear launches, the residual in
+            # o_proj's epilogue; `residual is True` needs the normalised x_q itself
+            att = self.attention
+            res = residual if torch.is_tensor(residual) else _norm(x_q, self.q_norm) if residual is True else None
+            a = att.attend(_linear(x_q, att.q_proj, self.q_norm), _linear(x_k, att.k_proj, self.k_norm), _linear(x_v, att.v_proj, self.v_norm),
+                           pad_mask=pad_mask, residual=res)
+            return self.mlp(a)
         x_q, x_k, x_v = self.q_norm(x_q), self.k_norm(x_k), self.v_norm(x_v)
         a = self.attention(x_q, x_k, x_v, pad_mask=pad_mask, attn_mask=attn_mask)
         if torch.is_tensor(residual):
@@ -121,6 +160,11 @@ class SelfAttention(nn.Module):
         self.mlp = MLP_attention(num_channels, mlp_ratio)
 
     def forward(self, x, pad_mask=None, attn_mask=None):
+        if _ops.token_layers() and attn_mask is None:
+            # opt-in (ops.set_token_layers): the LayerNorm once (its output is also the residual), three plain projections, the residual in o_proj's epilogue
+            att = self.attention
+            x = _norm(x, self.norm)
+            return self.mlp(att.attend(_linear(x, att.q_proj), _linear(x, att.k_proj), _linear(x, att.v_proj), pad_mask=pad_mask, residual=x))
         x = self.norm(x)
         return self.mlp(x + self.attention(x, x, x, pad_mask=pad_mask, attn_mask=attn_mask))
 

@@ -4,8 +4,10 @@ models/pose_estimator_3d.py:9-144 and the Block/Attention/Mlp/positional-embeddi
 
 On the MI355X its eight 3x3x3 convolutions (stride 1 and 2) + BatchNorm + LeakyReLU run on libforge_hip.so (convops.conv3d_rows, bn_act_rows on
 channels-last rows; round 5): in the joint fine-tune step (BASELINE configs[4]) MIOpen served them with its `naive_conv_*` fp32 kernels - 164 ms
-of a 256 ms step (profiles/r05_joint_grid32_kernel_share_before.txt). The attention block's 1x1 projections and MLP stay stock torch (rocBLAS
-GEMMs); its 4096-token softmax attentions run on forge_attention_fwd in inference and, in training, on torch's differentiable ops unless
+of a 256 ms step (profiles/r05_joint_grid32_kernel_share_before.txt). The attention block's 1x1 projections, LayerNorms and MLP stay stock torch (rocBLAS
+GEMMs) unless ops.set_token_layers(True) (or FORGE_TOKEN_LAYERS=1; off by default) routes them to ops.token_linear = forge_token_linear_fwd / _bwd:
+LN + encode_query, LN + encode_key, encode_value, LN + fc1 + GELU and fc2 + residual, five launches a Block, forward and backward (the [B,C,N]
+training route then goes tokens-major internally). pose_head_2 (a LayerNorm over 1024 channels on 4 rows) and `out` are torch in any case. Its 4096-token softmax attentions run on forge_attention_fwd in inference and, in training, on torch's differentiable ops unless
 ops.set_attention_training(True) (or FORGE_ATTENTION_TRAIN=1) routes them to forge_attention_fwd_lse / forge_attention_bwd. CPU tensors run
 the same modules on torch's own kernels (the architecture pin of tests/test_oracle_golden.py)."""
 import math
@@ -96,6 +98,8 @@ class Block(nn.Module):
     def _qk(self, query, key, query_embed, key_embed):
         q = query if query_embed is None else query + query_embed.to(query)
         k = key if key_embed is None else key + key_embed.to(key)
+        if self._tokens_route(q):
+            return self.qk_tokens(q.permute(0, 2, 1).contiguous(), k.permute(0, 2, 1).contiguous())       # opt-in: the same function, tokens-major
         q = self.norm(q.permute(0, 2, 1)).permute(0, 2, 1)
         k = self.norm(k.permute(0, 2, 1)).permute(0, 2, 1)
         return self.encode_query(q).permute(0, 2, 1), self.encode_key(k).permute(0, 2, 1)
@@ -103,18 +107,41 @@ class Block(nn.Module):
     # ---- tokens-major twins ([B,N,C] in and out): the 1x1 Conv1d encoders are linear layers over the channels, so with the tokens as rows - what
     # the HIP convolutions around the transformer produce and consume - LayerNorm, encoders, attention and MLP chain without a single permute copy
     @staticmethod
-    def _lin(conv, x):
-        return torch.nn.functional.linear(x, conv.weight[:, :, 0], conv.bias)
+    def _lin(conv, x, norm=None, site="3d.v"):
+        """conv(norm(x)) for a 1x1 Conv1d on tokens-major rows; one LN + Linear launch under ops.set_token_layers (opt-in) where the tensors are in
+        the kernels' domain"""
+        from . import ops
+        y = ops.module_token_linear(x, conv.weight[:, :, 0], conv.bias, norm=norm, site=site)
+        if y is not None:
+            return y
+        return torch.nn.functional.linear(x if norm is None else norm(x), conv.weight[:, :, 0], conv.bias)
+
+    @staticmethod
+    def _tokens_route(x):
+        """the [B,C,N] training route goes tokens-major internally under ops.set_token_layers (fp32 tensors on the MI355X)"""
+        from . import ops
+        return ops.token_layers() and x.is_cuda and x.dtype == torch.float32
 
     def qk_tokens(self, query, key):
-        return self._lin(self.encode_query, self.norm(query)), self._lin(self.encode_key, self.norm(key))
+        return self._lin(self.encode_query, query, self.norm, "3d.qk"), self._lin(self.encode_key, key, self.norm, "3d.qk")
+
+    def _mlp_tokens(self, x):
+        """x + mlp(norm2(x)); under ops.set_token_layers LN + fc1 + GELU in one launch and fc2 with the residual in another (not with an active dropout)"""
+        from . import ops
+        m = self.mlp
+        drop = dict(dropout_p=m.drop.p, training=m.training)
+        h = ops.module_token_linear(x, m.fc1.weight, m.fc1.bias, norm=self.norm2, act=m.act, site="3d.fc1", **drop)
+        if h is not None:
+            y = ops.module_token_linear(h, m.fc2.weight, m.fc2.bias, residual=x, site="3d.fc2", **drop)
+            return x + m.fc2(h) if y is None else y
+        return x + self.mlp(self.norm2(x))
 
     def forward_tokens(self, query, key):
         from . import ops
         q, k = self.qk_tokens(query, key)
         v = self._lin(self.encode_value, key)
         x = query + (ops.attention(q, k, v) if ops.attention_applies(q, k, v) else self.attn(query=q, key=k, value=v))    # (attn: the opt-in training kernels)
-        return x + self.mlp(self.norm2(x))
+        return self._mlp_tokens(x)
 
     def get_attn(self, query, key, query_embed=None, key_embed=None):
         q, k = self._qk(query, key, query_embed, key_embed)
@@ -122,6 +149,9 @@ class Block(nn.Module):
 
     def forward(self, query, key, query_embed=None, key_embed=None):
         b = query.shape[0]
+        if query_embed is None and key_embed is None and self._tokens_route(query):
+            x = self.forward_tokens(query.permute(0, 2, 1).contiguous(), key.permute(0, 2, 1).contiguous())      # opt-in: the same function, tokens-major
+            return x.permute(0, 2, 1).contiguous().view(b, self.channels, -1)
         q, k = self._qk(query, key, query_embed, key_embed)
         v = self.encode_value(key).permute(0, 2, 1)
         x = query.permute(0, 2, 1)

@@ -517,6 +517,51 @@ int forge_attention_mh_bwd(const float* q, const float* k, const float* v, const
                            long long k_bs, long long k_rs, long long v_bs, long long v_rs, long long out_bs, long long out_rs, float scale,
                            forge_stream_t stream);
 
+/* Token-row layers of the pose estimators' transformer blocks (csrc/token.hip; opt-in on the Python side: ops.set_token_layers): LayerNorm,
+ * Linear and exact-erf GELU on fp32 rows, the GEMMs on v_mfma_f32_32x32x2_f32 (a k-ordered fmaf chain).
+ * Common rules: fp32; channel stride 1; row strides (ld*, in floats) multiples of 4 and at least the row's width (FORGE_ESHAPE); every pointer
+ * 16-byte aligned (FORGE_EINVAL); R >= 1 rows of any count (the last 32-row tile is masked; R < 1 is FORGE_EINVAL); K and N multiples of 64, at
+ * most 1024, and K <= 256 wherever a LayerNorm is involved - its normalised 32-row tile lives in LDS (FORGE_ESHAPE). w [N][K] is nn.Linear's
+ * layout, dense. Every check runs before the first launch; nothing is allocated and nothing synchronises (capturable into a hipGraph). No
+ * atomics: every result is bitwise reproducible.
+ *
+ * forge_token_linear_fwd: y[R][N] = act( LN?(x[R][K]) w^T + bias ) (+ residual), one launch.
+ *   LayerNorm prologue iff gamma != NULL (beta then required, eps finite and >= 0): torch's definition - mean and biased variance per row,
+ *     (x - mean) rstd gamma + beta with rstd = 1 / sqrt(var + eps) - the statistics in two passes over the resident row (mean, then the centred
+ *     squares). stats [R][2] nullable (only with the prologue): (mean, rstd) per row, for the backward.
+ *   act: FORGE_TOKEN_ACT_NONE or FORGE_TOKEN_ACT_GELU (0.5 v (1 + erf(v / sqrt 2)), nn.GELU()'s default); anything else FORGE_EINVAL.
+ *     pre [R][N] dense, nullable: the pre-activation (after the bias), for the backward.
+ *   bias [N] and residual (row stride ldr) nullable. y (row stride ldy) may be a slice of a wider tensor (a q|k|v slab): the bits do not depend
+ *     on the strides. LN-prologue + linear gives the bits of forge_layer_norm_fwd followed by the plain linear. FLOPs 2 R K N.
+ * forge_layer_norm_fwd: y[R][K] = LN(x), the prologue's device code stand-alone; stats nullable.
+ * forge_token_linear_bwd: for the upstream dy [R][N] (row stride lddy) and g = dy o act'(pre), GELU'(v) = Phi(v) + v phi(v):
+ *     dbias [N] = sum_r g      dw [N][K] = sum_r g[r][n] xn[r][k]   (xn recomputed from x and stats: never stored)      dxn = g w
+ *     through the LayerNorm (gamma, beta, stats all given, or all NULL), xh = (x - mean) rstd:
+ *     dgamma [K] = sum_r dxn o xh    dbeta [K] = sum_r dxn    dx = rstd (dxn o gamma - mean_k(dxn o gamma) - xh mean_k(dxn o gamma o xh))
+ *   dx [R][K] dense, dw, dbias, dgamma, dbeta are each nullable: that chain is skipped (dbias needs dw: it is a by-product of the dW pass,
+ *   FORGE_EINVAL otherwise; dgamma / dbeta without a LayerNorm are FORGE_EINVAL). pre is required with GELU. The residual's gradient is dy itself.
+ *   The sums over rows split the rows into chunks by a plan that depends on (R, K, N) alone (forge_token_rows_plan: `chunks` chunks of
+ *   `chunk_rows` rows for dw / dbias; about 256 chunks for dgamma / dbeta); partial tiles go to the caller's workspace and are added in chunk
+ *   order. ws: forge_token_linear_bwd_ws_bytes(R, K, N, ln) bytes (ln = 1 with the LayerNorm prologue; may be 0, ws is then not read; -1 outside
+ *   the domain); a smaller ws_bytes is FORGE_EINVAL. Up to 6 launches. FLOPs 2 R K N for dxn and for dw each.
+ * forge_layer_norm_bwd: dx [R][K] dense, dgamma, dbeta (each nullable) of forge_layer_norm_fwd for dy (row stride lddy);
+ *   ws: forge_layer_norm_bwd_ws_bytes(R, K) bytes, needed for dgamma / dbeta. */
+#define FORGE_TOKEN_ACT_NONE 0
+#define FORGE_TOKEN_ACT_GELU 1
+int forge_token_linear_fwd(const float* x, long long ldx, const float* w, const float* bias, const float* gamma, const float* beta, float eps,
+                           const float* residual, long long ldr, float* y, long long ldy, float* pre, float* stats, int R, int K, int N, int act,
+                           forge_stream_t stream);
+int forge_layer_norm_fwd(const float* x, long long ldx, const float* gamma, const float* beta, float eps, float* y, long long ldy, float* stats,
+                         int R, int K, forge_stream_t stream);
+int forge_token_rows_plan(int R, int K, int N, int* chunks, int* chunk_rows);
+long long forge_token_linear_bwd_ws_bytes(int R, int K, int N, int ln);
+int forge_token_linear_bwd(const float* dy, long long lddy, const float* x, long long ldx, const float* w, const float* gamma, const float* beta,
+                           const float* stats, const float* pre, float* dx, float* dw, float* dbias, float* dgamma, float* dbeta, float* ws,
+                           long long ws_bytes, int R, int K, int N, int act, forge_stream_t stream);
+long long forge_layer_norm_bwd_ws_bytes(int R, int K);
+int forge_layer_norm_bwd(const float* dy, long long lddy, const float* x, long long ldx, const float* gamma, const float* stats, float* dx,
+                         float* dgamma, float* dbeta, float* ws, long long ws_bytes, int R, int K, forge_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * a1  ResNet stem helpers (torchvision conv1/bn1/relu/maxpool behind models/encoder.py:71-73).
  * forge_im2col_nchw: img [N][C][H][W] -> patch rows out [N*Ho*Wo][Kpad], k = (ky*kw + kx)*C + c, zeros outside the image and

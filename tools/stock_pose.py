@@ -3,7 +3,8 @@
 forge_amd.pose_estimator_{2d,3d} have ONE implementation - the libforge_hip.so convolutions + HIP BatchNorm on the MI355X - and raise on host
 tensors. What tests and probes compare that path against (the same module in float64 on the CPU, the same module on torch's own GPU kernels,
 the architecture pin of tests/test_oracle_golden.py against the reference's predictions) is the evaluation below: the module's OWN sub-modules
-(nn.Conv3d / nn.BatchNorm3d / nn.Sequential containers, the attention blocks) called the way the reference calls them
+(nn.Conv3d / nn.BatchNorm3d / nn.Sequential containers, the attention blocks - which dispatch on ops.set_multihead_attention / ops.set_token_layers / ops.set_attention_training, so this is the STOCK
+evaluation only with those switches off, or on host / float64 tensors, which are outside the kernels' domain) called the way the reference calls them
 (models/pose_estimator_3d.py:62-113, models/pose_estimator_2d.py:53-86, 113-136), on any device and dtype.
 
     from stock_pose import features_2d, features_3d, forward_2d, forward_3d, patched
