@@ -108,6 +108,7 @@ SIGNATURES = {
     "forge_ssim": [_P, _LL, _LL, _LL, _LL, _P, _LL, _LL, _LL, _LL, _I, _I, _I, _I, _D, _P, _P, _P],
     "forge_lpips_tap": [_P, _I, _I, _I, _P, _P, _P],
     "forge_lpips_finalize": [_P, _I, _I, _I, _I, _I, _I, _P, _P],
+    "forge_pose_sync": [_P, _P, _P, _I, _I, _I, _I, _I, _D, _P, _P, _P, _P],
     "forge_ncdhw_to_ndhwc": [_P, _P, _I, _I, _LL, _P],
     "forge_ndhwc_to_ncdhw": [_P, _P, _I, _I, _LL, _P],
 }

@@ -741,3 +741,69 @@ def module_layer_norm(x, norm, site=None):
     if ln is None or not token_layers_applies(x, ln=ln):
         return None
     return (layer_norm_train if torch.is_grad_enabled() else layer_norm)(x, *ln)
+
+
+# ------------------------------------------------------------------------------------------------------------- camera synchronisation
+POSE_SYNC_MASS, POSE_SYNC_RANK, POSE_SYNC_NONFINITE = 1, 2, 4      # status bits of forge_pose_sync
+_pose_sync_pairs = {}                                              # (pair list, N, device) -> device int32 [E, 2]
+
+
+def pose_sync_pairs(pairs, N, device=None):
+    """The pair list of a synchronisation problem, checked as utils/sync_utils.py:104-114 checks it (i != j, no pair twice in either order, every
+    view in some pair) plus both < N. Returns the list as a tuple of (i, j); with a device, the cached int32 [E, 2] tensor on it instead."""
+    N = int(N)
+    if not 3 <= N <= 8:
+        raise ValueError("pose_sync: N=%d outside 3..8 (two views are plain chaining: utils/sync_utils.py:camera_chaining)" % N)
+    key = tuple((int(i), int(j)) for i, j in pairs)
+    seen = set()
+    for i, j in key:
+        if i == j:
+            raise ValueError("pose_sync: pair (%d, %d) joins a view with itself" % (i, j))
+        if not (0 <= i < N and 0 <= j < N):
+            raise ValueError("pose_sync: pair (%d, %d) names a view outside 0..%d" % (i, j, N - 1))
+        if (i, j) in seen or (j, i) in seen:
+            raise ValueError("pose_sync: pair (%d, %d) is given twice (in either order)" % (i, j))
+        seen.add((i, j))
+    for v in range(N):
+        if not any(v in p for p in key):
+            raise ValueError("pose_sync: view %d is not in any pairwise views" % v)
+    if device is None:
+        return key
+    ck = (key, N, str(device))
+    if ck not in _pose_sync_pairs:
+        if len(_pose_sync_pairs) >= 64:                            # a protocol uses one or two pair lists; never grow without bound
+            _pose_sync_pairs.clear()
+        _pose_sync_pairs[ck] = torch.tensor(key, dtype=torch.int32).reshape(len(key), 2).to(device)
+    return _pose_sync_pairs[ck]
+
+
+@_lib.on_tensor_device
+def pose_sync(P, conf, pairs, N, squares=10, center_first_camera=False, rank_tol=1e-6, return_sv=False):
+    """utils/sync_utils.py:camera_synchronization(Ps, confidence, N, squares, so3_projection=True, normalize_confidences=True, double=True,
+    center_first_camera) as one launch of forge_pose_sync. P [B, E, 4, 4] float32: P[:, e] is the extrinsics pairs[e] = (i, j), i -> j;
+    conf [B, E]; pairs: a host sequence of (i, j). Returns (out [B, N, 4, 4] float32, status [B] int32) and, with return_sv, the float64
+    singular values [B, N, 3] of the rotation blocks before their projection. status bits: POSE_SYNC_MASS (the reference's assertion would have
+    fired), POSE_SYNC_RANK (sigma_min / sigma_max < rank_tol for some view: that rotation is not determined), POSE_SYNC_NONFINITE. Nothing is
+    read back: a caller that wants the reference's exception tests `status` itself. All arithmetic is float64 (the reference forms L in
+    float32 first)."""
+    if not torch.is_tensor(P) or not torch.is_tensor(conf):
+        raise TypeError("pose_sync: P and conf must be tensors")
+    _require_cuda(P, conf)
+    if P.dim() != 4 or tuple(P.shape[2:]) != (4, 4) or conf.shape != P.shape[:2] or P.device != conf.device:
+        raise ValueError("pose_sync: P [B, E, 4, 4] and conf [B, E] on one device, got %s and %s" % (tuple(P.shape), tuple(conf.shape)))
+    if P.dtype != torch.float32 or conf.dtype != torch.float32:
+        raise TypeError("pose_sync: float32 inputs (got %s, %s); they are widened to float64 on load" % (P.dtype, conf.dtype))
+    B, E = int(P.shape[0]), int(P.shape[1])
+    pairs_dev = pose_sync_pairs(pairs, N, P.device)
+    if pairs_dev.shape[0] != E:
+        raise ValueError("pose_sync: %d pairs for %d matrices" % (pairs_dev.shape[0], E))
+    if B < 1:
+        raise ValueError("pose_sync: empty batch")
+    N = int(N)
+    Pc, cc = P.detach().contiguous(), conf.detach().contiguous()
+    out = torch.empty(B, N, 4, 4, dtype=torch.float32, device=P.device)
+    status = torch.empty(B, dtype=torch.int32, device=P.device)
+    sv = torch.empty(B, N, 3, dtype=torch.float64, device=P.device) if return_sv else None
+    _lib.check(_lib.lib().forge_pose_sync(_lib.ptr(Pc), _lib.ptr(cc), _lib.ptr(pairs_dev), B, N, E, int(squares), 0 if center_first_camera else N // 2,
+                                          float(rank_tol), _lib.ptr(out), _lib.ptr(sv), _lib.ptr(status), _lib.current_stream()), "forge_pose_sync")
+    return (out, status, sv) if return_sv else (out, status)

@@ -149,6 +149,16 @@ def make_sample(b=1, n_views=10, img_size=256, camera_z=1.5, seed=0, elev_deg=10
     return {k: torch.stack(v).contiguous() for k, v in out.items()}
 
 
+def add_depths(sample, camera_z=1.5, seed=0):
+    """The sample with a `depths` entry [b, n, 1, H, W] (dataset/kubric.py's key, read by the evaluation protocol: kubric_eval.py:275):
+    camera_z + U(-0.2, 0.2) on the silhouette, 0 outside, seeded."""
+    g = torch.Generator().manual_seed(seed)
+    mask = sample["fg_probabilities"].cpu()
+    out = dict(sample)
+    out["depths"] = ((camera_z + 0.4 * (torch.rand(mask.shape, generator=g) - 0.5)) * mask).to(sample["fg_probabilities"].device).contiguous()
+    return out
+
+
 def blob_volumes(n, D, C=16, seed=0, peak=1.5, sigma2=0.08, vol_size=1.0):
     """Renderer micro-benchmark volumes: density = peak*exp(-|x|^2/sigma2) over the
     voxel-centre world grid (peaks > 1 exercise the unclamped-density path),

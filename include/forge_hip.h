@@ -648,6 +648,28 @@ int forge_lpips_tap(const float* f, int N, int HW, int C, const float* w, double
 int forge_lpips_finalize(const double* partial, int N, int hw0, int hw1, int hw2, int hw3, int hw4, float* out, forge_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * f5  Camera synchronisation of the evaluation protocol (kubric_eval.py:95-145 `sync_pose`): utils/sync_utils.py:76-191
+ * camera_synchronization(Ps, confidence, N, squares, so3_projection=True, normalize_confidences=True, double=True, center_first_camera=...).
+ *   P      [B][E][4][4] pairwise extrinsics i -> j of edge e = (pairs[e][0], pairs[e][1]), row-major float32
+ *   conf   [B][E] confidences
+ *   pairs  [E][2] DEVICE int32 (i, j): i != j, both < N, no pair twice in either order, every view in some pair (the caller's duty; an
+ *          entry outside 0..N-1 is skipped, never followed)
+ *   center the view whose block column of L^(2^squares) is kept: 0 for center_first_camera=True, N / 2 otherwise
+ *   out    [B][N][4][4] float32: the synchronised extrinsics, rotation blocks projected onto SO(3)
+ *   sv     [B][N][3] float64, nullable: singular values (descending) of the rotation blocks BEFORE the projection
+ *   status [B] int32 bit set: 1 a mass entry <= 0 (or NaN) - the reference's assertion "2**squares, or the set of edges, is too small";
+ *          2 for some view sigma_min / sigma_max < rank_tol or sigma_max = 0 - the projection is not determined by the data;
+ *          4 a non-finite value in this element's P or conf. out (and sv) are written in every case.
+ * One deliberate difference from the reference: all arithmetic is float64 from the first load on (the reference forms L in float32, then widens).
+ * One workgroup per batch element, L and its square in LDS, every product element one FMA chain over ascending k: bitwise reproducible,
+ * independent of B, no atomics, no allocation, no host synchronisation (graph-capturable). One launch.
+ * FORGE_ESHAPE unless 3 <= N <= 8 and N - 1 <= E <= N (N - 1) / 2; FORGE_EINVAL for a null pointer other than sv, B < 1, squares outside
+ * 1..16, center outside 0..N-1, rank_tol outside [0, 1).
+ */
+int forge_pose_sync(const float* P, const float* conf, const int* pairs, int B, int N, int E, int squares, int center, double rank_tol,
+                    float* out, double* sv, int* status, forge_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * layout helpers: NCDHW <-> channels-last for callers that hold plain-contiguous volumes.
  *   src [n][C][P] -> dst [n][P][C]   (P = D*H*W)   and back.
  */
