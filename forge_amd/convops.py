@@ -236,6 +236,7 @@ class _State:
     plan_override = None              # (tile letter or None, ksplit or None): set by force_plan() only (tools/conv_plan_sweep.py, tests)
     winograd = True                   # False: the direct implicit-GEMM kernel for every 3x3(x3) convolution
     wino_depth_nest = os.environ.get("FORGE_WINO_DEPTH_NEST", "1") != "0"     # False: the eval fusion's GRU launches stay on the four-point form
+    wino_depth_nest4 = os.environ.get("FORGE_WINO_DEPTH_NEST4", "1") != "0"   # False: the nest stays on F(2, 3) (wino_depth_nest = False switches both off)
 
 
 STATE = _State()
@@ -509,9 +510,10 @@ def wino_scene_chunk(b, D, H, W, C, views=1):
     return nb
 
 
-def wino_fits(n, D, H, W, C, views=1):
-    """H, W even, and every transformed operand ([n views D H/2 W/2][C] floats per Winograd point) within the kernel's 32-bit buffer offsets."""
-    return H % 2 == 0 and W % 2 == 0 and n * views * D * (H // 2) * (W // 2) * C * 4 <= MAX_OPERAND_BYTES
+def wino_fits(n, D, H, W, C, views=1, nest4=False):
+    """H, W even, and every transformed operand ([n views D H/2 W/2][C] floats per Winograd point) within the kernel's 32-bit buffer offsets.
+    nest4: the operands of the F(4, 3) depth nest, 6 planes per group of 4 (wino_input_dn4)."""
+    return H % 2 == 0 and W % 2 == 0 and n * views * D * (H // 2) * (W // 2) * C * 4 * (3 if nest4 else 2) // 2 <= MAX_OPERAND_BYTES
 
 
 @_lib.on_tensor_device
@@ -557,6 +559,65 @@ def wino_depth_nest_applies(R, D, Ht, Wt, Cout, Cin):
     forge_wino_gemm would give its 64 x 128 tile, with no forced plan, unless switched off (STATE.wino_depth_nest / FORGE_WINO_DEPTH_NEST=0)."""
     return (STATE.wino_depth_nest and STATE.plan_override is None and D % 2 == 0 and (Ht * Wt) % 64 == 0 and Cin % 32 == 0
             and R * Cout * 4 <= MAX_OPERAND_BYTES and wino_gemm_tile(R, Cout, Cin) == "B")
+
+
+@_lib.on_tensor_device
+def wino_input_dn4(x, C, ld, n, D, H, W, bs=0, out=None, nsum=1, sum_stride=0):
+    """wino_input with the depth stage of the F(4, 3) nest (forge_wino_input_dn4): V6 [16][n (D/4) 6 (H/2)(W/2)][C], 1.5 x wino_input's rows - position k
+    of group g of four planes is plane 6 g + k of the batch element. The operand of wino_gemm_dn4. out: a buffer of that shape."""
+    R6 = n * (D // 4) * 6 * (H // 2) * (W // 2)
+    V = out if out is not None else torch.empty(16, R6, C, dtype=torch.float32, device=x.device)
+    if V.shape != (16, R6, C) or not V.is_contiguous():
+        raise ValueError("depth-nest operand buffer %s is not [16][%d][%d]" % (tuple(V.shape), R6, C))
+    _lib.check(_lib.lib().forge_wino_input_dn4(_lib.ptr(x), ld, int(bs), _lib.ptr(V), C, 0, n, D, H, W, C, int(nsum), int(sum_stride),
+                                               _lib.current_stream()), "forge_wino_input_dn4")
+    return V
+
+
+@_lib.on_tensor_device
+def wino_pack_packed_dn4(wp):
+    """Packed weights [27][Cout][Cin] -> U'' [16][6][Cout][Cin] = G_depth (x) (G w G^T), the weights of the F(4, 3) depth nest (forge_wino_weights_dn4:
+    float64 inside, rounded once); position k along dimension 1."""
+    T, co_, ci_ = wp.shape
+    assert T == 27
+    wp = wp.detach()
+    wp = wp if wp.is_contiguous() else wp.contiguous()
+    U = torch.empty((16, 6, co_, ci_), dtype=torch.float32, device=wp.device)
+    _lib.check(_lib.lib().forge_wino_weights_dn4(_lib.ptr(wp), _lib.ptr(U), co_, ci_, _lib.current_stream()), "forge_wino_weights_dn4")
+    return U
+
+
+def wino_depth_nest4_applies(R, D, Ht, Wt, Cout, Cin):
+    """The launches of wino_depth_nest_applies that take the nest's F(4, 3) form (forge_wino_gemm_dn4: six K loops per four planes, 3/4 of the F(2, 3)
+    nest's matrix-core work, operands from wino_input_dn4): that rule plus D % 4 == 0 and D >= 8 (at D = 4 every group touches both grid edges and two
+    of its six positions are half empty), unless switched off (STATE.wino_depth_nest4 / FORGE_WINO_DEPTH_NEST4=0, or the nest as a whole)."""
+    return STATE.wino_depth_nest4 and D % 4 == 0 and D >= 8 and wino_depth_nest_applies(R, D, Ht, Wt, Cout, Cin)
+
+
+@_lib.on_tensor_device
+def wino_gemm_dn4(V1, C1, V2, C2, Ud, Mm, n, D, Ht, Wt, Cout, view=0, views=1):
+    """wino_gemm's 16 point products [16][R][Cout] through the F(4, 3) depth nest (forge_wino_gemm_dn4), from the wino_input_dn4 operands V1
+    [16][n views (D/4) 6 Ht Wt][C1] (this call reads view `view`), V2 [16][n (D/4) 6 Ht Wt][C2] or None, and Ud [16][6][Cout][C1 + C2]
+    (wino_pack_packed_dn4). Mm as wino_gemm; the caller has checked wino_depth_nest4_applies' shape conditions (the entry refuses the others)."""
+    vol = D * Ht * Wt
+    R, vol6 = n * vol, vol // 4 * 6
+    if Ud.shape != (16, 6, Cout, C1 + C2) or not Ud.is_contiguous():
+        raise ValueError("depth-nest weight %s does not match Cout=%d Cin=%d" % (tuple(Ud.shape), Cout, C1 + C2))
+    if V1.shape[1] != n * views * vol6 or (V2 is not None and V2.shape[1] != n * vol6):
+        raise ValueError("depth-nest operands %s / %s are not wino_input_dn4's %d (x %d views) rows per point" % (
+            tuple(V1.shape), None if V2 is None else tuple(V2.shape), n * vol6, views))
+    if Mm is None:
+        Mm = torch.empty(16, R, Cout, dtype=torch.float32, device=V1.device)
+    if not (Mm.is_contiguous() and Mm.dtype == torch.float32 and Mm.numel() >= 16 * R * Cout):
+        raise ValueError("point-product buffer %s %s%s cannot hold 16 x %d x %d float32" % (
+            tuple(Mm.shape), Mm.dtype, "" if Mm.is_contiguous() else " (not contiguous)", R, Cout))
+    if Mm.shape != (16, R, Cout):
+        Mm = Mm.as_strided((16, R, Cout), (R * Cout, Cout, 1))
+    p1 = ctypes.c_void_p(V1.data_ptr() + 4 * view * vol6 * C1)
+    _lib.check(_lib.lib().forge_wino_gemm_dn4(p1, C1, C1, views * vol6 if views > 1 else 0, V1.shape[1] * C1, _lib.ptr(V2), C2, C2, 0,
+                                              0 if V2 is None else V2.shape[1] * C2, _lib.ptr(Ud), _lib.ptr(Mm), n, D, Ht, Wt, Cout, 3,
+                                              _lib.current_stream()), "forge_wino_gemm_dn4")
+    return Mm
 
 
 @_lib.on_tensor_device

@@ -119,6 +119,13 @@ __device__ __forceinline__ int lds_off(int row, int chunk) {   // float offset o
 // offset) and combined with one fp32 operation per element on the ds_read_b128 results, in front of the MFMAs. The output side is A^T = [1 1 1 0; 0 1 -1 -1]
 // over the four positions - the four-point form's own skeleton: y_z = (m0 + m1) + m2 stored under k = 3's loop, y_{z+1} = (m1 - m2) - m3 - and the result
 // is the ordinary 16-plane Mm [16][R][Cout] of forge_wino_gemm. 2 x 32 KB of LDS: two workgroups per CU (resources: the remark above forge_wino_gemm_dn).
+//
+// RS = 3 (forge_wino_gemm_dn4, 64x128 tile): the depth nest with F(4, 3). A workgroup owns 64 tile rows of a GROUP of four planes 4g .. 4g + 3 for one point and
+// runs six K loops of K = Cin (1.5 per plane) on the depth-combined operand planes V6[.][g][k] that forge_wino_input_dn4 wrote - ONE A image per K-step, the
+// inner loop of RS = 1, no VALU in front of the MFMAs - against U''[p][k] (forge_wino_weights_dn4). The output side is A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0;
+// 0 1 1 4 4 0; 0 1 -1 8 -8 1] over the six positions, all scalings powers of two: loops 1, 2 -> s = m1 + m2, d = m1 - m2; loops 3, 4 -> S = m3 + m4,
+// D = m3 - m4; y1 = d + 2 D and y2 = s + 4 S are stored under the next loop; loop 0 accumulates onto s + S (y0, stored under loop 5), loop 5 onto d + 8 D (y3).
+// Four accumulator sets live; 2 x 24 KB of LDS (resources: the remark above forge_wino_gemm_dn4).
 template <int BM, int BN, int NW, int MT = 1, int RS = 0>
 __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
     constexpr int NP = RS ? 4 : 1;                   // points (RS = 2: depth positions) per workgroup
@@ -154,6 +161,7 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
     if (a.nbat > 1) {                                               // xcd_remap's contiguous chunks) an XCD's L2 holds the weights of its own problems only
         unsigned tiles = (unsigned)((M + BM - 1) / BM) * (unsigned)ntile_n;
         if constexpr (RS == 2) tiles = (unsigned)(M / (2 * BM)) * (unsigned)ntile_n;   // depth nest: the tiles of the even planes only
+        if constexpr (RS == 3) tiles = (unsigned)(M / (4 * BM)) * (unsigned)ntile_n;   // F(4, 3) depth nest: the tiles of every fourth plane
         pb = bid / tiles;
         bid -= (unsigned)pb * tiles;
     }
@@ -163,6 +171,10 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
             const unsigned tpl = (unsigned)(a.H * a.W) / BM;       // flat (n, z) axis (D even: a pair never straddles batch elements)
             const unsigned ti = bid / ntile_n, pair = ti / tpl;
             return (long long)(2u * pair * tpl + (ti - pair * tpl)) * BM;
+        } else if constexpr (RS == 3) {                             // tile ti of the first planes of the groups of four (D % 4 == 0: a group lies in one element)
+            const unsigned tpl = (unsigned)(a.H * a.W) / BM;
+            const unsigned ti = bid / ntile_n, grp = ti / tpl;
+            return (long long)(4u * grp * tpl + (ti - grp * tpl)) * BM;
         } else {
             return (long long)(bid / ntile_n) * BM;
         }
@@ -277,7 +289,7 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
 #pragma unroll
         for (int j = 0; j < BCH; ++j) lds_dma16(ww, boff[j] + wbase, stage + (unsigned)(A_FLOATS * 4 + j * NW * 1024));
     };
-    constexpr int NACC = RS ? 3 : 1;                               // accumulator sets (RS: the row stage frees one after point 2)
+    constexpr int NACC = RS == 3 ? 4 : RS ? 3 : 1;                 // accumulator sets (RS = 1, 2: the row stage frees one after point 2; RS = 3: s, d, m3, m4)
     f32x16 accs[NACC][MT][NT];
 #pragma unroll
     for (int q = 0; q < NACC; ++q)
@@ -527,6 +539,89 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
         }
         FORGE_STAMP(2);
         store_plane(1, [&](int r) { return accs[1][0][0][r] - accs[0][0][0][r]; });                               // y_{z+1} = u - m3
+        FORGE_STAMP(3);
+        return;
+    }
+
+    if constexpr (RS == 3) {
+        // F(4, 3) depth nest (see above). The tile's 64 rows lie in plane (n, 4 g) of the output; the host has checked H W % 64 == 0, D % 4 == 0 and
+        // that operands and an output plane stay below 2 GiB. The operand of position k is plane 6 g + k of the element's V6 block: one A image per K-step.
+        constexpr int STAGE = A_FLOATS + B_FLOATS, NPOS = 6;
+        static_assert(ACH == 1 && NT == 1 && MT == 1, "the depth nest is written for the 64 x 128 tile of 8 waves");
+        const unsigned HW = (unsigned)(a.H * a.W);
+        const unsigned plane0 = (unsigned)m0 / HW;                 // n D + 4 g, workgroup-uniform
+        const unsigned nb = plane0 / (unsigned)a.D, g4 = plane0 - nb * (unsigned)a.D;      // g4 = 4 g
+        const unsigned rin = (unsigned)m0 - plane0 * HW + (unsigned)ar[0];                 // this thread's row inside the plane
+        const unsigned row6 = (g4 + (g4 >> 1)) * HW + rin;         // row of position 0 in the element's [D/4][6][H W] block
+        const unsigned base1 = (unsigned)((((int)nb * (int)a.bs1r + (int)row6) * a.ld1 + asrc[0]) * 4);
+        const unsigned base2 = (unsigned)((((int)nb * (int)a.bs2r + (int)row6) * a.ld2 + asrc[0]) * 4);
+        const unsigned ps1 = HW * (unsigned)a.ld1 * 4u, ps2 = HW * (unsigned)a.ld2 * 4u;   // bytes from a position to the next in V1 / V2
+        // K loops in the order of the output schedule: positions 1, 2 | 3, 4 | 0 | 5
+        auto pos_of = [](int iq) { return iq < 4 ? iq + 1 : iq == 4 ? 0 : 5; };
+        int iq = 0, ikc = 0, ibuf = 0, ipos = 1;
+        eoff[0] = base1 + ps1; eoff2[0] = base2 + ps2;
+        auto issue_next = [&]() {                                  // the issue cursor runs one step ahead of the MFMAs, straight over the position switches
+            if (iq >= NPOS) return;
+            issue_step(ipos, ikc, ibuf);
+            ibuf ^= 1;
+            if (++ikc == kchunks) {
+                ikc = 0;
+                if (++iq < NPOS) {
+                    ipos = pos_of(iq);
+                    eoff[0] = base1 + (unsigned)ipos * ps1; eoff2[0] = base2 + (unsigned)ipos * ps2;
+                }
+            }
+        };
+        issue_next();
+        lds_dma_wait_barrier();
+        FORGE_STAMP(1);
+        const int ocol = n0 + wn * (BN / WN) + l31;
+        const unsigned ldo4 = (unsigned)a.ldo * 4u;
+        const unsigned ovb = ocol < a.Cout ? (unsigned)(((int)m0 + wm * 32 + 4 * half) * a.ldo + ocol) * 4u : OOB;
+        auto store_plane = [&](int plane, const f32x16& val) {     // the tile's rows of plane 4 g + `plane` (buffer-descriptor stores, as RS = 1 / 2)
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(outp, 0, (int)(M * a.ldo * 4), 0x00020000);
+            unsigned vb = ovb + (unsigned)plane * HW * ldo4;
+            asm volatile("" : "+v"(vb));
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val[r]), rs, (int)(vb + (unsigned)((r & 3) + 8 * (r >> 2)) * ldo4), 0, 0);
+        };
+        int buf = 0;
+#pragma unroll
+        for (int q = 0; q < NPOS; ++q) {
+            f32x16 (&aq)[MT][NT] = accs[q < 4 ? q : q - 4];         // m1, m2, m3, m4 into sets 0..3; position 0 onto set 0 (s + S), position 5 onto set 1 (d + 8 D)
+            for (int s = 0; s < kchunks; ++s) {
+                const float* sa = smem + buf * STAGE;
+                const float* sb = sa + A_FLOATS;
+                issue_next();                                      // into the stage read in step s - 1: every wave is past that barrier
+#pragma unroll
+                for (int g = 0; g < 4; ++g) mfma_group(aq, sa, sb, g);
+                lds_dma_wait_barrier();
+                buf ^= 1;
+            }
+            if (q == 1) {                                          // s = m1 + m2, d = m1 - m2
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float m1 = accs[0][0][0][r], m2 = accs[1][0][0][r];
+                    accs[0][0][0][r] = m1 + m2; accs[1][0][0][r] = m1 - m2;
+                }
+            } else if (q == 3) {                                   // S = m3 + m4, D = m3 - m4: y1 = d + 2 D, y2 = s + 4 S stored under position 0's loop
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float S = accs[2][0][0][r] + accs[3][0][0][r], Dl = accs[2][0][0][r] - accs[3][0][0][r];
+                    accs[2][0][0][r] = fmaf(4.f, S, accs[0][0][0][r]);     // y2
+                    accs[3][0][0][r] = fmaf(2.f, Dl, accs[1][0][0][r]);    // y1
+                    accs[0][0][0][r] = accs[0][0][0][r] + S;               // s + S: position 0 accumulates onto it
+                    accs[1][0][0][r] = fmaf(8.f, Dl, accs[1][0][0][r]);    // d + 8 D: position 5 accumulates onto it
+                }
+                store_plane(1, accs[3][0][0]);
+                store_plane(2, accs[2][0][0]);
+            } else if (q == 4) {
+                store_plane(0, accs[0][0][0]);                     // y0 = (s + S) + m0, in flight under position 5's loop
+            }
+        }
+        FORGE_STAMP(2);
+        store_plane(3, accs[1][0][0]);                             // y3 = (d + 8 D) + m5
         FORGE_STAMP(3);
         return;
     }
@@ -1073,6 +1168,14 @@ static int launch_conv_tile(const ConvArgs& a, char tile, hipStream_t st, int ro
         hipLaunchKernelGGL((conv_igemm_kernel<64, 128, 8, 1, 2>), dim3((unsigned)grid), dim3(8 * 64), lds, st, a);
         return 0;
     }
+    if (row_stage == 3) {                                            // forge_wino_gemm_dn4: the tiles of every fourth plane, 16 points
+        const long long grid = (M / 256) * ((a.Cout + 127) / 128) * a.nbat;
+        FORGE_REQUIRE(grid < (1ll << 31), FORGE_ESHAPE, "forge_wino_gemm_dn4: grid too large");
+        const size_t lds = 2 * (64 * BK + 128 * BK) * sizeof(float);
+        FORGE_SET_MAX_LDS_ONCE((conv_igemm_kernel<64, 128, 8, 1, 3>), lds);
+        hipLaunchKernelGGL((conv_igemm_kernel<64, 128, 8, 1, 3>), dim3((unsigned)grid), dim3(8 * 64), lds, st, a);
+        return 0;
+    }
     if (row_stage) {                                                 // forge_wino_gemm_half: a.nbat = 4 point columns, four points per workgroup
         const long long grid = nblk(64, 128) * a.nbat;
         FORGE_REQUIRE(grid < (1ll << 31), FORGE_ESHAPE, "forge_wino_gemm_half: grid too large");
@@ -1234,7 +1337,7 @@ extern "C" int forge_wino_gemm_tile(long long R, int Cout, int Cin) {
 // kd = 3 for the 3x3x3 convolutions, kd = 1 for the 3x3 convolutions of a 2-D network (D = 1 or D = images: planes do not mix).
 static int wino_gemm_impl(const float* V1, int C1, int ld1, long long bs1, long long pt1, const float* V2, int C2, int ld2, long long bs2,
                           long long pt2, const float* U, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, int tile, int form, forge_stream_t stream) {
-    const bool half = form == 1, dn = form == 2;                    // form: 0 = 16 points, 1 = the four-point row stage, 2 = the depth nest
+    const bool half = form == 1, dn = form == 2, dn4 = form == 3;   // form: 0 = 16 points, 1 = the four-point row stage, 2 = the depth nest, 3 = its F(4, 3) form
     FORGE_REQUIRE(tile == 0 || (tile >= 'A' && tile <= 'E'), FORGE_EINVAL, "forge_wino_gemm: tile must be 0 (default rule) or 'A'..'E'");
     FORGE_REQUIRE(V1 && U && Mm && (kd == 1 || kd == 3), FORGE_EINVAL, "forge_wino_gemm: null pointer argument / kd not 1 or 3");
     FORGE_REQUIRE(n > 0 && D > 0 && Ht > 0 && Wt > 0 && Cout > 16, FORGE_EINVAL, "forge_wino_gemm: bad dims n=%d D=%d Ht=%d Wt=%d Cout=%d (Cout > 16)", n,
@@ -1244,9 +1347,26 @@ static int wino_gemm_impl(const float* V1, int C1, int ld1, long long bs1, long 
     FORGE_REQUIRE(ld1 >= C1 && ld1 % 4 == 0 && (C2 == 0 || (ld2 >= C2 && ld2 % 4 == 0)), FORGE_EINVAL, "forge_wino_gemm: bad row strides");
     FORGE_REQUIRE(!dn || (kd == 3 && D % 2 == 0 && ((long long)Ht * Wt) % 64 == 0), FORGE_EINVAL,
                   "forge_wino_gemm_dn: needs three depth taps, an even D and Ht Wt %% 64 == 0 (kd=%d D=%d Ht=%d Wt=%d)", kd, D, Ht, Wt);
+    FORGE_REQUIRE(!dn4 || (kd == 3 && D % 4 == 0 && ((long long)Ht * Wt) % 64 == 0), FORGE_EINVAL,
+                  "forge_wino_gemm_dn4: needs three depth taps, D %% 4 == 0 and Ht Wt %% 64 == 0 (kd=%d D=%d Ht=%d Wt=%d)", kd, D, Ht, Wt);
     ConvArgs a;
     memset(&a, 0, sizeof(a));
     const long long vol = (long long)D * Ht * Wt, R = (long long)n * vol;
+    if (dn4) {                                                        // operands V6 [n][D/4][6][Ht Wt]: 1.5 vol rows per element; U'' [16][6][Cout][Cin]
+        const long long vol6 = vol / 4 * 6, Cin = C1 + C2;
+        a.in1 = V1; a.in2 = V2; a.C1 = C1; a.C2 = C2; a.ld1 = ld1; a.ld2 = ld2; a.bs1r = bs1 > 0 ? bs1 : vol6; a.bs2r = bs2 > 0 ? bs2 : vol6;
+        a.span1 = ((long long)(n - 1) * a.bs1r + vol6) * ld1 * 4;
+        a.span2 = V2 ? ((long long)(n - 1) * a.bs2r + vol6) * ld2 * 4 : 0;
+        FORGE_REQUIRE(a.span1 < (1ll << 31) && a.span2 < (1ll << 31) && R * Cout * 4 < (1ll << 31) && 6ll * Cout * Cin * 4 < (1ll << 31), FORGE_EINVAL,
+                      "forge_wino_gemm_dn4: an operand or an output plane spans >= 2 GiB (32-bit buffer offsets); split the batch");
+        a.wp = U; a.slope = 1.f; a.out = Mm; a.n = n; a.D = D; a.H = Ht; a.W = Wt; a.is = 1; a.Di = D; a.Hi = Ht; a.Wi = Wt;
+        a.Cout = Cout; a.ldo = Cout; a.ldr = Cout; a.ntaps = a.tpp = 6; a.os = 1; a.Do = D; a.Ho = Ht; a.Wo = Wt; a.nphase = 1; a.epi = EPI_BIAS;
+        a.ksplit = 1; a.nbat = 16; a.pt1 = pt1 > 0 ? pt1 : (long long)n * vol6 * ld1; a.pt2 = V2 ? (pt2 > 0 ? pt2 : (long long)n * vol6 * ld2) : 0;
+        a.ptw = 6ll * Cout * Cin; a.pto = R * Cout;
+        if (int rc = launch_conv_tile(a, 'B', (hipStream_t)stream, 3)) return rc;
+        FORGE_LAUNCH_CHECK("forge_wino_gemm_dn4");
+        return 0;
+    }
     a.in1 = V1; a.in2 = V2; a.C1 = C1; a.C2 = C2; a.ld1 = ld1; a.ld2 = ld2; a.bs1r = bs1 > 0 ? bs1 : vol; a.bs2r = bs2 > 0 ? bs2 : vol;
     a.span1 = ((long long)(n - 1) * a.bs1r + vol) * ld1 * 4;
     a.span2 = V2 ? ((long long)(n - 1) * a.bs2r + vol) * ld2 * 4 : 0;
@@ -1292,4 +1412,17 @@ extern "C" int forge_wino_gemm_dn(const float* V1, int C1, int ld1, long long bs
                                   long long pt2, const float* Ud, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, forge_stream_t stream) {
     FORGE_REQUIRE(C1 > 0 && C1 % BK == 0 && C2 >= 0 && C2 % BK == 0, FORGE_EINVAL, "forge_wino_gemm_dn: C1=%d / C2=%d must be multiples of %d", C1, C2, BK);
     return wino_gemm_impl(V1, C1, ld1, bs1, pt1, V2, C2, ld2, bs2, pt2, Ud, Mm, n, D, Ht, Wt, Cout, kd, 'B', 2, stream);
+}
+
+// forge_wino_gemm through the F(4, 3) depth nest (conv_igemm_kernel<64, 128, 8, 1, 3>): the same 16 point products Mm [16][R][Cout] of a three-depth-tap problem,
+// made with six K loops of C1 + C2 per group of FOUR planes instead of twelve, from the depth-combined operands V6 [16][n][D/4][6][Ht Wt][C]
+// (forge_wino_input_dn4; bs1 / bs2 in rows of that layout, 0 = dense) against Ud = U'' [16][6][Cout][C1 + C2] (forge_wino_weights_dn4). Not bitwise
+// forge_wino_gemm's result. FORGE_EINVAL, before any launch, unless kd == 3, D % 4 == 0, Ht Wt % 64 == 0, C1 and C2 are multiples of 32 and every
+// operand and output plane stays within 32-bit buffer offsets.
+// Code object (hipcc -O3, gfx950): 97 VGPRs, 0 AGPRs, 44 SGPRs, no scratch = 4 waves per SIMD by registers (four accumulator sets) -> TWO workgroups per CU;
+// 2 x 24 KB = 48 KB of dynamic LDS would allow three, which needs <= 80 VGPRs (the four-point form: 80 VGPRs with three sets).
+extern "C" int forge_wino_gemm_dn4(const float* V1, int C1, int ld1, long long bs1, long long pt1, const float* V2, int C2, int ld2, long long bs2,
+                                   long long pt2, const float* Ud, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, forge_stream_t stream) {
+    FORGE_REQUIRE(C1 > 0 && C1 % BK == 0 && C2 >= 0 && C2 % BK == 0, FORGE_EINVAL, "forge_wino_gemm_dn4: C1=%d / C2=%d must be multiples of %d", C1, C2, BK);
+    return wino_gemm_impl(V1, C1, ld1, bs1, pt1, V2, C2, ld2, bs2, pt2, Ud, Mm, n, D, Ht, Wt, Cout, kd, 'B', 3, stream);
 }

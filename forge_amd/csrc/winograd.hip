@@ -101,6 +101,86 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const WinoInArgs a) {
     }
 }
 
+// The input transform of the F(4, 3) depth nest (forge_wino_input_dn4): wino_input_kernel's B^T d B on the DEPTH-COMBINED patches of a group of four
+// planes. Group g of a batch element covers the output planes 4g .. 4g + 3 and reads the planes p_e = plane 4g - 1 + e, e = 0..5 (zero outside the batch
+// element's grid, never the neighbouring element's planes). Depth stage, per patch element, in this order (every multiplier is a power of two, so each
+// line is two rounded additions and one fused multiply-add whose product is exact - a plain multiply and add gives the same bits):
+//   q0 = 4 (p0 - p2) - (p2 - p4)      q1 = (p3 + p4) - 4 (p1 + p2)      q2 = (p4 - p3) + 4 (p1 - p2)
+//   q3 = (p4 - p2) + 2 (p3 - p1)      q4 = (p4 - p2) - 2 (p3 - p1)      q5 = 4 (p1 - p3) - (p3 - p5)
+// = the rows of B^T_depth = [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1]; then the 2-D stage of
+// wino_input_kernel on each q_k (rows first, then columns). Output V6 [16][n][D/4][6][Ht Wt][C]: position k of group g is plane 6 g + k of the element.
+// One thread = one tile of one group x ONE channel (96 values live): a wave reads and writes 256 contiguous bytes per instruction, every loaded value is
+// used for all six positions (96 loads, 96 stores).
+__global__ __launch_bounds__(256) void wino_input_dn4_kernel(const WinoInArgs a) {
+    const int Ht = a.H >> 1, Wt = a.W >> 1, Dg = a.D >> 2;
+    const long long idx = (long long)xcd_remap(blockIdx.x, gridDim.x) * 256 + threadIdx.x;
+    const long long RG = (long long)a.n * Dg * Ht * Wt;             // group tiles
+    if (idx >= RG * a.C) return;
+    const unsigned r = (unsigned)(idx / a.C);
+    const int c = (int)(idx - (long long)r * a.C);
+    unsigned q = r, t = q / (unsigned)Wt;
+    const int tw = (int)(q - t * (unsigned)Wt); q = t; t = q / (unsigned)Ht;
+    const int th = (int)(q - t * (unsigned)Ht); q = t; t = q / (unsigned)Dg;
+    const int g = (int)(q - t * (unsigned)Dg);                      // t = batch element
+    const long long HW = (long long)a.H * a.W;
+    const float* base = a.in + (long long)t * a.bs * a.ld + c;
+    const float inv = 1.f / (float)a.nsum;                           // ATen divides by a scalar as a multiplication by its fp32 reciprocal
+    float d[6][4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int y = 2 * th - 1 + i;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int x = 2 * tw - 1 + j;
+            const bool ok = (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
+            float p[6];
+#pragma unroll
+            for (int e = 0; e < 6; ++e) {
+                const int z = 4 * g - 1 + e;
+                float v = 0.f;
+                if (ok && (unsigned)z < (unsigned)a.D) {
+                    const float* s = base + ((long long)z * HW + (long long)y * a.W + x) * a.ld;
+                    v = *s;
+                    if (a.nsum > 1) {
+                        for (int k = 1; k < a.nsum; ++k) v += s[(long long)k * a.ss * a.ld];
+                        v *= inv;
+                    }
+                }
+                p[e] = v;
+            }
+            const float a02 = p[0] - p[2], a24 = p[2] - p[4], s34 = p[3] + p[4], s12 = p[1] + p[2], d43 = p[4] - p[3], d12 = p[1] - p[2];
+            const float d42 = p[4] - p[2], d31 = p[3] - p[1], d13 = p[1] - p[3], d35 = p[3] - p[5];
+            d[0][i][j] = fmaf(4.f, a02, -a24);
+            d[1][i][j] = fmaf(-4.f, s12, s34);
+            d[2][i][j] = fmaf(4.f, d12, d43);
+            d[3][i][j] = fmaf(2.f, d31, d42);
+            d[4][i][j] = fmaf(-2.f, d31, d42);
+            d[5][i][j] = fmaf(4.f, d13, -d35);
+        }
+    }
+    const long long HWt = (long long)Ht * Wt;
+    float* vp = a.V + ((((long long)t * Dg + g) * 6) * HWt + (long long)th * Wt + tw) * a.ldv + c;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        float w[4][4];                               // rows: B^T d
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            w[0][j] = d[k][0][j] - d[k][2][j];
+            w[1][j] = d[k][1][j] + d[k][2][j];
+            w[2][j] = d[k][2][j] - d[k][1][j];
+            w[3][j] = d[k][1][j] - d[k][3][j];
+        }
+        float* vk = vp + (long long)k * HWt * a.ldv;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {                // columns: (B^T d) B
+            vk[(4 * i + 0) * a.ptv] = w[i][0] - w[i][2];
+            vk[(4 * i + 1) * a.ptv] = w[i][1] + w[i][2];
+            vk[(4 * i + 2) * a.ptv] = w[i][2] - w[i][1];
+            vk[(4 * i + 3) * a.ptv] = w[i][1] - w[i][3];
+        }
+    }
+}
+
 // U[4i+j][kd][o][c] = (G w[kd] G^T)[i][j] from packed weights wp[(kd 3 + a) 3 + b][co][ci]: one thread per (kd, o, c). Evaluated in float64
 // (exact: at most 9 fp32 terms with coefficients 1, 1/2, 1/4) and rounded once. transpose: the weights of the DATA GRADIENT - the
 // correlation of dy with the flipped kernel and swapped channel roles: w'[kd][a][b][o = ci][c = co] = wp[(2-kd, 2-a, 2-b)][co][ci].
@@ -155,6 +235,45 @@ __global__ __launch_bounds__(256) void wino_weight_dn_kernel(const float* __rest
 #pragma unroll
             for (int b = 0; b < 3; ++b)
                 d[a][b] = k == 0 ? w[0][a][b] : k == 1 ? 0.5 * (w[0][a][b] + w[1][a][b] + w[2][a][b]) : k == 2 ? 0.5 * (w[0][a][b] - w[1][a][b] + w[2][a][b]) : w[2][a][b];
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {                // G d
+            g[0][b] = d[0][b];
+            g[1][b] = 0.5 * (d[0][b] + d[1][b] + d[2][b]);
+            g[2][b] = 0.5 * (d[0][b] - d[1][b] + d[2][b]);
+            g[3][b] = d[2][b];
+        }
+        float* up = U + k * per + idx;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {                // (G d) G^T
+            up[(4 * i + 0) * pt] = (float)g[i][0];
+            up[(4 * i + 1) * pt] = (float)(0.5 * (g[i][0] + g[i][1] + g[i][2]));
+            up[(4 * i + 2) * pt] = (float)(0.5 * (g[i][0] - g[i][1] + g[i][2]));
+            up[(4 * i + 3) * pt] = (float)g[i][2];
+        }
+    }
+}
+
+// Weights of the F(4, 3) depth nest (forge_wino_gemm_dn4): U''[4i+j][k][o][c] = sum_kd Gd[k][kd] (G w[kd] G^T)[i][j] with the six depth rows
+// Gd = [1/4 0 0; -1/6 -1/6 -1/6; -1/6 1/6 -1/6; 1/24 1/12 1/6; 1/24 -1/12 1/6; 0 0 1]. One thread per (o, c); float64 throughout, rounded once (the
+// sixths are not exact in float64: the result is the float64 evaluation below, correctly rounded to within one float64 rounding per operation).
+__global__ __launch_bounds__(256) void wino_weight_dn4_kernel(const float* __restrict__ wp, float* __restrict__ U, int Cout, int Cin) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, per = (long long)Cout * Cin;
+    if (idx >= per) return;
+    double w[3][3][3];
+#pragma unroll
+    for (int t = 0; t < 27; ++t) w[t / 9][(t / 3) % 3][t % 3] = (double)wp[t * per + idx];
+    const long long pt = 6 * per;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        double d[3][3], g[4][3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int b = 0; b < 3; ++b) {
+                const double w0 = w[0][a][b], w1 = w[1][a][b], w2 = w[2][a][b];
+                d[a][b] = k == 0 ? 0.25 * w0 : k == 1 ? -((w0 + w2) + w1) / 6.0 : k == 2 ? -((w0 + w2) - w1) / 6.0
+                        : k == 3 ? ((0.25 * w0 + w2) + 0.5 * w1) / 6.0 : k == 4 ? ((0.25 * w0 + w2) - 0.5 * w1) / 6.0 : w2;
+            }
 #pragma unroll
         for (int b = 0; b < 3; ++b) {                // G d
             g[0][b] = d[0][b];
@@ -432,6 +551,37 @@ extern "C" int forge_wino_input(const float* in, int ld, long long bs, float* V,
     a.dM = nullptr; a.ptm = 0;
     hipLaunchKernelGGL(wino_input_kernel<false>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
     FORGE_LAUNCH_CHECK("forge_wino_input");
+    return 0;
+}
+
+// forge_wino_input with the depth stage of the F(4, 3) nest (wino_input_dn4_kernel): V6 [16][n][D/4][6][H/2 W/2][C], the operand of forge_wino_gemm_dn4.
+// ptv: floats between points (0 = dense, n (D/4) 6 (H/2)(W/2) ldv).
+extern "C" int forge_wino_input_dn4(const float* in, int ld, long long bs, float* V6, int ldv, long long ptv, int n, int D, int H, int W, int C,
+                                    int nsum, long long sum_stride, forge_stream_t stream) {
+    FORGE_REQUIRE(in && V6, FORGE_EINVAL, "forge_wino_input_dn4: null pointer argument");
+    FORGE_REQUIRE(nsum >= 1 && (nsum == 1 || sum_stride > 0), FORGE_EINVAL, "forge_wino_input_dn4: nsum >= 1, and a positive sum_stride (rows) with nsum > 1");
+    FORGE_REQUIRE(D > 0 && D % 4 == 0, FORGE_EINVAL, "forge_wino_input_dn4: D=%d must be a multiple of 4", D);
+    FORGE_REQUIRE(n > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C > 0 && C % 4 == 0 && ld >= C && ld % 4 == 0 && ldv >= C && ldv % 4 == 0,
+                  FORGE_ESHAPE, "forge_wino_input_dn4: n=%d D=%d H=%d W=%d C=%d ld=%d ldv=%d (H, W even; C, ld, ldv multiples of 4)", n, D, H, W, C, ld, ldv);
+    WinoInArgs a;
+    a.in = in; a.ld = ld; a.bs = bs > 0 ? bs : (long long)D * H * W; a.V = V6; a.ldv = ldv; a.n = n; a.D = D; a.H = H; a.W = W; a.C = C;
+    a.nsum = nsum; a.ss = sum_stride;
+    const long long RG = (long long)n * (D / 4) * (H / 2) * (W / 2);
+    a.ptv = ptv > 0 ? ptv : 6 * RG * ldv;
+    FORGE_REQUIRE(6 * RG < (1ll << 31), FORGE_ESHAPE, "forge_wino_input_dn4: more than 2^31 operand rows; split the batch");
+    const long long total = RG * C, grid = (total + 255) / 256;
+    FORGE_REQUIRE(grid < (1ll << 31), FORGE_ESHAPE, "forge_wino_input_dn4: grid too large");
+    a.dM = nullptr; a.ptm = 0;
+    hipLaunchKernelGGL(wino_input_dn4_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
+    FORGE_LAUNCH_CHECK("forge_wino_input_dn4");
+    return 0;
+}
+
+extern "C" int forge_wino_weights_dn4(const float* wp, float* Ud, int Cout, int Cin, forge_stream_t stream) {
+    FORGE_REQUIRE(wp && Ud && Cout > 0 && Cin > 0, FORGE_EINVAL, "forge_wino_weights_dn4: bad argument");
+    const long long total = (long long)Cout * Cin;
+    hipLaunchKernelGGL(wino_weight_dn4_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, wp, Ud, Cout, Cin);
+    FORGE_LAUNCH_CHECK("forge_wino_weights_dn4");
     return 0;
 }
 

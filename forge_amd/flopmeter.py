@@ -1,6 +1,6 @@
 """Executed-FLOP meter for the matrix-core launches of libforge_hip.so (measurement aid for bench.py / tools; not on the product path).
 
-`with FlopMeter() as m: step()` wraps the ctypes entry points whose work runs on the fp32 MFMA pipe - forge_conv_igemm, forge_wino_gemm (_half, _dn),
+`with FlopMeter() as m: step()` wraps the ctypes entry points whose work runs on the fp32 MFMA pipe - forge_conv_igemm, forge_wino_gemm (_half, _dn, _dn4),
 forge_conv_wgrad, forge_wino_wgrad, forge_attention_fwd / _fwd_lse / _bwd / _mh_fwd / _mh_bwd, forge_token_linear_fwd / _bwd - for the duration of the block and sums the FLOPs each launch EXECUTES, computed from the call's own
 arguments (2 M N taps Cin for a direct / data-gradient / weight-gradient convolution, 2 x 16 R N kd Cin for the 16 Winograd point problems).
 Only eager launches made by this process are seen (a hipGraph replay makes no Python calls): meter one eager pass, time the replay.
@@ -26,6 +26,10 @@ def _wino_gemm(a):      # forge_wino_gemm(V1,C1,ld1,bs1,pt1,V2,C2,ld2,bs2,pt2,U,
 
 def _wino_gemm_dn(a):   # forge_wino_gemm_dn(V1,C1,ld1,bs1,pt1,V2,C2,ld2,bs2,pt2,Ud,Mm,n,D,Ht,Wt,Cout,kd,stream): 4 positions x Cin per PAIR of planes
     return 2.0 * 16 * _v(a[12]) * (_v(a[13]) // 2) * _v(a[14]) * _v(a[15]) * _v(a[16]) * 4 * (_v(a[1]) + _v(a[6]))
+
+
+def _wino_gemm_dn4(a):  # forge_wino_gemm_dn4(V1,C1,ld1,bs1,pt1,V2,C2,ld2,bs2,pt2,Ud,Mm,n,D,Ht,Wt,Cout,kd,stream): 6 positions x Cin per FOUR planes
+    return 2.0 * 16 * _v(a[12]) * (_v(a[13]) // 4) * _v(a[14]) * _v(a[15]) * _v(a[16]) * 6 * (_v(a[1]) + _v(a[6]))
 
 
 def _wgrad(a):          # forge_conv_wgrad(dy,ldy,x1,C1,ld1,bs1,x2,C2,ld2,bs2,dwp,n,D,H,W,is,Di,Hi,Wi,Cout,taps,ntaps,stream)
@@ -66,7 +70,7 @@ def _token_bwd(a):      # forge_token_linear_bwd(dy,lddy,x,ldx,w,gamma,beta,stat
     return 2.0 * _v(a[16]) * _v(a[17]) * _v(a[18]) * ((1 if dxn else 0) + (1 if _v(a[10]) else 0))
 
 
-_ENTRIES = {"forge_conv_igemm": _igemm, "forge_wino_gemm": _wino_gemm, "forge_wino_gemm_half": _wino_gemm, "forge_wino_gemm_dn": _wino_gemm_dn, "forge_conv_wgrad": _wgrad, "forge_wino_wgrad": _wino_wgrad,
+_ENTRIES = {"forge_conv_igemm": _igemm, "forge_wino_gemm": _wino_gemm, "forge_wino_gemm_half": _wino_gemm, "forge_wino_gemm_dn": _wino_gemm_dn, "forge_wino_gemm_dn4": _wino_gemm_dn4, "forge_conv_wgrad": _wgrad, "forge_wino_wgrad": _wino_wgrad,
             "forge_attention_fwd": _attention, "forge_attention_fwd_lse": _attention_lse, "forge_attention_bwd": _attention_bwd,
             "forge_attention_mh_fwd": _attention_mh, "forge_attention_mh_bwd": _attention_mh_bwd,
             "forge_token_linear_fwd": _token_fwd, "forge_token_linear_bwd": _token_bwd}

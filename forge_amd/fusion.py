@@ -446,7 +446,7 @@ def _h0_direct(p, xr, grp, t0, h):
                   epilogue=co.EPI_AFFINE_ACT)
 
 
-def _wino_step(geo, x, view, views, wg, wo, V, Mm, h, z, hr, hn, out=None, r=None, cand=None, nest=None):
+def _wino_step(geo, x, view, views, wg, wo, V, Mm, h, z, hr, hn, out=None, r=None, cand=None, nest=None, nest4=False):
     """One ConvGRU step on the Winograd launches over geo = (b, D, H, W): transform h, point GEMMs, inverse transform fused with the gate tail
     (z, hr = h r; r into `r`); transform hr, point GEMMs, inverse transform fused with tanh / lerp (hn; tanh(c) into `cand`, the fusion_norm
     folded output into `out`). (Fusing each inverse transform with the next input transform through LDS was built and measured slower -
@@ -456,12 +456,16 @@ def _wino_step(geo, x, view, views, wg, wo, V, Mm, h, z, hr, hn, out=None, r=Non
              hidden-half weights; the inverse transforms add view `view`'s products
     wg = (U, bias), wo = (U, bias, scale, shift). V: the buffer of both transforms, or None for a new one each (returned: the training node
     keeps them for the weight gradient). Mm: the point-product scratch (_step_scratch). nest (full form only) = (Ud_gates, Ud_state): both point
-    GEMMs run the depth nest (convops.wino_gemm with wino_pack_packed_dn's weights) on these weights and hand 16 planes to the same inverse transforms."""
+    GEMMs run the depth nest (convops.wino_gemm with wino_pack_packed_dn's weights) on these weights and hand 16 planes to the same inverse transforms.
+    nest4: the nest's F(4, 3) form - x and V hold wino_input_dn4's operands (1.5 x the rows), nest wino_pack_packed_dn4's weights."""
     b, D, H, W = geo
     C = h.shape[-1]
     split = isinstance(x, tuple)
 
     def conv(src, U, Cout, i):
+        if nest4:
+            Vs = co.wino_input_dn4(src, C, C, b, D, H, W, out=V)
+            return Vs, co.wino_gemm_dn4(x, C, Vs, C, nest[i], Mm, b, D, H // 2, W // 2, Cout, view=view, views=views), {}
         Vs = co.wino_input(src, C, C, b, D, H, W, out=V)
         if nest is not None:
             return Vs, co.wino_gemm(x, C, Vs, C, nest[i], Mm, b, D, H // 2, W // 2, Cout, view=view, views=views), {}
@@ -508,14 +512,11 @@ def _fuse_eval(gru, xr, groups, wino, split, h0=None, keep=None, const0=None):
     wk = "_U" if wino else "_w"
     weights = lambda half: ((p["gate" + wk + half], p["gate_b"]), (p["out" + wk + half], p["out_b"], *p["norm"]))
     wg, wo = weights("h" if split else "")
-    nest, nest_h0 = None, False
+    nest, nest_h0, nest4 = None, False, False
     # X, the input side of the steps: V_x (Winograd, full), the products (MXg, MXc) (Winograd, split) or per view (gx, cx) (direct, split)
     if wino:
         R = b * D * (H // 2) * (W // 2)
-        X = co.wino_input(xr, C, C, b * t, D, H, W)                       # [16][b t D Ht Wt][C]: all views of all scenes, one launch
-        if split:
-            X = (_input_products(X, p["gate_Ux"], b * t, geo, 2 * C), _input_products(X, p["out_Ux"], b * t, geo, C))
-        V = torch.empty(16, R, C, dtype=torch.float32, device=dev)
+        V = V6 = None
         # the full steps of the plain eval fusion take the depth nest where both of their launches qualify (K = 2C per depth position)
         if (not split and keep is None and const0 is None
                 and all(co.wino_depth_nest_applies(R, D, H // 2, W // 2, c, 2 * C) for c in (2 * C, C))):
@@ -523,6 +524,21 @@ def _fuse_eval(gru, xr, groups, wino, split, h0=None, keep=None, const0=None):
             nest = (pd["gate_Ud"], pd["out_Ud"])
             # fusion_conv's two launches (K = C per position) follow where the rule holds for them (tools/wino_dn_probe.py: 0.90 of the four-point pair)
             nest_h0 = co.wino_depth_nest_applies(R, D, H // 2, W // 2, C, C)
+            # the steps take the nest's F(4, 3) form where its rule holds and its 1.5 x operand planes fit the buffer range: X and the per-step
+            # transforms of h and h r through wino_input_dn4. fusion_conv (K = C per position, four K-steps per loop) stays on F(2, 3).
+            if (all(co.wino_depth_nest4_applies(R, D, H // 2, W // 2, c, 2 * C) for c in (2 * C, C))
+                    and co.wino_fits(b, D, H, W, C, views=t, nest4=True)):
+                pd = gru._packed_wino_dn4()
+                nest, nest4 = (pd["gate_Ud4"], pd["out_Ud4"]), True
+        if nest4:
+            X = co.wino_input_dn4(xr, C, C, b * t, D, H, W)               # [16][b t (D/4) 6 Ht Wt][C]
+            V6 = torch.empty(16, R // 4 * 6, C, dtype=torch.float32, device=dev)
+            V = V6.reshape(-1)[:16 * R * C].view(16, R, C)               # fusion_conv's transforms: the front of the same buffer
+        else:
+            X = co.wino_input(xr, C, C, b * t, D, H, W)                   # [16][b t D Ht Wt][C]: all views of all scenes, one launch
+            if split:
+                X = (_input_products(X, p["gate_Ux"], b * t, geo, 2 * C), _input_products(X, p["out_Ux"], b * t, geo, C))
+            V = torch.empty(16, R, C, dtype=torch.float32, device=dev)
         Mm = _step_scratch(R, C, dev, nest is not None)
     elif split:                                                            # the input halves once per view (no bias: added with the hidden half)
         X = {}
@@ -559,7 +575,7 @@ def _fuse_eval(gru, xr, groups, wino, split, h0=None, keep=None, const0=None):
             elif const0 is not None and k == 0:
                 _wino_step(geo, (const0["MXg0"], const0["MXc0"]), 0, 1, *weights("h"), V, Mm, h, z, hr, hn, last, r, cand)
             else:
-                _wino_step(geo, X, ti, t, wg, wo, V, Mm, h, z, hr, hn, last, r, cand, nest=nest)
+                _wino_step(geo, X, ti, t, wg, wo, V6 if nest4 else V, Mm, h, z, hr, hn, last, r, cand, nest=nest, nest4=nest4)
             if keep is not None:
                 keep += [h, z, r, cand]
             h, hn = hn, h
@@ -976,6 +992,13 @@ class ConvGRU_3D(co.PackedModule):
         p = self._packed_wino()
         if "gate_Ud" not in p:
             p.update({k + "_Ud": co.wino_pack_packed_dn(p[k + "_w"]) for k in ("gate", "out", "fc0", "fc3")})
+        return p
+
+    def _packed_wino_dn4(self):
+        """_packed_wino_dn plus the F(4, 3) nest's weights U'' [16][6][Cout][Cin] of the two GRU convolutions (convops.wino_pack_packed_dn4)."""
+        p = self._packed_wino_dn()
+        if "gate_Ud4" not in p:
+            p.update({k + "_Ud4": co.wino_pack_packed_dn4(p[k + "_w"]) for k in ("gate", "out")})
         return p
 
     def _packed_halves(self, wino):

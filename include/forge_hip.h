@@ -303,6 +303,23 @@ int forge_wino_output_half(const float* Mm8, const float* Mm2_8 /* nullable seco
 int forge_wino_gemm_dn(const float* V1, int C1, int ld1, long long bs1, long long pt1, const float* V2, int C2, int ld2, long long bs2,
                        long long pt2, const float* Ud, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, forge_stream_t stream);
 int forge_wino_weights_dn(const float* wp, float* Ud, int Cout, int Cin, forge_stream_t stream);
+/* The depth nest with F(4, 3): four K loops per plane pair become six per GROUP of four planes (1.5 per plane). Three entries:
+ * forge_wino_input_dn4: forge_wino_input (same arguments: bs, nsum / sum_stride, ldv, ptv) plus the depth stage. V6 [16][n][D/4][6][H/2 W/2][C]; position k
+ *   of group g combines the planes p_e = 4g - 1 + e, e = 0..5, of the batch element (zero outside ITS grid) per input element, in this order:
+ *   q0 = 4 (p0 - p2) - (p2 - p4), q1 = (p3 + p4) - 4 (p1 + p2), q2 = (p4 - p3) + 4 (p1 - p2), q3 = (p4 - p2) + 2 (p3 - p1), q4 = (p4 - p2) - 2 (p3 - p1),
+ *   q5 = 4 (p1 - p3) - (p3 - p5) (two rounded additions and one fused multiply-add with an exact product each), then B^T q B as forge_wino_input.
+ * forge_wino_weights_dn4: Ud [16][6][Cout][Cin] = G_depth (x) (G w G^T) from wp [27][Cout][Cin], depth rows w0 / 4, -(w0 + w2 + w1) / 6, -(w0 + w2 - w1) / 6,
+ *   (w0 / 4 + w2 + w1 / 2) / 6, (w0 / 4 + w2 - w1 / 2) / 6, w2; float64 throughout, rounded once.
+ * forge_wino_gemm_dn4: the 16 point products Mm [16][R][Cout] of forge_wino_gemm from V6 operands (V1 | V2 along K; bs1 / bs2 / pt1 / pt2 in rows / floats of
+ *   the V6 layout, 0 = dense) and Ud. Products m_k = V6[.][g][k] (x) Ud[p][k]; rows y0 = ((m1 + m2) + (m3 + m4)) + m0, y1 = (m1 - m2) + 2 (m3 - m4),
+ *   y2 = (m1 + m2) + 4 (m3 + m4), y3 = ((m1 - m2) + 8 (m3 - m4)) + m5, where m0 and m5 are accumulated onto the bracket in front of them.
+ *   FORGE_EINVAL, before any launch, unless kd == 3, D % 4 == 0, Ht Wt % 64 == 0, C1 and C2 are multiples of 32 and every operand and output plane
+ *   stays within 32-bit buffer offsets. Feeds forge_wino_output; not bitwise forge_wino_gemm's result. */
+int forge_wino_input_dn4(const float* in, int ld, long long bs, float* V6, int ldv, long long ptv, int n, int D, int H, int W, int C,
+                         int nsum, long long sum_stride, forge_stream_t stream);
+int forge_wino_weights_dn4(const float* wp, float* Ud, int Cout, int Cin, forge_stream_t stream);
+int forge_wino_gemm_dn4(const float* V1, int C1, int ld1, long long bs1, long long pt1, const float* V2, int C2, int ld2, long long bs2,
+                        long long pt2, const float* Ud, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, forge_stream_t stream);
 int forge_wino_gemm_tile(long long R, int Cout, int Cin);   /* the workgroup tile letter ('A'..'E', see forge_conv_igemm_plan) forge_wino_gemm uses for R tile rows per point, Cin = C1 + C2 */
 int forge_wino_output(const float* Mm, const float* Mm2, long long bs2, long long pt2, const float* bias, const float* scale, const float* shift, float slope, const float* residual,
                       const float* aux_h, const float* aux_z, float* out, float* out2, float* out3, int n, int D, int H, int W, int Cout,

@@ -1,14 +1,17 @@
-"""Probe of the depth nest (forge_wino_gemm_dn): what the real kernel buys, per launch and on the headline.
+"""Probe of the depth nest (forge_wino_gemm_dn, forge_wino_gemm_dn4): what the real kernels buy, per launch and on the headline.
 
     python tools/wino_dn_probe.py launch [--scenes B] [--out DIR]
         The gates, state and fusion_conv point-GEMM shapes of the step at R = 8192 B tile rows (32^3 voxels, C = 128): the nest (forge_wino_gemm_dn +
         forge_wino_output on 16 planes) against the four-point pair (forge_wino_gemm_half + forge_wino_output_half on 8 planes), device events over
-        ITERS launches, best of 3, and the largest difference of the two results.               -> DIR/r14_wino_dn_launch.txt
+        ITERS launches, best of 3, and the largest difference of the two results; then the F(4, 3) form: its operand transform of the hidden-state
+        operand (forge_wino_input_dn4 against forge_wino_input), its GEMM (forge_wino_gemm_dn4) and the transform + GEMM + inverse pair against both
+        the F(2, 3) nest's and the four-point form's.                                            -> DIR/<--tag>_launch.txt
     python tools/wino_dn_probe.py ab --parent-root DIR0 [--pairs 3] [--out DIR] [-- bench arguments]
         End to end: `python bench.py <bench arguments>` of a built checkout of the parent commit (DIR0) and of this tree, alternated --pairs times in
         fresh processes; one JSON line per run and the pair rule (new value_min above the parent's value_max in EVERY pair) with the median ratio.
         The parent runs from its own checkout rather than through FORGE_AMD_LIB: the binding of this tree lists forge_wino_gemm_dn, which the parent's
-        library does not export.                                                                  -> DIR/r14_wino_dn_headline.txt (appended)
+        library does not export.                                                                  -> DIR/<--tag>_headline.txt (appended)
+    --tag names the record files (default r18_wino_dn4).
 """
 import argparse
 import json
@@ -68,10 +71,26 @@ def launch(args):
                      "%7.1f us | pair ratio %.3f, GEMM ratio %.3f | max |diff| / max |y| %.1e" % (
                          name, Cin, Cout, t["gemm_dn"], tf(t["gemm_dn"], 2), t["out16"], t["gemm_half"], tf(t["gemm_half"], 3), t["out8"],
                          t["out16"] / t["out8"], t["gemm_dn"] / t["gemm_half"], diff))
+        # the F(4, 3) form: the hidden-state operand's transform is part of the pair (1.5 x the planes written)
+        Ch = C2 or C1
+        x = rn(M, Ch)
+        Ud4 = co.wino_pack_packed_dn4(wp)
+        W1, W2 = rn(16, R // 4 * 6, C1), (rn(16, R // 4 * 6, C2) if C2 else None)
+        Vh, Vh6 = torch.empty(16, R, Ch, device=dev), torch.empty(16, R // 4 * 6, Ch, device=dev)
+        g_d4 = lambda: co.wino_gemm_dn4(W1, C1, W2, C2, Ud4, Mm, b, D, Ht, Wt, Cout)
+        t_in, t_in6 = timed(lambda: co.wino_input(x, Ch, Ch, b, D, H, W, out=Vh)), timed(lambda: co.wino_input_dn4(x, Ch, Ch, b, D, H, W, out=Vh6))
+        t4 = timed(g_d4)
+        full = lambda f_in, f_g, o: (f_in(), outp(f_g(), o))
+        p4 = timed(lambda: full(lambda: co.wino_input_dn4(x, Ch, Ch, b, D, H, W, out=Vh6), g_d4, out_a))
+        p2 = timed(lambda: full(lambda: co.wino_input(x, Ch, Ch, b, D, H, W, out=Vh), g_dn, out_a))
+        p1 = timed(lambda: full(lambda: co.wino_input(x, Ch, Ch, b, D, H, W, out=Vh), g_h, out_b))
+        lines.append("%-12s F(4,3): GEMM %7.1f us (%5.1f TF executed), transform %6.1f us (plain %6.1f us) | transform + GEMM + inverse %7.1f us | "
+                     "F(2,3) nest %7.1f us, four-point %7.1f us | ratio to F(2,3) %.3f, to four-point %.3f" % (
+                         name, t4, tf(t4, 1.5), t_in6, t_in, p4, p2, p1, p4 / p2, p4 / p1))
     text = "\n".join(lines)
     print(text)
     os.makedirs(args.out, exist_ok=True)
-    with open(os.path.join(args.out, "r14_wino_dn_launch.txt"), "w") as f:
+    with open(os.path.join(args.out, args.tag + "_launch.txt"), "w") as f:
         f.write(text + "\n")
 
 
@@ -108,7 +127,7 @@ def ab(args):
             "MET" if rule else "NOT MET", statistics.median(ratios)))
         print(lines[-1], flush=True)
     os.makedirs(args.out, exist_ok=True)
-    with open(os.path.join(args.out, "r14_wino_dn_headline.txt"), "a") as f:
+    with open(os.path.join(args.out, args.tag + "_headline.txt"), "a") as f:
         f.write("\n".join(lines) + "\n")
 
 
@@ -118,6 +137,7 @@ if __name__ == "__main__":
     ap.add_argument("--scenes", type=int, default=1)
     ap.add_argument("--parent-root", default=None)
     ap.add_argument("--pairs", type=int, default=3)
+    ap.add_argument("--tag", default="r18_wino_dn4")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
     argv = sys.argv[1:]
     cut = argv.index("--") if "--" in argv else len(argv)       # after --: the arguments of bench.py (default: the headline run)
