@@ -112,6 +112,10 @@ SIGNATURES = {
     "forge_lpips_tap": [_P, _I, _I, _I, _P, _P, _P],
     "forge_lpips_finalize": [_P, _I, _I, _I, _I, _I, _I, _P, _P],
     "forge_pose_sync": [_P, _P, _P, _I, _I, _I, _I, _I, _D, _P, _P, _P, _P],
+    "forge_mesh_case_table": [_P, _I],
+    "forge_mesh_workspace_bytes": [_I, _I, _I, _I],
+    "forge_mesh_count": [_P, _I, _I, _I, _I, _F, _P, _LL, _P, _P],
+    "forge_mesh_emit": [_P, _P, _I, _I, _I, _I, _I, _F, _F, _P, _LL, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
     "forge_ncdhw_to_ndhwc": [_P, _P, _I, _I, _LL, _P],
     "forge_ndhwc_to_ncdhw": [_P, _P, _I, _I, _LL, _P],
 }
@@ -119,7 +123,7 @@ SIGNATURES = {
 
 _LL_RESULTS = ("forge_render_bwd_ws_bytes", "forge_conv_wgrad_det_ws_bytes", "forge_wino_wgrad_det_ws_bytes",     # byte counts: long long results
                "forge_conv_direct_wgrad_det_ws_bytes", "forge_rotate_bwd_det_ws_bytes", "forge_rotate_bwd_slots_det_ws_bytes",
-               "forge_token_linear_bwd_ws_bytes", "forge_layer_norm_bwd_ws_bytes")
+               "forge_token_linear_bwd_ws_bytes", "forge_layer_norm_bwd_ws_bytes", "forge_mesh_workspace_bytes")
 
 
 def lib():

@@ -807,3 +807,123 @@ def pose_sync(P, conf, pairs, N, squares=10, center_first_camera=False, rank_tol
     _lib.check(_lib.lib().forge_pose_sync(_lib.ptr(Pc), _lib.ptr(cc), _lib.ptr(pairs_dev), B, N, E, int(squares), 0 if center_first_camera else N // 2,
                                           float(rank_tol), _lib.ptr(out), _lib.ptr(sv), _lib.ptr(status), _lib.current_stream()), "forge_pose_sync")
     return (out, status, sv) if return_sv else (out, status)
+
+
+# ------------------------------------------------------------------------------------------------------------------- mesh extraction
+MESH_OVERFLOW = 1                                                  # status bit of forge_mesh_emit (FORGE_MESH_OVERFLOW)
+MESH_TABLE_INTS = 154
+_mesh_table = None
+
+
+def mesh_case_table():
+    """The marching-tetrahedra case table of csrc/mesh.hip (forge_mesh_case_table, host only: no device is touched), as int lists:
+    tet_corner [6][4], tet_flip [6], tet_edge [6][2], case_ntri [16], case_tri [16][2][3] (include/forge_hip.h section g1)."""
+    global _mesh_table
+    if _mesh_table is None:
+        import ctypes
+        buf = (ctypes.c_int * MESH_TABLE_INTS)()
+        _lib.check(_lib.lib().forge_mesh_case_table(buf, MESH_TABLE_INTS), "forge_mesh_case_table")
+        v = list(buf)
+        _mesh_table = {
+            "tet_corner": [v[4 * q:4 * q + 4] for q in range(6)],
+            "tet_flip": v[24:30],
+            "tet_edge": [v[30 + 2 * e:32 + 2 * e] for e in range(6)],
+            "case_ntri": v[42:58],
+            "case_tri": [[v[58 + 6 * m + 3 * t:61 + 6 * m + 3 * t] for t in range(2)] for m in range(16)],
+        }
+    return _mesh_table
+
+
+def _mesh_inputs(density, features, level):
+    if not torch.is_tensor(density) or (features is not None and not torch.is_tensor(features)):
+        raise TypeError("mesh: density (and features) must be tensors")
+    _require_cuda(density, features)
+    if density.dim() != 5 or density.shape[1] != 1:
+        raise ValueError("mesh: density must be [n,1,D,H,W] (encoder_3d.get_density3D), got %s" % (tuple(density.shape),))
+    if density.dtype != torch.float32:
+        raise TypeError("mesh: float32 density (got %s)" % density.dtype)
+    if not density.is_contiguous():
+        raise ValueError("mesh: density must be contiguous (strides %s)" % (density.stride(),))
+    n, _, D, H, W = (int(s) for s in density.shape)
+    if n < 1:
+        raise ValueError("mesh: empty batch")
+    level = float(level)
+    if not (level > 0.0 and math.isfinite(level)):
+        raise ValueError("mesh: level=%r must be finite and > 0 (the virtual shell around the volume is zero)" % level)
+    C = 0
+    if features is not None:
+        if features.dim() != 5 or features.shape[0] != n or tuple(features.shape[2:]) != (D, H, W) or features.device != density.device:
+            raise ValueError("mesh: features must be [%d,C,%d,%d,%d] on the density's device, got %s" % (n, D, H, W, tuple(features.shape)))
+        if features.dtype != torch.float32:
+            raise TypeError("mesh: float32 features (got %s)" % features.dtype)
+        C = int(features.shape[1])
+        if C < 4 or C % 4:
+            raise ValueError("mesh: C=%d feature channels must be a positive multiple of 4" % C)
+        if not features.permute(0, 2, 3, 4, 1).is_contiguous():
+            raise ValueError("mesh: features must be channels-last (torch.channels_last_3d; ops.to_channels_last_3d), got strides %s" % (features.stride(),))
+    return n, C, D, H, W, level
+
+
+def _mesh_ws_bytes(n, D, H, W):
+    b = int(_lib.lib().forge_mesh_workspace_bytes(n, D, H, W))
+    if b < 0:
+        _lib.check(b, "forge_mesh_workspace_bytes")
+    return b
+
+
+@_lib.on_tensor_device
+def mesh_count(density, level=0.5):
+    """forge_mesh_count: classify the cells of density [n,1,D,H,W] and scan. Returns (counts [n,2] int32 on the device: vertices and triangles
+    per volume, workspace): the workspace goes to mesh_emit together with the same density and level. Nothing is read back."""
+    n, _, D, H, W, level = _mesh_inputs(density, None, level)
+    nbytes = _mesh_ws_bytes(n, D, H, W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=density.device)
+    counts = torch.empty(n, 2, dtype=torch.int32, device=density.device)
+    _lib.check(_lib.lib().forge_mesh_count(_lib.ptr(density.detach()), n, D, H, W, level, _lib.ptr(ws), nbytes, _lib.ptr(counts), _lib.current_stream()),
+               "forge_mesh_count")
+    return counts, ws
+
+
+@_lib.on_tensor_device
+def mesh_emit(density, workspace, counts, max_vertices, max_faces, level=0.5, volume_size=1.0, features=None, offsets=None, out=None):
+    """forge_mesh_emit after mesh_count(density, level). offsets None: every volume gets max_vertices / max_faces rows, the result is
+    vertices [n,max_vertices,3], normals [n,max_vertices,3], faces [n,max_faces,3] int32, vertex features [n,max_vertices,C] or None, status [n].
+    offsets [n,2] int32 (the exclusive scan of counts over volumes): the volumes are packed one after the other into arrays of max_vertices /
+    max_faces rows in all: vertices [max_vertices,3], ... Rows that no vertex or triangle lands in are left as they were. status carries
+    MESH_OVERFLOW for a volume that did not fit; what fitted is the prefix of the full result. out: (vertices, normals, faces, features or None)
+    to write into, instead of fresh tensors. Nothing is read back."""
+    n, C, D, H, W, level = _mesh_inputs(density, features, level)
+    max_vertices, max_faces = int(max_vertices), int(max_faces)
+    if max_vertices < 0 or max_faces < 0:
+        raise ValueError("mesh_emit: negative capacity (%d, %d)" % (max_vertices, max_faces))
+    nbytes = _mesh_ws_bytes(n, D, H, W)
+    _require_cuda(workspace, counts, offsets)
+    if workspace.dtype != torch.uint8 or workspace.numel() < nbytes or not workspace.is_contiguous():
+        raise ValueError("mesh_emit: workspace is not the one mesh_count returned for this shape")
+    for name, t in (("counts", counts), ("offsets", offsets)):
+        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (n, 2) or not t.is_contiguous()):
+            raise ValueError("mesh_emit: %s must be a contiguous int32 [%d,2] tensor" % (name, n))
+    dev = density.device
+    lead = (n,) if offsets is None else ()
+    shapes = (lead + (max_vertices, 3), lead + (max_vertices, 3), lead + (max_faces, 3), lead + (max_vertices, C))
+    if out is None:
+        vertices = torch.empty(shapes[0], dtype=torch.float32, device=dev)
+        normals = torch.empty(shapes[1], dtype=torch.float32, device=dev)
+        faces = torch.empty(shapes[2], dtype=torch.int32, device=dev)
+        vfeat = torch.empty(shapes[3], dtype=torch.float32, device=dev) if features is not None else None
+    else:
+        vertices, normals, faces, vfeat = out
+        want = [(vertices, shapes[0], torch.float32), (normals, shapes[1], torch.float32), (faces, shapes[2], torch.int32)]
+        if features is not None:
+            want.append((vfeat, shapes[3], torch.float32))
+        else:
+            vfeat = None
+        for t, shape, dt in want:
+            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev:
+                raise ValueError("mesh_emit: every out tensor must be contiguous, here %s of shape %s on %s" % (dt, shape, dev))
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().forge_mesh_emit(_lib.ptr(density.detach()), _lib.ptr(None if features is None else features.detach()), n, C, D, H, W, level,
+                                          float(volume_size), _lib.ptr(workspace), nbytes, _lib.ptr(counts), _lib.ptr(offsets), max_vertices, max_faces,
+                                          _lib.ptr(vertices), _lib.ptr(normals), _lib.ptr(faces), _lib.ptr(vfeat), _lib.ptr(status), _lib.current_stream()),
+               "forge_mesh_emit")
+    return vertices, normals, faces, vfeat, status

@@ -687,6 +687,53 @@ int forge_pose_sync(const float* P, const float* conf, const int* pairs, int B, 
                     float* out, double* sv, int* status, forge_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * g1  Triangle-mesh extraction from density volumes: marching tetrahedra on the Kuhn 6-tetrahedron split of every cell. The reference has no
+ * geometry export; the field and the frame are the ray-marcher's (forge_render_fwd: align_corners=True sampling with zero padding).
+ *   density  [n][D][H][W] float32, the plane of the [n,1,D,H,W] tensor of encoder_3d.get_density3D
+ *   features [n][D][H][W][C] channels-last, nullable; C % 4 == 0, 16-byte aligned
+ *   level    finite and > 0; a grid point is INSIDE iff d > level (strict, an fp32 compare)
+ * Grid points have indices -1 .. N per axis; -1 and N are virtual zeros (and so is everything beyond them), which closes every surface, also one
+ * that reaches the volume border. Cells have their min corner p0 in -1 .. N-1 per axis: (D+1)(H+1)(W+1) cells, linear index z-major
+ * ((cz (H+1) + cy) (W+1) + cx with c = p0 + 1). Corner offset code: bit 0 = +x (W), bit 1 = +y (H), bit 2 = +z (D). Each cell is split into the six
+ * tetrahedra p0, p0+e_a, p0+e_a+e_b, p0+(1,1,1) over the permutations (a,b,c) of (x,y,z) in lexicographic order. Every edge runs from a point to
+ * that point plus a non-zero offset code and is OWNED by the cell whose min corner is its first point: edge direction k = 0..6 is offset code k+1.
+ *   vertices one per ACTIVE edge (one end inside, one outside), welded. With a the inside end: t = (level - d_a) / (d_b - d_a) in fp32, index
+ *            position idx = a + t (b - a), world position per axis ((2 idx) / (N-1) - 1) e, e = 0.5 (N-1) volume_size / N (fp32, this order;
+ *            N-1 is replaced by 1 where N = 1). Emitted as (x, y, z) <-> (W, H, D): the canonical world frame forge_render_fwd takes cameras in.
+ *   normals  -normalize(g_a + t (g_b - g_a)), g the central difference of the zero-padded field at a grid point scaled to world units
+ *            (per axis (f(p+1) - f(p-1)) N: the common factor 2 volume_size drops out); a zero vector stays zero. They point to the low-density side.
+ *   vertex_features  f_a + t (f_b - f_a), virtual points = 0 (only with features)
+ *   order    vertices by (volume, owner cell linear index, edge direction); triangles by (volume, cell linear index, tetrahedron 0..5, triangle
+ *            0..1); vertex indices are per volume; triangles are counter-clockwise seen from the low-density side. No atomics: the order, and
+ *            every bit of the output, is reproducible. Every undirected edge of the result is shared by exactly two oppositely directed triangles.
+ *
+ *   forge_mesh_case_table    host only, no device: copies the case table (the ONE copy, a constexpr table in mesh.hip) into table[154]:
+ *                            tet_corner[6][4] offset codes | tet_flip[6] (1: the path is negatively oriented, its triangles swap their last two
+ *                            vertices) | tet_edge[6][2] local corner pairs i < j | case_ntri[16] | case_tri[16][2][3] tetrahedron-edge ids, for a
+ *                            positively oriented tetrahedron, case = sum of 2^i over the inside local corners.
+ *   forge_mesh_workspace_bytes  bytes of the workspace (16-byte aligned) shared by the two calls below; negative FORGE_E* for bad extents.
+ *   forge_mesh_count         classify every cell, scan: counts[v] = (vertices, triangles) of volume v (device int32 [n][2]), the workspace holds the
+ *                            cell records and offsets that forge_mesh_emit reads. Three launches.
+ *   forge_mesh_emit          writes the mesh. offsets == NULL: volume v owns rows v max_vertices .. (v+1) max_vertices - 1 of vertices / normals /
+ *                            vertex_features and rows v max_faces .. of faces. offsets != NULL (device int32 [n][2], the exclusive scan of counts
+ *                            over volumes): volume v starts at row offsets[v] of arrays with max_vertices / max_faces rows IN ALL. Rows past
+ *                            the capacity are never written; status[v] (device int32) = FORGE_MESH_OVERFLOW when volume v did not fit, else 0;
+ *                            the rows that did fit are the prefix of the full result. Two launches.
+ * Nothing allocates, synchronises or reads the environment: both calls may sit in a captured graph.
+ * FORGE_EINVAL: null pointer, level <= 0 or not finite, volume_size <= 0 or not finite, an extent or n < 1, a workspace too small or unaligned,
+ * negative capacities. FORGE_ESHAPE: C % 4 != 0, more than (2^31 - 1) / 12 cells per volume (per-volume offsets are 32-bit), n > 65535.
+ */
+#define FORGE_MESH_OVERFLOW 1   /* status bit of forge_mesh_emit: the volume's vertices or triangles exceed the capacity */
+#define FORGE_MESH_TABLE_INTS 154
+int forge_mesh_case_table(int* table, int capacity);
+long long forge_mesh_workspace_bytes(int n, int D, int H, int W);
+int forge_mesh_count(const float* density, int n, int D, int H, int W, float level, void* workspace, long long workspace_bytes, int* counts,
+                     forge_stream_t stream);
+int forge_mesh_emit(const float* density, const float* features, int n, int C, int D, int H, int W, float level, float volume_size,
+                    const void* workspace, long long workspace_bytes, const int* counts, const int* offsets, int max_vertices, int max_faces,
+                    float* vertices, float* normals, int* faces, float* vertex_features, int* status, forge_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * layout helpers: NCDHW <-> channels-last for callers that hold plain-contiguous volumes.
  *   src [n][C][P] -> dst [n][P][C]   (P = D*H*W)   and back.
  */
