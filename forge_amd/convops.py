@@ -594,6 +594,27 @@ def wino_depth_nest4_applies(R, D, Ht, Wt, Cout, Cin):
     return STATE.wino_depth_nest4 and D % 4 == 0 and D >= 8 and wino_depth_nest_applies(R, D, Ht, Wt, Cout, Cin)
 
 
+def _point_products(Mm, P, R, Cout, device):
+    """The [P][R][Cout] point-product view of the front of the buffer Mm (None: a new tensor); ValueError when Mm cannot hold it."""
+    if Mm is None:
+        Mm = torch.empty(P, R, Cout, dtype=torch.float32, device=device)
+    if not (Mm.is_contiguous() and Mm.dtype == torch.float32 and Mm.numel() >= P * R * Cout):
+        raise ValueError("point-product buffer %s %s%s cannot hold %d x %d x %d float32" % (
+            tuple(Mm.shape), Mm.dtype, "" if Mm.is_contiguous() else " (not contiguous)", P, R, Cout))
+    if Mm.shape != (P, R, Cout):
+        Mm = Mm.as_strided((P, R, Cout), (R * Cout, Cout, 1))
+    return Mm
+
+
+def _wino_gemm_call(entry, V1, C1, V2, C2, U, Mm, n, D, Ht, Wt, Cout, kd, view, views, vol, *tile):
+    """One of the four forge_wino_gemm* entries on view `view` of V1, whose batch elements hold `views` views of `vol` rows each (`tile`: forge_wino_gemm's own)."""
+    p1 = ctypes.c_void_p(V1.data_ptr() + 4 * view * vol * C1)
+    _lib.check(getattr(_lib.lib(), entry)(p1, C1, C1, views * vol if views > 1 else 0, V1.shape[1] * C1, _lib.ptr(V2), C2, C2, 0,
+                                          0 if V2 is None else V2.shape[1] * C2, _lib.ptr(U), _lib.ptr(Mm), n, D, Ht, Wt, Cout, kd,
+                                          *tile, _lib.current_stream()), entry)
+    return Mm
+
+
 @_lib.on_tensor_device
 def wino_gemm_dn4(V1, C1, V2, C2, Ud, Mm, n, D, Ht, Wt, Cout, view=0, views=1):
     """wino_gemm's 16 point products [16][R][Cout] through the F(4, 3) depth nest (forge_wino_gemm_dn4), from the wino_input_dn4 operands V1
@@ -606,18 +627,8 @@ def wino_gemm_dn4(V1, C1, V2, C2, Ud, Mm, n, D, Ht, Wt, Cout, view=0, views=1):
     if V1.shape[1] != n * views * vol6 or (V2 is not None and V2.shape[1] != n * vol6):
         raise ValueError("depth-nest operands %s / %s are not wino_input_dn4's %d (x %d views) rows per point" % (
             tuple(V1.shape), None if V2 is None else tuple(V2.shape), n * vol6, views))
-    if Mm is None:
-        Mm = torch.empty(16, R, Cout, dtype=torch.float32, device=V1.device)
-    if not (Mm.is_contiguous() and Mm.dtype == torch.float32 and Mm.numel() >= 16 * R * Cout):
-        raise ValueError("point-product buffer %s %s%s cannot hold 16 x %d x %d float32" % (
-            tuple(Mm.shape), Mm.dtype, "" if Mm.is_contiguous() else " (not contiguous)", R, Cout))
-    if Mm.shape != (16, R, Cout):
-        Mm = Mm.as_strided((16, R, Cout), (R * Cout, Cout, 1))
-    p1 = ctypes.c_void_p(V1.data_ptr() + 4 * view * vol6 * C1)
-    _lib.check(_lib.lib().forge_wino_gemm_dn4(p1, C1, C1, views * vol6 if views > 1 else 0, V1.shape[1] * C1, _lib.ptr(V2), C2, C2, 0,
-                                              0 if V2 is None else V2.shape[1] * C2, _lib.ptr(Ud), _lib.ptr(Mm), n, D, Ht, Wt, Cout, 3,
-                                              _lib.current_stream()), "forge_wino_gemm_dn4")
-    return Mm
+    Mm = _point_products(Mm, 16, R, Cout, V1.device)
+    return _wino_gemm_call("forge_wino_gemm_dn4", V1, C1, V2, C2, Ud, Mm, n, D, Ht, Wt, Cout, 3, view, views, vol6)
 
 
 @_lib.on_tensor_device
@@ -628,18 +639,8 @@ def wino_gemm_dn(V1, C1, V2, C2, Ud, Mm, n, D, Ht, Wt, Cout, view=0, views=1):
     R = n * vol
     if Ud.shape != (16, 2, 2, Cout, C1 + C2) or not Ud.is_contiguous():
         raise ValueError("depth-nest weight %s does not match Cout=%d Cin=%d" % (tuple(Ud.shape), Cout, C1 + C2))
-    if Mm is None:
-        Mm = torch.empty(16, R, Cout, dtype=torch.float32, device=V1.device)
-    if not (Mm.is_contiguous() and Mm.dtype == torch.float32 and Mm.numel() >= 16 * R * Cout):
-        raise ValueError("point-product buffer %s %s%s cannot hold 16 x %d x %d float32" % (
-            tuple(Mm.shape), Mm.dtype, "" if Mm.is_contiguous() else " (not contiguous)", R, Cout))
-    if Mm.shape != (16, R, Cout):
-        Mm = Mm.as_strided((16, R, Cout), (R * Cout, Cout, 1))
-    p1 = ctypes.c_void_p(V1.data_ptr() + 4 * view * vol * C1)
-    _lib.check(_lib.lib().forge_wino_gemm_dn(p1, C1, C1, views * vol if views > 1 else 0, V1.shape[1] * C1, _lib.ptr(V2), C2, C2, 0,
-                                             0 if V2 is None else V2.shape[1] * C2, _lib.ptr(Ud), _lib.ptr(Mm), n, D, Ht, Wt, Cout, 3,
-                                             _lib.current_stream()), "forge_wino_gemm_dn")
-    return Mm
+    Mm = _point_products(Mm, 16, R, Cout, V1.device)
+    return _wino_gemm_call("forge_wino_gemm_dn", V1, C1, V2, C2, Ud, Mm, n, D, Ht, Wt, Cout, 3, view, views, vol)
 
 
 def wino_half_applies(R, Cout, Cin):
@@ -664,28 +665,14 @@ def wino_gemm(V1, C1, V2, C2, U, Mm, n, D, Ht, Wt, Cout, view=0, views=1, half=N
     R = n * vol
     if half is None:
         half = wino_half_applies(R, Cout, C1 + C2)
-    P = 8 if half else 16
     kd = U.shape[1]
     if U.shape != (16, kd, Cout, C1 + C2) or kd not in (1, 3):
         raise ValueError("transformed weight %s does not match Cout=%d Cin=%d" % (tuple(U.shape), Cout, C1 + C2))
-    if Mm is None:
-        Mm = torch.empty(P, R, Cout, dtype=torch.float32, device=V1.device)
-    if not (Mm.is_contiguous() and Mm.dtype == torch.float32 and Mm.numel() >= P * R * Cout):
-        raise ValueError("point-product buffer %s %s%s cannot hold %d x %d x %d float32" % (
-            tuple(Mm.shape), Mm.dtype, "" if Mm.is_contiguous() else " (not contiguous)", P, R, Cout))
-    if Mm.shape != (P, R, Cout):
-        Mm = Mm.as_strided((P, R, Cout), (R * Cout, Cout, 1))
-    p1 = ctypes.c_void_p(V1.data_ptr() + 4 * view * vol * C1)
+    Mm = _point_products(Mm, 8 if half else 16, R, Cout, V1.device)
     if half:
-        _lib.check(_lib.lib().forge_wino_gemm_half(p1, C1, C1, views * vol if views > 1 else 0, V1.shape[1] * C1, _lib.ptr(V2), C2, C2, 0,
-                                                   0 if V2 is None else V2.shape[1] * C2, _lib.ptr(U), _lib.ptr(Mm), n, D, Ht, Wt, Cout, kd,
-                                                   _lib.current_stream()), "forge_wino_gemm_half")
-        return Mm
-    _lib.check(_lib.lib().forge_wino_gemm(p1, C1, C1, views * vol if views > 1 else 0, V1.shape[1] * C1, _lib.ptr(V2), C2, C2, 0,
-                                          0 if V2 is None else V2.shape[1] * C2, _lib.ptr(U), _lib.ptr(Mm), n, D, Ht, Wt, Cout, kd,
-                                          ord(wino_gemm_tile(R, Cout, C1 + C2)), _lib.current_stream()),
-               "forge_wino_gemm")
-    return Mm
+        return _wino_gemm_call("forge_wino_gemm_half", V1, C1, V2, C2, U, Mm, n, D, Ht, Wt, Cout, kd, view, views, vol)
+    return _wino_gemm_call("forge_wino_gemm", V1, C1, V2, C2, U, Mm, n, D, Ht, Wt, Cout, kd, view, views, vol,
+                           ord(wino_gemm_tile(R, Cout, C1 + C2)))
 
 
 def wino_gemm_tile(R, Cout, Cin):

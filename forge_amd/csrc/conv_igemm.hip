@@ -73,8 +73,8 @@ struct ConvArgs {
 };
 
 constexpr int BK = 32, NTHREADS = 512;
-constexpr int RS_STAGES = 2;               // LDS stages of the four-point form (RS = 1): the launcher's dynamic LDS is RS_STAGES x 24 KB, and three such
-                                           // workgroups are resident per CU (80 VGPRs = 6 waves per SIMD; tests/test_conv_igemm_resources.py holds both)
+constexpr int RS_STAGES = 2;               // LDS stages of the point-GEMM forms (RS): the four-point form's dynamic LDS is RS_STAGES x 24 KB, and three such
+                                           // workgroups are resident per CU (at most 80 VGPRs = 6 waves per SIMD; tests/test_conv_igemm_resources.py holds both)
 
 #ifdef FORGE_CONV_TIMING   // debug build (tools/debug/conv_timing.py): per-workgroup clock stamps at entry / first barrier / loop end / exit
 __device__ long long g_conv_stamp[8192 * 4];
@@ -94,6 +94,100 @@ __device__ __forceinline__ int lds_off(int row, int chunk) {   // float offset o
     return row * BK + ((chunk ^ ((row >> 1) & 7)) << 2);
 }
 
+struct LanePos { int wm, wn, half, l31; };   // wave (wm, wn) of the WM x WN arrangement; half = lane >> 5, l31 = lane & 31
+
+struct ReadA {                                 // the A fragment as staged: one ds_read_b128
+    __device__ __forceinline__ float4 operator()(const float* p) const { return *reinterpret_cast<const float4*>(p); }
+};
+
+// One K-step = 4 MFMA groups of 8 k-values; read_a(address in the stage's first A image) gives the lane's A fragment. (A/B in round 1: issuing the
+// next tile's global loads after group 0 and its LDS writes after group 2, pinned with sched_barrier, changed nothing: 127.3 vs 126.3 TF on the
+// ConvGRU gates shape.)
+template <int BN, int WN, int MT, int NT, class Read>
+__device__ __forceinline__ void mfma_group(const LanePos& lp, f32x16 (&acc)[MT][NT], const float* sa, const float* sb, int g, Read&& read_a) {
+    float4 fa[MT], fb[NT];
+#pragma unroll
+    for (int i = 0; i < MT; ++i) fa[i] = read_a(sa + lds_off(lp.wm * (32 * MT) + i * 32 + lp.l31, 2 * g + lp.half));
+#pragma unroll
+    for (int j = 0; j < NT; ++j) fb[j] = *reinterpret_cast<const float4*>(sb + lds_off(lp.wn * (BN / WN) + j * 32 + lp.l31, 2 * g + lp.half));
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].x, fb[j].x, acc[i][j], 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].y, fb[j].y, acc[i][j], 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].z, fb[j].z, acc[i][j], 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].w, fb[j].w, acc[i][j], 0, 0, 0);
+}
+
+// The K loop of the point-GEMM forms (RS): nsteps K-steps into the accumulator set acc over the ring of RS_STAGES LDS stages of STAGE floats (B image
+// at B_AT), from stage buf on. issue() moves the form's issue cursor: the NEXT step's loads fly under this step's MFMAs, into the stage read in step
+// s - 1 (every wave is past that barrier). The step closes when that stage is in LDS, this wave's part and everybody else's; the forms' plane stores
+// are in flight too, hence lds_dma_wait_barrier (common.h).
+template <int STAGE, int B_AT, int BN, int WN, class Issue, class Read>
+__device__ __forceinline__ void k_loop(const LanePos& lp, f32x16 (&acc)[1][1], const float* smem, int& buf, int nsteps, Issue&& issue, Read&& read_a) {
+    for (int s = 0; s < nsteps; ++s) {
+        const float* sa = smem + buf * STAGE;
+        const float* sb = sa + B_AT;
+        issue();
+#pragma unroll
+        for (int g = 0; g < 4; ++g) mfma_group<BN, WN, 1, 1>(lp, acc, sa, sb, g, read_a);
+        lds_dma_wait_barrier();
+        buf = buf + 1 == RS_STAGES ? 0 : buf + 1;
+    }
+}
+
+// Plane store of the point-GEMM forms: the 16 values val(r) of this lane (C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) +
+// 4 (lane >> 5)) to the tile's rows of `plane`, row_off bytes further down (identity rows, no bias). Stores go through a buffer descriptor of the
+// plane: rows beyond M lie beyond its num_records and columns beyond Cout are sent to OOB - dropped by the hardware, no branch (plane < 2 GiB:
+// checked on the host).
+struct PlaneStore {
+    unsigned ldo4, ovb; int bytes;              // bytes per output row; byte offset of this lane's first element; bytes of a plane
+    __device__ __forceinline__ PlaneStore(const ConvArgs& a, long long M, long long m0, int col0, const LanePos& lp) {
+        const int ocol = col0 + lp.l31;
+        ldo4 = (unsigned)a.ldo * 4u;
+        ovb = ocol < a.Cout ? (unsigned)(((int)m0 + lp.wm * 32 + 4 * lp.half) * a.ldo + ocol) * 4u : OOB;
+        bytes = (int)(M * a.ldo * 4);
+    }
+    template <class Val>
+    __device__ __forceinline__ void operator()(float* plane, unsigned row_off, Val&& val) const {
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(plane, 0, bytes, 0x00020000);
+        unsigned vb = ovb + row_off;
+        asm volatile("" : "+v"(vb));                             // keeps the 16 row offsets from being computed ahead of the K loops and held in registers
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val(r)), rs, (int)(vb + (unsigned)((r & 3) + 8 * (r >> 2)) * ldo4), 0, 0);
+    }
+};
+
+// Output side of an F(2, 3) over four K loops, A^T = [1 1 1 0; 0 1 -1 -1]: s0 = (m0 + m1) + m2, s1 = (m1 - m2) - m3, wino_output_kernel's own operations
+// in its own order (RS = 1: the row stage over the four points; RS = 2: the two planes of the depth nest). Called after K loop q = 0..3, which ran into
+// set q (loop 3: set 0); store(i, val) stores output i. s0 is complete after loop 2: its stores fly under loop 3 (they count in vmcnt like the loads:
+// the first wait of that loop covers them, a whole K-step later) and loop 3 accumulates into the freed set - three sets live instead of four.
+template <class Store>
+__device__ __forceinline__ void f23_step(int q, f32x16 (&acc)[3][1][1], Store&& store) {
+    if (q == 1) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[0][0][0][r] = acc[0][0][0][r] + acc[1][0][0][r];              // t = m0 + m1
+    } else if (q == 2) {
+        store(0, [&](int r) { return acc[0][0][0][r] + acc[2][0][0][r]; });                            // s0 = t + m2
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { acc[1][0][0][r] = acc[1][0][0][r] - acc[2][0][0][r]; acc[0][0][0][r] = 0.f; }   // u = m1 - m2
+    } else if (q == 3) {
+        FORGE_STAMP(2);
+        store(1, [&](int r) { return acc[1][0][0][r] - acc[0][0][0][r]; });                            // s1 = u - m3
+        FORGE_STAMP(3);
+    }
+}
+
 // Operand staging is LDS-DMA: `buffer_load_dwordx4 ... offen lds` (M0 = the wave's LDS byte address; lane L lands at + 16 L, out-of-range
 // lanes write zeros) puts a K-step's A / B rows straight into the other LDS stage - no staging VGPRs, no ds_write. The loads are inline
 // assembly because the compiler's own waitcnt insertion would drain them (vmcnt(0)) BEFORE the step's MFMAs (round 2's builtin-based variant
@@ -104,28 +198,8 @@ __device__ __forceinline__ int lds_off(int row, int chunk) {   // float offset o
 // single-point tiles the extra LDS costs a resident workgroup per CU; on the four-point form (below), where it does not, a three-stage ring with a
 // counted vmcnt was still 1-3 % slower than two stages (profiles/TUNING_LOG.md, round 7).
 //
-// RS = 1 (forge_wino_gemm_half, 64x128 tile): one workgroup runs the FOUR Winograd points i = 0..3 of a point column j on its tile, one K loop after
-// the other (the first stage of the next point is loaded under the last step of the current one), and applies the ROW stage of the inverse
-// transform A^T M A in registers - the same lane holds element (row, col) of all four points: s0 = (m0 + m1) + m2, s1 = (m1 - m2) - m3,
-// wino_output_kernel's own operations in its own order - and stores 2 planes instead of 4: Mm8 [2][4][R][Cout]. The point products then cross HBM
-// as 2x instead of 4x the output tensor, written here and read by the inverse transform. s0 is stored as soon as point 2 is done, under point 3's
-// K loop, so three accumulator sets are live, not four: 80 VGPRs = 6 waves per SIMD = THREE resident workgroups per CU (3 x 48 KB of LDS;
-// with four sets and 96 VGPRs it was two - 512 slots chip-wide, not the 640 an earlier note assumed).
-//
-// RS = 2 (forge_wino_gemm_dn, 64x128 tile): the depth nest. A Winograd F(2, 3) over the three DEPTH taps on top of the 2-D points: a workgroup owns 64
-// tile rows of an EVEN plane z for one point p and runs four K loops k = 0..3 of K = Cin each (instead of 2 planes x 3 taps = six) on the operands
-//   k = 0: V[z-1] - V[z+1]   k = 1: V[z] + V[z+1]   k = 2: V[z+1] - V[z]   k = 3: V[z] - V[z+2]      (the rows of B^T; planes outside the grid are zero)
-// against U'[p][k] (forge_wino_weights_dn). Both planes of a position are staged as two A images by LDS-DMA (an out-of-grid plane at the out-of-range
-// offset) and combined with one fp32 operation per element on the ds_read_b128 results, in front of the MFMAs. The output side is A^T = [1 1 1 0; 0 1 -1 -1]
-// over the four positions - the four-point form's own skeleton: y_z = (m0 + m1) + m2 stored under k = 3's loop, y_{z+1} = (m1 - m2) - m3 - and the result
-// is the ordinary 16-plane Mm [16][R][Cout] of forge_wino_gemm. 2 x 32 KB of LDS: two workgroups per CU (resources: the remark above forge_wino_gemm_dn).
-//
-// RS = 3 (forge_wino_gemm_dn4, 64x128 tile): the depth nest with F(4, 3). A workgroup owns 64 tile rows of a GROUP of four planes 4g .. 4g + 3 for one point and
-// runs six K loops of K = Cin (1.5 per plane) on the depth-combined operand planes V6[.][g][k] that forge_wino_input_dn4 wrote - ONE A image per K-step, the
-// inner loop of RS = 1, no VALU in front of the MFMAs - against U''[p][k] (forge_wino_weights_dn4). The output side is A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0;
-// 0 1 1 4 4 0; 0 1 -1 8 -8 1] over the six positions, all scalings powers of two: loops 1, 2 -> s = m1 + m2, d = m1 - m2; loops 3, 4 -> S = m3 + m4,
-// D = m3 - m4; y1 = d + 2 D and y2 = s + 4 S are stored under the next loop; loop 0 accumulates onto s + S (y0, stored under loop 5), loop 5 onto d + 8 D (y3).
-// Four accumulator sets live; 2 x 24 KB of LDS (resources: the remark above forge_wino_gemm_dn4).
+// RS = 0: the convolution. RS = 1 / 2 / 3: the three Winograd point-GEMM forms on the 64x128 tile, each described at its branch below; they share the
+// tile origin, the staging geometry, prep_tap and issue_step with the convolution, and k_loop, PlaneStore and f23_step (above) among themselves.
 template <int BM, int BN, int NW, int MT = 1, int RS = 0>
 __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
     constexpr int NP = RS ? 4 : 1;                   // points (RS = 2: depth positions) per workgroup
@@ -157,24 +231,19 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
     const int pz = a.nphase > 1 ? (a.nphase == 8 ? (phase >> 2) & 1 : 0) : a.pz;
     const int py = a.nphase > 1 ? (phase >> 1) & 1 : a.py, px = a.nphase > 1 ? phase & 1 : a.px;
     const int t_lo = phase * a.tpp;
+    constexpr int PLANES = RS == 2 ? 2 : RS == 3 ? 4 : 1;          // depth nests: the tiles of every PLANES-th plane only (plane pairs / groups of four)
     long long pb = 0;                                               // batched problems: workgroups [p tiles, (p+1) tiles) do problem p, so that (with
     if (a.nbat > 1) {                                               // xcd_remap's contiguous chunks) an XCD's L2 holds the weights of its own problems only
-        unsigned tiles = (unsigned)((M + BM - 1) / BM) * (unsigned)ntile_n;
-        if constexpr (RS == 2) tiles = (unsigned)(M / (2 * BM)) * (unsigned)ntile_n;   // depth nest: the tiles of the even planes only
-        if constexpr (RS == 3) tiles = (unsigned)(M / (4 * BM)) * (unsigned)ntile_n;   // F(4, 3) depth nest: the tiles of every fourth plane
+        const unsigned tiles = (PLANES > 1 ? (unsigned)(M / (PLANES * BM)) : (unsigned)((M + BM - 1) / BM)) * (unsigned)ntile_n;
         pb = bid / tiles;
         bid -= (unsigned)pb * tiles;
     }
     float* const outp = a.out + pb * a.pto;
     const long long m0 = [&]() -> long long {
-        if constexpr (RS == 2) {                                    // tile ti of the even planes: plane pair ti / (HW / BM) = planes 2 pair, 2 pair + 1 of the
-            const unsigned tpl = (unsigned)(a.H * a.W) / BM;       // flat (n, z) axis (D even: a pair never straddles batch elements)
-            const unsigned ti = bid / ntile_n, pair = ti / tpl;
-            return (long long)(2u * pair * tpl + (ti - pair * tpl)) * BM;
-        } else if constexpr (RS == 3) {                             // tile ti of the first planes of the groups of four (D % 4 == 0: a group lies in one element)
-            const unsigned tpl = (unsigned)(a.H * a.W) / BM;
+        if constexpr (PLANES > 1) {                                 // tile ti of every PLANES-th plane: group ti / (HW / BM) = planes PLANES grp .. of the flat
+            const unsigned tpl = (unsigned)(a.H * a.W) / BM;       // (n, z) axis (D % PLANES == 0: a group never straddles batch elements)
             const unsigned ti = bid / ntile_n, grp = ti / tpl;
-            return (long long)(4u * grp * tpl + (ti - grp * tpl)) * BM;
+            return (long long)((unsigned)PLANES * grp * tpl + (ti - grp * tpl)) * BM;
         } else {
             return (long long)(bid / ntile_n) * BM;
         }
@@ -326,31 +395,9 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
         __syncthreads();
         FORGE_STAMP(1);
     }
-    // One K-step = 4 MFMA groups of 8 k-values. (A/B in round 1: issuing the next tile's global loads after group 0 and its LDS
-    // writes after group 2, pinned with sched_barrier, changed nothing: 127.3 vs 126.3 TF on the ConvGRU gates shape.)
-    auto mfma_group = [&](f32x16 (&acc)[MT][NT], const float* sa, const float* sb, int g) {
-        float4 fa[MT], fb[NT];
-#pragma unroll
-        for (int i = 0; i < MT; ++i) fa[i] = *reinterpret_cast<const float4*>(sa + lds_off(wm * (32 * MT) + i * 32 + l31, 2 * g + half));
-#pragma unroll
-        for (int j = 0; j < NT; ++j) fb[j] = *reinterpret_cast<const float4*>(sb + lds_off(wn * (BN / WN) + j * 32 + l31, 2 * g + half));
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].x, fb[j].x, acc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].y, fb[j].y, acc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].z, fb[j].z, acc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].w, fb[j].w, acc[i][j], 0, 0, 0);
-    };
+    const LanePos lp{wm, wn, half, l31};
+    [[maybe_unused]] const unsigned HW = (unsigned)(a.H * a.W);   // the forms: rows of a plane; first output column of this wave
+    [[maybe_unused]] const int col0 = n0 + wn * (BN / WN);
     if constexpr (!RS) {
     int buf = 0;
 #pragma unroll
@@ -363,21 +410,27 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
                 issue_step(t, kc, buf ^ 1);                       // in flight under this step's MFMAs
             }
 #pragma unroll
-            for (int g = 0; g < 4; ++g) mfma_group(accs[q], sa, sb, g);
+            for (int g = 0; g < 4; ++g) mfma_group<BN, WN, MT, NT>(lp, accs[q], sa, sb, g, ReadA{});
             lds_dma_wait();                                       // this wave's part of the next step is in LDS ...
             __syncthreads();                                      // ... and so is everybody else's
             buf ^= 1;
         }
     }
     } else if constexpr (RS == 1) {
+        // RS = 1 (forge_wino_gemm_half, 64x128 tile): one workgroup runs the FOUR Winograd points i = 0..3 of a point column j on its tile, one K loop after
+        // the other (the first stage of the next point is loaded under the last step of the current one), and applies the ROW stage of the inverse
+        // transform A^T M A in registers - the same lane holds element (row, col) of all four points: s0 = (m0 + m1) + m2, s1 = (m1 - m2) - m3,
+        // wino_output_kernel's own operations in its own order - and stores 2 planes instead of 4: Mm8 [2][4][R][Cout]. The point products then cross HBM
+        // as 2x instead of 4x the output tensor, written here and read by the inverse transform. s0 is stored as soon as point 2 is done, under point 3's
+        // K loop, so three accumulator sets are live, not four: at most 80 VGPRs = 6 waves per SIMD = THREE resident workgroups per CU (3 x 48 KB of LDS;
+        // with four sets and 96 VGPRs it was two - 512 slots chip-wide, not the 640 an earlier note assumed).
         // Four points, one K loop after the other. An issue cursor (point iq, tap it, chunk ikc) runs one step ahead of the MFMAs and walks straight
         // over the point switches (descriptors re-made there): the next point's first stage flies under the current point's last step.
-        constexpr int STAGE = A_FLOATS + B_FLOATS;
         // Depth taps that are zero for the WHOLE tile are not walked: when all valid rows of the tile lie in one depth plane z and z + dz is
         // outside the grid, that tap's Cin / 32 K-steps multiply DMA'd zeros. Workgroup-uniform. Bitwise neutral for finite weights: an
         // accumulator that starts at +0 never becomes -0, and x + (+-0) = x. Only leading / trailing taps are trimmed (the K order stays).
+        static_assert(NT == 1, "the row stage is written for one 32-column MFMA tile per wave");
         int t_first = 0, t_end = a.tpp;
-        const unsigned HW = (unsigned)(a.H * a.W);
         const long long mlast = (m0 + BM < M ? m0 + BM : M) - 1;
         const unsigned p0 = (unsigned)m0 / HW, p1 = (unsigned)mlast / HW;
         if (p0 == p1) {
@@ -409,56 +462,25 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
         issue_next();
         lds_dma_wait_barrier();
         FORGE_STAMP(1);
-        // Row stage of A^T M A over the four points, two planes stored (identity rows, no bias): s0 = (m0 + m1) + m2, s1 = (m1 - m2) - m3,
-        // wino_output_kernel's own operations in its own order. Stores go through a buffer descriptor of the plane: rows beyond M lie beyond
-        // its num_records and columns beyond Cout are sent to OOB - dropped by the hardware, no branch (plane < 2 GiB: checked on the host).
-        const int ocol = n0 + wn * (BN / WN) + l31;
-        const unsigned ldo4 = (unsigned)a.ldo * 4u;
-        const unsigned ovb = ocol < a.Cout ? (unsigned)(((int)m0 + wm * 32 + 4 * half) * a.ldo + ocol) * 4u : OOB;
-        auto store_plane = [&](int plane, auto&& val) {
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(a.out + (pb + 4 * plane) * a.pto, 0, (int)(M * a.ldo * 4), 0x00020000);
-            unsigned vb = ovb;
-            asm volatile("" : "+v"(vb));                             // keeps the 16 row offsets from being computed ahead of the K loops and held in registers
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val(r)), rs, (int)(vb + (unsigned)((r & 3) + 8 * (r >> 2)) * ldo4), 0, 0);
-        };
-        static_assert(NT == 1, "the row stage is written for one 32-column MFMA tile per wave");
+        const PlaneStore store_plane(a, M, m0, col0, lp);
         int buf = 0;
+        auto store = [&](int i, auto&& val) { store_plane(a.out + (pb + 4 * i) * a.pto, 0u, val); };       // plane i of point column pb
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
-            f32x16 (&aq)[MT][NT] = accs[q == 3 ? 0 : q];
-            for (int s = 0; s < nst; ++s) {
-                const float* sa = smem + buf * STAGE;
-                const float* sb = sa + A_FLOATS;
-                issue_next();                                      // into the stage read in step s - 1: every wave is past that barrier
-#pragma unroll
-                for (int g = 0; g < 4; ++g) mfma_group(aq, sa, sb, g);
-                lds_dma_wait_barrier();                            // the next step's stage is in LDS, this wave's part and everybody else's
-                buf = buf + 1 == RS_STAGES ? 0 : buf + 1;
-            }
-            // s0 is complete after point 2: its stores fly under point 3's K loop (they count in vmcnt like the loads: the first wait of that loop
-            // covers them, a whole K-step later) and point 3 accumulates into the freed set - three sets live instead of four.
-            if (q == 1) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) accs[0][0][0][r] = accs[0][0][0][r] + accs[1][0][0][r];              // t = m0 + m1
-            } else if (q == 2) {
-                store_plane(0, [&](int r) { return accs[0][0][0][r] + accs[2][0][0][r]; });                       // s0 = t + m2
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { accs[1][0][0][r] = accs[1][0][0][r] - accs[2][0][0][r]; accs[0][0][0][r] = 0.f; }   // u = m1 - m2
-            }
+            k_loop<A_FLOATS + B_FLOATS, A_FLOATS, BN, WN>(lp, accs[q == 3 ? 0 : q], smem, buf, nst, issue_next, ReadA{});
+            f23_step(q, accs, store);
         }
-        FORGE_STAMP(2);
-        store_plane(1, [&](int r) { return accs[1][0][0][r] - accs[0][0][0][r]; });                               // s1 = u - m3
-        FORGE_STAMP(3);
-        return;
-    }
-
-    if constexpr (RS == 2) {
-        // Depth nest (see above). All 64 rows of the tile lie in plane (n, z), z even; the host has checked H W % 64 == 0, D even, M H W ldo 4 < 2^31.
+    } else if constexpr (RS == 2) {
+        // RS = 2 (forge_wino_gemm_dn, 64x128 tile): the depth nest. A Winograd F(2, 3) over the three DEPTH taps on top of the 2-D points: a workgroup owns 64
+        // tile rows of an EVEN plane z for one point p and runs four K loops k = 0..3 of K = Cin each (instead of 2 planes x 3 taps = six) on the operands
+        //   k = 0: V[z-1] - V[z+1]   k = 1: V[z] + V[z+1]   k = 2: V[z+1] - V[z]   k = 3: V[z] - V[z+2]      (the rows of B^T; planes outside the grid are zero)
+        // against U'[p][k] (forge_wino_weights_dn). Both planes of a position are staged as two A images by LDS-DMA (an out-of-grid plane at the out-of-range
+        // offset) and combined with one fp32 operation per element on the ds_read_b128 results, in front of the MFMAs. The output side is A^T = [1 1 1 0; 0 1 -1 -1]
+        // over the four positions - the four-point form's own skeleton: y_z = (m0 + m1) + m2 stored under k = 3's loop, y_{z+1} = (m1 - m2) - m3 - and the result
+        // is the ordinary 16-plane Mm [16][R][Cout] of forge_wino_gemm. 2 x 32 KB of LDS: two workgroups per CU (resources: the remark above forge_wino_gemm_dn).
+        // All 64 rows of the tile lie in plane (n, z), z even; the host has checked H W % 64 == 0, D even, M H W ldo 4 < 2^31.
         constexpr int STAGE = 2 * A_FLOATS + B_FLOATS;             // [A image of plane a_k][A image of plane b_k][B]
-        static_assert(ACH == 1 && NT == 1 && MT == 1, "the depth nest is written for the 64 x 128 tile of 8 waves");
-        const unsigned HW = (unsigned)(a.H * a.W);
+        static_assert(ACH == 1 && NT == 1, "the depth nest is written for the 64 x 128 tile of 8 waves");
         const int z = (int)(((unsigned)m0 / HW) % (unsigned)a.D);  // workgroup-uniform
         const int sp0 = (az[0] * a.Hi + ay[0]) * a.Wi + ax[0];
         const unsigned base1 = (unsigned)(((an[0] * (int)a.bs1r + sp0) * a.ld1 + asrc[0]) * 4), base2 = (unsigned)(((an[0] * (int)a.bs2r + sp0) * a.ld2 + asrc[0]) * 4);
@@ -485,7 +507,7 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
             const unsigned wbase = (unsigned)((ik * a.Cout * Cin + c0) * 4);
 #pragma unroll
             for (int j = 0; j < BCH; ++j) lds_dma16(ww, boff[j] + wbase, stage + (unsigned)(2 * A_FLOATS * 4 + j * NW * 1024));
-            ibuf ^= 1;
+            ibuf = ibuf + 1 == RS_STAGES ? 0 : ibuf + 1;
             if (++ikc == kchunks) {
                 ikc = 0;
                 if (++ik < NP) prep_pos(ik);
@@ -495,60 +517,29 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
         issue_next();
         lds_dma_wait_barrier();
         FORGE_STAMP(1);
-        const int ocol = n0 + wn * (BN / WN) + l31;
-        const unsigned ldo4 = (unsigned)a.ldo * 4u;
-        const unsigned ovb = ocol < a.Cout ? (unsigned)(((int)m0 + wm * 32 + 4 * half) * a.ldo + ocol) * 4u : OOB;
-        auto store_plane = [&](int plane, auto&& val) {            // the tile's rows of plane z + `plane`: the first plane's plus H W (buffer-descriptor stores, as RS = 1)
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(outp, 0, (int)(M * a.ldo * 4), 0x00020000);
-            unsigned vb = ovb + (unsigned)plane * HW * ldo4;
-            asm volatile("" : "+v"(vb));
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val(r)), rs, (int)(vb + (unsigned)((r & 3) + 8 * (r >> 2)) * ldo4), 0, 0);
-        };
+        const PlaneStore store_plane(a, M, m0, col0, lp);
         int buf = 0;
+        auto store = [&](int i, auto&& val) { store_plane(outp, (unsigned)i * HW * store_plane.ldo4, val); };   // the tile's rows of plane z + i: the first plane's plus H W
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
-            f32x16& aq = accs[q == 3 ? 0 : q][0][0];
             const float sgn = q == 1 ? 1.f : -1.f;                 // a_k + b_k at k = 1, a_k - b_k elsewhere: fmaf(+-1, b, a) is that one rounded add / sub
-            for (int s = 0; s < kchunks; ++s) {
-                const float* sa = smem + buf * STAGE;
-                const float* sb = sa + 2 * A_FLOATS;
-                issue_next();                                      // into the stage read in step s - 1: every wave is past that barrier
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int ao = lds_off(wm * 32 + l31, 2 * g + half);
-                    const float4 pa = *reinterpret_cast<const float4*>(sa + ao), pq = *reinterpret_cast<const float4*>(sa + A_FLOATS + ao);
-                    const float4 fb = *reinterpret_cast<const float4*>(sb + lds_off(wn * (BN / WN) + l31, 2 * g + half));
-                    aq = __builtin_amdgcn_mfma_f32_32x32x2f32(fmaf(sgn, pq.x, pa.x), fb.x, aq, 0, 0, 0);
-                    aq = __builtin_amdgcn_mfma_f32_32x32x2f32(fmaf(sgn, pq.y, pa.y), fb.y, aq, 0, 0, 0);
-                    aq = __builtin_amdgcn_mfma_f32_32x32x2f32(fmaf(sgn, pq.z, pa.z), fb.z, aq, 0, 0, 0);
-                    aq = __builtin_amdgcn_mfma_f32_32x32x2f32(fmaf(sgn, pq.w, pa.w), fb.w, aq, 0, 0, 0);
-                }
-                lds_dma_wait_barrier();
-                buf ^= 1;
-            }
-            if (q == 1) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) accs[0][0][0][r] = accs[0][0][0][r] + accs[1][0][0][r];              // t = m0 + m1
-            } else if (q == 2) {
-                store_plane(0, [&](int r) { return accs[0][0][0][r] + accs[2][0][0][r]; });                       // y_z = t + m2, in flight under k = 3's loop
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { accs[1][0][0][r] = accs[1][0][0][r] - accs[2][0][0][r]; accs[0][0][0][r] = 0.f; }   // u = m1 - m2
-            }
+            k_loop<STAGE, 2 * A_FLOATS, BN, WN>(lp, accs[q == 3 ? 0 : q], smem, buf, kchunks, issue_next, [sgn](const float* p) {
+                const float4 pa = *reinterpret_cast<const float4*>(p), pq = *reinterpret_cast<const float4*>(p + A_FLOATS);
+                return make_float4(fmaf(sgn, pq.x, pa.x), fmaf(sgn, pq.y, pa.y), fmaf(sgn, pq.z, pa.z), fmaf(sgn, pq.w, pa.w));
+            });
+            f23_step(q, accs, store);
         }
-        FORGE_STAMP(2);
-        store_plane(1, [&](int r) { return accs[1][0][0][r] - accs[0][0][0][r]; });                               // y_{z+1} = u - m3
-        FORGE_STAMP(3);
-        return;
-    }
-
-    if constexpr (RS == 3) {
-        // F(4, 3) depth nest (see above). The tile's 64 rows lie in plane (n, 4 g) of the output; the host has checked H W % 64 == 0, D % 4 == 0 and
-        // that operands and an output plane stay below 2 GiB. The operand of position k is plane 6 g + k of the element's V6 block: one A image per K-step.
-        constexpr int STAGE = A_FLOATS + B_FLOATS, NPOS = 6;
-        static_assert(ACH == 1 && NT == 1 && MT == 1, "the depth nest is written for the 64 x 128 tile of 8 waves");
-        const unsigned HW = (unsigned)(a.H * a.W);
+    } else {
+        // RS = 3 (forge_wino_gemm_dn4, 64x128 tile): the depth nest with F(4, 3). A workgroup owns 64 tile rows of a GROUP of four planes 4g .. 4g + 3 for one point and
+        // runs six K loops of K = Cin (1.5 per plane) on the depth-combined operand planes V6[.][g][k] that forge_wino_input_dn4 wrote - ONE A image per K-step, the
+        // inner loop of RS = 1, no VALU in front of the MFMAs - against U''[p][k] (forge_wino_weights_dn4). The output side is A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0;
+        // 0 1 1 4 4 0; 0 1 -1 8 -8 1] over the six positions, all scalings powers of two: loops 1, 2 -> s = m1 + m2, d = m1 - m2; loops 3, 4 -> S = m3 + m4,
+        // D = m3 - m4; y1 = d + 2 D and y2 = s + 4 S are stored under the next loop; loop 0 accumulates onto s + S (y0, stored under loop 5), loop 5 onto d + 8 D (y3).
+        // Four accumulator sets live; 2 x 24 KB of LDS (resources: the remark above forge_wino_gemm_dn4).
+        // The tile's 64 rows lie in plane (n, 4 g) of the output; the host has checked H W % 64 == 0, D % 4 == 0 and that operands and an output plane
+        // stay below 2 GiB. The operand of position k is plane 6 g + k of the element's V6 block: one A image per K-step.
+        constexpr int NPOS = 6;
+        static_assert(ACH == 1 && NT == 1, "the depth nest is written for the 64 x 128 tile of 8 waves");
         const unsigned plane0 = (unsigned)m0 / HW;                 // n D + 4 g, workgroup-uniform
         const unsigned nb = plane0 / (unsigned)a.D, g4 = plane0 - nb * (unsigned)a.D;      // g4 = 4 g
         const unsigned rin = (unsigned)m0 - plane0 * HW + (unsigned)ar[0];                 // this thread's row inside the plane
@@ -563,7 +554,7 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
         auto issue_next = [&]() {                                  // the issue cursor runs one step ahead of the MFMAs, straight over the position switches
             if (iq >= NPOS) return;
             issue_step(ipos, ikc, ibuf);
-            ibuf ^= 1;
+            ibuf = ibuf + 1 == RS_STAGES ? 0 : ibuf + 1;
             if (++ikc == kchunks) {
                 ikc = 0;
                 if (++iq < NPOS) {
@@ -575,30 +566,12 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
         issue_next();
         lds_dma_wait_barrier();
         FORGE_STAMP(1);
-        const int ocol = n0 + wn * (BN / WN) + l31;
-        const unsigned ldo4 = (unsigned)a.ldo * 4u;
-        const unsigned ovb = ocol < a.Cout ? (unsigned)(((int)m0 + wm * 32 + 4 * half) * a.ldo + ocol) * 4u : OOB;
-        auto store_plane = [&](int plane, const f32x16& val) {     // the tile's rows of plane 4 g + `plane` (buffer-descriptor stores, as RS = 1 / 2)
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(outp, 0, (int)(M * a.ldo * 4), 0x00020000);
-            unsigned vb = ovb + (unsigned)plane * HW * ldo4;
-            asm volatile("" : "+v"(vb));
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val[r]), rs, (int)(vb + (unsigned)((r & 3) + 8 * (r >> 2)) * ldo4), 0, 0);
-        };
+        const PlaneStore store_plane(a, M, m0, col0, lp);
+        auto store = [&](int i, const f32x16& y) { store_plane(outp, (unsigned)i * HW * store_plane.ldo4, [&](int r) { return y[r]; }); };   // the tile's rows of plane 4 g + i
         int buf = 0;
 #pragma unroll
-        for (int q = 0; q < NPOS; ++q) {
-            f32x16 (&aq)[MT][NT] = accs[q < 4 ? q : q - 4];         // m1, m2, m3, m4 into sets 0..3; position 0 onto set 0 (s + S), position 5 onto set 1 (d + 8 D)
-            for (int s = 0; s < kchunks; ++s) {
-                const float* sa = smem + buf * STAGE;
-                const float* sb = sa + A_FLOATS;
-                issue_next();                                      // into the stage read in step s - 1: every wave is past that barrier
-#pragma unroll
-                for (int g = 0; g < 4; ++g) mfma_group(aq, sa, sb, g);
-                lds_dma_wait_barrier();
-                buf ^= 1;
-            }
+        for (int q = 0; q < NPOS; ++q) {                           // m1, m2, m3, m4 into sets 0..3; position 0 onto set 0 (s + S), position 5 onto set 1 (d + 8 D)
+            k_loop<A_FLOATS + B_FLOATS, A_FLOATS, BN, WN>(lp, accs[q < 4 ? q : q - 4], smem, buf, kchunks, issue_next, ReadA{});
             if (q == 1) {                                          // s = m1 + m2, d = m1 - m2
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
@@ -614,17 +587,17 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
                     accs[0][0][0][r] = accs[0][0][0][r] + S;               // s + S: position 0 accumulates onto it
                     accs[1][0][0][r] = fmaf(8.f, Dl, accs[1][0][0][r]);    // d + 8 D: position 5 accumulates onto it
                 }
-                store_plane(1, accs[3][0][0]);
-                store_plane(2, accs[2][0][0]);
+                store(1, accs[3][0][0]);
+                store(2, accs[2][0][0]);
             } else if (q == 4) {
-                store_plane(0, accs[0][0][0]);                     // y0 = (s + S) + m0, in flight under position 5's loop
+                store(0, accs[0][0][0]);                           // y0 = (s + S) + m0, in flight under position 5's loop
             }
         }
         FORGE_STAMP(2);
-        store_plane(3, accs[1][0][0]);                             // y3 = (d + 8 D) + m5
+        store(3, accs[1][0][0]);                                   // y3 = (d + 8 D) + m5
         FORGE_STAMP(3);
-        return;
     }
+    if constexpr (RS != 0) return;
 
     FORGE_STAMP(2);
     // ---- epilogue: C/D layout of 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
@@ -1156,35 +1129,26 @@ static ConvPlan plan_conv(long long M, int Cout, int Cin, int ntaps, bool can_sp
     return best;
 }
 
+// Launch one of the point-GEMM forms (64 x 128 tile, 8 waves): the tiles of every `planes`-th plane x ceil(Cout / 128) workgroups per batched problem.
+template <int RS>
+static int launch_point_form(const ConvArgs& a, int planes, size_t lds, const char* entry, hipStream_t st) {
+    const long long M = (long long)a.n * a.D * a.H * a.W;
+    const long long grid = ((M + 64 * planes - 1) / (64 * planes)) * ((a.Cout + 127) / 128) * a.nbat;
+    FORGE_REQUIRE(grid < (1ll << 31), FORGE_ESHAPE, "%s: grid too large", entry);
+    FORGE_REQUIRE(RS != 1 || M * a.ldo * 4 < (1ll << 31), FORGE_ESHAPE, "%s: an output plane spans >= 2 GiB (32-bit buffer offsets); split the batch", entry);
+    FORGE_SET_MAX_LDS_ONCE((conv_igemm_kernel<64, 128, 8, 1, RS>), lds);
+    hipLaunchKernelGGL((conv_igemm_kernel<64, 128, 8, 1, RS>), dim3((unsigned)grid), dim3(8 * 64), lds, st, a);
+    return 0;
+}
+
 // Launch conv_igemm_kernel with the planned tile: ceil(M / BM) x ceil(Cout / BN) workgroups per (K slice, phase, batched problem).
 static int launch_conv_tile(const ConvArgs& a, char tile, hipStream_t st, int row_stage = 0) {
     const long long M = (long long)a.n * a.D * a.H * a.W;
     auto nblk = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((a.Cout + bn - 1) / bn); };
-    if (row_stage == 2) {                                            // forge_wino_gemm_dn: the tiles of the even planes, 16 points
-        const long long grid = (M / 128) * ((a.Cout + 127) / 128) * a.nbat;
-        FORGE_REQUIRE(grid < (1ll << 31), FORGE_ESHAPE, "forge_wino_gemm_dn: grid too large");
-        const size_t lds = 2 * (2 * 64 * BK + 128 * BK) * sizeof(float);
-        FORGE_SET_MAX_LDS_ONCE((conv_igemm_kernel<64, 128, 8, 1, 2>), lds);
-        hipLaunchKernelGGL((conv_igemm_kernel<64, 128, 8, 1, 2>), dim3((unsigned)grid), dim3(8 * 64), lds, st, a);
-        return 0;
-    }
-    if (row_stage == 3) {                                            // forge_wino_gemm_dn4: the tiles of every fourth plane, 16 points
-        const long long grid = (M / 256) * ((a.Cout + 127) / 128) * a.nbat;
-        FORGE_REQUIRE(grid < (1ll << 31), FORGE_ESHAPE, "forge_wino_gemm_dn4: grid too large");
-        const size_t lds = 2 * (64 * BK + 128 * BK) * sizeof(float);
-        FORGE_SET_MAX_LDS_ONCE((conv_igemm_kernel<64, 128, 8, 1, 3>), lds);
-        hipLaunchKernelGGL((conv_igemm_kernel<64, 128, 8, 1, 3>), dim3((unsigned)grid), dim3(8 * 64), lds, st, a);
-        return 0;
-    }
-    if (row_stage) {                                                 // forge_wino_gemm_half: a.nbat = 4 point columns, four points per workgroup
-        const long long grid = nblk(64, 128) * a.nbat;
-        FORGE_REQUIRE(grid < (1ll << 31), FORGE_ESHAPE, "forge_wino_gemm_half: grid too large");
-        FORGE_REQUIRE(M * a.ldo * 4 < (1ll << 31), FORGE_ESHAPE, "forge_wino_gemm_half: an output plane spans >= 2 GiB (32-bit buffer offsets); split the batch");
-        const size_t lds = RS_STAGES * (64 * BK + 128 * BK) * sizeof(float);
-        FORGE_SET_MAX_LDS_ONCE((conv_igemm_kernel<64, 128, 8, 1, 1>), lds);
-        hipLaunchKernelGGL((conv_igemm_kernel<64, 128, 8, 1, 1>), dim3((unsigned)grid), dim3(8 * 64), lds, st, a);
-        return 0;
-    }
+    // the forms: a.nbat = 4 point columns with four points per workgroup (RS = 1) / 16 points on the even planes (2) / on every fourth plane (3)
+    if (row_stage == 1) { const size_t lds = RS_STAGES * (64 * BK + 128 * BK) * sizeof(float); return launch_point_form<1>(a, 1, lds, "forge_wino_gemm_half", st); }
+    if (row_stage == 2) { const size_t lds = RS_STAGES * (2 * 64 * BK + 128 * BK) * sizeof(float); return launch_point_form<2>(a, 2, lds, "forge_wino_gemm_dn", st); }
+    if (row_stage == 3) { const size_t lds = RS_STAGES * (64 * BK + 128 * BK) * sizeof(float); return launch_point_form<3>(a, 4, lds, "forge_wino_gemm_dn4", st); }
 #define FORGE_LAUNCH_CONV(BMv, BNv, NWv)                                                                                   \
     do {                                                                                                                   \
         const long long grid = nblk(BMv, BNv) * a.ksplit * a.nphase * a.nbat;                                              \
@@ -1249,11 +1213,16 @@ extern "C" int forge_conv_igemm(const float* in1, int C1, int ld1, long long bs1
     FORGE_REQUIRE(ld1 >= C1 && ld1 % 4 == 0 && (C2 == 0 || (ld2 >= C2 && ld2 % 4 == 0)) && ldo >= 1, FORGE_EINVAL,
                   "forge_conv_igemm: row strides must cover the channels and keep 16-byte alignment");
     ConvArgs a;
-    a.in1 = in1; a.in2 = in2; a.C1 = C1; a.C2 = C2; a.ld1 = ld1; a.ld2 = ld2; a.bs1r = bs1 > 0 ? bs1 : (long long)Di * Hi * Wi; a.bs2r = bs2 > 0 ? bs2 : (long long)Di * Hi * Wi;
+    a.in1 = in1; a.in2 = in2; a.C1 = C1; a.C2 = C2; a.ld1 = ld1; a.ld2 = ld2;
+    a.bs1r = bs1 > 0 ? bs1 : (long long)Di * Hi * Wi; a.bs2r = bs2 > 0 ? bs2 : (long long)Di * Hi * Wi;
     a.span1 = ((long long)(n - 1) * a.bs1r + (long long)Di * Hi * Wi) * ld1 * 4;
     a.span2 = in2 ? ((long long)(n - 1) * a.bs2r + (long long)Di * Hi * Wi) * ld2 * 4 : 0;
     FORGE_REQUIRE(a.span1 < (1ll << 31) && a.span2 < (1ll << 31) && (long long)ntaps * Cout * (C1 + C2) * 4 < (1ll << 31), FORGE_ESHAPE,
-                  "forge_conv_igemm: an operand spans >= 2 GiB (32-bit buffer offsets); split the batch"); a.is = is; a.Di = Di; a.Hi = Hi; a.Wi = Wi; a.residual = residual; a.ldr = (lift > 0 || epilogue == EPI_GRU_GATES || epilogue == EPI_GRU_OUT) ? Cout : ldo; a.lift = lift; a.ws = nullptr; a.ksplit = 1; a.stats = stats; a.wp = wp; a.bias = bias; a.scale = scale; a.shift = shift; a.slope = slope;
+                  "forge_conv_igemm: an operand spans >= 2 GiB (32-bit buffer offsets); split the batch");
+    a.is = is; a.Di = Di; a.Hi = Hi; a.Wi = Wi; a.residual = residual;
+    a.ldr = (lift > 0 || epilogue == EPI_GRU_GATES || epilogue == EPI_GRU_OUT) ? Cout : ldo;
+    a.lift = lift; a.ws = nullptr; a.ksplit = 1; a.stats = stats;
+    a.wp = wp; a.bias = bias; a.scale = scale; a.shift = shift; a.slope = slope;
     a.aux_h = aux_h; a.aux_z = aux_z; a.out = out; a.out2 = out2; a.out3 = out3; a.n = n; a.D = D; a.H = H; a.W = W; a.Cout = Cout; a.ldo = ldo;
     a.ntaps = ntaps; a.os = os; a.pz = pz; a.py = py; a.px = px; a.Do = Do; a.Ho = Ho; a.Wo = Wo; a.epi = epilogue;
     a.nphase = 1; a.tpp = ntaps; a.nbat = 1; a.pt1 = a.pt2 = a.ptw = a.pto = 0;
@@ -1351,42 +1320,33 @@ static int wino_gemm_impl(const float* V1, int C1, int ld1, long long bs1, long 
                   "forge_wino_gemm_dn4: needs three depth taps, D %% 4 == 0 and Ht Wt %% 64 == 0 (kd=%d D=%d Ht=%d Wt=%d)", kd, D, Ht, Wt);
     ConvArgs a;
     memset(&a, 0, sizeof(a));
-    const long long vol = (long long)D * Ht * Wt, R = (long long)n * vol;
-    if (dn4) {                                                        // operands V6 [n][D/4][6][Ht Wt]: 1.5 vol rows per element; U'' [16][6][Cout][Cin]
-        const long long vol6 = vol / 4 * 6, Cin = C1 + C2;
-        a.in1 = V1; a.in2 = V2; a.C1 = C1; a.C2 = C2; a.ld1 = ld1; a.ld2 = ld2; a.bs1r = bs1 > 0 ? bs1 : vol6; a.bs2r = bs2 > 0 ? bs2 : vol6;
-        a.span1 = ((long long)(n - 1) * a.bs1r + vol6) * ld1 * 4;
-        a.span2 = V2 ? ((long long)(n - 1) * a.bs2r + vol6) * ld2 * 4 : 0;
+    // operand rows per batch element and K loops per tile: vol rows and the kd depth taps; depth nest: U' [16][4][Cout][Cin], the four depth positions
+    // take the place of the taps; its F(4, 3) form: V6 [n][D/4][6][Ht Wt] = 1.5 vol rows, U'' [16][6][Cout][Cin]
+    const long long vol = (long long)D * Ht * Wt, R = (long long)n * vol, rows = dn4 ? vol / 4 * 6 : vol, Cin = C1 + C2;
+    const int npos = dn4 ? 6 : dn ? 4 : kd;
+    a.in1 = V1; a.in2 = V2; a.C1 = C1; a.C2 = C2; a.ld1 = ld1; a.ld2 = ld2; a.bs1r = bs1 > 0 ? bs1 : rows; a.bs2r = bs2 > 0 ? bs2 : rows;
+    a.span1 = ((long long)(n - 1) * a.bs1r + rows) * ld1 * 4;
+    a.span2 = V2 ? ((long long)(n - 1) * a.bs2r + rows) * ld2 * 4 : 0;
+    if (dn4) {
         FORGE_REQUIRE(a.span1 < (1ll << 31) && a.span2 < (1ll << 31) && R * Cout * 4 < (1ll << 31) && 6ll * Cout * Cin * 4 < (1ll << 31), FORGE_EINVAL,
                       "forge_wino_gemm_dn4: an operand or an output plane spans >= 2 GiB (32-bit buffer offsets); split the batch");
-        a.wp = U; a.slope = 1.f; a.out = Mm; a.n = n; a.D = D; a.H = Ht; a.W = Wt; a.is = 1; a.Di = D; a.Hi = Ht; a.Wi = Wt;
-        a.Cout = Cout; a.ldo = Cout; a.ldr = Cout; a.ntaps = a.tpp = 6; a.os = 1; a.Do = D; a.Ho = Ht; a.Wo = Wt; a.nphase = 1; a.epi = EPI_BIAS;
-        a.ksplit = 1; a.nbat = 16; a.pt1 = pt1 > 0 ? pt1 : (long long)n * vol6 * ld1; a.pt2 = V2 ? (pt2 > 0 ? pt2 : (long long)n * vol6 * ld2) : 0;
-        a.ptw = 6ll * Cout * Cin; a.pto = R * Cout;
-        if (int rc = launch_conv_tile(a, 'B', (hipStream_t)stream, 3)) return rc;
-        FORGE_LAUNCH_CHECK("forge_wino_gemm_dn4");
-        return 0;
-    }
-    a.in1 = V1; a.in2 = V2; a.C1 = C1; a.C2 = C2; a.ld1 = ld1; a.ld2 = ld2; a.bs1r = bs1 > 0 ? bs1 : vol; a.bs2r = bs2 > 0 ? bs2 : vol;
-    a.span1 = ((long long)(n - 1) * a.bs1r + vol) * ld1 * 4;
-    a.span2 = V2 ? ((long long)(n - 1) * a.bs2r + vol) * ld2 * 4 : 0;
-    FORGE_REQUIRE(a.span1 < (1ll << 31) && a.span2 < (1ll << 31) && R < (1ll << 31), FORGE_ESHAPE,
-                  "forge_wino_gemm: an operand spans >= 2 GiB per Winograd point (32-bit buffer offsets); split the batch");
-    a.wp = U; a.slope = 1.f; a.out = Mm; a.n = n; a.D = D; a.H = Ht; a.W = Wt; a.is = 1; a.Di = D; a.Hi = Ht; a.Wi = Wt;
-    a.Cout = Cout; a.ldo = Cout; a.ldr = Cout; a.ntaps = kd; a.os = 1; a.Do = D; a.Ho = Ht; a.Wo = Wt; a.nphase = 1; a.tpp = kd; a.epi = EPI_BIAS;
-    a.ksplit = 1; a.nbat = half ? 4 : 16; a.pt1 = pt1 > 0 ? pt1 : R * ld1; a.pt2 = V2 ? (pt2 > 0 ? pt2 : R * ld2) : 0;   // 0 = dense planes, as forge_wino_wgrad reads it
-    a.ptw = (long long)kd * Cout * (C1 + C2); a.pto = R * Cout;
-    if (dn) {                                                         // U' [16][4][Cout][Cin]: the four depth positions take the place of the taps
-        FORGE_REQUIRE(R * Cout * 4 < (1ll << 31) && 4ll * Cout * (C1 + C2) * 4 < (1ll << 31), FORGE_ESHAPE,
+    } else {
+        FORGE_REQUIRE(a.span1 < (1ll << 31) && a.span2 < (1ll << 31) && R < (1ll << 31), FORGE_ESHAPE,
+                      "forge_wino_gemm: an operand spans >= 2 GiB per Winograd point (32-bit buffer offsets); split the batch");
+        FORGE_REQUIRE(!dn || (R * Cout * 4 < (1ll << 31) && 4ll * Cout * Cin * 4 < (1ll << 31)), FORGE_ESHAPE,
                       "forge_wino_gemm_dn: an output plane spans >= 2 GiB (32-bit buffer offsets); split the batch");
-        a.ntaps = a.tpp = 4; a.ptw = 4ll * Cout * (C1 + C2);
-        if (int rc = launch_conv_tile(a, 'B', (hipStream_t)stream, 2)) return rc;
-        FORGE_LAUNCH_CHECK("forge_wino_gemm_dn");
-        return 0;
     }
-    if (kd == 3) { a.tap[0][0] = -1; a.tap[2][0] = 1; }                 // depth taps (-1,0,0), (0,0,0), (1,0,0); kd = 1: the 2-D convolution's single tap
-    if (int rc = launch_conv_tile(a, (char)(tile ? tile : forge_wino_gemm_tile(R, Cout, C1 + C2)), (hipStream_t)stream, half ? 1 : 0)) return rc;
-    FORGE_LAUNCH_CHECK("forge_wino_gemm");
+    a.wp = U; a.slope = 1.f; a.out = Mm; a.n = n; a.D = D; a.H = Ht; a.W = Wt; a.is = 1; a.Di = D; a.Hi = Ht; a.Wi = Wt;
+    a.Cout = Cout; a.ldo = Cout; a.ldr = Cout; a.ntaps = a.tpp = npos; a.os = 1; a.Do = D; a.Ho = Ht; a.Wo = Wt; a.nphase = 1; a.epi = EPI_BIAS;
+    a.ksplit = 1; a.nbat = half ? 4 : 16;
+    a.pt1 = pt1 > 0 ? pt1 : (long long)n * rows * ld1; a.pt2 = V2 ? (pt2 > 0 ? pt2 : (long long)n * rows * ld2) : 0;   // 0 = dense planes, as forge_wino_wgrad reads it
+    a.ptw = (long long)npos * Cout * Cin; a.pto = R * Cout;
+    if (form == 0 || half) {
+        if (kd == 3) { a.tap[0][0] = -1; a.tap[2][0] = 1; }             // depth taps (-1,0,0), (0,0,0), (1,0,0); kd = 1: the 2-D convolution's single tap
+        if (!tile) tile = forge_wino_gemm_tile(R, Cout, C1 + C2);
+    }
+    if (int rc = launch_conv_tile(a, (char)tile, (hipStream_t)stream, form)) return rc;
+    FORGE_LAUNCH_CHECK(dn4 ? "forge_wino_gemm_dn4" : dn ? "forge_wino_gemm_dn" : "forge_wino_gemm");
     return 0;
 }
 
@@ -1406,8 +1366,8 @@ extern "C" int forge_wino_gemm_half(const float* V1, int C1, int ld1, long long 
 // forge_wino_gemm through the depth nest (conv_igemm_kernel<64, 128, 8, 1, 2>): the same 16 point products Mm [16][R][Cout] of a three-depth-tap problem,
 // made with four K loops of C1 + C2 per plane pair instead of six, against Ud = U' [16][4][Cout][C1 + C2] (forge_wino_weights_dn). Rounded in another
 // order than forge_wino_gemm: not bitwise its result. FORGE_EINVAL unless kd == 3, D is even, Ht Wt % 64 == 0 and C1, C2 are multiples of 32.
-// Code object (hipcc -O3, gfx950): 87 VGPRs, 0 AGPRs, 52 SGPRs, no scratch = 5 waves per SIMD by registers; 2 x 32 KB = 64 KB of dynamic LDS -> TWO workgroups per CU
-// (the LDS binds; the four-point form: 80 VGPRs, 48 KB, three).
+// Code object (hipcc -O3, gfx950): 74 VGPRs, 0 AGPRs, no scratch = 6 waves per SIMD by registers; 2 x 32 KB = 64 KB of dynamic LDS -> TWO workgroups per CU
+// (the LDS binds; the four-point form: 76 VGPRs, 48 KB, three). tests/test_conv_igemm_resources.py holds the budget.
 extern "C" int forge_wino_gemm_dn(const float* V1, int C1, int ld1, long long bs1, long long pt1, const float* V2, int C2, int ld2, long long bs2,
                                   long long pt2, const float* Ud, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, forge_stream_t stream) {
     FORGE_REQUIRE(C1 > 0 && C1 % BK == 0 && C2 >= 0 && C2 % BK == 0, FORGE_EINVAL, "forge_wino_gemm_dn: C1=%d / C2=%d must be multiples of %d", C1, C2, BK);
@@ -1419,8 +1379,8 @@ extern "C" int forge_wino_gemm_dn(const float* V1, int C1, int ld1, long long bs
 // (forge_wino_input_dn4; bs1 / bs2 in rows of that layout, 0 = dense) against Ud = U'' [16][6][Cout][C1 + C2] (forge_wino_weights_dn4). Not bitwise
 // forge_wino_gemm's result. FORGE_EINVAL, before any launch, unless kd == 3, D % 4 == 0, Ht Wt % 64 == 0, C1 and C2 are multiples of 32 and every
 // operand and output plane stays within 32-bit buffer offsets.
-// Code object (hipcc -O3, gfx950): 97 VGPRs, 0 AGPRs, 44 SGPRs, no scratch = 4 waves per SIMD by registers (four accumulator sets) -> TWO workgroups per CU;
-// 2 x 24 KB = 48 KB of dynamic LDS would allow three, which needs <= 80 VGPRs (the four-point form: 80 VGPRs with three sets).
+// Code object (hipcc -O3, gfx950): 97 VGPRs, 0 AGPRs, no scratch = 4 waves per SIMD by registers (four accumulator sets) -> TWO workgroups per CU (tests/test_conv_igemm_resources.py);
+// 2 x 24 KB = 48 KB of dynamic LDS would allow three, which needs <= 80 VGPRs (the four-point form: 76 VGPRs with three sets).
 extern "C" int forge_wino_gemm_dn4(const float* V1, int C1, int ld1, long long bs1, long long pt1, const float* V2, int C2, int ld2, long long bs2,
                                    long long pt2, const float* Ud, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, forge_stream_t stream) {
     FORGE_REQUIRE(C1 > 0 && C1 % BK == 0 && C2 >= 0 && C2 % BK == 0, FORGE_EINVAL, "forge_wino_gemm_dn4: C1=%d / C2=%d must be multiples of %d", C1, C2, BK);
