@@ -4,8 +4,11 @@ Weight packing ([Cout,Cin,k..] -> [tap][Cout][Cin]), eval-mode BatchNorm folding
 ConvTranspose phase decomposition and the launch wrapper. No arithmetic of the hot path happens
 here apart from the one-off weight repacks (cached per parameter version).
 """
+import collections
 import ctypes
+import functools
 import os
+from fractions import Fraction
 
 import torch
 
@@ -364,19 +367,11 @@ def conv_stats_buffer(x1, in2, grid, in_grid, Cout, Cin, ntaps, ldo, device):
 # ------------------------------------------------------------------------------------------------------------------
 # Winograd F(2x2, 3x3) x 3 depth taps for the stride-1 3x3x3 convolutions of the inference path (csrc/winograd.hip)
 # ------------------------------------------------------------------------------------------------------------------
-@_lib.on_tensor_device
 def wino_pack_packed(wp, transpose=False):
     """Packed weights [27][Cout][Cin] (pack_conv3d_weight) -> U [16][3][Cout][Cin] = G w[kd] G^T (forge_wino_weights: float64 inside,
     rounded once). transpose: the weights of the DATA GRADIENT instead - the correlation of dy with the flipped kernel and swapped
     channel roles, U [16][3][Cin][Cout]. One small kernel: the training path calls it per convolution and step."""
-    T, co_, ci_ = wp.shape
-    assert T in (27, 9)                     # 3x3x3 kernels, or the 3x3 kernels of a 2-D convolution (pack_conv2d_weight): kd = 3 / 1 depth taps
-    kd = T // 9
-    wp = wp.detach()
-    wp = wp if wp.is_contiguous() else wp.contiguous()
-    U = torch.empty((16, kd, ci_, co_) if transpose else (16, kd, co_, ci_), dtype=torch.float32, device=wp.device)
-    _lib.check(_lib.lib().forge_wino_weights(_lib.ptr(wp), _lib.ptr(U), co_, ci_, kd, 1 if transpose else 0, _lib.current_stream()), "forge_wino_weights")
-    return U
+    return wino_pack(WINO_FORMS["points"], wp, transpose)
 
 
 def wino_pack_weight(w):
@@ -510,10 +505,11 @@ def wino_scene_chunk(b, D, H, W, C, views=1):
     return nb
 
 
-def wino_fits(n, D, H, W, C, views=1, nest4=False):
-    """H, W even, and every transformed operand ([n views D H/2 W/2][C] floats per Winograd point) within the kernel's 32-bit buffer offsets.
-    nest4: the operands of the F(4, 3) depth nest, 6 planes per group of 4 (wino_input_dn4)."""
-    return H % 2 == 0 and W % 2 == 0 and n * views * D * (H // 2) * (W // 2) * C * 4 * (3 if nest4 else 2) // 2 <= MAX_OPERAND_BYTES
+def wino_fits(n, D, H, W, C, views=1, nest4=False, form=None):
+    """H, W even, and every transformed operand ([n views D H/2 W/2][C] floats per Winograd point, times the operand rows per volume of `form`, a
+    WinoForm - default: the plain transform's; nest4 = True names the F(4, 3) nest's) within the kernel's 32-bit buffer offsets."""
+    rows = n * views * D * (H // 2) * (W // 2) * (form or WINO_FORMS["dn4" if nest4 else "points"]).rows
+    return H % 2 == 0 and W % 2 == 0 and rows * C * 4 <= MAX_OPERAND_BYTES
 
 
 @_lib.on_tensor_device
@@ -527,30 +523,12 @@ def wino_input_dy(dy, C, n, D, H, W):
     return V, dM
 
 
-@_lib.on_tensor_device
-def wino_input(x, C, ld, n, D, H, W, bs=0, out=None, nsum=1, sum_stride=0):
-    """V[16][n D H/2 W/2][C] = B^T d B of the channels-last rows x ([n][D][H][W] x ld floats, batch stride bs rows). nsum > 1: d is the
-    mean of nsum such tensors sum_stride rows apart (the view mean feeding fusion_conv, models/encoder.py:62)."""
-    R = n * D * (H // 2) * (W // 2)
-    V = out if out is not None else torch.empty(16, R, C, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().forge_wino_input(_lib.ptr(x), ld, int(bs), _lib.ptr(V), C, 0, n, D, H, W, C, int(nsum), int(sum_stride), _lib.current_stream()),
-               "forge_wino_input")
-    return V
-
-
-@_lib.on_tensor_device
-def wino_pack_packed_dn(wp):
-    """Packed weights [27][Cout][Cin] -> U' = G_depth (x) (G w G^T), the weights of the depth nest (forge_wino_weights_dn: float64 inside, rounded
-    once): the entry's [16][4][Cout][Cin], returned as [16][2][2][Cout][Cin] - position k = 2 i + j. The fifth dimension is what tells wino_gemm the
-    nest's weights from forge_wino_weights' [16][kd][Cout][Cin], and dimension 1 stays what it is there: the K loops of Cin a launch runs per output
-    plane (2 here: four positions per pair of planes), which is how launch meters count its work."""
-    T, co_, ci_ = wp.shape
-    assert T == 27
-    wp = wp.detach()
-    wp = wp if wp.is_contiguous() else wp.contiguous()
-    U = torch.empty((16, 2, 2, co_, ci_), dtype=torch.float32, device=wp.device)
-    _lib.check(_lib.lib().forge_wino_weights_dn(_lib.ptr(wp), _lib.ptr(U), co_, ci_, _lib.current_stream()), "forge_wino_weights_dn")
-    return U
+# ---- the point-GEMM forms: what a form is stands in ONE row of WINO_FORMS (+ its depth-row table in csrc/winograd.hip and its rule below)
+def wino_half_applies(R, Cout, Cin):
+    """The point-GEMM launches whose inverse transform's row stage runs in the GEMM epilogue (forge_wino_gemm_half / forge_wino_output_half: half the
+    point-product bytes through HBM; bitwise the same result without a second addend): those forge_wino_gemm would give its 64 x 128 tile - a rule
+    of (R, Cout) only - and no forced plan."""
+    return STATE.plan_override is None and wino_gemm_tile(R, Cout, Cin) == "B"
 
 
 def wino_depth_nest_applies(R, D, Ht, Wt, Cout, Cin):
@@ -561,37 +539,86 @@ def wino_depth_nest_applies(R, D, Ht, Wt, Cout, Cin):
             and R * Cout * 4 <= MAX_OPERAND_BYTES and wino_gemm_tile(R, Cout, Cin) == "B")
 
 
-@_lib.on_tensor_device
-def wino_input_dn4(x, C, ld, n, D, H, W, bs=0, out=None, nsum=1, sum_stride=0):
-    """wino_input with the depth stage of the F(4, 3) nest (forge_wino_input_dn4): V6 [16][n (D/4) 6 (H/2)(W/2)][C], 1.5 x wino_input's rows - position k
-    of group g of four planes is plane 6 g + k of the batch element. The operand of wino_gemm_dn4. out: a buffer of that shape."""
-    R6 = n * (D // 4) * 6 * (H // 2) * (W // 2)
-    V = out if out is not None else torch.empty(16, R6, C, dtype=torch.float32, device=x.device)
-    if V.shape != (16, R6, C) or not V.is_contiguous():
-        raise ValueError("depth-nest operand buffer %s is not [16][%d][%d]" % (tuple(V.shape), R6, C))
-    _lib.check(_lib.lib().forge_wino_input_dn4(_lib.ptr(x), ld, int(bs), _lib.ptr(V), C, 0, n, D, H, W, C, int(nsum), int(sum_stride),
-                                               _lib.current_stream()), "forge_wino_input_dn4")
-    return V
+def wino_depth_nest4_applies(R, D, Ht, Wt, Cout, Cin):
+    """The launches of wino_depth_nest_applies that take the nest's F(4, 3) form (forge_wino_gemm_dn4: six K loops per four planes, 3/4 of the F(2, 3)
+    nest's matrix-core work, operands from forge_wino_input_dn4): that rule plus D % 4 == 0 and D >= 8 (at D = 4 every group touches both grid edges and
+    two of its six positions are half empty), unless switched off (STATE.wino_depth_nest4 / FORGE_WINO_DEPTH_NEST4=0, or the nest as a whole)."""
+    return STATE.wino_depth_nest4 and D % 4 == 0 and D >= 8 and wino_depth_nest_applies(R, D, Ht, Wt, Cout, Cin)
+
+
+# One immutable record per form. Everything that depends on the form reads it here: wino_fits, fusion._step_scratch, wino_pack, the weight and operand
+# checks of wino_form_gemm, flopmeter's counters, fusion._fuse_eval's choice.
+#   P        planes of point products the launch writes ([P][R][Cout]; wino_output reads the form from P)
+#   gemm     the forge_wino_gemm* entry
+#   weights  the weight entry, ushape(kd, Cout, Cin) the shape of its tensor
+#   input    the input-transform entry, rows its operand rows per volume as a ratio to D Ht Wt
+#   kloops   K loops of Cin a launch runs per output plane (None: kd, the depth taps of the weights)
+#   applies  the form's rule, (R, D, Ht, Wt, Cout, Cin) -> bool ("points" always can)
+#   tile     the gemm entry takes a tile argument (the caller's plan: forge_wino_gemm alone)
+#   metered  its launches and input transforms go through wino_gemm / wino_input (see below)
+# Two things here are shaped by bench.py's --full recorder, which replaces the module attributes wino_gemm / wino_input / wino_output at run time and
+# counts a launch's FLOPs as U.shape[1] x Cin: (1) the points, half and F(2, 3)-nest launches go through wino_gemm and wino_input, looked up in this module
+# at call time (wino_calls) - the nest's [16][2][2][Cout][Cin] weight shape exists for exactly that meter, dimension 1 being its K loops per plane; (2) the
+# F(4, 3) launches and their input transform do NOT go through them (wino_form_gemm / wino_form_input directly): the recorder would count them 4 x too
+# high (U.shape[1] = 6 for 3/2 loops per plane), so that it does not see them is the lesser evil. That is the `metered` column.
+WinoForm = collections.namedtuple("WinoForm", "name P gemm weights ushape input rows kloops applies tile metered")
+_U4 = lambda kd, co_, ci_: (16, kd, co_, ci_)
+WINO_FORMS = {f.name: f for f in (
+    WinoForm("points", 16, "forge_wino_gemm", "forge_wino_weights", _U4, "forge_wino_input", 1, None, lambda R, D, Ht, Wt, Cout, Cin: True,
+             True, True),
+    WinoForm("half", 8, "forge_wino_gemm_half", "forge_wino_weights", _U4, "forge_wino_input", 1, None,
+             lambda R, D, Ht, Wt, Cout, Cin: wino_half_applies(R, Cout, Cin), False, True),
+    WinoForm("dn", 16, "forge_wino_gemm_dn", "forge_wino_weights_dn", lambda kd, co_, ci_: (16, 2, 2, co_, ci_), "forge_wino_input", 1, 2,
+             lambda *a: wino_depth_nest_applies(*a), False, True),
+    WinoForm("dn4", 16, "forge_wino_gemm_dn4", "forge_wino_weights_dn4", lambda kd, co_, ci_: (16, 6, co_, ci_), "forge_wino_input_dn4", Fraction(3, 2),
+             Fraction(3, 2), lambda *a: wino_depth_nest4_applies(*a), False, False),
+)}
+
+
+def wino_calls(form):
+    """(input transform, point GEMM) of `form` with the signatures of wino_input / wino_gemm - those two themselves, looked up at call time, for every
+    metered form (see the remark above WINO_FORMS)."""
+    if not form.metered:
+        return functools.partial(wino_form_input, form), functools.partial(wino_form_gemm, form)
+    return (lambda *a, **kw: wino_input(*a, **kw)), (lambda *a, **kw: wino_gemm(*a, **kw))
 
 
 @_lib.on_tensor_device
-def wino_pack_packed_dn4(wp):
-    """Packed weights [27][Cout][Cin] -> U'' [16][6][Cout][Cin] = G_depth (x) (G w G^T), the weights of the F(4, 3) depth nest (forge_wino_weights_dn4:
-    float64 inside, rounded once); position k along dimension 1."""
+def wino_pack(form, wp, transpose=False):
+    """Packed weights [27 | 9][Cout][Cin] (pack_conv3d_weight / pack_conv2d_weight) -> the transformed weights of `form`, form.ushape(kd, Cout, Cin)
+    (form.weights: float64 inside, rounded once). The nests' U = G_depth (x) (G w G^T), depth position k = 2 i + j of [16][2][2] / along dimension 1 of
+    [16][6], take 3x3x3 kernels only. transpose (the four-point forms): the weights of the DATA GRADIENT, see wino_pack_packed."""
     T, co_, ci_ = wp.shape
-    assert T == 27
+    nest = form.kloops is not None
+    assert T == 27 or (T == 9 and not nest)    # 3x3x3 kernels, or the 3x3 kernels of a 2-D convolution (pack_conv2d_weight): kd = 3 / 1 depth taps
+    assert not (nest and transpose)
+    kd = T // 9
     wp = wp.detach()
     wp = wp if wp.is_contiguous() else wp.contiguous()
-    U = torch.empty((16, 6, co_, ci_), dtype=torch.float32, device=wp.device)
-    _lib.check(_lib.lib().forge_wino_weights_dn4(_lib.ptr(wp), _lib.ptr(U), co_, ci_, _lib.current_stream()), "forge_wino_weights_dn4")
+    U = torch.empty(form.ushape(kd, ci_, co_) if transpose else form.ushape(kd, co_, ci_), dtype=torch.float32, device=wp.device)
+    own = () if nest else (kd, 1 if transpose else 0)
+    _lib.check(getattr(_lib.lib(), form.weights)(_lib.ptr(wp), _lib.ptr(U), co_, ci_, *own, _lib.current_stream()), form.weights)
     return U
 
 
-def wino_depth_nest4_applies(R, D, Ht, Wt, Cout, Cin):
-    """The launches of wino_depth_nest_applies that take the nest's F(4, 3) form (forge_wino_gemm_dn4: six K loops per four planes, 3/4 of the F(2, 3)
-    nest's matrix-core work, operands from wino_input_dn4): that rule plus D % 4 == 0 and D >= 8 (at D = 4 every group touches both grid edges and two
-    of its six positions are half empty), unless switched off (STATE.wino_depth_nest4 / FORGE_WINO_DEPTH_NEST4=0, or the nest as a whole)."""
-    return STATE.wino_depth_nest4 and D % 4 == 0 and D >= 8 and wino_depth_nest_applies(R, D, Ht, Wt, Cout, Cin)
+@_lib.on_tensor_device
+def wino_form_input(form, x, C, ld, n, D, H, W, bs=0, out=None, nsum=1, sum_stride=0):
+    """V [16][rows][C], rows = n D H/2 W/2 x form.rows: the input transform of `form` (form.input) of the channels-last rows x ([n][D][H][W] x ld floats,
+    batch stride bs rows). The plain transform is B^T d B per tile; forge_wino_input_dn4 puts the depth stage of the F(4, 3) nest in front - position k of
+    group g of four planes is plane 6 g + k of the batch element. nsum > 1: d is the mean of nsum such tensors sum_stride rows apart (the view mean feeding
+    fusion_conv, models/encoder.py:62). out: a buffer of that shape."""
+    rows = int(n * D * (H // 2) * (W // 2) * form.rows)
+    V = out if out is not None else torch.empty(16, rows, C, dtype=torch.float32, device=x.device)
+    if form.rows != 1 and (V.shape != (16, rows, C) or not V.is_contiguous()):
+        raise ValueError("depth-nest operand buffer %s is not [16][%d][%d]" % (tuple(V.shape), rows, C))
+    _lib.check(getattr(_lib.lib(), form.input)(_lib.ptr(x), ld, int(bs), _lib.ptr(V), C, 0, n, D, H, W, C, int(nsum), int(sum_stride), _lib.current_stream()),
+               form.input)
+    return V
+
+
+def wino_input(x, C, ld, n, D, H, W, bs=0, out=None, nsum=1, sum_stride=0):
+    """V[16][n D H/2 W/2][C] = B^T d B of the channels-last rows x: wino_form_input of the forms that share the plain transform."""
+    return wino_form_input(WINO_FORMS["points"], x, C, ld, n, D, H, W, bs=bs, out=out, nsum=nsum, sum_stride=sum_stride)
 
 
 def _point_products(Mm, P, R, Cout, device):
@@ -606,73 +633,45 @@ def _point_products(Mm, P, R, Cout, device):
     return Mm
 
 
-def _wino_gemm_call(entry, V1, C1, V2, C2, U, Mm, n, D, Ht, Wt, Cout, kd, view, views, vol, *tile):
-    """One of the four forge_wino_gemm* entries on view `view` of V1, whose batch elements hold `views` views of `vol` rows each (`tile`: forge_wino_gemm's own)."""
+@_lib.on_tensor_device
+def wino_form_gemm(form, V1, C1, V2, C2, U, Mm, n, D, Ht, Wt, Cout, view=0, views=1):
+    """The point GEMMs of `form` (form.gemm) over R = n D Ht Wt tile rows: the point products [form.P][R][Cout], a view of the front of Mm (wino_gemm).
+    V1 [16][n views vol][C1], vol = D Ht Wt x form.rows operand rows per volume, holds `views` views per batch element and this call reads view `view`;
+    V2 [16][n vol][C2] or None; U = wino_pack(form, .) of Cin = C1 + C2. The caller has checked form.applies' shape conditions (the entries refuse the
+    others)."""
+    R = n * D * Ht * Wt
+    vol = int(D * Ht * Wt * form.rows)
+    nest = form.kloops is not None
+    kd = 3 if nest else U.shape[1]
+    if U.shape != form.ushape(kd, Cout, C1 + C2) or (kd not in (1, 3)) or (nest and not U.is_contiguous()):
+        raise ValueError("%s weight %s does not match Cout=%d Cin=%d" % ("depth-nest" if nest else "transformed", tuple(U.shape), Cout, C1 + C2))
+    if form.rows != 1 and (V1.shape[1] != n * views * vol or (V2 is not None and V2.shape[1] != n * vol)):
+        raise ValueError("depth-nest operands %s / %s are not %s's %d (x %d views) rows per point" % (
+            tuple(V1.shape), None if V2 is None else tuple(V2.shape), form.input, n * vol, views))
+    Mm = _point_products(Mm, form.P, R, Cout, V1.device)
+    tile = (ord(wino_gemm_tile(R, Cout, C1 + C2)),) if form.tile else ()
     p1 = ctypes.c_void_p(V1.data_ptr() + 4 * view * vol * C1)
-    _lib.check(getattr(_lib.lib(), entry)(p1, C1, C1, views * vol if views > 1 else 0, V1.shape[1] * C1, _lib.ptr(V2), C2, C2, 0,
-                                          0 if V2 is None else V2.shape[1] * C2, _lib.ptr(U), _lib.ptr(Mm), n, D, Ht, Wt, Cout, kd,
-                                          *tile, _lib.current_stream()), entry)
+    _lib.check(getattr(_lib.lib(), form.gemm)(p1, C1, C1, views * vol if views > 1 else 0, V1.shape[1] * C1, _lib.ptr(V2), C2, C2, 0,
+                                              0 if V2 is None else V2.shape[1] * C2, _lib.ptr(U), _lib.ptr(Mm), n, D, Ht, Wt, Cout, kd,
+                                              *tile, _lib.current_stream()), form.gemm)
     return Mm
 
 
-@_lib.on_tensor_device
-def wino_gemm_dn4(V1, C1, V2, C2, Ud, Mm, n, D, Ht, Wt, Cout, view=0, views=1):
-    """wino_gemm's 16 point products [16][R][Cout] through the F(4, 3) depth nest (forge_wino_gemm_dn4), from the wino_input_dn4 operands V1
-    [16][n views (D/4) 6 Ht Wt][C1] (this call reads view `view`), V2 [16][n (D/4) 6 Ht Wt][C2] or None, and Ud [16][6][Cout][C1 + C2]
-    (wino_pack_packed_dn4). Mm as wino_gemm; the caller has checked wino_depth_nest4_applies' shape conditions (the entry refuses the others)."""
-    vol = D * Ht * Wt
-    R, vol6 = n * vol, vol // 4 * 6
-    if Ud.shape != (16, 6, Cout, C1 + C2) or not Ud.is_contiguous():
-        raise ValueError("depth-nest weight %s does not match Cout=%d Cin=%d" % (tuple(Ud.shape), Cout, C1 + C2))
-    if V1.shape[1] != n * views * vol6 or (V2 is not None and V2.shape[1] != n * vol6):
-        raise ValueError("depth-nest operands %s / %s are not wino_input_dn4's %d (x %d views) rows per point" % (
-            tuple(V1.shape), None if V2 is None else tuple(V2.shape), n * vol6, views))
-    Mm = _point_products(Mm, 16, R, Cout, V1.device)
-    return _wino_gemm_call("forge_wino_gemm_dn4", V1, C1, V2, C2, Ud, Mm, n, D, Ht, Wt, Cout, 3, view, views, vol6)
-
-
-@_lib.on_tensor_device
-def wino_gemm_dn(V1, C1, V2, C2, Ud, Mm, n, D, Ht, Wt, Cout, view=0, views=1):
-    """wino_gemm's 16 point products [16][R][Cout] through the depth nest (forge_wino_gemm_dn), from Ud [16][2][2][Cout][C1 + C2] (wino_pack_packed_dn).
-    Operands and the buffer Mm as wino_gemm; the caller has checked wino_depth_nest_applies' shape conditions (the entry refuses the others)."""
-    vol = D * Ht * Wt
-    R = n * vol
-    if Ud.shape != (16, 2, 2, Cout, C1 + C2) or not Ud.is_contiguous():
-        raise ValueError("depth-nest weight %s does not match Cout=%d Cin=%d" % (tuple(Ud.shape), Cout, C1 + C2))
-    Mm = _point_products(Mm, 16, R, Cout, V1.device)
-    return _wino_gemm_call("forge_wino_gemm_dn", V1, C1, V2, C2, Ud, Mm, n, D, Ht, Wt, Cout, 3, view, views, vol)
-
-
-def wino_half_applies(R, Cout, Cin):
-    """The point-GEMM launches whose inverse transform's row stage runs in the GEMM epilogue (forge_wino_gemm_half / forge_wino_output_half: half the
-    point-product bytes through HBM; bitwise the same result without a second addend): those forge_wino_gemm would give its 64 x 128 tile - a rule
-    of (R, Cout) only - and no forced plan."""
-    return STATE.plan_override is None and wino_gemm_tile(R, Cout, Cin) == "B"
-
-
-@_lib.on_tensor_device
 def wino_gemm(V1, C1, V2, C2, U, Mm, n, D, Ht, Wt, Cout, view=0, views=1, half=None):
     """The 16 point GEMMs over R = n D Ht Wt tile rows, returned as the point products [P][R][Cout]: a view of the front of Mm's storage, in the
     form the inverse transform reads from its shape (wino_output). V1 [16][n views D Ht Wt][C1] may hold `views` views per batch element (the
     transformed inputs of every view of a scene, made by ONE wino_input launch): this call reads view `view`. V2 [16][R][C2] or None.
-    half chooses the form - True: P = 8 planes [2][4][R][Cout], the row stage of the inverse transform applied in the GEMM epilogue
-    (forge_wino_gemm_half); False: the P = 16 points; None: wino_half_applies(R, Cout, C1 + C2). A producer whose products another launch adds
-    (wino_output's Mm2) passes that launch's form. Mm: a contiguous float32 buffer of at least P R Cout elements (ValueError otherwise), or None
-    for a new [P][R][Cout] tensor. U of five dimensions (wino_pack_packed_dn): the depth nest, 16 points (wino_gemm_dn)."""
+    The form follows from the weights: U of five dimensions (wino_pack of the "dn" form) is the depth nest, 16 points; else half chooses - True: P = 8
+    planes [2][4][R][Cout], the row stage of the inverse transform applied in the GEMM epilogue (forge_wino_gemm_half); False: the P = 16 points; None:
+    the half form's rule (wino_half_applies). A producer whose products another launch adds (wino_output's Mm2) passes that launch's form. Mm: a contiguous
+    float32 buffer of at least P R Cout elements (ValueError otherwise), or None for a new [P][R][Cout] tensor."""
     if U.dim() == 5:
-        return wino_gemm_dn(V1, C1, V2, C2, U, Mm, n, D, Ht, Wt, Cout, view=view, views=views)
-    vol = D * Ht * Wt
-    R = n * vol
-    if half is None:
-        half = wino_half_applies(R, Cout, C1 + C2)
-    kd = U.shape[1]
-    if U.shape != (16, kd, Cout, C1 + C2) or kd not in (1, 3):
-        raise ValueError("transformed weight %s does not match Cout=%d Cin=%d" % (tuple(U.shape), Cout, C1 + C2))
-    Mm = _point_products(Mm, 8 if half else 16, R, Cout, V1.device)
-    if half:
-        return _wino_gemm_call("forge_wino_gemm_half", V1, C1, V2, C2, U, Mm, n, D, Ht, Wt, Cout, kd, view, views, vol)
-    return _wino_gemm_call("forge_wino_gemm", V1, C1, V2, C2, U, Mm, n, D, Ht, Wt, Cout, kd, view, views, vol,
-                           ord(wino_gemm_tile(R, Cout, C1 + C2)))
+        form = "dn"
+    else:
+        if half is None:
+            half = WINO_FORMS["half"].applies(n * D * Ht * Wt, D, Ht, Wt, Cout, C1 + C2)
+        form = "half" if half else "points"
+    return wino_form_gemm(WINO_FORMS[form], V1, C1, V2, C2, U, Mm, n, D, Ht, Wt, Cout, view=view, views=views)
 
 
 def wino_gemm_tile(R, Cout, Cin):

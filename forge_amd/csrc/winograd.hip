@@ -18,8 +18,77 @@
 
 namespace forge {
 
-__device__ __forceinline__ float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 f4_sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
+__device__ __forceinline__ float4 add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+__device__ __forceinline__ float4 sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
+__device__ __forceinline__ float add(float a, float b) { return a + b; }
+__device__ __forceinline__ float sub(float a, float b) { return a - b; }
+
+// ---- the pieces the kernels below are written on. Free functions whose arguments are formed where the kernels formed them before they were shared:
+// the signatures (a row and its stride instead of a pointer, a shift instead of a factor) keep the compiler's instruction order
+// (profiles/r20_wino_forms_isa.txt).
+// idx -> (r, c, tw, th, t): thread idx of a [tile rows][per] grid works on tile row r = idx / per and channel c = (idx % per) << cs;
+// r = (t Ht + th) Wt + tw with t the plane index (batch element x depth). 32-bit divisions: the launchers refuse 2^31 tile rows.
+__device__ __forceinline__ void tile_decode(long long idx, int per, int cs, int Ht, int Wt, unsigned& r, int& c, int& tw, int& th, unsigned& t) {
+    r = (unsigned)(idx / per);
+    c = (int)(idx - (long long)r * per) << cs;
+    unsigned q = r;
+    t = q / (unsigned)Wt;
+    tw = (int)(q - t * (unsigned)Wt); q = t; t = q / (unsigned)Ht;
+    th = (int)(q - t * (unsigned)Ht);
+}
+
+// V[4i + j] = (B^T d B)[i][j] of one 4 x 4 patch d (T = float4: four channels; float: one): point p goes to V + row ld + c + p ptv
+template <typename T, typename I>
+__device__ __forceinline__ void bt_d_b_store(const T (&d)[4][4], float* V, I row, int ld, int c, long long ptv) {
+    T w[4][4];                                       // rows: B^T d
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        w[0][j] = sub(d[0][j], d[2][j]);
+        w[1][j] = add(d[1][j], d[2][j]);
+        w[2][j] = sub(d[2][j], d[1][j]);
+        w[3][j] = sub(d[1][j], d[3][j]);
+    }
+    float* vp = V + (long long)row * ld + c;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {                    // columns: (B^T d) B
+        *reinterpret_cast<T*>(vp + (4 * i + 0) * ptv) = sub(w[i][0], w[i][2]);
+        *reinterpret_cast<T*>(vp + (4 * i + 1) * ptv) = add(w[i][1], w[i][2]);
+        *reinterpret_cast<T*>(vp + (4 * i + 2) * ptv) = sub(w[i][2], w[i][1]);
+        *reinterpret_cast<T*>(vp + (4 * i + 3) * ptv) = sub(w[i][1], w[i][3]);
+    }
+}
+
+// dM[4i + j] = (A y A^T)[i][j] of one 2 x 2 output tile y, A = [1 0; 1 1; 1 -1; 0 -1]; point p at mp + p ptm
+__device__ __forceinline__ void a_y_at_store(float4 y00, float4 y01, float4 y10, float4 y11, float* mp, long long ptm) {
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 s[4][2] = {{y00, y01}, {add(y00, y10), add(y01, y11)}, {sub(y00, y10), sub(y01, y11)}, {sub(zero, y10), sub(zero, y11)}};   // A y
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {                    // (A y) A^T
+        *reinterpret_cast<float4*>(mp + (4 * i + 0) * ptm) = s[i][0];
+        *reinterpret_cast<float4*>(mp + (4 * i + 1) * ptm) = add(s[i][0], s[i][1]);
+        *reinterpret_cast<float4*>(mp + (4 * i + 2) * ptm) = sub(s[i][0], s[i][1]);
+        *reinterpret_cast<float4*>(mp + (4 * i + 3) * ptm) = sub(zero, s[i][1]);
+    }
+}
+
+// U[4i + j] = (float)(G d G^T)[i][j] of one 3 x 3 kernel slice d in float64, rounded once; point p at up + p pt
+__device__ __forceinline__ void g_d_gt_store(const double (&d)[3][3], float* up, long long pt) {
+    double g[4][3];                                  // G d
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        g[0][b] = d[0][b];
+        g[1][b] = 0.5 * (d[0][b] + d[1][b] + d[2][b]);
+        g[2][b] = 0.5 * (d[0][b] - d[1][b] + d[2][b]);
+        g[3][b] = d[2][b];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {                    // (G d) G^T
+        up[(4 * i + 0) * pt] = (float)g[i][0];
+        up[(4 * i + 1) * pt] = (float)(0.5 * (g[i][0] + g[i][1] + g[i][2]));
+        up[(4 * i + 2) * pt] = (float)(0.5 * (g[i][0] - g[i][1] + g[i][2]));
+        up[(4 * i + 3) * pt] = (float)g[i][2];
+    }
+}
 
 struct WinoInArgs {
     const float* in; int ld; long long bs;        // rows [n][D][H][W] x ld floats, batch stride bs rows
@@ -42,12 +111,11 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const WinoInArgs a) {
     const long long idx = (long long)xcd_remap(blockIdx.x, gridDim.x) * 256 + threadIdx.x;
     const long long R = (long long)a.n * a.D * Ht * Wt;
     if (idx >= R * C4) return;
-    const unsigned r = (unsigned)(idx / C4);
-    const int c = (int)(idx - (long long)r * C4) << 2;
-    unsigned q = r, t = q / (unsigned)Wt;
-    const int tw = (int)(q - t * (unsigned)Wt); q = t; t = q / (unsigned)Ht;
-    const int th = (int)(q - t * (unsigned)Ht); q = t; t = q / (unsigned)a.D;
-    const int z = (int)(q - t * (unsigned)a.D);
+    unsigned r, t;
+    int c, tw, th;
+    tile_decode(idx, C4, 2, Ht, Wt, r, c, tw, th, t);
+    const unsigned q = t; t = q / (unsigned)a.D;
+    const int z = (int)(q - t * (unsigned)a.D);                      // t = batch element
     const float* base = a.in + ((long long)t * a.bs + (long long)z * a.H * a.W) * a.ld + c;
     float4 d[4][4];
 #pragma unroll
@@ -62,7 +130,7 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const WinoInArgs a) {
                 const float* p = base + ((long long)y * a.W + x) * a.ld;
                 v = *reinterpret_cast<const float4*>(p);
                 if (a.nsum > 1) {
-                    for (int k = 1; k < a.nsum; ++k) v = f4_add(v, *reinterpret_cast<const float4*>(p + (long long)k * a.ss * a.ld));
+                    for (int k = 1; k < a.nsum; ++k) v = add(v, *reinterpret_cast<const float4*>(p + (long long)k * a.ss * a.ld));
                     const float inv = 1.f / (float)a.nsum;           // ATen divides by a scalar as a multiplication by its fp32 reciprocal
                     v = make_float4(v.x * inv, v.y * inv, v.z * inv, v.w * inv);
                 }
@@ -70,35 +138,8 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const WinoInArgs a) {
             d[i][j] = v;
         }
     }
-    if constexpr (DY) {
-        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-        float* mp = a.dM + (long long)r * a.C + c;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {                // rows of A y: y0, y0 + y1, y0 - y1, -y1 (y = d[1..2][1..2]); then (A y) A^T
-            const float4 s0 = i == 0 ? d[1][1] : i == 1 ? f4_add(d[1][1], d[2][1]) : i == 2 ? f4_sub(d[1][1], d[2][1]) : f4_sub(zero, d[2][1]);
-            const float4 s1 = i == 0 ? d[1][2] : i == 1 ? f4_add(d[1][2], d[2][2]) : i == 2 ? f4_sub(d[1][2], d[2][2]) : f4_sub(zero, d[2][2]);
-            *reinterpret_cast<float4*>(mp + (4 * i + 0) * a.ptm) = s0;
-            *reinterpret_cast<float4*>(mp + (4 * i + 1) * a.ptm) = f4_add(s0, s1);
-            *reinterpret_cast<float4*>(mp + (4 * i + 2) * a.ptm) = f4_sub(s0, s1);
-            *reinterpret_cast<float4*>(mp + (4 * i + 3) * a.ptm) = f4_sub(zero, s1);
-        }
-    }
-    float4 w[4][4];                                  // rows: B^T d
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        w[0][j] = f4_sub(d[0][j], d[2][j]);
-        w[1][j] = f4_add(d[1][j], d[2][j]);
-        w[2][j] = f4_sub(d[2][j], d[1][j]);
-        w[3][j] = f4_sub(d[1][j], d[3][j]);
-    }
-    float* vp = a.V + (long long)r * a.ldv + c;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {                    // columns: (B^T d) B
-        *reinterpret_cast<float4*>(vp + (4 * i + 0) * a.ptv) = f4_sub(w[i][0], w[i][2]);
-        *reinterpret_cast<float4*>(vp + (4 * i + 1) * a.ptv) = f4_add(w[i][1], w[i][2]);
-        *reinterpret_cast<float4*>(vp + (4 * i + 2) * a.ptv) = f4_sub(w[i][2], w[i][1]);
-        *reinterpret_cast<float4*>(vp + (4 * i + 3) * a.ptv) = f4_sub(w[i][1], w[i][3]);
-    }
+    if constexpr (DY) a_y_at_store(d[1][1], d[1][2], d[2][1], d[2][2], a.dM + (long long)r * a.C + c, a.ptm);    // y = the centre of the patch
+    bt_d_b_store(d, a.V, r, a.ldv, c, a.ptv);
 }
 
 // The input transform of the F(4, 3) depth nest (forge_wino_input_dn4): wino_input_kernel's B^T d B on the DEPTH-COMBINED patches of a group of four
@@ -116,11 +157,10 @@ __global__ __launch_bounds__(256) void wino_input_dn4_kernel(const WinoInArgs a)
     const long long idx = (long long)xcd_remap(blockIdx.x, gridDim.x) * 256 + threadIdx.x;
     const long long RG = (long long)a.n * Dg * Ht * Wt;             // group tiles
     if (idx >= RG * a.C) return;
-    const unsigned r = (unsigned)(idx / a.C);
-    const int c = (int)(idx - (long long)r * a.C);
-    unsigned q = r, t = q / (unsigned)Wt;
-    const int tw = (int)(q - t * (unsigned)Wt); q = t; t = q / (unsigned)Ht;
-    const int th = (int)(q - t * (unsigned)Ht); q = t; t = q / (unsigned)Dg;
+    unsigned r, t;
+    int c, tw, th;
+    tile_decode(idx, a.C, 0, Ht, Wt, r, c, tw, th, t);
+    const unsigned q = t; t = q / (unsigned)Dg;
     const int g = (int)(q - t * (unsigned)Dg);                      // t = batch element
     const long long HW = (long long)a.H * a.W;
     const float* base = a.in + (long long)t * a.bs * a.ld + c;
@@ -161,24 +201,7 @@ __global__ __launch_bounds__(256) void wino_input_dn4_kernel(const WinoInArgs a)
     const long long HWt = (long long)Ht * Wt;
     float* vp = a.V + ((((long long)t * Dg + g) * 6) * HWt + (long long)th * Wt + tw) * a.ldv + c;
 #pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        float w[4][4];                               // rows: B^T d
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            w[0][j] = d[k][0][j] - d[k][2][j];
-            w[1][j] = d[k][1][j] + d[k][2][j];
-            w[2][j] = d[k][2][j] - d[k][1][j];
-            w[3][j] = d[k][1][j] - d[k][3][j];
-        }
-        float* vk = vp + (long long)k * HWt * a.ldv;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {                // columns: (B^T d) B
-            vk[(4 * i + 0) * a.ptv] = w[i][0] - w[i][2];
-            vk[(4 * i + 1) * a.ptv] = w[i][1] + w[i][2];
-            vk[(4 * i + 2) * a.ptv] = w[i][2] - w[i][1];
-            vk[(4 * i + 3) * a.ptv] = w[i][1] - w[i][3];
-        }
-    }
+    for (int k = 0; k < 6; ++k) bt_d_b_store(d[k], vp, k * HWt, a.ldv, 0, a.ptv);
 }
 
 // U[4i+j][kd][o][c] = (G w[kd] G^T)[i][j] from packed weights wp[(kd 3 + a) 3 + b][co][ci]: one thread per (kd, o, c). Evaluated in float64
@@ -199,96 +222,37 @@ __global__ __launch_bounds__(256) void wino_weight_kernel(const float* __restric
             const int tap = transpose ? ((KD - 1 - kd) * 3 + (2 - a)) * 3 + (2 - b) : (kd * 3 + a) * 3 + b;
             w[a][b] = (double)wp[((long long)tap * Cout + (transpose ? c : o)) * Cin + (transpose ? o : c)];
         }
-    double g[4][3];                                  // G w
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-        g[0][b] = w[0][b];
-        g[1][b] = 0.5 * (w[0][b] + w[1][b] + w[2][b]);
-        g[2][b] = 0.5 * (w[0][b] - w[1][b] + w[2][b]);
-        g[3][b] = w[2][b];
-    }
-    float* up = U + ((long long)kd * No + o) * Nc + c;
-    const long long pt = KD * per;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {                    // (G w) G^T
-        up[(4 * i + 0) * pt] = (float)g[i][0];
-        up[(4 * i + 1) * pt] = (float)(0.5 * (g[i][0] + g[i][1] + g[i][2]));
-        up[(4 * i + 2) * pt] = (float)(0.5 * (g[i][0] - g[i][1] + g[i][2]));
-        up[(4 * i + 3) * pt] = (float)g[i][2];
-    }
+    g_d_gt_store(w, U + ((long long)kd * No + o) * Nc + c, KD * per);
 }
 
-// Weights of the depth nest (forge_wino_gemm_dn): U'[4i+j][k][o][c] = sum_kd Gd[k][kd] (G w[kd] G^T)[i][j] with the depth rows Gd = G: w0, (w0 + w1 + w2) / 2,
-// (w0 - w1 + w2) / 2, w2. One thread per (o, c); float64 (exact: at most 27 fp32 terms with coefficients 1, 1/2, 1/4, 1/8), rounded once.
-__global__ __launch_bounds__(256) void wino_weight_dn_kernel(const float* __restrict__ wp, float* __restrict__ U, int Cout, int Cin) {
+// Weights of the depth nests: U'[4i+j][k][o][c] = sum_kd Gd[k][kd] (G w[kd] G^T)[i][j] over K depth positions k, Gd[k] evaluated by ROW(k, w0, w1, w2) on
+// every element of the three depth slices. One thread per (o, c); float64 throughout, rounded once.
+//   F(2, 3) (forge_wino_gemm_dn): Gd = G, the rows w0, (w0 + w1 + w2) / 2, (w0 - w1 + w2) / 2, w2 (exact: at most 27 fp32 terms with coefficients 1, 1/2, 1/4, 1/8)
+//   F(4, 3) (forge_wino_gemm_dn4): Gd = [1/4 0 0; -1/6 -1/6 -1/6; -1/6 1/6 -1/6; 1/24 1/12 1/6; 1/24 -1/12 1/6; 0 0 1] (the sixths are not exact in float64: the
+//           result is the float64 evaluation below, correctly rounded to within one float64 rounding per operation)
+__device__ __forceinline__ double depth_row_f23(int k, double w0, double w1, double w2) {
+    return k == 0 ? w0 : k == 1 ? 0.5 * (w0 + w1 + w2) : k == 2 ? 0.5 * (w0 - w1 + w2) : w2;
+}
+__device__ __forceinline__ double depth_row_f43(int k, double w0, double w1, double w2) {
+    return k == 0 ? 0.25 * w0 : k == 1 ? -((w0 + w2) + w1) / 6.0 : k == 2 ? -((w0 + w2) - w1) / 6.0
+         : k == 3 ? ((0.25 * w0 + w2) + 0.5 * w1) / 6.0 : k == 4 ? ((0.25 * w0 + w2) - 0.5 * w1) / 6.0 : w2;
+}
+
+template <int K, double (*ROW)(int, double, double, double)>
+__global__ __launch_bounds__(256) void wino_weight_nest_kernel(const float* __restrict__ wp, float* __restrict__ U, int Cout, int Cin) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, per = (long long)Cout * Cin;
     if (idx >= per) return;
     double w[3][3][3];
 #pragma unroll
     for (int t = 0; t < 27; ++t) w[t / 9][(t / 3) % 3][t % 3] = (double)wp[t * per + idx];
-    const long long pt = 4 * per;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        double d[3][3], g[4][3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = 0; b < 3; ++b)
-                d[a][b] = k == 0 ? w[0][a][b] : k == 1 ? 0.5 * (w[0][a][b] + w[1][a][b] + w[2][a][b]) : k == 2 ? 0.5 * (w[0][a][b] - w[1][a][b] + w[2][a][b]) : w[2][a][b];
-#pragma unroll
-        for (int b = 0; b < 3; ++b) {                // G d
-            g[0][b] = d[0][b];
-            g[1][b] = 0.5 * (d[0][b] + d[1][b] + d[2][b]);
-            g[2][b] = 0.5 * (d[0][b] - d[1][b] + d[2][b]);
-            g[3][b] = d[2][b];
-        }
-        float* up = U + k * per + idx;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {                // (G d) G^T
-            up[(4 * i + 0) * pt] = (float)g[i][0];
-            up[(4 * i + 1) * pt] = (float)(0.5 * (g[i][0] + g[i][1] + g[i][2]));
-            up[(4 * i + 2) * pt] = (float)(0.5 * (g[i][0] - g[i][1] + g[i][2]));
-            up[(4 * i + 3) * pt] = (float)g[i][2];
-        }
-    }
-}
-
-// Weights of the F(4, 3) depth nest (forge_wino_gemm_dn4): U''[4i+j][k][o][c] = sum_kd Gd[k][kd] (G w[kd] G^T)[i][j] with the six depth rows
-// Gd = [1/4 0 0; -1/6 -1/6 -1/6; -1/6 1/6 -1/6; 1/24 1/12 1/6; 1/24 -1/12 1/6; 0 0 1]. One thread per (o, c); float64 throughout, rounded once (the
-// sixths are not exact in float64: the result is the float64 evaluation below, correctly rounded to within one float64 rounding per operation).
-__global__ __launch_bounds__(256) void wino_weight_dn4_kernel(const float* __restrict__ wp, float* __restrict__ U, int Cout, int Cin) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, per = (long long)Cout * Cin;
-    if (idx >= per) return;
-    double w[3][3][3];
-#pragma unroll
-    for (int t = 0; t < 27; ++t) w[t / 9][(t / 3) % 3][t % 3] = (double)wp[t * per + idx];
-    const long long pt = 6 * per;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        double d[3][3], g[4][3];
+    for (int k = 0; k < K; ++k) {
+        double d[3][3];
 #pragma unroll
         for (int a = 0; a < 3; ++a)
 #pragma unroll
-            for (int b = 0; b < 3; ++b) {
-                const double w0 = w[0][a][b], w1 = w[1][a][b], w2 = w[2][a][b];
-                d[a][b] = k == 0 ? 0.25 * w0 : k == 1 ? -((w0 + w2) + w1) / 6.0 : k == 2 ? -((w0 + w2) - w1) / 6.0
-                        : k == 3 ? ((0.25 * w0 + w2) + 0.5 * w1) / 6.0 : k == 4 ? ((0.25 * w0 + w2) - 0.5 * w1) / 6.0 : w2;
-            }
-#pragma unroll
-        for (int b = 0; b < 3; ++b) {                // G d
-            g[0][b] = d[0][b];
-            g[1][b] = 0.5 * (d[0][b] + d[1][b] + d[2][b]);
-            g[2][b] = 0.5 * (d[0][b] - d[1][b] + d[2][b]);
-            g[3][b] = d[2][b];
-        }
-        float* up = U + k * per + idx;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {                // (G d) G^T
-            up[(4 * i + 0) * pt] = (float)g[i][0];
-            up[(4 * i + 1) * pt] = (float)(0.5 * (g[i][0] + g[i][1] + g[i][2]));
-            up[(4 * i + 2) * pt] = (float)(0.5 * (g[i][0] - g[i][1] + g[i][2]));
-            up[(4 * i + 3) * pt] = (float)g[i][2];
-        }
+            for (int b = 0; b < 3; ++b) d[a][b] = ROW(k, w[0][a][b], w[1][a][b], w[2][a][b]);
+        g_d_gt_store(d, U + k * per + idx, K * per);
     }
 }
 
@@ -305,6 +269,25 @@ struct WinoOutArgs {
     int n, D, H, W, Cout, epi;
 };
 
+// m[i][j] = plane 4 i + j of Mm (+ of Mm2, when given: the second addend in the same form - the transform is linear) at tile row r, channels c .. c + 3;
+// ROWS = 4: the 16 points, 2: the 8 planes of the half form. R1: tile rows per batch element (Mm2's batch elements lie bs2 rows apart)
+template <int ROWS>
+__device__ __forceinline__ void load_planes(float4 (&m)[ROWS][4], const float* Mm, long long ptm, const float* Mm2, long long ptm2, long long bs2, int Cout, unsigned R1, unsigned r, int c) {
+    const float* mp = Mm + (long long)r * Cout + c;
+#pragma unroll
+    for (int i = 0; i < ROWS; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) m[i][j] = *reinterpret_cast<const float4*>(mp + (4 * i + j) * ptm);
+    if (Mm2) {
+        const unsigned nn = r / R1;
+        const float* mp2 = Mm2 + ((long long)nn * bs2 + (r - nn * R1)) * Cout + c;
+#pragma unroll
+        for (int i = 0; i < ROWS; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) m[i][j] = add(m[i][j], *reinterpret_cast<const float4*>(mp2 + (4 * i + j) * ptm2));
+    }
+}
+
 // one thread = one tile x 4 output channels: 16 float4 loads, 24 float4 additions, then the element-wise tail of 2x2 output voxels
 // HALF: Mm (and Mm2) hold 8 planes [2][4] - the row stage s = A^T m was applied by the GEMM's epilogue (forge_wino_gemm_half) - and this kernel runs the
 // column stage only (8 instead of 16 float4 loads per operand).
@@ -314,51 +297,26 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const WinoOutArgs a) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long R = (long long)a.n * a.D * Ht * Wt;
     if (idx >= R * C4) return;
-    const unsigned r = (unsigned)(idx / C4);
-    const int c = (int)(idx - (long long)r * C4) << 2;
-    unsigned q = r, t = q / (unsigned)Wt;
-    const int tw = (int)(q - t * (unsigned)Wt); q = t; t = q / (unsigned)Ht;
-    const int th = (int)(q - t * (unsigned)Ht);                    // q / Ht = (n, z) plane index
-    const float* mp = a.Mm + (long long)r * a.Cout + c;
+    unsigned r, t;                                   // t = (n, z) plane index
+    int c, tw, th;
+    tile_decode(idx, C4, 2, Ht, Wt, r, c, tw, th, t);
     float4 s[2][4];                                  // A^T m
     if constexpr (HALF) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) s[i][j] = *reinterpret_cast<const float4*>(mp + (4 * i + j) * a.ptm);
-        if (a.Mm2) {                                  // the second addend in the same 8-plane form (the transform is linear)
-            const unsigned R1 = (unsigned)(a.D * Ht * Wt), nn = r / R1;
-            const float* mp2 = a.Mm2 + ((long long)nn * a.bs2 + (r - nn * R1)) * a.Cout + c;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) s[i][j] = f4_add(s[i][j], *reinterpret_cast<const float4*>(mp2 + (4 * i + j) * a.ptm2));
-        }
+        load_planes<2>(s, a.Mm, a.ptm, a.Mm2, a.ptm2, a.bs2, a.Cout, (unsigned)(a.D * Ht * Wt), r, c);
     } else {
         float4 m[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) m[i][j] = *reinterpret_cast<const float4*>(mp + (4 * i + j) * a.ptm);
-        if (a.Mm2) {
-            const unsigned R1 = (unsigned)(a.D * Ht * Wt), nn = r / R1;
-            const float* mp2 = a.Mm2 + ((long long)nn * a.bs2 + (r - nn * R1)) * a.Cout + c;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) m[i][j] = f4_add(m[i][j], *reinterpret_cast<const float4*>(mp2 + (4 * i + j) * a.ptm2));
-        }
+        load_planes<4>(m, a.Mm, a.ptm, a.Mm2, a.ptm2, a.bs2, a.Cout, (unsigned)(a.D * Ht * Wt), r, c);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            s[0][j] = f4_add(f4_add(m[0][j], m[1][j]), m[2][j]);
-            s[1][j] = f4_sub(f4_sub(m[1][j], m[2][j]), m[3][j]);
+            s[0][j] = add(add(m[0][j], m[1][j]), m[2][j]);
+            s[1][j] = sub(sub(m[1][j], m[2][j]), m[3][j]);
         }
     }
     float4 y[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        y[i][0] = f4_add(f4_add(s[i][0], s[i][1]), s[i][2]);
-        y[i][1] = f4_sub(f4_sub(s[i][1], s[i][2]), s[i][3]);
+        y[i][0] = add(add(s[i][0], s[i][1]), s[i][2]);
+        y[i][1] = sub(sub(s[i][1], s[i][2]), s[i][3]);
     }
     float4 bias = make_float4(0.f, 0.f, 0.f, 0.f), sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = bias;
     if (a.bias) bias = *reinterpret_cast<const float4*>(a.bias + c);
@@ -432,34 +390,16 @@ __global__ __launch_bounds__(256) void wino_dy_kernel(const WinoDyArgs a) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long R = (long long)a.n * a.D * Ht * Wt;
     if (idx >= R * C4) return;
-    const unsigned r = (unsigned)(idx / C4);
-    const int c = (int)(idx - (long long)r * C4) << 2;
-    unsigned q = r, t = q / (unsigned)Wt;
-    const int tw = (int)(q - t * (unsigned)Wt); q = t; t = q / (unsigned)Ht;
-    const int th = (int)(q - t * (unsigned)Ht);                    // t = (n, z) plane index
+    unsigned r, t;                                   // t = (n, z) plane index
+    int c, tw, th;
+    tile_decode(idx, C4, 2, Ht, Wt, r, c, tw, th, t);
     const float* yp = a.dy + ((long long)t * a.H * a.W + (long long)(2 * th) * a.W + 2 * tw) * a.ldy + c;
     float4 y[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) y[i][j] = *reinterpret_cast<const float4*>(yp + ((long long)i * a.W + j) * a.ldy);
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 s[4][2];                                  // A y
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        s[0][j] = y[0][j];
-        s[1][j] = f4_add(y[0][j], y[1][j]);
-        s[2][j] = f4_sub(y[0][j], y[1][j]);
-        s[3][j] = f4_sub(zero, y[1][j]);
-    }
-    float* mp = a.dM + (long long)r * a.Cout + c;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {                    // (A y) A^T
-        *reinterpret_cast<float4*>(mp + (4 * i + 0) * a.ptm) = s[i][0];
-        *reinterpret_cast<float4*>(mp + (4 * i + 1) * a.ptm) = f4_add(s[i][0], s[i][1]);
-        *reinterpret_cast<float4*>(mp + (4 * i + 2) * a.ptm) = f4_sub(s[i][0], s[i][1]);
-        *reinterpret_cast<float4*>(mp + (4 * i + 3) * a.ptm) = f4_sub(zero, s[i][1]);
-    }
+    a_y_at_store(y[0][0], y[0][1], y[1][0], y[1][1], a.dM + (long long)r * a.Cout + c, a.ptm);
 }
 
 // dw[(kd 3 + a) 3 + b][co][ci] += sum_ij G[i][a] G[j][b] dU[4i+j][kd][co][ci]   (G^T dU G): one thread per (kd, co, ci); accumulates into dw
@@ -518,87 +458,74 @@ extern "C" int forge_wino_dw(const float* dU, float* dw, int Cout, int Cin, int 
     return 0;
 }
 
+// the one launch behind the three weight entries: one thread per element of `total`
+template <typename K, typename... A>
+static int wino_weights_launch(const char* name, K kernel, long long total, forge_stream_t stream, A... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, args...);
+    FORGE_LAUNCH_CHECK(name);
+    return 0;
+}
+
 extern "C" int forge_wino_weights(const float* wp, float* U, int Cout, int Cin, int kd, int transpose, forge_stream_t stream) {
     FORGE_REQUIRE(wp && U && Cout > 0 && Cin > 0 && (kd == 1 || kd == 3), FORGE_EINVAL, "forge_wino_weights: bad argument (kd = 1 or 3)");
-    const long long total = (long long)kd * Cout * Cin;
-    hipLaunchKernelGGL(wino_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, wp, U, Cout, Cin, kd, transpose);
-    FORGE_LAUNCH_CHECK("forge_wino_weights");
-    return 0;
+    return wino_weights_launch("forge_wino_weights", wino_weight_kernel, (long long)kd * Cout * Cin, stream, wp, U, Cout, Cin, kd, transpose);
 }
 
 extern "C" int forge_wino_weights_dn(const float* wp, float* Ud, int Cout, int Cin, forge_stream_t stream) {
     FORGE_REQUIRE(wp && Ud && Cout > 0 && Cin > 0, FORGE_EINVAL, "forge_wino_weights_dn: bad argument");
-    const long long total = (long long)Cout * Cin;
-    hipLaunchKernelGGL(wino_weight_dn_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, wp, Ud, Cout, Cin);
-    FORGE_LAUNCH_CHECK("forge_wino_weights_dn");
+    return wino_weights_launch("forge_wino_weights_dn", wino_weight_nest_kernel<4, depth_row_f23>, (long long)Cout * Cin, stream, wp, Ud, Cout, Cin);
+}
+
+extern "C" int forge_wino_weights_dn4(const float* wp, float* Ud, int Cout, int Cin, forge_stream_t stream) {
+    FORGE_REQUIRE(wp && Ud && Cout > 0 && Cin > 0, FORGE_EINVAL, "forge_wino_weights_dn4: bad argument");
+    return wino_weights_launch("forge_wino_weights_dn4", wino_weight_nest_kernel<6, depth_row_f43>, (long long)Cout * Cin, stream, wp, Ud, Cout, Cin);
+}
+
+// The three input entries. IN_DN4: the depth stage of the F(4, 3) nest in front (wino_input_dn4_kernel: one thread per tile of a GROUP of four planes and channel,
+// six operand rows per group tile); IN_DY: also dM = A y A^T (wino_input_kernel<true>; dense operands, no view mean).
+enum WinoInKind { IN_PLAIN, IN_DN4, IN_DY };
+
+static int wino_input_impl(const char* name, WinoInKind kind, const float* in, int ld, long long bs, float* V, int ldv, long long ptv, float* dM, int n, int D, int H,
+                           int W, int C, int nsum, long long sum_stride, forge_stream_t stream) {
+    const bool dn4 = kind == IN_DN4;
+    FORGE_REQUIRE(in && V && (kind != IN_DY || dM), FORGE_EINVAL, "%s: null pointer argument", name);
+    FORGE_REQUIRE(nsum >= 1 && (nsum == 1 || sum_stride > 0), FORGE_EINVAL, "%s: nsum >= 1, and a positive sum_stride (rows) with nsum > 1", name);
+    FORGE_REQUIRE(!dn4 || (D > 0 && D % 4 == 0), FORGE_EINVAL, "%s: D=%d must be a multiple of 4", name, D);
+    const bool ok = n > 0 && D > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C > 0 && C % 4 == 0 && ld >= C && ld % 4 == 0 && ldv >= C && ldv % 4 == 0;
+    if (kind == IN_DY)                                // (this entry takes no ldv: its operands are dense)
+        FORGE_REQUIRE(ok, FORGE_ESHAPE, "%s: n=%d D=%d H=%d W=%d C=%d ld=%d (H, W even; C, ld multiples of 4)", name, n, D, H, W, C, ld);
+    FORGE_REQUIRE(ok, FORGE_ESHAPE, "%s: n=%d D=%d H=%d W=%d C=%d ld=%d ldv=%d (H, W even; C, ld, ldv multiples of 4)", name, n, D, H, W, C, ld, ldv);
+    WinoInArgs a;
+    a.in = in; a.ld = ld; a.bs = bs > 0 ? bs : (long long)D * H * W; a.V = V; a.ldv = ldv; a.n = n; a.D = D; a.H = H; a.W = W; a.C = C;
+    a.nsum = nsum; a.ss = sum_stride;
+    const long long R = (long long)n * (dn4 ? D / 4 : D) * (H / 2) * (W / 2), rows = dn4 ? 6 * R : R;      // thread tiles; operand rows per point
+    a.ptv = ptv > 0 ? ptv : rows * ldv;
+    a.dM = dM; a.ptm = dM ? R * C : 0;
+    FORGE_REQUIRE(rows < (1ll << 31), FORGE_ESHAPE, dn4 ? "%s: more than 2^31 operand rows; split the batch" : "%s: more than 2^31 tiles; split the batch", name);
+    const long long total = R * (dn4 ? C : C / 4), grid = (total + 255) / 256;
+    FORGE_REQUIRE(grid < (1ll << 31), FORGE_ESHAPE, "%s: grid too large", name);
+    const dim3 g((unsigned)grid), b(256);
+    if (dn4) hipLaunchKernelGGL(wino_input_dn4_kernel, g, b, 0, (hipStream_t)stream, a);
+    else if (kind == IN_DY) hipLaunchKernelGGL(wino_input_kernel<true>, g, b, 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(wino_input_kernel<false>, g, b, 0, (hipStream_t)stream, a);
+    FORGE_LAUNCH_CHECK(name);
     return 0;
 }
 
 extern "C" int forge_wino_input(const float* in, int ld, long long bs, float* V, int ldv, long long ptv, int n, int D, int H, int W, int C,
                                 int nsum, long long sum_stride, forge_stream_t stream) {
-    FORGE_REQUIRE(in && V, FORGE_EINVAL, "forge_wino_input: null pointer argument");
-    FORGE_REQUIRE(nsum >= 1 && (nsum == 1 || sum_stride > 0), FORGE_EINVAL, "forge_wino_input: nsum >= 1, and a positive sum_stride (rows) with nsum > 1");
-    FORGE_REQUIRE(n > 0 && D > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C > 0 && C % 4 == 0 && ld >= C && ld % 4 == 0 && ldv >= C && ldv % 4 == 0,
-                  FORGE_ESHAPE, "forge_wino_input: n=%d D=%d H=%d W=%d C=%d ld=%d ldv=%d (H, W even; C, ld, ldv multiples of 4)", n, D, H, W, C, ld, ldv);
-    WinoInArgs a;
-    a.in = in; a.ld = ld; a.bs = bs > 0 ? bs : (long long)D * H * W; a.V = V; a.ldv = ldv; a.n = n; a.D = D; a.H = H; a.W = W; a.C = C;
-    a.nsum = nsum; a.ss = sum_stride;
-    const long long R = (long long)n * D * (H / 2) * (W / 2);
-    a.ptv = ptv > 0 ? ptv : R * ldv;
-    FORGE_REQUIRE(R < (1ll << 31), FORGE_ESHAPE, "forge_wino_input: more than 2^31 tiles; split the batch");
-    const long long total = R * (C / 4), grid = (total + 255) / 256;
-    FORGE_REQUIRE(grid < (1ll << 31), FORGE_ESHAPE, "forge_wino_input: grid too large");
-    a.dM = nullptr; a.ptm = 0;
-    hipLaunchKernelGGL(wino_input_kernel<false>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
-    FORGE_LAUNCH_CHECK("forge_wino_input");
-    return 0;
+    return wino_input_impl("forge_wino_input", IN_PLAIN, in, ld, bs, V, ldv, ptv, nullptr, n, D, H, W, C, nsum, sum_stride, stream);
 }
 
 // forge_wino_input with the depth stage of the F(4, 3) nest (wino_input_dn4_kernel): V6 [16][n][D/4][6][H/2 W/2][C], the operand of forge_wino_gemm_dn4.
 // ptv: floats between points (0 = dense, n (D/4) 6 (H/2)(W/2) ldv).
 extern "C" int forge_wino_input_dn4(const float* in, int ld, long long bs, float* V6, int ldv, long long ptv, int n, int D, int H, int W, int C,
                                     int nsum, long long sum_stride, forge_stream_t stream) {
-    FORGE_REQUIRE(in && V6, FORGE_EINVAL, "forge_wino_input_dn4: null pointer argument");
-    FORGE_REQUIRE(nsum >= 1 && (nsum == 1 || sum_stride > 0), FORGE_EINVAL, "forge_wino_input_dn4: nsum >= 1, and a positive sum_stride (rows) with nsum > 1");
-    FORGE_REQUIRE(D > 0 && D % 4 == 0, FORGE_EINVAL, "forge_wino_input_dn4: D=%d must be a multiple of 4", D);
-    FORGE_REQUIRE(n > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C > 0 && C % 4 == 0 && ld >= C && ld % 4 == 0 && ldv >= C && ldv % 4 == 0,
-                  FORGE_ESHAPE, "forge_wino_input_dn4: n=%d D=%d H=%d W=%d C=%d ld=%d ldv=%d (H, W even; C, ld, ldv multiples of 4)", n, D, H, W, C, ld, ldv);
-    WinoInArgs a;
-    a.in = in; a.ld = ld; a.bs = bs > 0 ? bs : (long long)D * H * W; a.V = V6; a.ldv = ldv; a.n = n; a.D = D; a.H = H; a.W = W; a.C = C;
-    a.nsum = nsum; a.ss = sum_stride;
-    const long long RG = (long long)n * (D / 4) * (H / 2) * (W / 2);
-    a.ptv = ptv > 0 ? ptv : 6 * RG * ldv;
-    FORGE_REQUIRE(6 * RG < (1ll << 31), FORGE_ESHAPE, "forge_wino_input_dn4: more than 2^31 operand rows; split the batch");
-    const long long total = RG * C, grid = (total + 255) / 256;
-    FORGE_REQUIRE(grid < (1ll << 31), FORGE_ESHAPE, "forge_wino_input_dn4: grid too large");
-    a.dM = nullptr; a.ptm = 0;
-    hipLaunchKernelGGL(wino_input_dn4_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
-    FORGE_LAUNCH_CHECK("forge_wino_input_dn4");
-    return 0;
-}
-
-extern "C" int forge_wino_weights_dn4(const float* wp, float* Ud, int Cout, int Cin, forge_stream_t stream) {
-    FORGE_REQUIRE(wp && Ud && Cout > 0 && Cin > 0, FORGE_EINVAL, "forge_wino_weights_dn4: bad argument");
-    const long long total = (long long)Cout * Cin;
-    hipLaunchKernelGGL(wino_weight_dn4_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, wp, Ud, Cout, Cin);
-    FORGE_LAUNCH_CHECK("forge_wino_weights_dn4");
-    return 0;
+    return wino_input_impl("forge_wino_input_dn4", IN_DN4, in, ld, bs, V6, ldv, ptv, nullptr, n, D, H, W, C, nsum, sum_stride, stream);
 }
 
 extern "C" int forge_wino_input_dy(const float* dy, int ld, float* V, float* dM, int n, int D, int H, int W, int C, forge_stream_t stream) {
-    FORGE_REQUIRE(dy && V && dM, FORGE_EINVAL, "forge_wino_input_dy: null pointer argument");
-    FORGE_REQUIRE(n > 0 && D > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C > 0 && C % 4 == 0 && ld >= C && ld % 4 == 0, FORGE_ESHAPE,
-                  "forge_wino_input_dy: n=%d D=%d H=%d W=%d C=%d ld=%d (H, W even; C, ld multiples of 4)", n, D, H, W, C, ld);
-    WinoInArgs a;
-    a.in = dy; a.ld = ld; a.bs = (long long)D * H * W; a.V = V; a.ldv = C; a.n = n; a.D = D; a.H = H; a.W = W; a.C = C; a.nsum = 1; a.ss = 0;
-    const long long R = (long long)n * D * (H / 2) * (W / 2);
-    a.ptv = R * C; a.dM = dM; a.ptm = R * C;
-    FORGE_REQUIRE(R < (1ll << 31), FORGE_ESHAPE, "forge_wino_input_dy: more than 2^31 tiles; split the batch");
-    const long long total = R * (C / 4), grid = (total + 255) / 256;
-    FORGE_REQUIRE(grid < (1ll << 31), FORGE_ESHAPE, "forge_wino_input_dy: grid too large");
-    hipLaunchKernelGGL(wino_input_kernel<true>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
-    FORGE_LAUNCH_CHECK("forge_wino_input_dy");
-    return 0;
+    return wino_input_impl("forge_wino_input_dy", IN_DY, dy, ld, 0, V, C, 0, dM, n, D, H, W, C, 1, 0, stream);
 }
 
 static int wino_output_impl(const float* Mm, const float* Mm2, long long bs2, long long pt2, const float* bias, const float* scale, const float* shift, float slope, const float* residual,

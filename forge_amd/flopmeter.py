@@ -8,6 +8,7 @@ Only eager launches made by this process are seen (a hipGraph replay makes no Py
 import torch
 
 from . import _lib
+from .convops import WINO_FORMS
 
 
 def _v(a):
@@ -20,16 +21,11 @@ def _igemm(a):          # forge_conv_igemm(in1,C1,ld1,bs1,in2,C2,ld2,bs2,wp,bias
     return 2.0 * n * D * H * W * Cout * ntaps * (C1 + C2)          # merged transposed-conv phases: M rows x ntaps / P taps x P phases = the same product
 
 
-def _wino_gemm(a):      # forge_wino_gemm(V1,C1,ld1,bs1,pt1,V2,C2,ld2,bs2,pt2,U,Mm,n,D,Ht,Wt,Cout,kd,tile,stream) / forge_wino_gemm_half (same, no tile)
-    return 2.0 * 16 * _v(a[12]) * _v(a[13]) * _v(a[14]) * _v(a[15]) * _v(a[16]) * _v(a[17]) * (_v(a[1]) + _v(a[6]))
-
-
-def _wino_gemm_dn(a):   # forge_wino_gemm_dn(V1,C1,ld1,bs1,pt1,V2,C2,ld2,bs2,pt2,Ud,Mm,n,D,Ht,Wt,Cout,kd,stream): 4 positions x Cin per PAIR of planes
-    return 2.0 * 16 * _v(a[12]) * (_v(a[13]) // 2) * _v(a[14]) * _v(a[15]) * _v(a[16]) * 4 * (_v(a[1]) + _v(a[6]))
-
-
-def _wino_gemm_dn4(a):  # forge_wino_gemm_dn4(V1,C1,ld1,bs1,pt1,V2,C2,ld2,bs2,pt2,Ud,Mm,n,D,Ht,Wt,Cout,kd,stream): 6 positions x Cin per FOUR planes
-    return 2.0 * 16 * _v(a[12]) * (_v(a[13]) // 4) * _v(a[14]) * _v(a[15]) * _v(a[16]) * 6 * (_v(a[1]) + _v(a[6]))
+def _wino_counter(form):    # forge_wino_gemm* (V1,C1,ld1,bs1,pt1,V2,C2,ld2,bs2,pt2,U,Mm,n,D,Ht,Wt,Cout,kd,[tile,]stream): 16 points x R rows x Cout x the form's
+    def count(a):           # K loops of Cin per output plane (convops.WINO_FORMS: kd, 2 - four positions per PAIR of planes - or 3/2 - six per FOUR planes)
+        loops = _v(a[17]) if form.kloops is None else form.kloops
+        return float(2 * 16 * _v(a[12]) * _v(a[13]) * _v(a[14]) * _v(a[15]) * _v(a[16]) * loops * (_v(a[1]) + _v(a[6])))
+    return count
 
 
 def _wgrad(a):          # forge_conv_wgrad(dy,ldy,x1,C1,ld1,bs1,x2,C2,ld2,bs2,dwp,n,D,H,W,is,Di,Hi,Wi,Cout,taps,ntaps,stream)
@@ -70,10 +66,11 @@ def _token_bwd(a):      # forge_token_linear_bwd(dy,lddy,x,ldx,w,gamma,beta,stat
     return 2.0 * _v(a[16]) * _v(a[17]) * _v(a[18]) * ((1 if dxn else 0) + (1 if _v(a[10]) else 0))
 
 
-_ENTRIES = {"forge_conv_igemm": _igemm, "forge_wino_gemm": _wino_gemm, "forge_wino_gemm_half": _wino_gemm, "forge_wino_gemm_dn": _wino_gemm_dn, "forge_wino_gemm_dn4": _wino_gemm_dn4, "forge_conv_wgrad": _wgrad, "forge_wino_wgrad": _wino_wgrad,
+_ENTRIES = {"forge_conv_igemm": _igemm, **{f.gemm: _wino_counter(f) for f in WINO_FORMS.values()}, "forge_conv_wgrad": _wgrad, "forge_wino_wgrad": _wino_wgrad,
             "forge_attention_fwd": _attention, "forge_attention_fwd_lse": _attention_lse, "forge_attention_bwd": _attention_bwd,
             "forge_attention_mh_fwd": _attention_mh, "forge_attention_mh_bwd": _attention_mh_bwd,
             "forge_token_linear_fwd": _token_fwd, "forge_token_linear_bwd": _token_bwd}
+_wino_gemm, _wino_gemm_dn, _wino_gemm_dn4 = (_ENTRIES[WINO_FORMS[k].gemm] for k in ("points", "dn", "dn4"))      # the counters by form, for the tests
 
 
 class FlopMeter:

@@ -237,11 +237,12 @@ def bn_act_rows(bn, rows, slope=1.0, residual=None, stats=None):
     raise RuntimeError("forge_amd: unsupported BatchNorm configuration %r" % (bn,))
 
 
-def _step_scratch(R, C, dev, nest=False):
+def _step_scratch(R, C, dev, form=None):
     """One buffer for the point products of a GRU step's 2C-column (gates) and C-column (state, fusion_conv) launches over R tile rows, sized for the
-    larger of their forms: convops.wino_gemm returns each launch's products as a view of its front. nest: the step's launches take the depth nest
-    (16 planes)."""
-    P2, P1 = (8 if co.wino_half_applies(R, c, C) and not nest else 16 for c in (2 * C, C))
+    larger of their forms: convops.wino_gemm returns each launch's products as a view of its front. form: the convops.WinoForm of the step's
+    launches (None: each launch's own choice between the points and their half form)."""
+    F = co.WINO_FORMS
+    P2, P1 = ((form or F["half" if co.wino_half_applies(R, c, C) else "points"]).P for c in (2 * C, C))
     return torch.empty(max(P2 * 2 * C, P1 * C) * R, dtype=torch.float32, device=dev)
 
 
@@ -423,11 +424,11 @@ def _input_products(Vx, U, n, geo, Cout):
     return co.wino_gemm(Vx, C, None, 0, U, None, n, D, H // 2, W // 2, Cout, half=co.wino_half_applies(R, Cout, C))
 
 
-def _h0_wino(p, xr, grp, V, Mm, t0, h, nest=False):
+def _h0_wino(p, xr, grp, V, Mm, t0, h, wk="_U"):
     """h = fusion_conv(mean of the views grp of xr [b,t,D,H,W,C]): two Winograd convolutions with the folded BatchNorm + LeakyReLU tails
-    (scratch V, Mm, t0). nest: their point GEMMs run the depth nest on p's fc0_Ud / fc3_Ud."""
+    (scratch V, Mm, t0). wk: the key suffix of their weights in p - "_Ud": their point GEMMs run the depth nest."""
     b, t, D, H, W, C = xr.shape
-    gemm = lambda k: co.wino_gemm(V, C, None, 0, p[k + ("_Ud" if nest else "_U")], Mm, b, D, H // 2, W // 2, C)
+    gemm = lambda k: co.wino_gemm(V, C, None, 0, p[k + wk], Mm, b, D, H // 2, W // 2, C)
     _wino_view_mean(xr, grp, V)
     Mp = gemm("fc0")
     co.wino_output(Mp, p["fc0_b"], *p["bn1"], 0.01, None, None, None, t0, None, None, b, D, H, W, C, C, co.EPI_AFFINE_ACT)
@@ -446,7 +447,7 @@ def _h0_direct(p, xr, grp, t0, h):
                   epilogue=co.EPI_AFFINE_ACT)
 
 
-def _wino_step(geo, x, view, views, wg, wo, V, Mm, h, z, hr, hn, out=None, r=None, cand=None, nest=None, nest4=False):
+def _wino_step(geo, x, view, views, wg, wo, V, Mm, h, z, hr, hn, out=None, r=None, cand=None, calls=None):
     """One ConvGRU step on the Winograd launches over geo = (b, D, H, W): transform h, point GEMMs, inverse transform fused with the gate tail
     (z, hr = h r; r into `r`); transform hr, point GEMMs, inverse transform fused with tanh / lerp (hn; tanh(c) into `cand`, the fusion_norm
     folded output into `out`). (Fusing each inverse transform with the next input transform through LDS was built and measured slower -
@@ -455,23 +456,17 @@ def _wino_step(geo, x, view, views, wg, wo, V, Mm, h, z, hr, hn, out=None, r=Non
       split  x = (MXg, MXc), the input-half products of `views` views per scene (_input_products): point GEMMs over V_h alone, K = 3C,
              hidden-half weights; the inverse transforms add view `view`'s products
     wg = (U, bias), wo = (U, bias, scale, shift). V: the buffer of both transforms, or None for a new one each (returned: the training node
-    keeps them for the weight gradient). Mm: the point-product scratch (_step_scratch). nest (full form only) = (Ud_gates, Ud_state): both point
-    GEMMs run the depth nest (convops.wino_gemm with wino_pack_packed_dn's weights) on these weights and hand 16 planes to the same inverse transforms.
-    nest4: the nest's F(4, 3) form - x and V hold wino_input_dn4's operands (1.5 x the rows), nest wino_pack_packed_dn4's weights."""
+    keeps them for the weight gradient). Mm: the point-product scratch (_step_scratch). calls = (input transform, point GEMM) of the form that x, V
+    and the weights are in (convops.wino_calls; default: convops.wino_input / wino_gemm, which read the form from the weights)."""
     b, D, H, W = geo
     C = h.shape[-1]
-    split = isinstance(x, tuple)
+    transform, gemm = calls or co.wino_calls(co.WINO_FORMS["points"])
 
     def conv(src, U, Cout, i):
-        if nest4:
-            Vs = co.wino_input_dn4(src, C, C, b, D, H, W, out=V)
-            return Vs, co.wino_gemm_dn4(x, C, Vs, C, nest[i], Mm, b, D, H // 2, W // 2, Cout, view=view, views=views), {}
-        Vs = co.wino_input(src, C, C, b, D, H, W, out=V)
-        if nest is not None:
-            return Vs, co.wino_gemm(x, C, Vs, C, nest[i], Mm, b, D, H // 2, W // 2, Cout, view=view, views=views), {}
-        if split:
-            return Vs, co.wino_gemm(Vs, C, None, 0, U, Mm, b, D, H // 2, W // 2, Cout), dict(Mm2=x[i], view=view, views=views)
-        return Vs, co.wino_gemm(x, C, Vs, C, U, Mm, b, D, H // 2, W // 2, Cout, view=view, views=views), {}
+        Vs = transform(src, C, C, b, D, H, W, out=V)
+        if isinstance(x, tuple):                      # split adds Mm2, full does not
+            return Vs, gemm(Vs, C, None, 0, U, Mm, b, D, H // 2, W // 2, Cout), dict(Mm2=x[i], view=view, views=views)
+        return Vs, gemm(x, C, Vs, C, U, Mm, b, D, H // 2, W // 2, Cout, view=view, views=views), {}
 
     Vh, G, add = conv(h, wg[0], 2 * C, 0)
     co.wino_output(G, wg[1], None, None, 1.0, None, h, None, z, hr, r, *geo, 2 * C, C, co.EPI_GRU_GATES, **add)
@@ -496,6 +491,10 @@ def _direct_step(grid, x, wg, wo, h, z, hr, hn, out=None, r=None, cand=None, bs=
     co.conv_igemm(*ops, *wo, 1.0, res, h, z, hn, out, grid, ig, C, C, taps, epilogue=co.EPI_GRU_OUT, bs1=bs, out3=cand)
 
 
+_WKEY = {None: "_U", co.WINO_FORMS["dn"]: "_Ud", co.WINO_FORMS["dn4"]: "_Ud4"}      # form -> key suffix of its weights in ConvGRU_3D's pack cache
+_PACKS = ((None, ("gate", "out", "fc0", "fc3")), (co.WINO_FORMS["dn"], ("gate", "out", "fc0", "fc3")), (co.WINO_FORMS["dn4"], ("gate", "out")))
+
+
 def _fuse_eval(gru, xr, groups, wino, split, h0=None, keep=None, const0=None):
     """The forward of the eval-weight fusions (ConvGRU_3D.fuse_hip, fuse_groups_hip, _FuseFrozen) over xr [b,t,D,H,W,C] rows, on the Winograd
     launches (wino: the caller has checked wino_fits) or the direct implicit-GEMM kernel. Per group of views: h = fusion_conv(mean of its views)
@@ -508,38 +507,36 @@ def _fuse_eval(gru, xr, groups, wino, split, h0=None, keep=None, const0=None):
     dev, M, vol = xr.device, b * D * H * W, D * H * W
     geo = (b, D, H, W)
     new = lambda c=C: torch.empty(M, c, dtype=torch.float32, device=dev)
-    p = gru._packed_halves(wino) if (split or const0 is not None) else gru._packed_wino() if wino else gru._packed()
-    wk = "_U" if wino else "_w"
-    weights = lambda half: ((p["gate" + wk + half], p["gate_b"]), (p["out" + wk + half], p["out_b"], *p["norm"]))
-    wg, wo = weights("h" if split else "")
-    nest, nest_h0, nest4 = None, False, False
-    # X, the input side of the steps: V_x (Winograd, full), the products (MXg, MXc) (Winograd, split) or per view (gx, cx) (direct, split)
+    # the form of the steps' two launches and that of fusion_conv's, chosen once per call from the rules of convops.WINO_FORMS; None (Winograd): the
+    # launch's own choice between the points and their half form, read from the "_U" weights by convops.wino_gemm
+    step, conv0 = None, None
     if wino:
         R = b * D * (H // 2) * (W // 2)
-        V = V6 = None
+        F = co.WINO_FORMS
+        both = lambda form: all(form.applies(R, D, H // 2, W // 2, c, 2 * C) for c in (2 * C, C))
         # the full steps of the plain eval fusion take the depth nest where both of their launches qualify (K = 2C per depth position)
-        if (not split and keep is None and const0 is None
-                and all(co.wino_depth_nest_applies(R, D, H // 2, W // 2, c, 2 * C) for c in (2 * C, C))):
-            pd = gru._packed_wino_dn()
-            nest = (pd["gate_Ud"], pd["out_Ud"])
-            # fusion_conv's two launches (K = C per position) follow where the rule holds for them (tools/wino_dn_probe.py: 0.90 of the four-point pair)
-            nest_h0 = co.wino_depth_nest_applies(R, D, H // 2, W // 2, C, C)
-            # the steps take the nest's F(4, 3) form where its rule holds and its 1.5 x operand planes fit the buffer range: X and the per-step
-            # transforms of h and h r through wino_input_dn4. fusion_conv (K = C per position, four K-steps per loop) stays on F(2, 3).
-            if (all(co.wino_depth_nest4_applies(R, D, H // 2, W // 2, c, 2 * C) for c in (2 * C, C))
-                    and co.wino_fits(b, D, H, W, C, views=t, nest4=True)):
-                pd = gru._packed_wino_dn4()
-                nest, nest4 = (pd["gate_Ud4"], pd["out_Ud4"]), True
-        if nest4:
-            X = co.wino_input_dn4(xr, C, C, b * t, D, H, W)               # [16][b t (D/4) 6 Ht Wt][C]
-            V6 = torch.empty(16, R // 4 * 6, C, dtype=torch.float32, device=dev)
-            V = V6.reshape(-1)[:16 * R * C].view(16, R, C)               # fusion_conv's transforms: the front of the same buffer
-        else:
-            X = co.wino_input(xr, C, C, b * t, D, H, W)                   # [16][b t D Ht Wt][C]: all views of all scenes, one launch
-            if split:
-                X = (_input_products(X, p["gate_Ux"], b * t, geo, 2 * C), _input_products(X, p["out_Ux"], b * t, geo, C))
-            V = torch.empty(16, R, C, dtype=torch.float32, device=dev)
-        Mm = _step_scratch(R, C, dev, nest is not None)
+        if not split and keep is None and const0 is None and both(F["dn"]):
+            # its F(4, 3) form where that rule holds and its 1.5 x operand planes fit the buffer range: X and the per-step transforms of h and h r
+            # through forge_wino_input_dn4
+            step = F["dn4"] if both(F["dn4"]) and co.wino_fits(b, D, H, W, C, views=t, form=F["dn4"]) else F["dn"]
+            # fusion_conv's two launches (K = C per position) follow where the rule holds for them (tools/wino_dn_probe.py: 0.90 of the four-point
+            # pair) and stay on F(2, 3) (four K-steps per loop)
+            conv0 = F["dn"] if F["dn"].applies(R, D, H // 2, W // 2, C, C) else None
+    p = gru._packed_halves(wino) if (split or const0 is not None) else gru._packed_wino(step) if wino else gru._packed()
+    wk = _WKEY[step] if wino else "_w"
+    weights = lambda half: ((p["gate" + wk + half], p["gate_b"]), (p["out" + wk + half], p["out_b"], *p["norm"]))
+    wg, wo = weights("h" if split else "")
+    # X, the input side of the steps: V_x (Winograd, full), the products (MXg, MXc) (Winograd, split) or per view (gx, cx) (direct, split)
+    if wino:
+        calls = co.wino_calls(step or F["points"])
+        X = calls[0](xr, C, C, b * t, D, H, W)                            # [16][b t D Ht Wt x step's rows][C]: all views of all scenes, one launch
+        if split:
+            X = (_input_products(X, p["gate_Ux"], b * t, geo, 2 * C), _input_products(X, p["out_Ux"], b * t, geo, C))
+        # one buffer for the transforms of h and h r in the steps' form; fusion_conv's plain transforms (and const0's step) alias its front - the
+        # F(4, 3) operands have 1.5 x the rows
+        Vs = torch.empty(16, int(R * (step.rows if step else 1)), C, dtype=torch.float32, device=dev)
+        V = Vs.reshape(-1)[:16 * R * C].view(16, R, C)
+        Mm = _step_scratch(R, C, dev, step)
     elif split:                                                            # the input halves once per view (no bias: added with the hidden half)
         X = {}
         for ti in sorted({ti for g in groups for ti in g}):
@@ -554,7 +551,7 @@ def _fuse_eval(gru, xr, groups, wino, split, h0=None, keep=None, const0=None):
         if h0 is not None:
             h.copy_(h0.permute(0, 2, 3, 4, 1).reshape(M, C))
         elif wino:
-            _h0_wino(p, xr, grp, V, Mm, t0, h, nest_h0)
+            _h0_wino(p, xr, grp, V, Mm, t0, h, _WKEY[conv0])
         else:
             _h0_direct(p, xr, grp, t0, h)
         if keep is not None:
@@ -575,7 +572,7 @@ def _fuse_eval(gru, xr, groups, wino, split, h0=None, keep=None, const0=None):
             elif const0 is not None and k == 0:
                 _wino_step(geo, (const0["MXg0"], const0["MXc0"]), 0, 1, *weights("h"), V, Mm, h, z, hr, hn, last, r, cand)
             else:
-                _wino_step(geo, X, ti, t, wg, wo, V6 if nest4 else V, Mm, h, z, hr, hn, last, r, cand, nest=nest, nest4=nest4)
+                _wino_step(geo, X, ti, t, wg, wo, Vs, Mm, h, z, hr, hn, last, r, cand, calls=calls)
             if keep is not None:
                 keep += [h, z, r, cand]
             h, hn = hn, h
@@ -978,27 +975,16 @@ class ConvGRU_3D(co.PackedModule):
         t = x.shape[1]
         return _eval_chunks(x, lambda xr, wino, i, j: _fuse_eval(self, xr, [range(t)], wino, False, h0=None if h0 is None else h0[i:j]))[0]
 
-    def _packed_wino(self):
-        """Winograd-domain weights U = G w G^T [16][3][Cout][Cin] of the four 3x3x3 convolutions (convops.wino_pack_weight)."""
+    def _packed_wino(self, form=None):
+        """_packed plus the Winograd-domain weights (convops.wino_pack) under their _WKEY suffix, filled in the order of _PACKS up to `form` (a
+        convops.WINO_FORMS row; None: the first only): U = G w G^T [16][3][Cout][Cin] of the four 3x3x3 convolutions ("<conv>_U"), the F(2, 3)
+        nest's [16][2][2][Cout][Cin] of all four ("_Ud"), the F(4, 3) nest's [16][6][Cout][Cin] of the two GRU convolutions ("_Ud4")."""
         p = self._packed()
-        if "gate_U" not in p:
-            cell, fc = self.cells[0], self.fusion_conv
-            p.update({"gate_U": co.wino_pack_weight(cell.conv_gate.weight), "out_U": co.wino_pack_weight(cell.out_gate.weight),
-                      "fc0_U": co.wino_pack_weight(fc[0].weight), "fc3_U": co.wino_pack_weight(fc[3].weight)})
-        return p
-
-    def _packed_wino_dn(self):
-        """_packed_wino plus the depth-nest weights U' [16][2][2][Cout][Cin] of the four 3x3x3 convolutions (convops.wino_pack_packed_dn)."""
-        p = self._packed_wino()
-        if "gate_Ud" not in p:
-            p.update({k + "_Ud": co.wino_pack_packed_dn(p[k + "_w"]) for k in ("gate", "out", "fc0", "fc3")})
-        return p
-
-    def _packed_wino_dn4(self):
-        """_packed_wino_dn plus the F(4, 3) nest's weights U'' [16][6][Cout][Cin] of the two GRU convolutions (convops.wino_pack_packed_dn4)."""
-        p = self._packed_wino_dn()
-        if "gate_Ud4" not in p:
-            p.update({k + "_Ud4": co.wino_pack_packed_dn4(p[k + "_w"]) for k in ("gate", "out")})
+        for f, convs in _PACKS:
+            if convs[0] + _WKEY[f] not in p:
+                p.update({k + _WKEY[f]: co.wino_pack(f or co.WINO_FORMS["points"], p[k + "_w"]) for k in convs})
+            if f is form:
+                break
         return p
 
     def _packed_halves(self, wino):

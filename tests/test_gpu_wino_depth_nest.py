@@ -26,13 +26,11 @@ import conv_igemm_cases as cc
 import convgru_cases as gc
 import wino_cases as wc
 import wino_dn_cases as dn
+from wino_gpu_util import EINVAL, F32, FWD, NAN, OutBuf, P, emitter, padded, twice
 from forge_amd import _lib, convops as co, flopmeter, synthetic as syn
 from forge_amd.fusion import ConvGRU_3D
 
 pytestmark = pytest.mark.gpu
-F32, NAN = torch.float32, float("nan")
-FWD = 1e-5                    # test_gpu_convgru_matrix.py's forward bound (relative to max |reference|)
-EINVAL = -1
 
 CASES = [wc.mk("dn_n%d_d%d_c%d_%d_o%d" % (n, D, C1, C2, Cout), "", n, D, 16, 16, C1, Cout, C2=C2)
          for D, n, (C1, C2), Cout in itertools.product((2, 4, 6), (1, 2), ((32, 32), (64, 0)), (32, 160))]
@@ -47,48 +45,7 @@ def dev():
     return torch.device("cuda:0")
 
 
-def emit(line):
-    print("wino_dn_matrix " + line)
-
-
-def P(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-class OutBuf:
-    """planes x rows x ld floats inside a CANARY-filled allocation with guard rows on both sides; every element of the body is named."""
-
-    def __init__(self, dev, planes, rows, ld):
-        self.shape, self.G = (planes, rows, ld), 4 * ld
-        self.t = torch.full((2 * self.G + planes * rows * ld,), cc.CANARY, dtype=torch.int32, device=dev)
-
-    def ptr(self):
-        return ctypes.c_void_p(self.t.data_ptr() + 4 * self.G)
-
-    def fetch(self, what):
-        torch.cuda.synchronize()
-        raw = self.t.cpu()
-        assert (raw[:self.G] == cc.CANARY).all() and (raw[-self.G:] == cc.CANARY).all(), (what, "guard rows were written")
-        body = raw[self.G:-self.G].view(F32).reshape(self.shape).clone()
-        assert torch.isfinite(body).all(), (what, "a named element is not finite")
-        return body
-
-
-def twice(fn, buf, what):
-    outs = []
-    for _ in range(2):
-        buf.t.fill_(cc.CANARY)
-        fn()
-        outs.append(buf.fetch(what))
-    assert torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32)), (what, "two runs differ")
-    return outs[0]
-
-
-def padded(t, dev, guard=4096):
-    """t on the device between NaN guards (operand padding): the tensor view of the middle."""
-    flat = torch.full((t.numel() + 2 * guard,), NAN, dtype=F32)
-    flat[guard:guard + t.numel()] = t.reshape(-1)
-    return flat.to(dev)[guard:guard + t.numel()].view(t.shape)
+emit = emitter("wino_dn_matrix")
 
 
 def run_chain(c, dev):

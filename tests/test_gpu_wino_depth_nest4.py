@@ -14,6 +14,7 @@ that depth to F(2, 3)), (C1, C2) in {(32, 32), (64, 0)}, Cout in {32, 160} (ragg
   ratio          q against the F(2, 3) nest and the four-point chain on the same inputs: printed, a row of profiles/r18_wino_dn4_matrix.txt under -s
   repeat         every launch once more on fresh canaries, bitwise
 test_bounds_reject_wrong_references: a swapped +- pair, a wrong sign in row 3 of A^T, rotated output planes, planes taken across the batch boundary.
+test_input_dn4_of_a_view_mean: forge_wino_input_dn4 with nsum = 2 on 1 x 8 x 4 x 4 x 4, torch.equal with the float32 restatement.
 test_refusals: D % 4 != 0, Ht Wt = 16, one depth tap, C1 / C2 not multiples of 32, an output plane beyond 32-bit offsets -> FORGE_EINVAL, no launch.
 test_fuse_hip_*: ConvGRU_3D.fuse_hip on 2 scenes x 3 views x 8 x 16 x 16 x 32 against the oracle GRU in float64 under test_gpu_convgru_matrix.py's forward
 bound, launch counts by entry; either switch off gives the launches and bits of before.
@@ -29,13 +30,11 @@ import convgru_cases as gc
 import wino_cases as wc
 import wino_dn4_cases as d4
 import wino_dn_cases as dn
+from wino_gpu_util import EINVAL, F32, FWD, NAN, OutBuf, P, emitter, padded, twice
 from forge_amd import _lib, convops as co, flopmeter, synthetic as syn
 from forge_amd.fusion import ConvGRU_3D
 
 pytestmark = pytest.mark.gpu
-F32, NAN = torch.float32, float("nan")
-FWD = 1e-5                    # test_gpu_convgru_matrix.py's forward bound (relative to max |reference|), as test_gpu_wino_depth_nest.py
-EINVAL = -1
 
 CASES = [wc.mk("dn4_n2_d8_c%d_%d_o%d" % (C1, C2, Cout), "", 2, 8, 16, 16, C1, Cout, C2=C2) for (C1, C2), Cout in itertools.product(((32, 32), (64, 0)), (32, 160))]
 CASES.append(wc.mk("dn4_n2_d4_c32_32_o32", "", 2, 4, 16, 16, 32, 32, C2=32))
@@ -50,48 +49,7 @@ def dev():
     return torch.device("cuda:0")
 
 
-def emit(line):
-    print("wino_dn4_matrix " + line)
-
-
-def P(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-class OutBuf:
-    """planes x rows x ld floats inside a CANARY-filled allocation with guard rows on both sides; every element of the body is named."""
-
-    def __init__(self, dev, planes, rows, ld):
-        self.shape, self.G = (planes, rows, ld), 4 * ld
-        self.t = torch.full((2 * self.G + planes * rows * ld,), cc.CANARY, dtype=torch.int32, device=dev)
-
-    def ptr(self):
-        return ctypes.c_void_p(self.t.data_ptr() + 4 * self.G)
-
-    def fetch(self, what):
-        torch.cuda.synchronize()
-        raw = self.t.cpu()
-        assert (raw[:self.G] == cc.CANARY).all() and (raw[-self.G:] == cc.CANARY).all(), (what, "guard rows were written")
-        body = raw[self.G:-self.G].view(F32).reshape(self.shape).clone()
-        assert torch.isfinite(body).all(), (what, "a named element is not finite")
-        return body
-
-
-def twice(fn, buf, what):
-    outs = []
-    for _ in range(2):
-        buf.t.fill_(cc.CANARY)
-        fn()
-        outs.append(buf.fetch(what))
-    assert torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32)), (what, "two runs differ")
-    return outs[0]
-
-
-def padded(t, dev, guard=4096):
-    """t on the device between NaN guards (operand padding): the tensor view of the middle."""
-    flat = torch.full((t.numel() + 2 * guard,), NAN, dtype=F32)
-    flat[guard:guard + t.numel()] = t.reshape(-1)
-    return flat.to(dev)[guard:guard + t.numel()].view(t.shape)
+emit = emitter("wino_dn4_matrix")
 
 
 def run_chain(c, dev):
@@ -195,6 +153,20 @@ def test_bounds_reject_wrong_references(dev, name):
         ratio = max(a / b for a, b in zip(wc.q_of(ch["out"], wrong, sig), yard))
         emit("%-22s wrong reference %-12s q / yardstick %.3g" % (name, mut, ratio))
         assert ratio > wc.SHARP, (name, mut, ratio)
+
+
+def test_input_dn4_of_a_view_mean(dev):
+    """forge_wino_input_dn4 with nsum > 1 - the argument path the three input entries share, otherwise only pinned for the plain transform: the mean of
+    two views sum_stride rows apart, then both stages, torch.equal with the float32 restatement. The smallest shape with an interior and both depth
+    edges: n = 1, D = 8 (two groups), H = W = 4, C = 4."""
+    L, st = _lib.lib(), _lib.current_stream
+    n, D, H, W, C, nsum = 1, 8, 4, 4, 4, 2
+    x = torch.randn(nsum, n, D, H, W, C, generator=torch.Generator().manual_seed(20))
+    xd = padded(x, dev)
+    vb = OutBuf(dev, 16, n * (D // 4) * 6 * (H // 2) * (W // 2), C)
+    got = twice(lambda: _lib.check(L.forge_wino_input_dn4(P(xd), C, 0, vb.ptr(), C, 0, n, D, H, W, C, nsum, n * D * H * W, st()), "forge_wino_input_dn4"),
+                vb, "input_dn4 of a view mean")
+    assert torch.equal(got, d4.input_transform_dn4(x, nsum, F32))
 
 
 def test_refusals(dev):

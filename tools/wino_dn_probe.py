@@ -55,11 +55,12 @@ def launch(args):
         Cin = C1 + C2
         V1, V2 = rn(16, R, C1), (rn(16, R, C2) if C2 else None)
         wp = rn(27, Cout, Cin) / (27 * Cin) ** 0.5
-        U, Ud = co.wino_pack_packed(wp), co.wino_pack_packed_dn(wp)
+        F = co.WINO_FORMS
+        U, Ud = co.wino_pack_packed(wp), co.wino_pack(F["dn"], wp)
         Mm = torch.empty(16 * R * Cout, device=dev)
         out_a, out_b = torch.empty(M, Cout, device=dev), torch.empty(M, Cout, device=dev)
         outp = lambda m, o: co.wino_output(m, None, None, None, 1.0, None, None, None, o, None, None, b, D, H, W, Cout, Cout, co.EPI_BIAS)
-        g_dn = lambda: co.wino_gemm_dn(V1, C1, V2, C2, Ud, Mm, b, D, Ht, Wt, Cout)
+        g_dn = lambda: co.wino_form_gemm(F["dn"], V1, C1, V2, C2, Ud, Mm, b, D, Ht, Wt, Cout)
         g_h = lambda: co.wino_gemm(V1, C1, V2, C2, U, Mm, b, D, Ht, Wt, Cout, half=True)
         t = {"gemm_dn": timed(g_dn), "out16": timed(lambda: outp(g_dn(), out_a)) , "gemm_half": timed(g_h), "out8": timed(lambda: outp(g_h(), out_b))}
         outp(g_dn(), out_a)
@@ -74,14 +75,14 @@ def launch(args):
         # the F(4, 3) form: the hidden-state operand's transform is part of the pair (1.5 x the planes written)
         Ch = C2 or C1
         x = rn(M, Ch)
-        Ud4 = co.wino_pack_packed_dn4(wp)
+        Ud4 = co.wino_pack(F["dn4"], wp)
         W1, W2 = rn(16, R // 4 * 6, C1), (rn(16, R // 4 * 6, C2) if C2 else None)
         Vh, Vh6 = torch.empty(16, R, Ch, device=dev), torch.empty(16, R // 4 * 6, Ch, device=dev)
-        g_d4 = lambda: co.wino_gemm_dn4(W1, C1, W2, C2, Ud4, Mm, b, D, Ht, Wt, Cout)
-        t_in, t_in6 = timed(lambda: co.wino_input(x, Ch, Ch, b, D, H, W, out=Vh)), timed(lambda: co.wino_input_dn4(x, Ch, Ch, b, D, H, W, out=Vh6))
+        g_d4 = lambda: co.wino_form_gemm(F["dn4"], W1, C1, W2, C2, Ud4, Mm, b, D, Ht, Wt, Cout)
+        t_in, t_in6 = timed(lambda: co.wino_input(x, Ch, Ch, b, D, H, W, out=Vh)), timed(lambda: co.wino_form_input(F["dn4"], x, Ch, Ch, b, D, H, W, out=Vh6))
         t4 = timed(g_d4)
         full = lambda f_in, f_g, o: (f_in(), outp(f_g(), o))
-        p4 = timed(lambda: full(lambda: co.wino_input_dn4(x, Ch, Ch, b, D, H, W, out=Vh6), g_d4, out_a))
+        p4 = timed(lambda: full(lambda: co.wino_form_input(F["dn4"], x, Ch, Ch, b, D, H, W, out=Vh6), g_d4, out_a))
         p2 = timed(lambda: full(lambda: co.wino_input(x, Ch, Ch, b, D, H, W, out=Vh), g_dn, out_a))
         p1 = timed(lambda: full(lambda: co.wino_input(x, Ch, Ch, b, D, H, W, out=Vh), g_h, out_b))
         lines.append("%-12s F(4,3): GEMM %7.1f us (%5.1f TF executed), transform %6.1f us (plain %6.1f us) | transform + GEMM + inverse %7.1f us | "
