@@ -89,14 +89,33 @@ __device__ __forceinline__ void atomic_add_f32(float* p, float v) { unsafeAtomic
 // in front of the barrier that publishes the stage, AFTER the step's MFMAs (the builtin form is drained before them). M0 is declared
 // clobbered: the compiler must not keep a live M0 value (LDS / movrel / readlane uses) across the statement.
 typedef int forge_v4i32 __attribute__((ext_vector_type(4)));
+typedef __attribute__((ext_vector_type(16))) float f32x16;   // accumulator of the 32x32 fp32 MFMA
 
-__device__ __forceinline__ forge_v4i32 make_rsrc_words(const void* base, long long bytes) {     // raw dword buffer, stride 0
+constexpr int RSRC_RAW_DWORD = 0x00020000;  // descriptor word 3 of a raw dword buffer, stride 0
+constexpr unsigned OOB = 0x80000000u;      // byte offset beyond any buffer (< 2 GiB spans enforced on the host side): such a lane of an LDS-DMA load
+                                           // lands as zeros - the zero padding of out-of-grid taps and of rows / columns beyond M / Cout costs neither
+                                           // a branch nor a select
+
+__device__ __forceinline__ forge_v4i32 make_rsrc_words(const void* base, long long bytes) {
     const unsigned long long p = (unsigned long long)base;
     forge_v4i32 r;
     // readfirstlane: the words must live in SGPRs (an "s" operand of the inline assembly) even where the compiler cannot prove the base uniform
     r.x = __builtin_amdgcn_readfirstlane((int)(p & 0xffffffffull)); r.y = __builtin_amdgcn_readfirstlane((int)((p >> 32) & 0xffffull));
-    r.z = __builtin_amdgcn_readfirstlane((int)bytes); r.w = 0x00020000;
+    r.z = __builtin_amdgcn_readfirstlane((int)bytes); r.w = RSRC_RAW_DWORD;
     return r;
+}
+
+// The same descriptor in the form the compiler's raw-buffer builtins take (their loads and stores are visible to its waitcnt insertion).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, long long bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, RSRC_RAW_DWORD);
+}
+
+__device__ __forceinline__ float4 buf_load16(__amdgpu_buffer_rsrc_t r, unsigned off) {          // 16 bytes at byte offset off; zeros beyond the buffer
+    typedef __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned u32x4;
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
+    float4 f;
+    __builtin_memcpy(&f, &v, 16);
+    return f;
 }
 
 #pragma clang diagnostic push

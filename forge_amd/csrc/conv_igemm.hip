@@ -34,8 +34,6 @@
 
 namespace forge {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
 enum ConvEpilogue : int {
     EPI_BIAS = 0,        // y = acc + bias
     EPI_AFFINE_ACT = 1,  // y = lrelu((acc + bias) * scale + shift, slope)   (eval BN folded; slope 1 = none, 0 = ReLU)
@@ -85,10 +83,6 @@ extern "C" int forge_debug_conv_stamps(long long* host, int n) {
 #else
 #define FORGE_STAMP(k) do { } while (0)
 #endif
-
-constexpr unsigned OOB = 0x80000000u;      // byte offset beyond any buffer (< 2 GiB spans enforced on the host side): such a lane of an LDS-DMA load
-                                           // lands as zeros - the zero padding of out-of-grid taps and of rows / columns beyond M / Cout costs neither
-                                           // a branch nor a select
 
 __device__ __forceinline__ int lds_off(int row, int chunk) {   // float offset of a 16-byte chunk
     return row * BK + ((chunk ^ ((row >> 1) & 7)) << 2);
@@ -159,7 +153,7 @@ struct PlaneStore {
     }
     template <class Val>
     __device__ __forceinline__ void operator()(float* plane, unsigned row_off, Val&& val) const {
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(plane, 0, bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = make_rsrc(plane, bytes);
         unsigned vb = ovb + row_off;
         asm volatile("" : "+v"(vb));                             // keeps the 16 row offsets from being computed ahead of the K loops and held in registers
 #pragma unroll

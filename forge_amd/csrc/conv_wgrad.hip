@@ -16,17 +16,6 @@
 
 namespace forge {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16w;
-typedef __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned u32x4w;
-constexpr unsigned OOBW = 0x80000000u;
-
-__device__ __forceinline__ float4 buf_load16w(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    u32x4w v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
-    float4 f;
-    __builtin_memcpy(&f, &v, 16);
-    return f;
-}
-
 struct WgradArgs {
     const float* dy; int ldy;                 // [M][ldy], Cout channels used
     const float* x1; const float* x2;         // channel-concatenated inputs [rows][ld1], [rows][ld2]; x2 nullable
@@ -42,6 +31,21 @@ struct WgradArgs {
 };
 
 constexpr int WT = 128, WK = 16, WJ = WK / 8;  // tile 128 x 128, K-step 16 voxels (32 KiB of LDS: 4 workgroups per CU)
+
+// Row of accumulator value r in the C/D layout of the 32x32 fp32 MFMA (column = lane & 31, half = lane >> 5).
+__device__ __forceinline__ int mfma32_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+
+// The epilogue of the kernels of this file (but see conv_wgrad_small_kernel's deterministic store): one partial sum v of dW[t][co][ci]. DET: stored into slab `slab` of the slab set dw points at;
+// otherwise added to dW with a hardware atomic. Cin = the row length of dW, widened at the call: there the compiler still sees the caller's
+// ci < Cin test and multiplies by an unsigned 32-bit factor (with an int parameter the tap-grouped tiles and the small kernel took a full 64-bit
+// multiply per element; through a reference to the argument struct every tile kernel came out 13 - 29 instructions longer).
+template <bool DET>
+__device__ __forceinline__ void wgrad_emit(float* dw, int ntaps, int Cout, long long Cin, long long slab, int t, int co, int ci, float v) {
+    if (co < Cout) {
+        if constexpr (DET) dw[((slab * ntaps + t) * Cout + co) * Cin + ci] = v;
+        else atomic_add_f32(dw + ((long long)t * Cout + co) * Cin + ci, v);
+    }
+}
 
 // CIW = width of the Cin tile: 128 (4 waves as 2 x 2, wave tile 64 co x 64 ci, even/odd interleave on both operands), or for
 // narrow inputs 64 / 32 (4 waves as 4 x 1, wave tile 32 co x CIW ci) so that a Cin <= 64 problem (conv1: 64, the transpose conv
@@ -114,7 +118,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
     const int is_ = a.is, Wg = a.W, Hg = a.H, Dg = a.D, Wi_ = a.Wi, Hi_ = a.Hi, Di_ = a.Di;
     const int trow = tid >> 5;
     // LDS-DMA staging (common.h: lds_dma16): chunk j of this thread is LDS bytes 16 tid + 4096 j of the A / B image = per wave a lane-linear
-    // 1 KB block; rows / taps / channels out of range read offset OOBW and land as zeros.
+    // 1 KB block; rows / taps / channels out of range read offset OOB and land as zeros.
     const unsigned lds_wave = lds_addr(smem) + (unsigned)__builtin_amdgcn_readfirstlane(wave) * 1024u;
     auto issue_step = [&](int s, int buf) {
         const unsigned stage = lds_wave + (unsigned)buf * (unsigned)(2 * WK * WT * 4);
@@ -123,11 +127,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
             // 32-bit offsets: every operand span is < 2 GiB (checked on the host side)
             const unsigned m = mbeg_u + (unsigned)(s * WK + trow + 8 * j);
             const bool mok = m < mend_u;
-            lds_dma16(ry, (mok && ycol_ok) ? (m * ldy_u + ycol_off) * 4u : OOBW, stage + (unsigned)(j * 4096));
+            lds_dma16(ry, (mok && ycol_ok) ? (m * ldy_u + ycol_off) * 4u : OOB, stage + (unsigned)(j * 4096));
             const int x = rx_[j] * is_ + dx, y = ry_[j] * is_ + dy_, z = rz_[j] * is_ + dz;
             const bool ok = mok && xcol_ok && (unsigned)z < (unsigned)Di_ && (unsigned)y < (unsigned)Hi_ && (unsigned)x < (unsigned)Wi_;
             const unsigned e = (unsigned)rn_[j] * bsx_u + (unsigned)((z * Hi_ + y) * Wi_ + x);
-            lds_dma16(rx, ok ? (e * ldx_u + xcol_off) * 4u : OOBW, stage + (unsigned)(WK * WT * 4 + j * 4096));
+            lds_dma16(rx, ok ? (e * ldx_u + xcol_off) * 4u : OOB, stage + (unsigned)(WK * WT * 4 + j * 4096));
             rx_[j] += WK;                                         // advance to the row of the next K-step
             while (rx_[j] >= Wg) {
                 rx_[j] -= Wg;
@@ -138,7 +142,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
 
     // accumulators: [co parity][ci parity]; MFMA row i <-> co = co0 + wm*64 + 2 i + pco, col j <-> ci = ci0 + wn*64 + 2 j + pci:
     // one 8-byte LDS read per lane then feeds TWO MFMA operands (even / odd channel), halving the LDS instruction count.
-    f32x16w acc[P][Q];
+    f32x16 acc[P][Q];
 #pragma unroll
     for (int p = 0; p < P; ++p)
 #pragma unroll
@@ -171,7 +175,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
         __syncthreads();
     }
 
-    // D[i][j]: col j = lane & 31, row i = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
         const int col = Q == 2 ? wn * 64 + 2 * l31 + q : l31;       // column of the tile
@@ -182,13 +185,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
         for (int p = 0; p < P; ++p)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int i = (r & 3) + 8 * (r >> 2) + 4 * half;
-                const int co = co0 + (P == 2 ? wm * 64 + 2 * i + p : wm * 32 + i);
-                if constexpr (DET) {
-                    if (co < a.Cout) a.dw[(((long long)chunk * a.ntaps + te) * a.Cout + co) * Cin + ci] = acc[p][q][r];
-                } else {
-                    if (co < a.Cout) atomic_add_f32(a.dw + ((long long)te * a.Cout + co) * Cin + ci, acc[p][q][r]);
-                }
+                const int i = mfma32_row(r, half);
+                wgrad_emit<DET>(a.dw, a.ntaps, a.Cout, Cin, chunk, te, co0 + (P == 2 ? wm * 64 + 2 * i + p : wm * 32 + i), ci, acc[p][q][r]);
             }
     }
 }
@@ -211,8 +209,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_small_kernel(const WgradArgs a
     const long long mend = mbeg + rows_per_wave < M ? mbeg + rows_per_wave : M;
     const int t0 = tg * 4;
     const int Cin = a.C1;                                          // single input, Cin <= 32
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void*)a.dy, 0, (int)a.spany, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x1, 0, (int)a.span1, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ry = make_rsrc(a.dy, a.spany), rx = make_rsrc(a.x1, a.span1);
     const bool yc = l31 < a.Cout, xc = l31 < Cin;
 
     int tdz[4], tdy[4], tdx[4]; bool tok[4];
@@ -229,7 +226,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_small_kernel(const WgradArgs a
     int cz = (int)(v % (unsigned)a.D); v /= (unsigned)a.D;
     int cn = (int)v;
 
-    f32x16w acc[4];
+    f32x16 acc[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -237,13 +234,13 @@ __global__ __launch_bounds__(256) void conv_wgrad_small_kernel(const WgradArgs a
 
     for (long long m = mbeg + half; m < mend + half; m += 2) {      // all 64 lanes iterate together (m - half is wave-uniform)
         const bool mok = m < mend;
-        const float fa = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ry, (mok && yc) ? (unsigned)((m * a.ldy + l31) * 4) : OOBW, 0, 0));
+        const float fa = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ry, (mok && yc) ? (unsigned)((m * a.ldy + l31) * 4) : OOB, 0, 0));
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int x = cx * a.is + tdx[q], y = cy * a.is + tdy[q], z = cz * a.is + tdz[q];
             const bool ok = mok && xc && tok[q] && (unsigned)z < (unsigned)a.Di && (unsigned)y < (unsigned)a.Hi && (unsigned)x < (unsigned)a.Wi;
             const long long e = cn * a.bs1r + ((long long)z * a.Hi + y) * a.Wi + x;
-            const float fb = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, ok ? (unsigned)((e * a.ld1 + l31) * 4) : OOBW, 0, 0));
+            const float fb = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, ok ? (unsigned)((e * a.ld1 + l31) * 4) : OOB, 0, 0));
             acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa, fb, acc[q], 0, 0, 0);
         }
         cx += 2;
@@ -257,192 +254,116 @@ __global__ __launch_bounds__(256) void conv_wgrad_small_kernel(const WgradArgs a
         if (!tok[q] || l31 >= Cin) continue;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int co = (r & 3) + 8 * (r >> 2) + 4 * half;
-            if constexpr (DET) {                                   // slab = this wave's voxel chunk
+            const int co = mfma32_row(r, half);
+            // slab = this wave's voxel chunk. The store is written out: with the tap handed to wgrad_emit as t0 + q the compiler no longer forms
+            // chunk ntaps + t0 once with q as a constant offset - 36 instead of 32 VGPRs, 4 instead of 5 waves per SIMD, and this kernel has no LDS:
+            // occupancy is what hides its load latency.
+            if constexpr (DET) {
                 if (co < a.Cout) a.dw[(((wave_id / tap_groups) * a.ntaps + t0 + q) * a.Cout + co) * Cin + l31] = acc[q][r];
             } else {
-                if (co < a.Cout) atomic_add_f32(a.dw + ((long long)(t0 + q) * a.Cout + co) * Cin + l31, acc[q][r]);
+                wgrad_emit<false>(a.dw, a.ntaps, a.Cout, Cin, 0, t0 + q, co, l31, acc[q][r]);
             }
         }
     }
 }
-
 
 // ------------------------------------------------------------------------------------------------
 // Narrow variant with operand reuse across taps (stride-1 "same" convolutions with Cout, Cin <= 32 whose taps span <= 9 distinct
-// (dz, dy) lines and |dx| <= 2: the heads' 3x3x3 convolutions, conv_rgb's 5x5). conv_wgrad_small_kernel above loads one X element per
+// (dz, dy) lines and |dx| <= 3: the heads' 3x3x3 convolutions, conv_rgb's 5x5). conv_wgrad_small_kernel above loads one X element per
 // lane per MFMA (12.8 FLOP per byte of L1/L2 traffic -> 35 TF); but the 27 taps of a voxel segment read the same dY rows and almost
 // the same X rows. Here a workgroup stages, for a segment of 32 consecutive x-voxels of one (n, z, y) line, the dY rows and the X
 // halo - every needed (dz, dy) line, 32 + 2 rx voxels long - in LDS once (43 KB for 3x3x3 at 32 channels) and feeds all taps from
-// it: each wave owns every 4th tap (<= 7 accumulator tiles), one ds_read_b32 per operand per MFMA, conflict-free (a half-wave reads
-// 32 consecutive floats of one LDS row). Workgroups walk segments grid-stride with the next segment's global loads in flight under the
-// current segment's MFMAs, and add their partial 32x32 tiles to dW with fp32 atomics once at the end.
-constexpr int LSEG = 32, LMAXL = 9, LMAXR = 3, LROWS = LSEG + 2 * LMAXR, LTAPS = 7;
+// it: each wave owns every NWV-th tap (<= LT accumulator tiles), one ds_read_b32 per operand per MFMA, conflict-free (a wave-instruction
+// reads consecutive floats of one LDS row per k). Workgroups walk segments grid-stride with the next segment's global loads in flight
+// under the current segment's MFMAs, and add their partial tiles to dW with fp32 atomics once at the end.
+constexpr int LSEG = 32, LMAXL = 9, LMAXL_S2 = 6, LMAXR = 3, LTAPS = 7;
 
 struct LineTable { signed char dz[LMAXL], dy[LMAXL]; int nlines, rx; };
 
-template <bool DET = false>
-__global__ __launch_bounds__(256) void conv_wgrad_lines_kernel(const WgradArgs a, const LineTable lt) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];   // dYs [LSEG][32] | Xs [nlines][LSEG + 2 rx][32]
-    float* dYs = smem;
-    float* Xs = smem + LSEG * 32;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
-    const int Cin = a.C1, xrows = LSEG + 2 * lt.rx;
-    const int nsx = (a.W + LSEG - 1) / LSEG;
-    const long long nseg = (long long)a.n * a.D * a.H * nsx;
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void*)a.dy, 0, (int)a.spany, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx_ = __builtin_amdgcn_make_buffer_rsrc((void*)a.x1, 0, (int)a.span1, 0x00020000);
-    // staging geometry: one float4 (4 channels) per thread per pass; 8 threads per 32-channel row
-    const int c4 = (tid & 7) << 2, srow = tid >> 3;                 // 32 rows per pass
-    const int xchunks = lt.nlines * xrows;                           // X rows to stage
-    constexpr int XP = (LMAXL * LROWS + 31) / 32;                    // passes (upper bound 11)
-    float4 ry4, rx4[XP];
-    auto load_seg = [&](long long sg) {
-        long long q = sg;
-        const int sx = (int)(q % nsx); q /= nsx;
-        const int y = (int)(q % a.H); q /= a.H;
-        const int z = (int)(q % a.D); q /= a.D;
-        const int nn = (int)q, x0 = sx * LSEG;
-        {   // dY row srow of the segment
-            const int x = x0 + srow;
-            const long long m = (((long long)nn * a.D + z) * a.H + y) * a.W + x;
-            ry4 = buf_load16w(ry, (x < a.W && c4 < a.Cout) ? (unsigned)((m * a.ldy + c4) * 4) : OOBW);
-        }
-#pragma unroll
-        for (int p = 0; p < XP; ++p) {
-            const int r = srow + 32 * p;                             // staged X row: (line, xr)
-            unsigned off = OOBW;
-            if (r < xchunks && c4 < Cin) {
-                const int ln = r / xrows, xr = r - ln * xrows;
-                const int zi = z + lt.dz[ln], yi = y + lt.dy[ln], xi = x0 - lt.rx + xr;
-                if ((unsigned)zi < (unsigned)a.D && (unsigned)yi < (unsigned)a.H && (unsigned)xi < (unsigned)a.W)
-                    off = (unsigned)((((long long)nn * a.bs1r + ((long long)zi * a.H + yi) * a.W + xi) * a.ld1 + c4) * 4);
-            }
-            rx4[p] = buf_load16w(rx_, off);
-        }
-    };
-    auto store_seg = [&]() {
-        *reinterpret_cast<float4*>(dYs + srow * 32 + c4) = ry4;
-#pragma unroll
-        for (int p = 0; p < XP; ++p) {
-            const int r = srow + 32 * p;
-            if (r < xchunks) *reinterpret_cast<float4*>(Xs + r * 32 + c4) = rx4[p];
-        }
-    };
-    // this wave's taps: t = wave, wave + 4, ... (<= LTAPS); LDS row offset of each tap's first X row
-    int tb[LTAPS];
-    bool tok[LTAPS];
-#pragma unroll
-    for (int j = 0; j < LTAPS; ++j) {
-        const int t = wave + 4 * j;
-        tok[j] = t < a.ntaps;
-        const int tt = tok[j] ? t : 0;
-        tb[j] = (a.tap[tt][3] * xrows + a.tap[tt][2] + lt.rx) * 32;  // (line, dx + rx)
-    }
-    f32x16w acc[LTAPS];
-#pragma unroll
-    for (int j = 0; j < LTAPS; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+// The MFMA shape of a line kernel: ROWS = rows of the Cout tile = floats of a staged dY row = columns of one accumulator, KR = voxel rows per
+// instruction (lane l supplies A[i = l % ROWS][k = l / ROWS] and B[k][j = l % ROWS]), NV accumulator values per lane, value r in row row(r, k).
+struct Mfma32x32x2 {                          // Cout <= 32
+    static constexpr int ROWS = 32, KR = 2, NV = 16;
+    typedef f32x16 Acc;
+    static __device__ __forceinline__ Acc mma(float fa, float fb, Acc c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(fa, fb, c, 0, 0, 0); }
+    static __device__ __forceinline__ int row(int r, int k) { return mfma32_row(r, k); }
+};
+// Cout <= 16 on the 16x16x4 fp32 MFMA: the 32-row tile executes 2x (Cout = 16: the features head's 32 -> 16) to 4x (Cout = 8: the density
+// head's 32 -> 8, conv_rgb's 16 -> 8) the useful matrix work. dYs rows are 16 floats, so the four voxel rows a wave-instruction reads fall
+// into disjoint banks.
+struct Mfma16x16x4 {
+    static constexpr int ROWS = 16, KR = 4, NV = 4;
+    typedef __attribute__((ext_vector_type(4))) float Acc;
+    static __device__ __forceinline__ Acc mma(float fa, float fb, Acc c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(fa, fb, c, 0, 0, 0); }
+    static __device__ __forceinline__ int row(int r, int k) { return 4 * k + r; }
+};
 
-    long long sg = blockIdx.x;
-    if (sg < nseg) load_seg(sg);
-    for (; sg < nseg; sg += gridDim.x) {
-        __syncthreads();                                             // previous segment's MFMAs have read the LDS images
-        store_seg();
-        __syncthreads();
-        if (sg + gridDim.x < nseg) load_seg(sg + gridDim.x);         // in flight under this segment's MFMAs
-#pragma unroll 4
-        for (int k = 0; k < LSEG / 2; ++k) {
-            const int row = 2 * k + half;
-            const float fa = dYs[row * 32 + l31];
-#pragma unroll
-            for (int j = 0; j < LTAPS; ++j) {
-                if (!tok[j]) continue;                               // wave-uniform
-                const float fb = Xs[tb[j] + row * 32 + l31];
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa, fb, acc[j], 0, 0, 0);
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < LTAPS; ++j) {
-        if (!tok[j] || l31 >= Cin) continue;
-        const int t = wave + 4 * j;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int co = (r & 3) + 8 * (r >> 2) + 4 * half;
-            if constexpr (DET) {                                   // slab = this workgroup
-                if (co < a.Cout) a.dw[(((long long)blockIdx.x * a.ntaps + t) * a.Cout + co) * Cin + l31] = acc[j][r];
-            } else {
-                if (co < a.Cout && acc[j][r] != 0.f) atomic_add_f32(a.dw + ((long long)t * a.Cout + co) * Cin + l31, acc[j][r]);
-            }
-        }
-    }
-}
-
-// The same for Cout <= 16 on the 16x16x4 fp32 MFMA (A[i = l & 15][k = l >> 4], B[k = l >> 4][j = l & 15], D[row = 4 (l >> 4) + r][col = l & 15]):
-// the 32-row tile of the kernel above executes 2x (Cout = 16: the features head's 32 -> 16) to 4x (Cout = 8: the density head's 32 -> 8,
-// conv_rgb's 16 -> 8) the useful matrix work. CIT = 32: the Cin tile is two 16-column MFMAs fed by ONE 8-byte LDS read per lane (even / odd
-// input channel); CIT = 16: one MFMA. dYs rows are 16 floats, so the four voxel rows a wave-instruction reads fall into disjoint banks.
-typedef __attribute__((ext_vector_type(4))) float f32x4w;
-
+// CIT = width of the Cin tile: MM::ROWS (one MFMA per tap and k), or 2 MM::ROWS: two MFMAs fed by ONE 8-byte LDS read per lane (even / odd
+// input channel).
 // IS = 2 (CIT = 16, LT = 9 taps per wave): the gathered operand lives on the 2x finer grid (voxel m reads row 2 m + tap) - the weight gradient of
 // a stride-2 transposed convolution (conv_rgb's ConvTranspose2d(16, 16, 6, stride 2): 36 taps on 6 lines, |dx| <= 3), whose staged X segment is
-// 2 LSEG - 1 + 2 rx rows long and is read with a row stride of 2.
-// NWV = waves per workgroup: 4, or 8 for CIT = 32 (the heads' 32 -> 16 / 32 -> 8 layers): with 4 waves that instantiation needs 189 VGPRs
-// (7 taps x 2 accumulators per wave + 11 staging passes), i.e. spills at 3 workgroups per CU and runs 1.5x slower at 2 (1124 vs 732 us);
-// 8 waves share one staged segment with 4 taps and 6 staging passes each.
-template <int CIT, int IS = 1, int LT = LTAPS, int NWV = 4, bool DET = false>
-__global__ __launch_bounds__(64 * NWV, NWV == 8 ? 2 : ((CIT == 16 && IS == 1) ? 4 : 3)) void conv_wgrad_lines16_kernel(const WgradArgs a, const LineTable lt) {
-    constexpr int NT = CIT / 16, NTHR = 64 * NWV;
-    extern __shared__ __attribute__((aligned(16))) float smem[];   // dYs [LSEG][16] | Xs [nlines][LSEG + 2 rx][CIT]
+// 2 LSEG - 1 + 2 rx rows long and is read with a row stride of 2. IS = 1: the host dispatches only Di, Hi, Wi = D, H, W.
+// Segment index and operand offsets are 32-bit, as in conv_wgrad_kernel: every operand span is < 2 GiB (checked on the host side), so M < 2^27 rows.
+// In 64 bits the decode's three divisions and the offsets kept so many scalars live that the compiler spilled up to 14 of them into VGPR lanes.
+// NWV = waves per workgroup: 4, or 8 for CIT = 32 on the 16-row tile (the heads' 32 -> 16 / 32 -> 8 layers): with 4 waves that instantiation
+// needs 189 VGPRs (7 taps x 2 accumulators per wave + 11 staging passes), i.e. spills at 3 workgroups per CU and runs 1.5x slower at 2
+// (1124 vs 732 us); 8 waves share one staged segment with 4 taps and 6 staging passes each.
+// MINW = the waves per SIMD the register allocation is held to (0: no bound beyond the workgroup size).
+template <class MM, int CIT, int IS, int LT, int NWV, int MINW, bool DET>
+__global__ __launch_bounds__(64 * NWV, MINW) void conv_wgrad_lines_kernel(const WgradArgs a, const LineTable lt) {
+    constexpr int YW = MM::ROWS, NT = CIT / YW, NTHR = 64 * NWV;
+    static_assert(NT == 1 || NT == 2, "one or two accumulators per tap");
+    extern __shared__ __attribute__((aligned(16))) float smem[];   // dYs [LSEG][YW] | Xs [nlines][(LSEG - 1) IS + 1 + 2 rx][CIT]
     float* dYs = smem;
-    float* Xs = smem + LSEG * 16;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, kq = lane >> 4;
+    float* Xs = smem + LSEG * YW;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lc = lane % YW, kq = lane / YW;
     const int Cin = a.C1, xrows = (LSEG - 1) * IS + 1 + 2 * lt.rx;
+    const int Di = IS == 1 ? a.D : a.Di, Hi = IS == 1 ? a.H : a.Hi, Wi = IS == 1 ? a.W : a.Wi;   // IS = 1: the input grid is the row grid (host)
     const int nsx = (a.W + LSEG - 1) / LSEG;
-    const long long nseg = (long long)a.n * a.D * a.H * nsx;
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void*)a.dy, 0, (int)a.spany, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx_ = __builtin_amdgcn_make_buffer_rsrc((void*)a.x1, 0, (int)a.span1, 0x00020000);
-    // staging: one float4 per thread per pass; CIT / 4 threads per X row (4 per dY row: threads 0..127 stage the 32 dY rows)
-    constexpr int TPR = CIT / 4, RPP = NTHR / TPR;                   // threads per row, rows per pass
+    const unsigned nseg = (unsigned)(a.n * a.D * a.H * nsx);
+    const __amdgpu_buffer_rsrc_t ry = make_rsrc(a.dy, a.spany), rx_ = make_rsrc(a.x1, a.span1);
+    // staging: one float4 per thread per pass; CIT / 4 threads per X row, YW / 4 per dY row (the first LSEG YW / 4 threads stage the 32 dY rows)
+    constexpr int TPR = CIT / 4, RPP = NTHR / TPR, TPY = YW / 4;     // threads per row, rows per pass
     const int c4 = (tid % TPR) << 2, srow = tid / TPR;
-    const int yc4 = (tid & 3) << 2, yrow = tid >> 2;
-    const int xchunks = lt.nlines * xrows;
-    constexpr int XP = ((IS == 2 ? 6 : LMAXL) * ((LSEG - 1) * IS + 1 + 2 * LMAXR) + RPP - 1) / RPP;   // IS = 2: <= 6 lines (host)
+    const int yc4 = (tid % TPY) << 2, yrow = tid / TPY;
+    constexpr bool YALL = NTHR / TPY == LSEG;                        // every thread stages a dY row
+    const int xchunks = lt.nlines * xrows;                           // X rows to stage
+    const int yw_t = yc4 < a.Cout ? a.W : 0;                         // voxels of a line whose dY this thread's channels load
+    constexpr int XP = ((IS == 2 ? LMAXL_S2 : LMAXL) * ((LSEG - 1) * IS + 1 + 2 * LMAXR) + RPP - 1) / RPP;   // passes; IS = 2: <= 6 lines (host)
     float4 ry4 = make_float4(0.f, 0.f, 0.f, 0.f), rx4[XP];
-    auto load_seg = [&](long long sg) {
-        long long q = sg;
-        const int sx = (int)(q % nsx); q /= nsx;
-        const int y = (int)(q % a.H); q /= a.H;
-        const int z = (int)(q % a.D); q /= a.D;
+    auto load_seg = [&](unsigned sg) {
+        unsigned q = sg;
+        const int sx = (int)(q % (unsigned)nsx); q /= (unsigned)nsx;
+        const int y = (int)(q % (unsigned)a.H); q /= (unsigned)a.H;
+        const int z = (int)(q % (unsigned)a.D); q /= (unsigned)a.D;
         const int nn = (int)q, x0 = sx * LSEG;
-        if (yrow < LSEG) {
+        if (YALL || yrow < LSEG) {   // dY row yrow of the segment
             const int x = x0 + yrow;
-            const long long m = (((long long)nn * a.D + z) * a.H + y) * a.W + x;
-            ry4 = buf_load16w(ry, (x < a.W && yc4 < a.Cout) ? (unsigned)((m * a.ldy + yc4) * 4) : OOBW);
+            const unsigned m = ((unsigned)(nn * a.D + z) * (unsigned)a.H + (unsigned)y) * (unsigned)a.W + (unsigned)x;
+            ry4 = buf_load16(ry, x < yw_t ? (m * (unsigned)a.ldy + (unsigned)yc4) * 4u : OOB);
         }
 #pragma unroll
         for (int p = 0; p < XP; ++p) {
-            const int r = srow + RPP * p;
-            unsigned off = OOBW;
+            const int r = srow + RPP * p;                            // staged X row: (line, xr)
+            unsigned off = OOB;
             if (r < xchunks && c4 < Cin) {
                 const int ln = r / xrows, xr = r - ln * xrows;
                 const int zi = z * IS + lt.dz[ln], yi = y * IS + lt.dy[ln], xi = x0 * IS - lt.rx + xr;
-                if ((unsigned)zi < (unsigned)a.Di && (unsigned)yi < (unsigned)a.Hi && (unsigned)xi < (unsigned)a.Wi)
-                    off = (unsigned)((((long long)nn * a.bs1r + ((long long)zi * a.Hi + yi) * a.Wi + xi) * a.ld1 + c4) * 4);
+                if ((unsigned)zi < (unsigned)Di && (unsigned)yi < (unsigned)Hi && (unsigned)xi < (unsigned)Wi)
+                    off = (((unsigned)nn * (unsigned)a.bs1r + (unsigned)((zi * Hi + yi) * Wi + xi)) * (unsigned)a.ld1 + (unsigned)c4) * 4u;
             }
-            rx4[p] = buf_load16w(rx_, off);
+            rx4[p] = buf_load16(rx_, off);
         }
     };
     auto store_seg = [&]() {
-        if (yrow < LSEG) *reinterpret_cast<float4*>(dYs + yrow * 16 + yc4) = ry4;
+        if (YALL || yrow < LSEG) *reinterpret_cast<float4*>(dYs + yrow * YW + yc4) = ry4;
 #pragma unroll
         for (int p = 0; p < XP; ++p) {
             const int r = srow + RPP * p;
             if (r < xchunks) *reinterpret_cast<float4*>(Xs + r * CIT + c4) = rx4[p];
         }
     };
+    // this wave's taps: t = wave, wave + NWV, ... (<= LT); LDS row offset of each tap's first X row
     int tb[LT];
     bool tok[LT];
 #pragma unroll
@@ -452,56 +373,50 @@ __global__ __launch_bounds__(64 * NWV, NWV == 8 ? 2 : ((CIT == 16 && IS == 1) ? 
         const int tt = tok[j] ? t : 0;
         tb[j] = (a.tap[tt][3] * xrows + a.tap[tt][2] + lt.rx) * CIT;  // (line, dx + rx)
     }
-    f32x4w acc[LT][NT];
+    typename MM::Acc acc[LT][NT];
 #pragma unroll
     for (int j = 0; j < LT; ++j)
 #pragma unroll
         for (int n = 0; n < NT; ++n)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc[j][n][r] = 0.f;
+            for (int r = 0; r < MM::NV; ++r) acc[j][n][r] = 0.f;
 
-    long long sg = blockIdx.x;
+    unsigned sg = blockIdx.x;
     if (sg < nseg) load_seg(sg);
     for (; sg < nseg; sg += gridDim.x) {
-        __syncthreads();
+        __syncthreads();                                             // previous segment's MFMAs have read the LDS images
         store_seg();
         __syncthreads();
-        if (sg + gridDim.x < nseg) load_seg(sg + gridDim.x);
+        if (sg + gridDim.x < nseg) load_seg(sg + gridDim.x);         // in flight under this segment's MFMAs
 #pragma unroll 4
-        for (int k = 0; k < LSEG / 4; ++k) {
-            const int row = 4 * k + kq;
-            const float fa = dYs[row * 16 + l15];
+        for (int k = 0; k < LSEG / MM::KR; ++k) {
+            const int row = MM::KR * k + kq;
+            const float fa = dYs[row * YW + lc];
 #pragma unroll
             for (int j = 0; j < LT; ++j) {
                 if (!tok[j]) continue;                               // wave-uniform
                 if constexpr (NT == 2) {
-                    const float2 fb = *reinterpret_cast<const float2*>(Xs + tb[j] + row * (CIT * IS) + 2 * l15);     // input channels 2 l15, 2 l15 + 1
-                    acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa, fb.x, acc[j][0], 0, 0, 0);
-                    acc[j][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa, fb.y, acc[j][1], 0, 0, 0);
+                    const float2 fb = *reinterpret_cast<const float2*>(Xs + tb[j] + row * (CIT * IS) + 2 * lc);     // input channels 2 lc, 2 lc + 1
+                    acc[j][0] = MM::mma(fa, fb.x, acc[j][0]);
+                    acc[j][1] = MM::mma(fa, fb.y, acc[j][1]);
                 } else {
-                    const float fb = Xs[tb[j] + row * (CIT * IS) + l15];
-                    acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa, fb, acc[j][0], 0, 0, 0);
+                    const float fb = Xs[tb[j] + row * (CIT * IS) + lc];
+                    acc[j][0] = MM::mma(fa, fb, acc[j][0]);
                 }
             }
         }
     }
+    // slab = this workgroup. The atomic path skips exact zeros (taps wholly outside the grid, channels of a ragged tile); a slab takes them all.
 #pragma unroll
     for (int j = 0; j < LT; ++j) {
         if (!tok[j]) continue;
-        const int t = wave + NWV * j;
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
-            const int ci = NT == 2 ? 2 * l15 + n : l15;
+            const int ci = NT == 2 ? 2 * lc + n : lc;
             if (ci >= Cin) continue;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int co = 4 * kq + r;
-                if constexpr (DET) {
-                    if (co < a.Cout) a.dw[(((long long)blockIdx.x * a.ntaps + t) * a.Cout + co) * Cin + ci] = acc[j][n][r];
-                } else {
-                    if (co < a.Cout && acc[j][n][r] != 0.f) atomic_add_f32(a.dw + ((long long)t * a.Cout + co) * Cin + ci, acc[j][n][r]);
-                }
-            }
+            for (int r = 0; r < MM::NV; ++r)
+                if (DET || acc[j][n][r] != 0.f) wgrad_emit<DET>(a.dw, a.ntaps, a.Cout, Cin, blockIdx.x, wave + NWV * j, MM::row(r, kq), ci, acc[j][n][r]);
         }
     }
 }
@@ -557,10 +472,79 @@ static long long det_cap(long long slab_floats) {
     return c < 1 ? 1 : c;
 }
 
-// conv_wgrad_kernel<ciw> over (taps x Cout tiles x Cin tiles x voxel chunks) workgroups.
-static int launch_wgrad_tiles(WgradArgs& a, int ciw, hipStream_t stream, DetPlan* det, WgradPlan* plan = nullptr) {
+// Dynamic LDS of the two kernel families that use it, launched and largest alike.
+constexpr size_t TILES_LDS = 2 * 2 * WK * WT * sizeof(float);   // 32 KiB
+constexpr size_t lines_lds(int yw, int cit, int is, int nlines, int rx) {     // dYs [LSEG][yw] | Xs [nlines][(LSEG - 1) is + 1 + 2 rx][cit]
+    return (size_t)(LSEG * yw + nlines * ((LSEG - 1) * is + 1 + 2 * rx) * cit) * sizeof(float);
+}
+
+// The kernels of this file, one row per atomic / deterministic pair.
+constexpr int NUM_CU = 256;
+struct WgradRow {
+    int family, p1, p2, nwv;     // what forge_conv_wgrad_plan reports (WgradPlan); block = 64 nwv threads
+    const void* kernel[2];       // atomic, deterministic
+    int yw;                      // line kernels: floats of a staged dY row (the MFMA shape's ROWS)
+    size_t max_lds;              // the largest dynamic LDS a launch may ask for (0: none)
+    int resident;                // persistent kernels: workgroups per CU - the segments are walked by NUM_CU x resident workgroups
+    bool lds_raised[2][64];      // max_lds requested for kernel[k] on device d
+};
+template <class... A> static const void* kfn(void (*f)(A...)) { return (const void*)f; }
+using M32 = Mfma32x32x2;
+using M16 = Mfma16x16x4;
+// A line-kernel row: the plan words, the dY row width and the largest LDS (most lines, widest halo) all follow from the template arguments.
+// MINW is the launch bound: resident NWV / 4 waves per SIMD for the 4-wave 16x16x4 rows; the 8-wave row asks for 2 and gets the 4 its two
+// workgroups need (112 VGPRs); the 32x32x2 row states none - with 2 the compiler took 233 VGPRs and no AGPRs instead of 131 + 112.
+template <class MM, int CIT, int IS, int LT, int NWV, int MINW>
+static WgradRow line_row(int family, int resident) {
+    return {family, CIT, IS, NWV, {kfn(conv_wgrad_lines_kernel<MM, CIT, IS, LT, NWV, MINW, false>), kfn(conv_wgrad_lines_kernel<MM, CIT, IS, LT, NWV, MINW, true>)},
+            MM::ROWS, lines_lds(MM::ROWS, CIT, IS, IS == 2 ? LMAXL_S2 : LMAXL, LMAXR), resident, {}};
+}
+enum { ROW_T128, ROW_T64, ROW_T32, ROW_T32_TG4, ROW_T64_TG2, ROW_SMALL, ROW_LINES, ROW_L16, ROW_L16_C32, ROW_L16_S2, NUM_ROWS };
+static WgradRow g_rows[NUM_ROWS] = {
+    {1, 128, 1, 4, {kfn(conv_wgrad_kernel<128, 1, false>), kfn(conv_wgrad_kernel<128, 1, true>)}, 0, TILES_LDS, 0, {}},
+    {1, 64, 1, 4, {kfn(conv_wgrad_kernel<64, 1, false>), kfn(conv_wgrad_kernel<64, 1, true>)}, 0, TILES_LDS, 0, {}},
+    {1, 32, 1, 4, {kfn(conv_wgrad_kernel<32, 1, false>), kfn(conv_wgrad_kernel<32, 1, true>)}, 0, TILES_LDS, 0, {}},
+    {1, 32, 4, 4, {kfn(conv_wgrad_kernel<32, 4, false>), kfn(conv_wgrad_kernel<32, 4, true>)}, 0, TILES_LDS, 0, {}},
+    {1, 64, 2, 4, {kfn(conv_wgrad_kernel<64, 2, false>), kfn(conv_wgrad_kernel<64, 2, true>)}, 0, TILES_LDS, 0, {}},
+    {2, 32, 4, 4, {kfn(conv_wgrad_small_kernel<false>), kfn(conv_wgrad_small_kernel<true>)}, 0, 0, 0, {}},
+    // 2 workgroups per CU (244 VGPRs), each walking its share of the segments
+    line_row<M32, 32, 1, LTAPS, 4, 0>(3, 2),
+    // narrow outputs: the 16x16x4 MFMA tile (no 32-row padding); 4 workgroups per CU (108 VGPRs)
+    line_row<M16, 16, 1, LTAPS, 4, 4>(4, 4),
+    // 8-wave workgroups, 2 per CU
+    line_row<M16, 32, 1, 4, 8, 2>(4, 2),
+    // the stride-2 gathered operand: 3 workgroups per CU (~150 VGPRs)
+    line_row<M16, 16, 2, 9, 4, 3>(4, 3),
+};
+
+// The launch of row r over `grid` workgroups whose partial sums fill `nslab` slabs in the deterministic mode: note the plan, stop there on a dry
+// run; point the kernel at the slabs; raise the kernel's dynamic-LDS limit once per device (the attribute is per device, and hipGetDevice and the
+// attribute call touch no stream: safe under stream capture); launch; reduce the slabs. arg1 / arg2: the kernel's arguments after `a`.
+static int launch_row(int r, WgradArgs& a, void* arg1, void* arg2, long long grid, long long nslab, size_t lds, int nlines, hipStream_t stream,
+                      DetPlan* det, WgradPlan* plan) {
+    WgradRow& row = g_rows[r];
+    if (plan_note(plan, row.family, row.p1, row.p2, row.nwv, grid, nslab, a.mchunk, nlines)) return 0;
+    if (det) {
+        if (int rc = det_prepare(a, *det, nslab, "forge_conv_wgrad_det")) return rc < 0 ? rc : 0;
+    }
+    const int k = det ? 1 : 0;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (row.max_lds > 0 && dev >= 0 && dev < 64 && !row.lds_raised[k][dev]) {
+        (void)hipFuncSetAttribute(row.kernel[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)row.max_lds);
+        row.lds_raised[k][dev] = true;
+    }
+    void* args[3] = {&a, arg1, arg2};
+    (void)hipLaunchKernel(row.kernel[k], dim3((unsigned)grid), dim3(64 * row.nwv), args, lds, stream);
+    FORGE_LAUNCH_CHECK("forge_conv_wgrad");
+    return det ? det_finish(*det, stream, "forge_conv_wgrad_det") : 0;
+}
+
+// conv_wgrad_kernel<ciw, tg> over (taps x Cout tiles x Cin tiles x voxel chunks) workgroups.
+static int launch_wgrad_tiles(WgradArgs& a, hipStream_t stream, DetPlan* det, WgradPlan* plan = nullptr) {
     const long long M = (long long)a.n * a.D * a.H * a.W;
     const int Cin = a.C1 + a.C2, Cout = a.Cout, ntaps = a.ntaps;
+    const int ciw = (a.x2 == nullptr && Cin <= 32) ? 32 : (a.x2 == nullptr && Cin <= 64) ? 64 : WT;   // the narrowest Cin tile that holds a single input
     // narrow single inputs with several taps: TG taps share one 128-column tile (kernel header)
     // (large problems only: on the trunk's 64 -> 64 3x3 layers, M = 81920, the coarser tiles leave the chip under-filled: 125 -> 166 us)
     const bool grp = a.x2 == nullptr && a.tpp == 0 && M >= 131072;
@@ -585,30 +569,26 @@ static int launch_wgrad_tiles(WgradArgs& a, int ciw, hipStream_t stream, DetPlan
     nchunk = (M + mchunk - 1) / mchunk;
     const long long grid = tiles * nchunk;
     FORGE_REQUIRE(grid < (1ll << 31), FORGE_ESHAPE, "forge_conv_wgrad: grid too large");
-    if (plan_note(plan, 1, ciw, tg, 4, grid, nchunk, a.mchunk, 0)) return 0;
-    if (det) {
-        if (int rc = det_prepare(a, *det, nchunk, "forge_conv_wgrad_det")) return rc < 0 ? rc : 0;
-    }
-    const size_t lds = 2 * 2 * WK * WT * sizeof(float);     // 32 KiB
-#define FORGE_LAUNCH_WGRAD_K(DETv, CIWv, TGv)                                                                                           \
-    do {                                                                                                                             \
-        FORGE_SET_MAX_LDS_ONCE((conv_wgrad_kernel<CIWv, TGv, DETv>), lds);                                                                                 \
-        hipLaunchKernelGGL((conv_wgrad_kernel<CIWv, TGv, DETv>), dim3((unsigned)grid), dim3(256), lds, stream, a);                                         \
-    } while (0)
-#define FORGE_LAUNCH_WGRAD(CIWv, TGv)                                                                                                \
-    do {                                                                                                                             \
-        if (det) FORGE_LAUNCH_WGRAD_K(true, CIWv, TGv);                                                             \
-        else FORGE_LAUNCH_WGRAD_K(false, CIWv, TGv);                                                                     \
-    } while (0)
-    if (ciw == 32 && tg == 4) FORGE_LAUNCH_WGRAD(32, 4);
-    else if (ciw == 64 && tg == 2) FORGE_LAUNCH_WGRAD(64, 2);
-    else if (ciw == 32) FORGE_LAUNCH_WGRAD(32, 1);
-    else if (ciw == 64) FORGE_LAUNCH_WGRAD(64, 1);
-    else FORGE_LAUNCH_WGRAD(128, 1);
-#undef FORGE_LAUNCH_WGRAD
-#undef FORGE_LAUNCH_WGRAD_K
-    FORGE_LAUNCH_CHECK("forge_conv_wgrad");
-    return det ? det_finish(*det, stream, "forge_conv_wgrad_det") : 0;
+    const int r = ciw == 32 ? (tg == 4 ? ROW_T32_TG4 : ROW_T32) : ciw == 64 ? (tg == 2 ? ROW_T64_TG2 : ROW_T64) : ROW_T128;
+    return launch_row(r, a, nullptr, nullptr, grid, nchunk, TILES_LDS, 0, stream, det, plan);
+}
+
+// The operands of a launch: batch strides (0 = dense: the input volume), the byte spans the buffer descriptors are built from, and the refusal
+// of a span the 32-bit offsets cannot address. fn / per: the caller's name and its unit of an operand, for the message.
+static int wgrad_operands(WgradArgs& a, const float* dy, int ldy, const float* x1, int C1, int ld1, long long bs1, const float* x2, int C2, int ld2,
+                          long long bs2, float* dw, int n, int D, int H, int W, int is, int Di, int Hi, int Wi, int Cout, int ntaps,
+                          const char* fn, const char* per) {
+    memset(&a, 0, sizeof(a));
+    a.dy = dy; a.ldy = ldy; a.x1 = x1; a.x2 = x2; a.C1 = C1; a.C2 = C2; a.ld1 = ld1; a.ld2 = ld2; a.dw = dw;
+    a.n = n; a.D = D; a.H = H; a.W = W; a.is = is; a.Di = Di; a.Hi = Hi; a.Wi = Wi; a.Cout = Cout; a.ntaps = ntaps;
+    const long long vol = (long long)Di * Hi * Wi;
+    a.bs1r = bs1 > 0 ? bs1 : vol; a.bs2r = bs2 > 0 ? bs2 : vol;
+    a.spany = (long long)n * D * H * W * ldy * 4;
+    a.span1 = ((long long)(n - 1) * a.bs1r + vol) * ld1 * 4;
+    a.span2 = x2 ? ((long long)(n - 1) * a.bs2r + vol) * ld2 * 4 : 0;
+    FORGE_REQUIRE(a.spany < (1ll << 31) && a.span1 < (1ll << 31) && a.span2 < (1ll << 31), FORGE_ESHAPE,
+                  "%s: an operand spans >= 2 GiB%s (32-bit buffer offsets); split the batch", fn, per);
+    return 0;
 }
 
 static int conv_wgrad_run(const float* dy, int ldy, const float* x1, int C1, int ld1, long long bs1, const float* x2, int C2, int ld2,
@@ -622,17 +602,10 @@ static int conv_wgrad_run(const float* dy, int ldy, const float* x1, int C1, int
     FORGE_REQUIRE((C2 == 0) == (x2 == nullptr), FORGE_EINVAL, "forge_conv_wgrad: x2/C2 mismatch");
     FORGE_REQUIRE(C2 == 0 || C1 % WT == 0, FORGE_ESHAPE, "forge_conv_wgrad: with two inputs C1 must be a multiple of %d", WT);
     WgradArgs a;
-    a.dy = dy; a.ldy = ldy; a.x1 = x1; a.x2 = x2; a.C1 = C1; a.C2 = C2; a.ld1 = ld1; a.ld2 = ld2; a.dw = dw;
-    a.n = n; a.D = D; a.H = H; a.W = W; a.is = is; a.Di = Di; a.Hi = Hi; a.Wi = Wi; a.Cout = Cout; a.ntaps = ntaps;
-    a.tpp = 0; a.pty = a.pt1 = a.pt2 = 0;
-    a.bs1r = bs1 > 0 ? bs1 : (long long)Di * Hi * Wi; a.bs2r = bs2 > 0 ? bs2 : (long long)Di * Hi * Wi;
+    if (int rc = wgrad_operands(a, dy, ldy, x1, C1, ld1, bs1, x2, C2, ld2, bs2, dw, n, D, H, W, is, Di, Hi, Wi, Cout, ntaps, "forge_conv_wgrad", ""))
+        return rc;
     const long long M = (long long)n * D * H * W;
-    a.spany = M * ldy * 4;
-    a.span1 = ((long long)(n - 1) * a.bs1r + (long long)Di * Hi * Wi) * ld1 * 4;
-    a.span2 = x2 ? ((long long)(n - 1) * a.bs2r + (long long)Di * Hi * Wi) * ld2 * 4 : 0;
-    FORGE_REQUIRE(a.spany < (1ll << 31) && a.span1 < (1ll << 31) && a.span2 < (1ll << 31), FORGE_ESHAPE,
-                  "forge_conv_wgrad: an operand spans >= 2 GiB (32-bit buffer offsets); split the batch");
-    for (int k = 0; k < 3 * ntaps; ++k)       // the kernels carry the taps as signed bytes
+    for (int k = 0; k < 3 * ntaps; ++k)      // the kernels carry the taps as signed bytes
         FORGE_REQUIRE(taps[k] >= -128 && taps[k] <= 127, FORGE_EINVAL, "forge_conv_wgrad: tap %d component %d = %d outside [-128, 127]", k / 3, k % 3, taps[k]);
     for (int t = 0; t < 64; ++t) {
         for (int k = 0; k < 3; ++k) a.tap[t][k] = (signed char)(t < ntaps ? taps[t * 3 + k] : 0);
@@ -661,75 +634,24 @@ static int conv_wgrad_run(const float* dy, int ldy, const float* x1, int C1, int
             a.tap[t][3] = (signed char)ln;
         }
         if (ok) {
+            // narrow outputs (Cout <= 16): the 16x16x4 MFMA tile, no 32-row padding
+            const int r = lines_s2 ? ROW_L16_S2 : Cout > 16 ? ROW_LINES : Cin <= 16 ? ROW_L16 : ROW_L16_C32;
+            const WgradRow& row = g_rows[r];
             const long long nseg = (long long)n * D * H * ((W + LSEG - 1) / LSEG);
-            const size_t lds = (size_t)(LSEG * 32 + lt.nlines * (LSEG + 2 * lt.rx) * 32) * sizeof(float);
-            if ((!det || det->launch) && !(plan && plan->dry)) FORGE_SET_MAX_LDS_ONCE(conv_wgrad_lines_kernel<>, (LSEG * 32 + LMAXL * LROWS * 32) * sizeof(float));
             a.mchunk = 0;
-            // det: one slab per workgroup (each walks its own segments), at most det_cap slabs
+            // persistent workgroups, each walking its share of the segments; det: one slab per workgroup, at most det_cap slabs
             const long long cap = det ? det_cap((long long)ntaps * Cout * Cin) : (1ll << 40);
-            auto clamp_grid = [&](long long g) { g = nseg < g ? nseg : g; return g < cap ? g : cap; };
-            if (lines_s2) {
-                const size_t lds16 = (size_t)(LSEG * 16 + lt.nlines * (2 * LSEG - 1 + 2 * lt.rx) * 16) * sizeof(float);
-                const long long grid16 = clamp_grid(768);                           // 3 resident workgroups per CU
-                if (plan_note(plan, 4, 16, 2, 4, grid16, grid16, 0, lt.nlines)) return 0;
-                if (det) { if (int rc = det_prepare(a, *det, grid16, "forge_conv_wgrad_det")) return rc < 0 ? rc : 0; }
-                if (det) {
-                    FORGE_SET_MAX_LDS_ONCE((conv_wgrad_lines16_kernel<16, 2, 9, 4, true>), (LSEG * 16 + 6 * (2 * LSEG - 1 + 2 * LMAXR) * 16) * sizeof(float));
-                    hipLaunchKernelGGL((conv_wgrad_lines16_kernel<16, 2, 9, 4, true>), dim3((unsigned)grid16), dim3(256), lds16, (hipStream_t)stream, a, lt);
-                } else {
-                    FORGE_SET_MAX_LDS_ONCE((conv_wgrad_lines16_kernel<16, 2, 9>), (LSEG * 16 + 6 * (2 * LSEG - 1 + 2 * LMAXR) * 16) * sizeof(float));
-                    hipLaunchKernelGGL((conv_wgrad_lines16_kernel<16, 2, 9>), dim3((unsigned)grid16), dim3(256), lds16, (hipStream_t)stream, a, lt);
-                }
-                FORGE_LAUNCH_CHECK("forge_conv_wgrad");
-                return det ? det_finish(*det, (hipStream_t)stream, "forge_conv_wgrad_det") : 0;
-            }
-            if (Cout <= 16) {
-                // narrow outputs: the 16x16x4 MFMA tile (no 32-row padding); 4 workgroups per CU walk the segments
-                const int cit = Cin <= 16 ? 16 : 32;
-                const size_t lds16 = (size_t)(LSEG * 16 + lt.nlines * (LSEG + 2 * lt.rx) * cit) * sizeof(float);
-                const long long grid16 = clamp_grid(cit == 16 ? 1024 : 768);        // 4 / 3 resident workgroups per CU (108 / ~150 VGPRs)
-                if (cit == 16) {
-                    if (plan_note(plan, 4, 16, 1, 4, grid16, grid16, 0, lt.nlines)) return 0;
-                    if (det) { if (int rc = det_prepare(a, *det, grid16, "forge_conv_wgrad_det")) return rc < 0 ? rc : 0; }
-                    if (det) {
-                        FORGE_SET_MAX_LDS_ONCE((conv_wgrad_lines16_kernel<16, 1, LTAPS, 4, true>), (LSEG * 16 + LMAXL * LROWS * 16) * sizeof(float));
-                        hipLaunchKernelGGL((conv_wgrad_lines16_kernel<16, 1, LTAPS, 4, true>), dim3((unsigned)grid16), dim3(256), lds16, (hipStream_t)stream, a, lt);
-                    } else {
-                        FORGE_SET_MAX_LDS_ONCE(conv_wgrad_lines16_kernel<16>, (LSEG * 16 + LMAXL * LROWS * 16) * sizeof(float));
-                        hipLaunchKernelGGL(conv_wgrad_lines16_kernel<16>, dim3((unsigned)grid16), dim3(256), lds16, (hipStream_t)stream, a, lt);
-                    }
-                } else {
-                    const long long grid32 = clamp_grid(512);              // 8-wave workgroups, 2 per CU
-                    if (plan_note(plan, 4, 32, 1, 8, grid32, grid32, 0, lt.nlines)) return 0;
-                    if (det) { if (int rc = det_prepare(a, *det, grid32, "forge_conv_wgrad_det")) return rc < 0 ? rc : 0; }
-                    if (det) {
-                        FORGE_SET_MAX_LDS_ONCE((conv_wgrad_lines16_kernel<32, 1, 4, 8, true>), (LSEG * 16 + LMAXL * LROWS * 32) * sizeof(float));
-                        hipLaunchKernelGGL((conv_wgrad_lines16_kernel<32, 1, 4, 8, true>), dim3((unsigned)grid32), dim3(512), lds16, (hipStream_t)stream, a, lt);
-                    } else {
-                        FORGE_SET_MAX_LDS_ONCE((conv_wgrad_lines16_kernel<32, 1, 4, 8>), (LSEG * 16 + LMAXL * LROWS * 32) * sizeof(float));
-                        hipLaunchKernelGGL((conv_wgrad_lines16_kernel<32, 1, 4, 8>), dim3((unsigned)grid32), dim3(512), lds16, (hipStream_t)stream, a, lt);
-                    }
-                }
-                FORGE_LAUNCH_CHECK("forge_conv_wgrad");
-                return det ? det_finish(*det, (hipStream_t)stream, "forge_conv_wgrad_det") : 0;
-            }
-            const long long grid = clamp_grid(512);                  // 2 workgroups per CU (244 VGPRs), each walking its share of the segments
-            if (plan_note(plan, 3, 32, 1, 4, grid, grid, 0, lt.nlines)) return 0;
-            if (det) {
-                if (int rc = det_prepare(a, *det, grid, "forge_conv_wgrad_det")) return rc < 0 ? rc : 0;
-                FORGE_SET_MAX_LDS_ONCE(conv_wgrad_lines_kernel<true>, (LSEG * 32 + LMAXL * LROWS * 32) * sizeof(float));
-                hipLaunchKernelGGL(conv_wgrad_lines_kernel<true>, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, a, lt);
-            } else {
-                hipLaunchKernelGGL(conv_wgrad_lines_kernel<>, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, a, lt);
-            }
-            FORGE_LAUNCH_CHECK("forge_conv_wgrad");
-            return det ? det_finish(*det, (hipStream_t)stream, "forge_conv_wgrad_det") : 0;
+            long long grid = (long long)NUM_CU * row.resident;
+            if (grid > nseg) grid = nseg;
+            if (grid > cap) grid = cap;
+            const size_t lds = lines_lds(row.yw, row.p1, row.p2, lt.nlines, lt.rx);
+            return launch_row(r, a, &lt, nullptr, grid, grid, lds, lt.nlines, (hipStream_t)stream, det, plan);
         }
         for (int t = 0; t < ntaps; ++t) a.tap[t][3] = 0;
     }
     if (Cout <= 32 && Cin <= 32 && x2 == nullptr && W % 2 == 0) {
         // narrow channels: independent waves, 4 taps each, fed straight from global memory
-        const int tap_groups = (ntaps + 3) / 4;
+        int tap_groups = (ntaps + 3) / 4;
         long long rows = (M * tap_groups + 4095) / 4096;            // ~4096 waves
         rows = (rows + 1) / 2 * 2;
         if (rows < 256) rows = 256;
@@ -738,18 +660,10 @@ static int conv_wgrad_run(const float* dy, int ldy, const float* x1, int C1, int
             if ((M + rows - 1) / rows > cap) rows = ((M + cap - 1) / cap + 1) / 2 * 2;
         }
         a.mchunk = (int)rows;
-        const long long waves = ((M + rows - 1) / rows) * tap_groups;
-        if (plan_note(plan, 2, 32, 4, 4, (waves + 3) / 4, (M + rows - 1) / rows, (int)rows, 0)) return 0;
-        if (det) {
-            if (int rc = det_prepare(a, *det, (M + rows - 1) / rows, "forge_conv_wgrad_det")) return rc < 0 ? rc : 0;
-            hipLaunchKernelGGL(conv_wgrad_small_kernel<true>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a, tap_groups, (int)rows);
-        } else {
-            hipLaunchKernelGGL(conv_wgrad_small_kernel<>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a, tap_groups, (int)rows);
-        }
-        FORGE_LAUNCH_CHECK("forge_conv_wgrad");
-        return det ? det_finish(*det, (hipStream_t)stream, "forge_conv_wgrad_det") : 0;
+        const long long nchunk = (M + rows - 1) / rows, waves = nchunk * tap_groups;
+        return launch_row(ROW_SMALL, a, &tap_groups, &a.mchunk, (waves + 3) / 4, nchunk, 0, 0, (hipStream_t)stream, det, plan);
     }
-    return launch_wgrad_tiles(a, (x2 == nullptr && Cin <= 32) ? 32 : (x2 == nullptr && Cin <= 64) ? 64 : WT, (hipStream_t)stream, det, plan);
+    return launch_wgrad_tiles(a, (hipStream_t)stream, det, plan);
 }
 
 extern "C" int forge_conv_wgrad(const float* dy, int ldy, const float* x1, int C1, int ld1, long long bs1, const float* x2, int C2, int ld2,
@@ -802,20 +716,13 @@ static int wino_wgrad_run(const float* dMm, const float* V1, int C1, long long b
                   (C2 == 0) == (V2 == nullptr) && (C2 == 0 || C1 % WT == 0), FORGE_ESHAPE,
                   "forge_wino_wgrad: bad dims (channel counts multiples of 4; with two inputs C1 a multiple of %d)", WT);
     WgradArgs a;
-    memset(&a, 0, sizeof(a));
-    const long long vol = (long long)D * Ht * Wt, R = (long long)n * vol;
-    a.dy = dMm; a.ldy = Cout; a.x1 = V1; a.x2 = V2; a.C1 = C1; a.C2 = C2; a.ld1 = C1; a.ld2 = C2; a.dw = dU;
-    a.n = n; a.D = D; a.H = Ht; a.W = Wt; a.is = 1; a.Di = D; a.Hi = Ht; a.Wi = Wt; a.Cout = Cout; a.ntaps = 16 * kd;
-    a.bs1r = bs1 > 0 ? bs1 : vol; a.bs2r = bs2 > 0 ? bs2 : vol;
-    a.spany = R * Cout * 4;
-    a.span1 = ((long long)(n - 1) * a.bs1r + vol) * C1 * 4;
-    a.span2 = V2 ? ((long long)(n - 1) * a.bs2r + vol) * C2 * 4 : 0;
-    FORGE_REQUIRE(a.spany < (1ll << 31) && a.span1 < (1ll << 31) && a.span2 < (1ll << 31), FORGE_ESHAPE,
-                  "forge_wino_wgrad: an operand spans >= 2 GiB per Winograd point (32-bit buffer offsets); split the batch");
+    if (int rc = wgrad_operands(a, dMm, Cout, V1, C1, C1, bs1, V2, C2, C2, bs2, dU, n, D, Ht, Wt, 1, D, Ht, Wt, Cout, 16 * kd, "forge_wino_wgrad",
+                                " per Winograd point"))
+        return rc;
+    const long long R = (long long)n * D * Ht * Wt;
     a.tpp = kd; a.pty = R * Cout; a.pt1 = pt1 > 0 ? pt1 : R * C1; a.pt2 = V2 ? (pt2 > 0 ? pt2 : R * C2) : 0;
     for (int t = 0; t < 16 * kd; ++t) a.tap[t][0] = (signed char)(kd == 3 ? t % 3 - 1 : 0);
-    const int Cin = C1 + C2;
-    return launch_wgrad_tiles(a, (V2 == nullptr && Cin <= 32) ? 32 : (V2 == nullptr && Cin <= 64) ? 64 : WT, (hipStream_t)stream, det);
+    return launch_wgrad_tiles(a, (hipStream_t)stream, det);
 }
 
 extern "C" int forge_wino_wgrad(const float* dMm, const float* V1, int C1, long long bs1, long long pt1, const float* V2, int C2, long long bs2,

@@ -379,7 +379,7 @@ long long forge_conv_wgrad_det_ws_bytes(int C1, int C2, int n, int D, int H, int
                                         const int* taps, int ntaps);
 /* Host-only, like the query above: what forge_conv_wgrad (det = 0) or forge_conv_wgrad_det (det = 1) launches for dense operands of this
  * shape - the dispatch itself with the launch switched off, refusals included (< 0). plan[8]:
- *   [0] kernel family  1 conv_wgrad_kernel<CIW, TG>  2 conv_wgrad_small_kernel  3 conv_wgrad_lines_kernel  4 conv_wgrad_lines16_kernel<CIT, IS, .., NWV>
+ *   [0] kernel family  1 conv_wgrad_kernel<CIW, TG>  2 conv_wgrad_small_kernel  3 conv_wgrad_lines_kernel on the 32x32x2 MFMA  4 on the 16x16x4 MFMA <CIT, IS, .., NWV>
  *   [1] CIW (128 / 64 / 32) or CIT (16 / 32); 32 for families 2, 3      [2] TG (1 / 2 / 4) or IS (1 / 2); taps per wave (4) for family 2
  *   [3] waves per workgroup (NWV)                                       [4] workgroups of the launch
  *   [5] voxel chunks (families 1, 2) or persistent workgroups walking the 32-voxel segments (3, 4): the slab count of the deterministic mode

@@ -676,7 +676,7 @@ def test_conv_rgb_autograd_hip_vs_torch(dev):
 @pytest.mark.parametrize("n,H,W,k,pad", [(3, 24, 40, 6, 2), (1, 7, 33, 6, 2), (2, 16, 64, 4, 1), (5, 9, 5, 6, 2)])
 def test_narrow_transposed_conv_s2_autograd_vs_torch(dev, n, H, W, k, pad):
     """ConvTranspose2d(16, 16, k, stride 2) on NHWC rows (conv_rgb[0], models/volume_render.py:29-31) with autograd: forward (phase GEMMs on the
-    narrow-N kernel), data gradient (stride-2 gather GEMM) and weight gradient - conv_wgrad_lines16_kernel<16, 2, 9>: k^2 <= 36 taps on <= 6
+    narrow-N kernel), data gradient (stride-2 gather GEMM) and weight gradient - conv_wgrad_lines_kernel<Mfma16x16x4, 16, 2, 9, 4>: k^2 <= 36 taps on <= 6
     lines, the gathered operand on the 2x finer grid - against torch's own autograd; widths that are no multiple of the 32-voxel segment,
     single rows of segments, several images."""
     from forge_amd import convops as co
