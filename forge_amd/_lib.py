@@ -51,6 +51,10 @@ SIGNATURES = {
     "forge_wino_input_dn4": [_P, _I, _LL, _P, _I, _LL, _I, _I, _I, _I, _I, _I, _LL, _P],
     "forge_wino_weights_dn4": [_P, _P, _I, _I, _P],
     "forge_wino_gemm_dn4": [_P, _I, _I, _LL, _LL, _P, _I, _I, _LL, _LL, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "forge_wino_input_dn4h": [_P, _I, _LL, _P, _I, _LL, _I, _I, _I, _I, _I, _I, _LL, _P],
+    "forge_wino_weights_dn4h": [_P, _P, _I, _I, _P],
+    "forge_wino_gemm_dn4h": [_P, _I, _I, _LL, _LL, _P, _I, _I, _LL, _LL, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "forge_wino_output_dn4h": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "forge_wino_output_half": [_P, _P, _LL, _LL, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "forge_wino_gemm_tile": [_LL, _I, _I],
     "forge_wino_output": [_P, _P, _LL, _LL, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],

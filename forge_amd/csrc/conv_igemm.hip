@@ -1300,7 +1300,10 @@ extern "C" int forge_wino_gemm_tile(long long R, int Cout, int Cin) {
 // kd = 3 for the 3x3x3 convolutions, kd = 1 for the 3x3 convolutions of a 2-D network (D = 1 or D = images: planes do not mix).
 static int wino_gemm_impl(const float* V1, int C1, int ld1, long long bs1, long long pt1, const float* V2, int C2, int ld2, long long bs2,
                           long long pt2, const float* U, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, int tile, int form, forge_stream_t stream) {
-    const bool half = form == 1, dn = form == 2, dn4 = form == 3;   // form: 0 = 16 points, 1 = the four-point row stage, 2 = the depth nest, 3 = its F(4, 3) form
+    // form: 0 = 16 points, 1 = the four-point row stage, 2 = the depth nest, 3 = its F(4, 3) form, 4 = that form on the 24 points of F(4, 3) along H (the same launch
+    // with 24 batched problems on the grid of 4 x 2 tiles)
+    const bool half = form == 1, dn = form == 2, dn4h = form == 4, dn4 = form == 3 || dn4h;
+    const char* const name4 = dn4h ? "forge_wino_gemm_dn4h" : "forge_wino_gemm_dn4";
     FORGE_REQUIRE(tile == 0 || (tile >= 'A' && tile <= 'E'), FORGE_EINVAL, "forge_wino_gemm: tile must be 0 (default rule) or 'A'..'E'");
     FORGE_REQUIRE(V1 && U && Mm && (kd == 1 || kd == 3), FORGE_EINVAL, "forge_wino_gemm: null pointer argument / kd not 1 or 3");
     FORGE_REQUIRE(n > 0 && D > 0 && Ht > 0 && Wt > 0 && Cout > 16, FORGE_EINVAL, "forge_wino_gemm: bad dims n=%d D=%d Ht=%d Wt=%d Cout=%d (Cout > 16)", n,
@@ -1311,7 +1314,8 @@ static int wino_gemm_impl(const float* V1, int C1, int ld1, long long bs1, long 
     FORGE_REQUIRE(!dn || (kd == 3 && D % 2 == 0 && ((long long)Ht * Wt) % 64 == 0), FORGE_EINVAL,
                   "forge_wino_gemm_dn: needs three depth taps, an even D and Ht Wt %% 64 == 0 (kd=%d D=%d Ht=%d Wt=%d)", kd, D, Ht, Wt);
     FORGE_REQUIRE(!dn4 || (kd == 3 && D % 4 == 0 && ((long long)Ht * Wt) % 64 == 0), FORGE_EINVAL,
-                  "forge_wino_gemm_dn4: needs three depth taps, D %% 4 == 0 and Ht Wt %% 64 == 0 (kd=%d D=%d Ht=%d Wt=%d)", kd, D, Ht, Wt);
+                  "%s: needs three depth taps, D %% 4 == 0 and Ht Wt %% 64 == 0 (kd=%d D=%d Ht=%d Wt=%d)", name4, kd, D, Ht, Wt);
+    FORGE_REQUIRE(!dn4h || D >= 8, FORGE_EINVAL, "forge_wino_gemm_dn4h: D=%d must be at least 8", D);
     ConvArgs a;
     memset(&a, 0, sizeof(a));
     // operand rows per batch element and K loops per tile: vol rows and the kd depth taps; depth nest: U' [16][4][Cout][Cin], the four depth positions
@@ -1323,7 +1327,7 @@ static int wino_gemm_impl(const float* V1, int C1, int ld1, long long bs1, long 
     a.span2 = V2 ? ((long long)(n - 1) * a.bs2r + rows) * ld2 * 4 : 0;
     if (dn4) {
         FORGE_REQUIRE(a.span1 < (1ll << 31) && a.span2 < (1ll << 31) && R * Cout * 4 < (1ll << 31) && 6ll * Cout * Cin * 4 < (1ll << 31), FORGE_EINVAL,
-                      "forge_wino_gemm_dn4: an operand or an output plane spans >= 2 GiB (32-bit buffer offsets); split the batch");
+                      "%s: an operand or an output plane spans >= 2 GiB (32-bit buffer offsets); split the batch", name4);
     } else {
         FORGE_REQUIRE(a.span1 < (1ll << 31) && a.span2 < (1ll << 31) && R < (1ll << 31), FORGE_ESHAPE,
                       "forge_wino_gemm: an operand spans >= 2 GiB per Winograd point (32-bit buffer offsets); split the batch");
@@ -1332,15 +1336,15 @@ static int wino_gemm_impl(const float* V1, int C1, int ld1, long long bs1, long 
     }
     a.wp = U; a.slope = 1.f; a.out = Mm; a.n = n; a.D = D; a.H = Ht; a.W = Wt; a.is = 1; a.Di = D; a.Hi = Ht; a.Wi = Wt;
     a.Cout = Cout; a.ldo = Cout; a.ldr = Cout; a.ntaps = a.tpp = npos; a.os = 1; a.Do = D; a.Ho = Ht; a.Wo = Wt; a.nphase = 1; a.epi = EPI_BIAS;
-    a.ksplit = 1; a.nbat = half ? 4 : 16;
+    a.ksplit = 1; a.nbat = half ? 4 : dn4h ? 24 : 16;
     a.pt1 = pt1 > 0 ? pt1 : (long long)n * rows * ld1; a.pt2 = V2 ? (pt2 > 0 ? pt2 : (long long)n * rows * ld2) : 0;   // 0 = dense planes, as forge_wino_wgrad reads it
     a.ptw = (long long)npos * Cout * Cin; a.pto = R * Cout;
     if (form == 0 || half) {
         if (kd == 3) { a.tap[0][0] = -1; a.tap[2][0] = 1; }             // depth taps (-1,0,0), (0,0,0), (1,0,0); kd = 1: the 2-D convolution's single tap
         if (!tile) tile = forge_wino_gemm_tile(R, Cout, C1 + C2);
     }
-    if (int rc = launch_conv_tile(a, (char)tile, (hipStream_t)stream, form)) return rc;
-    FORGE_LAUNCH_CHECK(dn4 ? "forge_wino_gemm_dn4" : dn ? "forge_wino_gemm_dn" : "forge_wino_gemm");
+    if (int rc = launch_conv_tile(a, (char)tile, (hipStream_t)stream, dn4h ? 3 : form)) return rc;
+    FORGE_LAUNCH_CHECK(dn4 ? name4 : dn ? "forge_wino_gemm_dn" : "forge_wino_gemm");
     return 0;
 }
 
@@ -1379,4 +1383,13 @@ extern "C" int forge_wino_gemm_dn4(const float* V1, int C1, int ld1, long long b
                                    long long pt2, const float* Ud, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, forge_stream_t stream) {
     FORGE_REQUIRE(C1 > 0 && C1 % BK == 0 && C2 >= 0 && C2 % BK == 0, FORGE_EINVAL, "forge_wino_gemm_dn4: C1=%d / C2=%d must be multiples of %d", C1, C2, BK);
     return wino_gemm_impl(V1, C1, ld1, bs1, pt1, V2, C2, ld2, bs2, pt2, Ud, Mm, n, D, Ht, Wt, Cout, kd, 'B', 3, stream);
+}
+
+// forge_wino_gemm_dn4 on the 24 points of F(4, 3) along H x F(2, 3) along W (the same kernel, 24 batched problems): the point products Mm [24][R][Cout],
+// R = n D Ht Wt tile rows of the grid of 4 x 2 tiles (Ht = H / 4), from the operands V [24][n][D/4][6][Ht Wt][C] (forge_wino_input_dn4h) against
+// Ud [24][6][Cout][C1 + C2] (forge_wino_weights_dn4h); forge_wino_output_dn4h inverts them. forge_wino_gemm_dn4's preconditions on this grid, and D >= 8.
+extern "C" int forge_wino_gemm_dn4h(const float* V1, int C1, int ld1, long long bs1, long long pt1, const float* V2, int C2, int ld2, long long bs2,
+                                    long long pt2, const float* Ud, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, forge_stream_t stream) {
+    FORGE_REQUIRE(C1 > 0 && C1 % BK == 0 && C2 >= 0 && C2 % BK == 0, FORGE_EINVAL, "forge_wino_gemm_dn4h: C1=%d / C2=%d must be multiples of %d", C1, C2, BK);
+    return wino_gemm_impl(V1, C1, ld1, bs1, pt1, V2, C2, ld2, bs2, pt2, Ud, Mm, n, D, Ht, Wt, Cout, kd, 'B', 4, stream);
 }

@@ -22,6 +22,25 @@ __device__ __forceinline__ float4 add(float4 a, float4 b) { return make_float4(a
 __device__ __forceinline__ float4 sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
 __device__ __forceinline__ float add(float a, float b) { return a + b; }
 __device__ __forceinline__ float sub(float a, float b) { return a - b; }
+__device__ __forceinline__ float4 fma4(float k, float4 a, float4 b) { return make_float4(fmaf(k, a.x, b.x), fmaf(k, a.y, b.y), fmaf(k, a.z, b.z), fmaf(k, a.w, b.w)); }
+
+// The six lines of B^T of F(4, 3) = [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1] on six values p0 .. p5 (q may be p itself), in this
+// order (every multiplier is a power of two, so each line is two rounded additions and one fused multiply-add whose product is exact - a plain multiply and
+// add gives the same bits):
+//   q0 = 4 (p0 - p2) - (p2 - p4)      q1 = (p3 + p4) - 4 (p1 + p2)      q2 = (p4 - p3) + 4 (p1 - p2)
+//   q3 = (p4 - p2) + 2 (p3 - p1)      q4 = (p4 - p2) - 2 (p3 - p1)      q5 = 4 (p1 - p3) - (p3 - p5)
+// The depth stage of both F(4, 3) nests and the row stage of forge_wino_input_dn4h.
+__device__ __forceinline__ void f43_six_lines(float p0, float p1, float p2, float p3, float p4, float p5, float& q0, float& q1, float& q2, float& q3, float& q4,
+                                              float& q5) {
+    const float a02 = p0 - p2, a24 = p2 - p4, s34 = p3 + p4, s12 = p1 + p2, d43 = p4 - p3, d12 = p1 - p2;
+    const float d42 = p4 - p2, d31 = p3 - p1, d13 = p1 - p3, d35 = p3 - p5;
+    q0 = fmaf(4.f, a02, -a24);
+    q1 = fmaf(-4.f, s12, s34);
+    q2 = fmaf(4.f, d12, d43);
+    q3 = fmaf(2.f, d31, d42);
+    q4 = fmaf(-2.f, d31, d42);
+    q5 = fmaf(4.f, d13, -d35);
+}
 
 // ---- the pieces the kernels below are written on. Free functions whose arguments are formed where the kernels formed them before they were shared:
 // the signatures (a row and its stride instead of a pointer, a shift instead of a factor) keep the compiler's instruction order
@@ -38,6 +57,15 @@ __device__ __forceinline__ void tile_decode(long long idx, int per, int cs, int 
 }
 
 // V[4i + j] = (B^T d B)[i][j] of one 4 x 4 patch d (T = float4: four channels; float: one): point p goes to V + row ld + c + p ptv
+// the column stage w B of one row w of B^T d: the four points 4 i + j of point row i go to vp + (4 i + j) ptv
+template <typename T>
+__device__ __forceinline__ void bt_cols_store(const T (&w)[4], float* vp, int i, long long ptv) {
+    *reinterpret_cast<T*>(vp + (4 * i + 0) * ptv) = sub(w[0], w[2]);
+    *reinterpret_cast<T*>(vp + (4 * i + 1) * ptv) = add(w[1], w[2]);
+    *reinterpret_cast<T*>(vp + (4 * i + 2) * ptv) = sub(w[2], w[1]);
+    *reinterpret_cast<T*>(vp + (4 * i + 3) * ptv) = sub(w[1], w[3]);
+}
+
 template <typename T, typename I>
 __device__ __forceinline__ void bt_d_b_store(const T (&d)[4][4], float* V, I row, int ld, int c, long long ptv) {
     T w[4][4];                                       // rows: B^T d
@@ -50,12 +78,7 @@ __device__ __forceinline__ void bt_d_b_store(const T (&d)[4][4], float* V, I row
     }
     float* vp = V + (long long)row * ld + c;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {                    // columns: (B^T d) B
-        *reinterpret_cast<T*>(vp + (4 * i + 0) * ptv) = sub(w[i][0], w[i][2]);
-        *reinterpret_cast<T*>(vp + (4 * i + 1) * ptv) = add(w[i][1], w[i][2]);
-        *reinterpret_cast<T*>(vp + (4 * i + 2) * ptv) = sub(w[i][2], w[i][1]);
-        *reinterpret_cast<T*>(vp + (4 * i + 3) * ptv) = sub(w[i][1], w[i][3]);
-    }
+    for (int i = 0; i < 4; ++i) bt_cols_store(w[i], vp, i, ptv);      // columns: (B^T d) B
 }
 
 // dM[4i + j] = (A y A^T)[i][j] of one 2 x 2 output tile y, A = [1 0; 1 1; 1 -1; 0 -1]; point p at mp + p ptm
@@ -71,18 +94,29 @@ __device__ __forceinline__ void a_y_at_store(float4 y00, float4 y01, float4 y10,
     }
 }
 
-// U[4i + j] = (float)(G d G^T)[i][j] of one 3 x 3 kernel slice d in float64, rounded once; point p at up + p pt
+// Row k of the weight matrix G of a 1-D Winograd form on the three taps w0, w1, w2, in float64:
+//   F(2, 3): G = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1] (exact on fp32 taps)
+//   F(4, 3): G = [1/4 0 0; -1/6 -1/6 -1/6; -1/6 1/6 -1/6; 1/24 1/12 1/6; 1/24 -1/12 1/6; 0 0 1] (the sixths are not exact in float64: the result is the
+//            evaluation below, correctly rounded to within one float64 rounding per operation)
+__device__ __forceinline__ double depth_row_f23(int k, double w0, double w1, double w2) {
+    return k == 0 ? w0 : k == 1 ? 0.5 * (w0 + w1 + w2) : k == 2 ? 0.5 * (w0 - w1 + w2) : w2;
+}
+__device__ __forceinline__ double depth_row_f43(int k, double w0, double w1, double w2) {
+    return k == 0 ? 0.25 * w0 : k == 1 ? -((w0 + w2) + w1) / 6.0 : k == 2 ? -((w0 + w2) - w1) / 6.0
+         : k == 3 ? ((0.25 * w0 + w2) + 0.5 * w1) / 6.0 : k == 4 ? ((0.25 * w0 + w2) - 0.5 * w1) / 6.0 : w2;
+}
+
+// U[4i + j] = (float)(G_H d G^T)[i][j] of one 3 x 3 kernel slice d in float64, rounded once; point p at up + p pt. G_H = the NH rows HROW of the form along H
+// (F(2, 3): 4 rows, 16 points; F(4, 3): 6 rows, 24 points), G = F(2, 3) along W.
+template <int NH = 4, double (*HROW)(int, double, double, double) = depth_row_f23>
 __device__ __forceinline__ void g_d_gt_store(const double (&d)[3][3], float* up, long long pt) {
-    double g[4][3];                                  // G d
+    double g[NH][3];                                 // G_H d
 #pragma unroll
-    for (int b = 0; b < 3; ++b) {
-        g[0][b] = d[0][b];
-        g[1][b] = 0.5 * (d[0][b] + d[1][b] + d[2][b]);
-        g[2][b] = 0.5 * (d[0][b] - d[1][b] + d[2][b]);
-        g[3][b] = d[2][b];
-    }
+    for (int b = 0; b < 3; ++b)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {                    // (G d) G^T
+        for (int i = 0; i < NH; ++i) g[i][b] = HROW(i, d[0][b], d[1][b], d[2][b]);
+#pragma unroll
+    for (int i = 0; i < NH; ++i) {                   // (G_H d) G^T
         up[(4 * i + 0) * pt] = (float)g[i][0];
         up[(4 * i + 1) * pt] = (float)(0.5 * (g[i][0] + g[i][1] + g[i][2]));
         up[(4 * i + 2) * pt] = (float)(0.5 * (g[i][0] - g[i][1] + g[i][2]));
@@ -144,16 +178,23 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const WinoInArgs a) {
 
 // The input transform of the F(4, 3) depth nest (forge_wino_input_dn4): wino_input_kernel's B^T d B on the DEPTH-COMBINED patches of a group of four
 // planes. Group g of a batch element covers the output planes 4g .. 4g + 3 and reads the planes p_e = plane 4g - 1 + e, e = 0..5 (zero outside the batch
-// element's grid, never the neighbouring element's planes). Depth stage, per patch element, in this order (every multiplier is a power of two, so each
-// line is two rounded additions and one fused multiply-add whose product is exact - a plain multiply and add gives the same bits):
-//   q0 = 4 (p0 - p2) - (p2 - p4)      q1 = (p3 + p4) - 4 (p1 + p2)      q2 = (p4 - p3) + 4 (p1 - p2)
-//   q3 = (p4 - p2) + 2 (p3 - p1)      q4 = (p4 - p2) - 2 (p3 - p1)      q5 = 4 (p1 - p3) - (p3 - p5)
-// = the rows of B^T_depth = [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1]; then the 2-D stage of
-// wino_input_kernel on each q_k (rows first, then columns). Output V6 [16][n][D/4][6][Ht Wt][C]: position k of group g is plane 6 g + k of the element.
+// element's grid, never the neighbouring element's planes). Depth stage, per patch element: q0 .. q5 = f43_six_lines(p0 .. p5), the rows of B^T of F(4, 3);
+// then the 2-D stage of wino_input_kernel on each q_k (rows first, then columns). Output V6 [16][n][D/4][6][Ht Wt][C]: position k of group g is plane
+// 6 g + k of the element.
 // One thread = one tile of one group x ONE channel (96 values live): a wave reads and writes 256 contiguous bytes per instruction, every loaded value is
 // used for all six positions (96 loads, 96 stores).
+// TH = 4 (forge_wino_input_dn4h): F(4, 3) along H as well - tiles of 4 x 2 output pixels, Ht = H / 4; the patch of tile (th, tw) is the six rows 4 th - 1 ..
+// 4 th + 4 x the four columns 2 tw - 1 .. 2 tw + 2. Three stages, in this order:
+//   depth   q_k[i][j] = f43_six_lines over the six planes of the group, per patch element                     (the same code as TH = 2)
+//   rows    w_k[i'][j] = f43_six_lines over the six patch rows i of q_k, per depth position k and patch column j
+//   cols    V[4 i' + j'] = w_k[i'] B of F(2, 3): w0 - w2, w1 + w2, w2 - w1, w1 - w3                             (bt_cols_store: wino_input_kernel's column stage)
+// Output V [24][n][D/4][6][Ht Wt][C], point p = 4 i' + j': the same operand layout on the (Ht, Wt) grid with 24 points. 144 loads, 144 values live, 144
+// stores per thread (a float4 of channels per thread would need 576 registers). Code object (hipcc -O3, gfx950): 170 VGPRs, no scratch = 2 waves per SIMD
+// (TH = 2: 120 VGPRs, 4 waves); per launch 21.9 us against 24.1 us at one scene, 172 against 231 us at eight (profiles/r22_wino_dn4h_launch.txt).
+template <int TH>
 __global__ __launch_bounds__(256) void wino_input_dn4_kernel(const WinoInArgs a) {
-    const int Ht = a.H >> 1, Wt = a.W >> 1, Dg = a.D >> 2;
+    constexpr int NR = TH + 2;                                       // patch rows
+    const int Ht = TH == 4 ? a.H >> 2 : a.H >> 1, Wt = a.W >> 1, Dg = a.D >> 2;
     const long long idx = (long long)xcd_remap(blockIdx.x, gridDim.x) * 256 + threadIdx.x;
     const long long RG = (long long)a.n * Dg * Ht * Wt;             // group tiles
     if (idx >= RG * a.C) return;
@@ -165,10 +206,10 @@ __global__ __launch_bounds__(256) void wino_input_dn4_kernel(const WinoInArgs a)
     const long long HW = (long long)a.H * a.W;
     const float* base = a.in + (long long)t * a.bs * a.ld + c;
     const float inv = 1.f / (float)a.nsum;                           // ATen divides by a scalar as a multiplication by its fp32 reciprocal
-    float d[6][4][4];
+    float d[6][NR][4];                                               // [depth position k][patch row i][patch column j]
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int y = 2 * th - 1 + i;
+    for (int i = 0; i < NR; ++i) {
+        const int y = TH * th - 1 + i;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int x = 2 * tw - 1 + j;
@@ -188,20 +229,24 @@ __global__ __launch_bounds__(256) void wino_input_dn4_kernel(const WinoInArgs a)
                 }
                 p[e] = v;
             }
-            const float a02 = p[0] - p[2], a24 = p[2] - p[4], s34 = p[3] + p[4], s12 = p[1] + p[2], d43 = p[4] - p[3], d12 = p[1] - p[2];
-            const float d42 = p[4] - p[2], d31 = p[3] - p[1], d13 = p[1] - p[3], d35 = p[3] - p[5];
-            d[0][i][j] = fmaf(4.f, a02, -a24);
-            d[1][i][j] = fmaf(-4.f, s12, s34);
-            d[2][i][j] = fmaf(4.f, d12, d43);
-            d[3][i][j] = fmaf(2.f, d31, d42);
-            d[4][i][j] = fmaf(-2.f, d31, d42);
-            d[5][i][j] = fmaf(4.f, d13, -d35);
+            f43_six_lines(p[0], p[1], p[2], p[3], p[4], p[5], d[0][i][j], d[1][i][j], d[2][i][j], d[3][i][j], d[4][i][j], d[5][i][j]);
         }
     }
     const long long HWt = (long long)Ht * Wt;
     float* vp = a.V + ((((long long)t * Dg + g) * 6) * HWt + (long long)th * Wt + tw) * a.ldv + c;
+    if constexpr (TH == 4) {
 #pragma unroll
-    for (int k = 0; k < 6; ++k) bt_d_b_store(d[k], vp, k * HWt, a.ldv, 0, a.ptv);
+        for (int k = 0; k < 6; ++k) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                f43_six_lines(d[k][0][j], d[k][1][j], d[k][2][j], d[k][3][j], d[k][4][j], d[k][5][j], d[k][0][j], d[k][1][j], d[k][2][j], d[k][3][j], d[k][4][j], d[k][5][j]);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) bt_cols_store(d[k][i], vp + k * HWt * a.ldv, i, a.ptv);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) bt_d_b_store(d[k], vp, k * HWt, a.ldv, 0, a.ptv);
+    }
 }
 
 // U[4i+j][kd][o][c] = (G w[kd] G^T)[i][j] from packed weights wp[(kd 3 + a) 3 + b][co][ci]: one thread per (kd, o, c). Evaluated in float64
@@ -229,16 +274,11 @@ __global__ __launch_bounds__(256) void wino_weight_kernel(const float* __restric
 // every element of the three depth slices. One thread per (o, c); float64 throughout, rounded once.
 //   F(2, 3) (forge_wino_gemm_dn): Gd = G, the rows w0, (w0 + w1 + w2) / 2, (w0 - w1 + w2) / 2, w2 (exact: at most 27 fp32 terms with coefficients 1, 1/2, 1/4, 1/8)
 //   F(4, 3) (forge_wino_gemm_dn4): Gd = [1/4 0 0; -1/6 -1/6 -1/6; -1/6 1/6 -1/6; 1/24 1/12 1/6; 1/24 -1/12 1/6; 0 0 1] (the sixths are not exact in float64: the
-//           result is the float64 evaluation below, correctly rounded to within one float64 rounding per operation)
-__device__ __forceinline__ double depth_row_f23(int k, double w0, double w1, double w2) {
-    return k == 0 ? w0 : k == 1 ? 0.5 * (w0 + w1 + w2) : k == 2 ? 0.5 * (w0 - w1 + w2) : w2;
-}
-__device__ __forceinline__ double depth_row_f43(int k, double w0, double w1, double w2) {
-    return k == 0 ? 0.25 * w0 : k == 1 ? -((w0 + w2) + w1) / 6.0 : k == 2 ? -((w0 + w2) - w1) / 6.0
-         : k == 3 ? ((0.25 * w0 + w2) + 0.5 * w1) / 6.0 : k == 4 ? ((0.25 * w0 + w2) - 0.5 * w1) / 6.0 : w2;
-}
-
-template <int K, double (*ROW)(int, double, double, double)>
+//           result is depth_row_f43's float64 evaluation, correctly rounded to within one float64 rounding per operation)
+//   F(4, 3) on depth AND on H (forge_wino_gemm_dn4h, NH = 6, HROW = the F(4, 3) rows): U''' [24][6][Cout][Cin] = G4(depth) (x) G4(H) (x) G2(W), point p = 4 i + j with
+//           i = 0..5 the H point: the depth rows on every element, then the H rows, then the W rows, all in float64, rounded once
+// (the rows: depth_row_f23 / depth_row_f43 above g_d_gt_store)
+template <int K, double (*ROW)(int, double, double, double), int NH = 4, double (*HROW)(int, double, double, double) = depth_row_f23>
 __global__ __launch_bounds__(256) void wino_weight_nest_kernel(const float* __restrict__ wp, float* __restrict__ U, int Cout, int Cin) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, per = (long long)Cout * Cin;
     if (idx >= per) return;
@@ -252,7 +292,7 @@ __global__ __launch_bounds__(256) void wino_weight_nest_kernel(const float* __re
         for (int a = 0; a < 3; ++a)
 #pragma unroll
             for (int b = 0; b < 3; ++b) d[a][b] = ROW(k, w[0][a][b], w[1][a][b], w[2][a][b]);
-        g_d_gt_store(d, U + k * per + idx, K * per);
+        g_d_gt_store<NH, HROW>(d, U + k * per + idx, K * per);
     }
 }
 
@@ -291,17 +331,35 @@ __device__ __forceinline__ void load_planes(float4 (&m)[ROWS][4], const float* M
 // one thread = one tile x 4 output channels: 16 float4 loads, 24 float4 additions, then the element-wise tail of 2x2 output voxels
 // HALF: Mm (and Mm2) hold 8 planes [2][4] - the row stage s = A^T m was applied by the GEMM's epilogue (forge_wino_gemm_half) - and this kernel runs the
 // column stage only (8 instead of 16 float4 loads per operand).
-template <int EPI, bool HALF = false>
+// TH = 4 (forge_wino_output_dn4h): tiles of 4 x 2 voxels, Ht = H / 4, from forge_wino_gemm_dn4h's 24 point products, point p = 4 i + j with i = 0..5 the H
+// point: the row stage is A^T of F(4, 3) = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1] in the four lines of the depth-nest GEMM's output schedule
+// (s = m1 + m2, d = m1 - m2, S = m3 + m4, D = m3 - m4: (s + S) + m0 | d + 2 D | s + 4 S | (d + 8 D) + m5, the scalings fused and exact); 24 float4 loads, no
+// second addend.
+template <int EPI, bool HALF = false, int TH = 2>
 __global__ __launch_bounds__(256) void wino_output_kernel(const WinoOutArgs a) {
-    const int C4 = a.Cout >> 2, Ht = a.H >> 1, Wt = a.W >> 1;
+    static_assert(TH == 2 || (TH == 4 && !HALF), "tiles of 2 x 2 voxels, or of 4 x 2 from the 24 points");
+    const int C4 = a.Cout >> 2, Ht = TH == 4 ? a.H >> 2 : a.H >> 1, Wt = a.W >> 1;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long R = (long long)a.n * a.D * Ht * Wt;
     if (idx >= R * C4) return;
     unsigned r, t;                                   // t = (n, z) plane index
     int c, tw, th;
     tile_decode(idx, C4, 2, Ht, Wt, r, c, tw, th, t);
-    float4 s[2][4];                                  // A^T m
-    if constexpr (HALF) {
+    float4 s[TH][4];                                 // A^T m
+    if constexpr (TH == 4) {
+        const float* mp = a.Mm + (long long)r * a.Cout + c;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float4 m[6];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) m[i] = *reinterpret_cast<const float4*>(mp + (4 * i + j) * a.ptm);
+            const float4 sl = add(m[1], m[2]), dl = sub(m[1], m[2]), Sl = add(m[3], m[4]), Dl = sub(m[3], m[4]);
+            s[0][j] = add(add(sl, Sl), m[0]);
+            s[1][j] = fma4(2.f, Dl, dl);
+            s[2][j] = fma4(4.f, Sl, sl);
+            s[3][j] = add(fma4(8.f, Dl, dl), m[5]);
+        }
+    } else if constexpr (HALF) {
         load_planes<2>(s, a.Mm, a.ptm, a.Mm2, a.ptm2, a.bs2, a.Cout, (unsigned)(a.D * Ht * Wt), r, c);
     } else {
         float4 m[4][4];
@@ -312,9 +370,9 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const WinoOutArgs a) {
             s[1][j] = sub(sub(m[1][j], m[2][j]), m[3][j]);
         }
     }
-    float4 y[2][2];
+    float4 y[TH][2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < TH; ++i) {
         y[i][0] = add(add(s[i][0], s[i][1]), s[i][2]);
         y[i][1] = sub(sub(s[i][1], s[i][2]), s[i][3]);
     }
@@ -327,10 +385,10 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const WinoOutArgs a) {
     const int Ch = a.Cout >> 1;
     const long long plane = (long long)t * a.H * a.W;               // first output row of plane (n, z)
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < TH; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const long long orow = plane + (long long)(2 * th + i) * a.W + (2 * tw + j);
+            const long long orow = plane + (long long)(TH * th + i) * a.W + (2 * tw + j);
             float v[4] = {y[i][j].x + bias.x, y[i][j].y + bias.y, y[i][j].z + bias.z, y[i][j].w + bias.w};
             if (a.residual) {
                 const float4 rr = *reinterpret_cast<const float4*>(a.residual + orow * a.Cout + c);
@@ -481,16 +539,24 @@ extern "C" int forge_wino_weights_dn4(const float* wp, float* Ud, int Cout, int 
     return wino_weights_launch("forge_wino_weights_dn4", wino_weight_nest_kernel<6, depth_row_f43>, (long long)Cout * Cin, stream, wp, Ud, Cout, Cin);
 }
 
-// The three input entries. IN_DN4: the depth stage of the F(4, 3) nest in front (wino_input_dn4_kernel: one thread per tile of a GROUP of four planes and channel,
-// six operand rows per group tile); IN_DY: also dM = A y A^T (wino_input_kernel<true>; dense operands, no view mean).
-enum WinoInKind { IN_PLAIN, IN_DN4, IN_DY };
+extern "C" int forge_wino_weights_dn4h(const float* wp, float* Ud, int Cout, int Cin, forge_stream_t stream) {
+    FORGE_REQUIRE(wp && Ud && Cout > 0 && Cin > 0, FORGE_EINVAL, "forge_wino_weights_dn4h: bad argument");
+    return wino_weights_launch("forge_wino_weights_dn4h", wino_weight_nest_kernel<6, depth_row_f43, 6, depth_row_f43>, (long long)Cout * Cin, stream, wp, Ud, Cout, Cin);
+}
+
+// The four input entries. IN_DN4: the depth stage of the F(4, 3) nest in front (wino_input_dn4_kernel: one thread per tile of a GROUP of four planes and channel,
+// six operand rows per group tile); IN_DN4H: that with F(4, 3) along H as well (wino_input_dn4_kernel<4>: tiles of 4 x 2 pixels, H % 4 == 0);
+// IN_DY: also dM = A y A^T (wino_input_kernel<true>; dense operands, no view mean).
+enum WinoInKind { IN_PLAIN, IN_DN4, IN_DY, IN_DN4H };
 
 static int wino_input_impl(const char* name, WinoInKind kind, const float* in, int ld, long long bs, float* V, int ldv, long long ptv, float* dM, int n, int D, int H,
                            int W, int C, int nsum, long long sum_stride, forge_stream_t stream) {
-    const bool dn4 = kind == IN_DN4;
+    const bool dn4 = kind == IN_DN4 || kind == IN_DN4H;                 // six operand rows per tile of a group of four planes
+    const int th = kind == IN_DN4H ? 4 : 2;                             // output rows per tile
     FORGE_REQUIRE(in && V && (kind != IN_DY || dM), FORGE_EINVAL, "%s: null pointer argument", name);
     FORGE_REQUIRE(nsum >= 1 && (nsum == 1 || sum_stride > 0), FORGE_EINVAL, "%s: nsum >= 1, and a positive sum_stride (rows) with nsum > 1", name);
     FORGE_REQUIRE(!dn4 || (D > 0 && D % 4 == 0), FORGE_EINVAL, "%s: D=%d must be a multiple of 4", name, D);
+    FORGE_REQUIRE(kind != IN_DN4H || (D >= 8 && H > 0 && H % 4 == 0), FORGE_EINVAL, "%s: D=%d H=%d (D >= 8; H a multiple of 4)", name, D, H);
     const bool ok = n > 0 && D > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C > 0 && C % 4 == 0 && ld >= C && ld % 4 == 0 && ldv >= C && ldv % 4 == 0;
     if (kind == IN_DY)                                // (this entry takes no ldv: its operands are dense)
         FORGE_REQUIRE(ok, FORGE_ESHAPE, "%s: n=%d D=%d H=%d W=%d C=%d ld=%d (H, W even; C, ld multiples of 4)", name, n, D, H, W, C, ld);
@@ -498,14 +564,15 @@ static int wino_input_impl(const char* name, WinoInKind kind, const float* in, i
     WinoInArgs a;
     a.in = in; a.ld = ld; a.bs = bs > 0 ? bs : (long long)D * H * W; a.V = V; a.ldv = ldv; a.n = n; a.D = D; a.H = H; a.W = W; a.C = C;
     a.nsum = nsum; a.ss = sum_stride;
-    const long long R = (long long)n * (dn4 ? D / 4 : D) * (H / 2) * (W / 2), rows = dn4 ? 6 * R : R;      // thread tiles; operand rows per point
+    const long long R = (long long)n * (dn4 ? D / 4 : D) * (H / th) * (W / 2), rows = dn4 ? 6 * R : R;     // thread tiles; operand rows per point
     a.ptv = ptv > 0 ? ptv : rows * ldv;
     a.dM = dM; a.ptm = dM ? R * C : 0;
     FORGE_REQUIRE(rows < (1ll << 31), FORGE_ESHAPE, dn4 ? "%s: more than 2^31 operand rows; split the batch" : "%s: more than 2^31 tiles; split the batch", name);
     const long long total = R * (dn4 ? C : C / 4), grid = (total + 255) / 256;
     FORGE_REQUIRE(grid < (1ll << 31), FORGE_ESHAPE, "%s: grid too large", name);
     const dim3 g((unsigned)grid), b(256);
-    if (dn4) hipLaunchKernelGGL(wino_input_dn4_kernel, g, b, 0, (hipStream_t)stream, a);
+    if (kind == IN_DN4H) hipLaunchKernelGGL(wino_input_dn4_kernel<4>, g, b, 0, (hipStream_t)stream, a);
+    else if (dn4) hipLaunchKernelGGL(wino_input_dn4_kernel<2>, g, b, 0, (hipStream_t)stream, a);
     else if (kind == IN_DY) hipLaunchKernelGGL(wino_input_kernel<true>, g, b, 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(wino_input_kernel<false>, g, b, 0, (hipStream_t)stream, a);
     FORGE_LAUNCH_CHECK(name);
@@ -522,6 +589,13 @@ extern "C" int forge_wino_input(const float* in, int ld, long long bs, float* V,
 extern "C" int forge_wino_input_dn4(const float* in, int ld, long long bs, float* V6, int ldv, long long ptv, int n, int D, int H, int W, int C,
                                     int nsum, long long sum_stride, forge_stream_t stream) {
     return wino_input_impl("forge_wino_input_dn4", IN_DN4, in, ld, bs, V6, ldv, ptv, nullptr, n, D, H, W, C, nsum, sum_stride, stream);
+}
+
+// forge_wino_input_dn4 with F(4, 3) along H as well (wino_input_dn4_kernel<4>): V [24][n][D/4][6][H/4 W/2][C], the operand of forge_wino_gemm_dn4h.
+// ptv: floats between points (0 = dense, n (D/4) 6 (H/4)(W/2) ldv). FORGE_EINVAL unless D % 4 == 0, D >= 8 and H % 4 == 0.
+extern "C" int forge_wino_input_dn4h(const float* in, int ld, long long bs, float* V, int ldv, long long ptv, int n, int D, int H, int W, int C,
+                                     int nsum, long long sum_stride, forge_stream_t stream) {
+    return wino_input_impl("forge_wino_input_dn4h", IN_DN4H, in, ld, bs, V, ldv, ptv, nullptr, n, D, H, W, C, nsum, sum_stride, stream);
 }
 
 extern "C" int forge_wino_input_dy(const float* dy, int ld, float* V, float* dM, int n, int D, int H, int W, int C, forge_stream_t stream) {
@@ -583,4 +657,31 @@ extern "C" int forge_wino_output_half(const float* Mm8, const float* Mm2_8, long
                                       const float* residual, const float* aux_h, const float* aux_z, float* out, float* out2, float* out3, int n, int D, int H, int W,
                                       int Cout, int ldo, int epilogue, forge_stream_t stream) {
     return wino_output_impl(Mm8, Mm2_8, bs2, pt2, bias, scale, shift, slope, residual, aux_h, aux_z, out, out2, out3, n, D, H, W, Cout, ldo, epilogue, true, stream);
+}
+
+// The inverse transform of forge_wino_gemm_dn4h's point products Mm [24][n D H/4 W/2][Cout] with the GRU tails of forge_wino_output (epilogue 2: gates, ldo ==
+// Cout / 2; 3: state): wino_output_kernel<., false, 4>. The steps of the eval fusion are its only callers: no second addend, no residual, no other epilogue.
+extern "C" int forge_wino_output_dn4h(const float* Mm, const float* bias, const float* scale, const float* shift, const float* aux_h, const float* aux_z, float* out,
+                                      float* out2, float* out3, int n, int D, int H, int W, int Cout, int ldo, int epilogue, forge_stream_t stream) {
+    FORGE_REQUIRE(Mm && out && aux_h, FORGE_EINVAL, "forge_wino_output_dn4h: null pointer argument");
+    FORGE_REQUIRE(n > 0 && D > 0 && H > 0 && W > 0 && H % 4 == 0 && W % 2 == 0 && Cout > 0 && Cout % 8 == 0 && ldo % 4 == 0, FORGE_ESHAPE,
+                  "forge_wino_output_dn4h: n=%d D=%d H=%d W=%d Cout=%d ldo=%d (H multiple of 4, W even; Cout multiple of 8; ldo of 4)", n, D, H, W, Cout, ldo);
+    FORGE_REQUIRE(epilogue == W_GRU_GATES || epilogue == W_GRU_OUT, FORGE_EINVAL, "forge_wino_output_dn4h: epilogue %d is not a GRU tail (2, 3)", epilogue);
+    FORGE_REQUIRE(epilogue == W_GRU_GATES ? ldo == Cout / 2 : ldo >= Cout, FORGE_ESHAPE,
+                  "forge_wino_output_dn4h: ldo=%d (epilogue 3: ldo >= Cout=%d; epilogue 2: ldo == Cout / 2)", ldo, Cout);
+    FORGE_REQUIRE(epilogue != W_GRU_GATES || out2, FORGE_EINVAL, "forge_wino_output_dn4h: GRU gate epilogue needs out2");
+    FORGE_REQUIRE(epilogue != W_GRU_OUT || (aux_z && (!out2 || (scale && shift))), FORGE_EINVAL,
+                  "forge_wino_output_dn4h: GRU out epilogue needs aux_z (and scale/shift with out2)");
+    WinoOutArgs a;
+    const long long R = (long long)n * D * (H / 4) * (W / 2);
+    a.Mm = Mm; a.ptm = R * Cout; a.Mm2 = nullptr; a.bs2 = 0; a.ptm2 = 0; a.bias = bias; a.scale = scale; a.shift = shift; a.slope = 1.f; a.residual = nullptr;
+    a.aux_h = aux_h; a.aux_z = aux_z; a.out = out; a.out2 = out2; a.out3 = out3; a.ldo = ldo; a.n = n; a.D = D; a.H = H; a.W = W; a.Cout = Cout; a.epi = epilogue;
+    FORGE_REQUIRE(R < (1ll << 31), FORGE_ESHAPE, "forge_wino_output_dn4h: more than 2^31 tiles; split the batch");
+    const long long total = R * (Cout / 4), grid = (total + 255) / 256;
+    FORGE_REQUIRE(grid < (1ll << 31), FORGE_ESHAPE, "forge_wino_output_dn4h: grid too large");
+    const dim3 g((unsigned)grid), b(256);
+    if (epilogue == W_GRU_GATES) hipLaunchKernelGGL((wino_output_kernel<W_GRU_GATES, false, 4>), g, b, 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((wino_output_kernel<W_GRU_OUT, false, 4>), g, b, 0, (hipStream_t)stream, a);
+    FORGE_LAUNCH_CHECK("forge_wino_output_dn4h");
+    return 0;
 }

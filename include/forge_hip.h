@@ -320,6 +320,27 @@ int forge_wino_input_dn4(const float* in, int ld, long long bs, float* V6, int l
 int forge_wino_weights_dn4(const float* wp, float* Ud, int Cout, int Cin, forge_stream_t stream);
 int forge_wino_gemm_dn4(const float* V1, int C1, int ld1, long long bs1, long long pt1, const float* V2, int C2, int ld2, long long bs2,
                         long long pt2, const float* Ud, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, forge_stream_t stream);
+/* The F(4, 3) depth nest with F(4, 3) along H as well ("dn4h"): tiles of 4 x 2 output voxels, Ht = H / 4, Wt = W / 2, 24 points p = 4 i + j (i = 0..5 the H point,
+ * j = 0..3 the W point of F(2, 3)) - 3 multiplies per output against 4, operands and point products at 3/4 of forge_wino_gemm_dn4's bytes. Four entries:
+ * forge_wino_input_dn4h: V [24][n][D/4][6][Ht Wt][C] (arguments as forge_wino_input_dn4). Per tile (th, tw) of group g the patch is the six rows 4 th - 1 .. 4 th + 4
+ *   x the four columns 2 tw - 1 .. 2 tw + 2 of the six planes 4 g - 1 .. 4 g + 4 (zero outside the element's grid). Three stages, in this order:
+ *   (1) depth, per patch element: forge_wino_input_dn4's six lines q0 .. q5 on the planes; (2) rows, per position k and patch column: THE SAME six lines on the
+ *   six patch rows of q_k; (3) columns, per position and point row: w0 - w2, w1 + w2, w2 - w1, w1 - w3 (forge_wino_input's column stage). Every multiplier is
+ *   a power of two: a float32 evaluation in this order reproduces the bits. FORGE_EINVAL unless D % 4 == 0, D >= 8, H % 4 == 0.
+ * forge_wino_weights_dn4h: Ud [24][6][Cout][Cin] = G4(depth) (x) G4(H) (x) G2(W) from wp [27][Cout][Cin]: forge_wino_weights_dn4's depth rows on every element,
+ *   then the same six rows over the kernel's H taps, then w0, (w0 + w1 + w2) / 2, (w0 - w1 + w2) / 2, w2 over its W taps; float64 throughout, rounded once.
+ * forge_wino_gemm_dn4h: forge_wino_gemm_dn4's launch with 24 batched problems on the grid (n, D, Ht, Wt): Mm [24][n D Ht Wt][Cout]. FORGE_EINVAL, before any
+ *   launch, unless kd == 3, D % 4 == 0, D >= 8, Ht Wt % 64 == 0, C1 and C2 are multiples of 32 and every operand and output plane stays within 32-bit offsets.
+ * forge_wino_output_dn4h: the inverse transform with the GRU tails of forge_wino_output (epilogue 2: gates, ldo == Cout / 2; 3: state; no second addend, no
+ *   residual): over the six H points s = m1 + m2, d = m1 - m2, S = m3 + m4, D = m3 - m4, rows (s + S) + m0 | d + 2 D | s + 4 S | (d + 8 D) + m5 (the scalings
+ *   fused, exact), then forge_wino_output's (s0 + s1) + s2 | (s1 - s2) - s3 over the four W points. FORGE_ESHAPE unless H % 4 == 0, W even, Cout % 8 == 0. */
+int forge_wino_input_dn4h(const float* in, int ld, long long bs, float* V, int ldv, long long ptv, int n, int D, int H, int W, int C,
+                          int nsum, long long sum_stride, forge_stream_t stream);
+int forge_wino_weights_dn4h(const float* wp, float* Ud, int Cout, int Cin, forge_stream_t stream);
+int forge_wino_gemm_dn4h(const float* V1, int C1, int ld1, long long bs1, long long pt1, const float* V2, int C2, int ld2, long long bs2,
+                         long long pt2, const float* Ud, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, forge_stream_t stream);
+int forge_wino_output_dn4h(const float* Mm, const float* bias, const float* scale, const float* shift, const float* aux_h, const float* aux_z, float* out,
+                           float* out2, float* out3, int n, int D, int H, int W, int Cout, int ldo, int epilogue, forge_stream_t stream);
 int forge_wino_gemm_tile(long long R, int Cout, int Cin);   /* the workgroup tile letter ('A'..'E', see forge_conv_igemm_plan) forge_wino_gemm uses for R tile rows per point, Cin = C1 + C2 */
 int forge_wino_output(const float* Mm, const float* Mm2, long long bs2, long long pt2, const float* bias, const float* scale, const float* shift, float slope, const float* residual,
                       const float* aux_h, const float* aux_z, float* out, float* out2, float* out3, int n, int D, int H, int W, int Cout,
