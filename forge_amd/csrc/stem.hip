@@ -2,7 +2,8 @@
 //   * patch gather for the 7x7 stride-2 conv on the 3-channel image: rows [n*Ho*Wo][Kpad], k = (ky*kw + kx)*C + c,
 //     zero outside the image and for k >= kh*kw*C. The conv itself then runs on the MFMA GEMM kernel (taps = 1, K = Kpad)
 //     with BN + ReLU folded into its epilogue. (The 3-channel input cannot feed the 32-wide K-step tap-by-tap.)
-//   * 3x3 stride-2 max-pool on channels-last activations (-inf padding semantics, as nn.MaxPool2d).
+//   * 3x3 stride-2 max-pool on channels-last activations (-inf padding semantics, as nn.MaxPool2d). A NaN in a window is that window's
+//     result, as in nn.MaxPool2d: the maximum is a compare + select per lane, not fmaxf, which would return the other operand.
 // Both are HBM-bound streaming kernels: 0.8 MB image -> 52 MB patch matrix per 5 views; 21 MB -> 5 MB pool.
 #include "common.h"
 
@@ -28,6 +29,9 @@ __global__ __launch_bounds__(256) void im2col_nchw_kernel(const float* __restric
     }
 }
 
+// max that keeps a NaN (fmaxf returns the other operand): once m is a NaN neither test is true again, so it stays
+__device__ __forceinline__ float nanmax(float m, float v) { return (v > m || v != v) ? v : m; }
+
 __global__ __launch_bounds__(256) void maxpool2d_nhwc_kernel(const float4* __restrict__ in, float4* __restrict__ out, int N, int H, int W, int C4,
                                                              int k, int stride, int pad, int Ho, int Wo) {
     const long long total = (long long)N * Ho * Wo * C4;
@@ -45,7 +49,7 @@ __global__ __launch_bounds__(256) void maxpool2d_nhwc_kernel(const float4* __res
                 const int x = ox * stride - pad + kx;
                 if ((unsigned)x >= (unsigned)W) continue;
                 const float4 v = in[(((long long)n * H + y) * W + x) * C4 + c];
-                m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+                m.x = nanmax(m.x, v.x); m.y = nanmax(m.y, v.y); m.z = nanmax(m.z, v.z); m.w = nanmax(m.w, v.w);
             }
         }
         out[i] = m;

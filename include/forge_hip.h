@@ -606,6 +606,7 @@ int forge_layer_norm_bwd(const float* dy, long long lddy, const float* x, long l
  *   for k >= kh*kw*C; Ho = (H + 2 pad - kh)/stride + 1. The 7x7/s2 stem conv then runs as forge_conv_igemm with one tap and
  *   C1 = Kpad (BN + ReLU in its epilogue).
  * forge_maxpool2d_nhwc: in [N][H][W][C] -> out [N][Ho][Wo][C], window k, -inf padding (nn.MaxPool2d semantics), C % 4 == 0.
+ *   A NaN inside a window is that window's result, as in nn.MaxPool2d.
  */
 int forge_im2col_nchw(const float* img, float* out, int N, int C, int H, int W, int kh, int kw, int stride, int pad,
                       int Kpad, forge_stream_t stream);

@@ -7,10 +7,10 @@ The two depth nests (<64, 128, 8, 1, 2>, forge_wino_gemm_dn; <64, 128, 8, 1, 3>,
 at least 4 waves per SIMD, and 2 x their launched LDS (64 KB / 48 KB) within 160 KB."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
+
+from resource_remarks import kernel_remarks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "forge_amd", "csrc", "conv_igemm.hip")
@@ -18,33 +18,11 @@ LDS_PER_CU = 160 * 1024
 WAVES_PER_WORKGROUP, SIMDS = 8, 4
 
 
-def _hipcc():
-    from forge_amd import build
-    try:
-        return build.hipcc()
-    except RuntimeError:
-        return shutil.which("hipcc")
-
-
 @pytest.fixture(scope="module")
 def remarks(tmp_path_factory):
-    cc = _hipcc()
-    if not cc:
+    out = kernel_remarks(SRC, tmp_path_factory.mktemp("res"))
+    if out is None:
         pytest.skip("hipcc not found")
-    from forge_amd import build
-    obj = str(tmp_path_factory.mktemp("res") / "conv_igemm.o")
-    p = subprocess.run([cc] + build.FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-x", "hip", "-c", SRC, "-o", obj],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert p.returncode == 0, p.stdout[-4000:]
-    out, cur = {}, None
-    for line in p.stdout.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+) \[-Rpass", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
     return out
 
 

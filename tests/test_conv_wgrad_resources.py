@@ -8,13 +8,11 @@ and R x the largest dynamic LDS a launch of the kernel can ask for fits into the
 matrix case with more segments than the cap, the occupancy from the remarks; the largest LDS follows from the limits of the line kernels
 (include/forge_hip.h, tests/conv_wgrad_cases.py: 32-voxel segments, |dx| <= 3, at most 9 lines, 6 with a stride-2 gathered operand)."""
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
 import conv_wgrad_cases as wc
+from resource_remarks import kernel_remarks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "forge_amd", "csrc", "conv_wgrad.hip")
@@ -31,34 +29,12 @@ PERSISTENT = {
 }
 
 
-def _hipcc():
-    from forge_amd import build
-    try:
-        return build.hipcc()
-    except RuntimeError:
-        return shutil.which("hipcc")
-
-
 @pytest.fixture(scope="module")
 def remarks(tmp_path_factory):
-    cc = _hipcc()
-    if not cc:
+    out = kernel_remarks(SRC, tmp_path_factory.mktemp("res"), "conv_wgrad")
+    if out is None:
         pytest.skip("hipcc not found")
-    from forge_amd import build
-    obj = str(tmp_path_factory.mktemp("res") / "conv_wgrad.o")
-    p = subprocess.run([cc] + build.FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-x", "hip", "-c", SRC, "-o", obj],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert p.returncode == 0, p.stdout[-4000:]
-    out, cur = {}, None
-    for line in p.stdout.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:.*?\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+) \[-Rpass", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    return {k: v for k, v in out.items() if "conv_wgrad" in k}
+    return out
 
 
 def test_no_instantiation_uses_scratch_or_spills(remarks):

@@ -5,10 +5,10 @@ float tile in LDS, FOUR of them per CU (2 waves per SIMD); the dW kernel is a 4-
 backward is a 4-wave workgroup with a 32 x 257 float reduction tile, at least two per CU. No kernel may use scratch."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
+
+from resource_remarks import kernel_remarks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "forge_amd", "csrc", "token.hip")
@@ -18,33 +18,11 @@ PLANNED = {"token_linear_fwd_kernel": (2, 4), "layer_norm_fwd_kernel": (2, 4), "
            "layer_norm_bwd_kernel": (4, 2)}
 
 
-def _hipcc():
-    from forge_amd import build
-    try:
-        return build.hipcc()
-    except RuntimeError:
-        return shutil.which("hipcc")
-
-
 @pytest.fixture(scope="module")
 def remarks(tmp_path_factory):
-    cc = _hipcc()
-    if not cc:
+    out = kernel_remarks(SRC, tmp_path_factory.mktemp("res"))
+    if out is None:
         pytest.skip("hipcc not found")
-    from forge_amd import build
-    obj = str(tmp_path_factory.mktemp("res") / "token.o")
-    p = subprocess.run([cc] + build.FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-x", "hip", "-c", SRC, "-o", obj],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert p.returncode == 0, p.stdout[-4000:]
-    out, cur = {}, None
-    for line in p.stdout.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+) \[-Rpass", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
     return out
 
 
