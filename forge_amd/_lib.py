@@ -120,6 +120,8 @@ SIGNATURES = {
     "forge_mesh_workspace_bytes": [_I, _I, _I, _I],
     "forge_mesh_count": [_P, _I, _I, _I, _I, _F, _P, _LL, _P, _P],
     "forge_mesh_emit": [_P, _P, _I, _I, _I, _I, _I, _F, _F, _P, _LL, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
+    "forge_mesh_bake": [_P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _F, _F, _F, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _F, _F, _I, _F, _F, _I, _F, _P, _P, _P,
+                        _P],
     "forge_ncdhw_to_ndhwc": [_P, _P, _I, _I, _LL, _P],
     "forge_ndhwc_to_ncdhw": [_P, _P, _I, _I, _LL, _P],
 }

@@ -927,3 +927,67 @@ def mesh_emit(density, workspace, counts, max_vertices, max_faces, level=0.5, vo
                                           _lib.ptr(vertices), _lib.ptr(normals), _lib.ptr(faces), _lib.ptr(vfeat), _lib.ptr(status), _lib.current_stream()),
                "forge_mesh_emit")
     return vertices, normals, faces, vfeat, status
+
+
+# ------------------------------------------------------------------------------------------------------------------- vertex colour bake
+BAKE_MODES = {"blend": 0, "best": 1}
+
+
+@_lib.on_tensor_device
+def mesh_bake(vertices, normals, counts, density, images, cam, view2vol, *, offsets=None, view_weight=None, view_gain=None, half, S, step, offset,
+              cos_power=2, z_near=1e-3, w_min=1e-3, mode="blend", fill=0.5, out=None):
+    """forge_mesh_bake (include/forge_hip.h section g2): colours for the rows mesh_emit wrote, from posed images, weighted by facing and by the
+    transmittance of the density field between the vertex and the camera. vertices / normals [n,max_vertices,3] with counts [n,2] (offsets None:
+    every volume owns max_vertices rows) or [max_vertices,3] with offsets [n,2] (the volumes packed one after the other); density [n,1,D,H,W];
+    images [V,C,Hi,Wi] (C in 1..4), cam [V,16] (R, T, fx, fy, cx, cy in pixels of `images`), view2vol [V] int32, view_weight [V,Hi,Wi] and
+    view_gain [V] optional; half = (hx, hy, hz), the half extents of W, H, D. mode "blend" (weighted mean) or "best" (the best view's colour).
+    Returns (colors [...,C], weight [...], best [...] int32), the rows laid out as vertices; rows past a volume's count are left as they were
+    (out: the three tensors to write into). Nothing is read back."""
+    tensors = (vertices, normals, counts, density, images, cam, view2vol)
+    if not all(torch.is_tensor(t) for t in tensors) or not all(t is None or torch.is_tensor(t) for t in (offsets, view_weight, view_gain)):
+        raise TypeError("mesh_bake: vertices, normals, counts, density, images, cam, view2vol (and offsets, view_weight, view_gain) must be tensors")
+    _require_cuda(*tensors, offsets, view_weight, view_gain)
+    dev = density.device
+    if density.dim() != 5 or density.shape[1] != 1:
+        raise ValueError("mesh_bake: density must be [n,1,D,H,W] (encoder_3d.get_density3D), got %s" % (tuple(density.shape),))
+    n, _, D, H, W = (int(s) for s in density.shape)
+    if n < 1:
+        raise ValueError("mesh_bake: empty batch")
+    lead = (n,) if offsets is None else ()
+    if vertices.dim() != len(lead) + 2 or tuple(vertices.shape[:len(lead)]) != lead or vertices.shape[-1] != 3 or normals.shape != vertices.shape:
+        raise ValueError("mesh_bake: vertices and normals must both be %s, got %s and %s"
+                         % ("[%d,max_vertices,3]" % n if offsets is None else "[max_vertices,3] (packed: offsets given)", tuple(vertices.shape), tuple(normals.shape)))
+    max_vertices = int(vertices.shape[-2])
+    if images.dim() != 4 or not 1 <= images.shape[1] <= 4 or images.shape[0] < 1:
+        raise ValueError("mesh_bake: images must be [V,C,Hi,Wi] with C in 1..4 and V >= 1, got %s" % (tuple(images.shape),))
+    V, C, Hi, Wi = (int(s) for s in images.shape)
+    want = [("vertices", vertices, vertices.shape, torch.float32), ("normals", normals, vertices.shape, torch.float32),
+            ("counts", counts, (n, 2), torch.int32), ("offsets", offsets, (n, 2), torch.int32), ("density", density, density.shape, torch.float32),
+            ("images", images, images.shape, torch.float32), ("cam", cam, (V, 16), torch.float32), ("view2vol", view2vol, (V,), torch.int32),
+            ("view_weight", view_weight, (V, Hi, Wi), torch.float32), ("view_gain", view_gain, (V,), torch.float32)]
+    for name, t, shape, dt in want:
+        if t is None:
+            continue
+        if t.dtype != dt:
+            raise TypeError("mesh_bake: %s must be %s (got %s)" % (name, dt, t.dtype))
+        if tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != dev:
+            raise ValueError("mesh_bake: %s must be a contiguous %s tensor on %s, got %s with strides %s on %s"
+                             % (name, tuple(shape), dev, tuple(t.shape), t.stride(), t.device))
+    if mode not in BAKE_MODES:
+        raise ValueError("mesh_bake: mode=%r (one of %s)" % (mode, sorted(BAKE_MODES)))
+    hx, hy, hz = (float(h) for h in half)
+    rows = lead + (max_vertices,)
+    shapes = ((rows + (C,), torch.float32), (rows, torch.float32), (rows, torch.int32))
+    if out is None:
+        colors, weight, best = (torch.empty(s, dtype=dt, device=dev) for s, dt in shapes)
+    else:
+        colors, weight, best = out
+        for t, (shape, dt) in zip(out, shapes):
+            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev:
+                raise ValueError("mesh_bake: every out tensor must be contiguous, here %s of shape %s on %s" % (dt, shape, dev))
+    _lib.check(_lib.lib().forge_mesh_bake(_lib.ptr(vertices.detach()), _lib.ptr(normals.detach()), _lib.ptr(counts), _lib.ptr(offsets), n, max_vertices,
+                                          _lib.ptr(density.detach()), D, H, W, hx, hy, hz, _lib.ptr(images.detach()), _lib.ptr(view_weight), C, Hi, Wi,
+                                          _lib.ptr(cam.detach()), _lib.ptr(view2vol), _lib.ptr(view_gain), V, int(S), float(step), float(offset),
+                                          int(cos_power), float(z_near), float(w_min), BAKE_MODES[mode], float(fill), _lib.ptr(colors), _lib.ptr(weight),
+                                          _lib.ptr(best), _lib.current_stream()), "forge_mesh_bake")
+    return colors, weight, best

@@ -756,6 +756,45 @@ int forge_mesh_emit(const float* density, const float* features, int n, int C, i
                     float* vertices, float* normals, int* faces, float* vertex_features, int* status, forge_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * g2  Vertex colours for the meshes of g1, baked from posed images with a visibility test (csrc/bake.hip). A vertex is visible from a camera if
+ * transmittance stays high along the segment from the vertex to the camera centre, through the field the ray-marcher and the mesh use
+ * (align_corners=True trilinear sampling with zero padding): no depth maps, no rasteriser, no atomics. The reference has no counterpart.
+ *   vertices, normals  the rows forge_mesh_emit wrote; counts [n][2], offsets [n][2] (nullable) and max_vertices select the same two row layouts:
+ *                      offsets == NULL: volume k owns rows k max_vertices .. (k+1) max_vertices - 1; otherwise volume k starts at row offsets[k][0]
+ *                      of arrays with max_vertices rows IN ALL. Volume k has min(counts[k][0], rows left to it) rows: a volume that overflowed bakes
+ *                      the prefix that fitted. Rows past that are never written.
+ *   density  [n][D][H][W]; hx, hy, hz the half extents of W, H, D as forge_render_fwd takes them (finite, > 0)
+ *   images   [V][C][Hi][Wi] planar, C in 1 .. 4; view_weight [V][Hi][Wi], nullable (= 1): a per-pixel confidence or foreground map
+ *   cam      [V][16]: R[9] row-major (OpenCV world->camera, x_cam = R p + T), T[3], fx, fy, cx, cy in pixels OF THE GIVEN IMAGES (not the
+ *            renderer's half resolution); the ray through pixel (h, w) is the renderer's, ((w+.5-cx)/fx, (h+.5-cy)/fy, 1)
+ *   view2vol [V] the volume view v depicts; a vertex of volume k looks at the views with view2vol == k, in increasing v; a view whose index is
+ *            outside 0 .. n-1 is ignored (a device-side compare, no read-back);  view_gain [V], nullable (= 1)
+ *   colors [rows][C], weight [rows], best [rows] (int32), the rows laid out as vertices
+ * For vertex p with normal nh, in a view v of its volume (all arithmetic fp32):
+ *   projection     x_cam = R p + T; (x, y) = (fx x_cam.x / x_cam.z + cx - 0.5, fy x_cam.y / x_cam.z + cy - 0.5); IN VIEW iff x_cam.z >= z_near,
+ *                  0 <= x <= Wi-1 and 0 <= y <= Hi-1. Colour c_v (per channel) and map value m_v: bilinear at (x, y), i0 = floor, the far tap
+ *                  index clamped to the last row / column (its weight is 0 there), w00 I00 + w01 I01 + w10 I10 + w11 I11 in this order with
+ *                  w00 = (1-ax)(1-ay), w01 = ax (1-ay), w10 = (1-ax) ay, w11 = ax ay.
+ *   facing         c = -R^T T, dist = |c - p|, u = (c - p) / dist; max(0, nh.u)^cos_power by repeated multiplication; a zero normal: 1.
+ *   transmittance  p0 = p + offset nh (p for a zero normal); for s = 0 .. S-1, t_s = (s + 0.5) step: a_s = clamp(d(p0 + t_s u), 0, 1) if t_s < dist,
+ *                  else 0, with d the trilinear zero-padded sample at pix = ((pos / (hx,hy,hz) + 1) / 2) (N - 1) per axis, as in forge_render_fwd.
+ *                  T_v = prod_s (1 - a_s), combined in a FIXED order: the eight partial products over s = j (mod 8), each in increasing s,
+ *                  then pairwise j ^ 1, j ^ 2, j ^ 4. Samples with no tap inside the volume are exact factors of 1.
+ *   weight         w_v = view_gain[v] m_v T_v facing (left to right) when in view, else 0.
+ * Per row: weight = sum_v w_v in increasing v; best = the v of the largest w_v (ties: the lowest v; -1 if no w_v > 0); colors = (sum_v w_v c_v,
+ * an fma chain in increasing v) / weight with mode 0, c_best with mode 1; where best = -1 or weight < w_min, colors = fill in every channel.
+ * One launch; nothing allocates, synchronises or reads the environment (graph-capturable); every bit is reproducible. max_vertices = 0: no launch,
+ * returns 0.
+ * FORGE_EINVAL: a null pointer (offsets, view_weight, view_gain excepted), an extent, n or V < 1, S < 1, step or a half extent not finite or
+ * <= 0, z_near not finite or <= 0, cos_power outside 1 .. 8, mode outside {0, 1}, offset or w_min negative or not finite, max_vertices < 0.
+ * FORGE_ESHAPE: C outside 1 .. 4, D H W or Hi Wi or (offsets == NULL) n max_vertices beyond 2^31 - 1, n > 65535.
+ */
+int forge_mesh_bake(const float* vertices, const float* normals, const int* counts, const int* offsets, int n, int max_vertices,
+                    const float* density, int D, int H, int W, float hx, float hy, float hz, const float* images, const float* view_weight,
+                    int C, int Hi, int Wi, const float* cam, const int* view2vol, const float* view_gain, int V, int S, float step, float offset,
+                    int cos_power, float z_near, float w_min, int mode, float fill, float* colors, float* weight, int* best, forge_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * layout helpers: NCDHW <-> channels-last for callers that hold plain-contiguous volumes.
  *   src [n][C][P] -> dst [n][P][C]   (P = D*H*W)   and back.
  */
