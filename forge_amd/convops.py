@@ -241,6 +241,7 @@ class _State:
     wino_depth_nest = os.environ.get("FORGE_WINO_DEPTH_NEST", "1") != "0"     # False: the eval fusion's GRU launches stay on the four-point form
     wino_depth_nest4 = os.environ.get("FORGE_WINO_DEPTH_NEST4", "1") != "0"   # False: the nest stays on F(2, 3) (wino_depth_nest = False switches both off)
     wino_h4 = os.environ.get("FORGE_WINO_H4", "1") != "0"                     # False: the F(4, 3) nest stays on F(2, 3) along H (tiles of 2 x 2, 16 points)
+    conv_fast_epilogue = os.environ.get("FORGE_CONV_FAST_EPILOGUE", "1") != "0"   # False: every launch of the wide kernel keeps the row-table epilogue
 
 
 STATE = _State()
@@ -262,6 +263,31 @@ class force_plan:
     def __exit__(self, *exc):
         STATE.plan_override = self.prev
         return False
+
+
+_pushed_fast_epilogue = None
+
+
+def _conv_lib():
+    """The library handle for a launch of the wide implicit-GEMM kernel, with STATE.conv_fast_epilogue carried over to the library's process-wide
+    switch (forge_conv_fast_epilogue; the library itself reads no environment variables) whenever it has changed since the last launch."""
+    global _pushed_fast_epilogue
+    L = _lib.lib()
+    want = bool(STATE.conv_fast_epilogue)
+    if want is not _pushed_fast_epilogue:
+        L.forge_conv_fast_epilogue(int(want))
+        _pushed_fast_epilogue = want
+    return L
+
+
+def conv_epilogue_is_direct(M, Cout, ldo, ldr=0, residual=False, ostride=1, same_grid=True, nphase=1, lift=0, ksplit=1, stats=False, epilogue=EPI_BIAS):
+    """True when such a launch of the wide kernel stores through the direct-store epilogue, False for the row-table one: forge_conv_igemm_epilogue's
+    rule under the current switch (host arithmetic only)."""
+    fast = ctypes.c_int(0)
+    _lib.check(_conv_lib().forge_conv_igemm_epilogue(int(M), int(Cout), int(ldo), int(ldr), int(bool(residual)), int(ostride), int(bool(same_grid)),
+                                                     int(nphase), int(lift), int(ksplit), int(bool(stats)), int(epilogue), ctypes.byref(fast)),
+               "forge_conv_igemm_epilogue")
+    return bool(fast.value)
 
 
 def conv_plan(M, Cout, Cin, ntaps, epilogue, ldo, nphase=1):
@@ -310,7 +336,7 @@ def conv_igemm(in1, C1, ld1, in2, C2, ld2, wp, bias, scale, shift, slope, residu
     nc = n
     while nc > 1 and (span(nc, b1, ld1) > limit or (in2 is not None and span(nc, b2, ld2) > limit)):
         nc = (nc + 1) // 2
-    L, st, arr = _lib.lib(), _lib.current_stream(), _taps_array(taps)
+    L, st, arr = _conv_lib(), _lib.current_stream(), _taps_array(taps)
     nphase = 1
     if tuple(phase) == (-1, -1, -1):
         nphase = 8 if Do == 2 * D else 4
@@ -668,9 +694,9 @@ def wino_form_gemm(form, V1, C1, V2, C2, U, Mm, n, D, Ht, Wt, Cout, view=0, view
     Mm = _point_products(Mm, form.P, R, Cout, V1.device)
     tile = (ord(wino_gemm_tile(R, Cout, C1 + C2)),) if form.tile else ()
     p1 = ctypes.c_void_p(V1.data_ptr() + 4 * view * vol * C1)
-    _lib.check(getattr(_lib.lib(), form.gemm)(p1, C1, C1, views * vol if views > 1 else 0, V1.shape[1] * C1, _lib.ptr(V2), C2, C2, 0,
-                                              0 if V2 is None else V2.shape[1] * C2, _lib.ptr(U), _lib.ptr(Mm), n, D, Ht, Wt, Cout, kd,
-                                              *tile, _lib.current_stream()), form.gemm)
+    _lib.check(getattr(_conv_lib(), form.gemm)(p1, C1, C1, views * vol if views > 1 else 0, V1.shape[1] * C1, _lib.ptr(V2), C2, C2, 0,
+                                               0 if V2 is None else V2.shape[1] * C2, _lib.ptr(U), _lib.ptr(Mm), n, D, Ht, Wt, Cout, kd,
+                                               *tile, _lib.current_stream()), form.gemm)
     return Mm
 
 

@@ -67,6 +67,8 @@ struct ConvArgs {
     float* ws; int ksplit;                 // split-K: raw partial tiles go to ws[ks][M][Cout], a second kernel reduces + applies the epilogue
     double* stats;                         // EPI_BIAS, nullable: per 32-row block of M the column sums / sums of squares of the OUTPUT, [ceil(M/32)..][2][Cout] float64 -
                                            // the batch statistics of the BatchNorm behind this convolution as a by-product of its epilogue (csrc/bnorm.hip finalizes them)
+    int flat_rows;                         // 1: one tap (0,0,0), is == 1, input grid == row grid, dense batch strides: GEMM row m IS input row m (set by launch_conv_tile only)
+    int fast_epi;                          // 1: the direct-store epilogue of the convolution body (conv_fast_epilogue_applies, set by launch_conv_tile only)
     signed char tap[MAX_TAPS][4];          // (dz, dy, dx, 0)
 };
 
@@ -212,8 +214,9 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
     const long long M = (long long)a.n * a.D * a.H * a.W;
     const int ntile_n = (a.Cout + BN - 1) / BN;
     const unsigned bid_all = xcd_remap(blockIdx.x, gridDim.x);
-    const int ks = (int)(bid_all % (unsigned)a.ksplit);           // K-slice of this workgroup (split-K for small M x N problems)
-    unsigned bid = bid_all / (unsigned)a.ksplit;
+    int ks = 0;                                                   // K-slice of this workgroup (split-K for small M x N problems)
+    unsigned bid = bid_all;
+    if (!RS && a.ksplit > 1) { ks = (int)(bid_all % (unsigned)a.ksplit); bid = bid_all / (unsigned)a.ksplit; }
     int phase = 0;
     if (a.nphase > 1) {
         // merged transposed-conv phases, phase fastest: the 2^nd output phases of one row tile read the same 3^nd neighbourhood of input rows -
@@ -246,7 +249,13 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
     const int Cin = a.C1 + a.C2;
     const int kchunks = Cin / BK;
     const int nsteps_all = a.tpp * kchunks;
-    const int s_begin = (int)((long long)ks * nsteps_all / a.ksplit), s_end = (int)((long long)(ks + 1) * nsteps_all / a.ksplit);
+    // K-steps [s_begin, s_end) of slice ks. Without split-K (every launch of the trunk) no division at all, with it 32-bit ones (ksplit <= 8: the products
+    // stay far below 2^32): this arithmetic sits in front of the first load of every workgroup, and two 64-bit divisions were some 300 instructions of it
+    int s_begin = 0, s_end = nsteps_all;
+    if (!RS && a.ksplit > 1) {
+        s_begin = (int)((unsigned)ks * (unsigned)nsteps_all / (unsigned)a.ksplit);
+        s_end = (int)((unsigned)(ks + 1) * (unsigned)nsteps_all / (unsigned)a.ksplit);
+    }
     const int nsteps = s_end - s_begin;
 
     // RS: pb = the point column j; the workgroup's points are pb, pb + 4, pb + 8, pb + 12 (descriptors re-made at every point switch)
@@ -256,6 +265,29 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
     const unsigned lds_wave = lds_addr(smem) + (unsigned)__builtin_amdgcn_readfirstlane(wave) * 1024u;
     // ---- per-thread staging geometry: ACH A rows, BCH B rows, one 16-byte chunk each
     const int cp = tid & 7;                                      // physical chunk in the 128-byte LDS row
+    int br[BCH]; unsigned boff[BCH];
+#pragma unroll
+    for (int j = 0; j < BCH; ++j) {
+        br[j] = (tid >> 3) + RPP * j;
+        const int bsrc = (cp ^ ((br[j] >> 1) & 7)) << 2;
+        boff[j] = (n0 + br[j]) < a.Cout ? (unsigned)(((n0 + br[j]) * Cin + bsrc) * 4) : OOB;
+    }
+    constexpr bool KC_OUTER = (BM == 128 && BN == 128);
+    int kc, t;                                                   // K cursor: channel chunk and tap of the next step (orders: see the K loop below)
+    if constexpr (KC_OUTER) { kc = s_begin / a.tpp; t = s_begin - kc * a.tpp; }
+    else { t = s_begin / kchunks; kc = s_begin - t * kchunks; }
+    t += t_lo;
+    // LDS-DMA: chunk j of this thread is row (tid >> 3) + RPP j = LDS bytes 16 tid + j NW 1024 -> per wave a lane-linear 1 KB block
+    auto issue_b = [&](int t, int kc, int buf) {
+        const unsigned stage = lds_wave + (unsigned)buf * (unsigned)((A_FLOATS + B_FLOATS) * 4);
+        const unsigned wbase = (unsigned)((t * a.Cout * Cin + kc * BK) * 4);
+#pragma unroll
+        for (int j = 0; j < BCH; ++j) lds_dma16(ww, boff[j] + wbase, stage + (unsigned)(A_FLOATS * 4 + j * NW * 1024));
+    };
+    // The convolution's first weight stage needs n0 and tid only: it is issued here, ahead of the A-row decode (three divisions per row), and flies under it
+    if constexpr (!RS) issue_b(t, kc, 0);
+    const bool flat = !RS && a.flat_rows;                        // workgroup-uniform: GEMM row m is input row m (the point forms never are: their rows are tiles)
+    const int Wi_ = flat ? (int)M : a.Wi;                        // input width the taps are tested against
     int ar[ACH], az[ACH], ay[ACH], ax[ACH], an[ACH], asrc[ACH];
     bool aval[ACH];
 #pragma unroll
@@ -264,27 +296,23 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
         const long long vl = m0 + ar[j];
         aval[j] = vl < M;
         unsigned v = aval[j] ? (unsigned)vl : 0u;                // M < 2^31 (checked on the host): 32-bit divisions (64-bit ones are ~100 instructions each)
-        unsigned q = v / (unsigned)a.W;
-        ax[j] = (int)(v - q * (unsigned)a.W) * a.is; v = q;
-        q = v / (unsigned)a.H;
-        ay[j] = (int)(v - q * (unsigned)a.H) * a.is; v = q;
-        q = v / (unsigned)a.D;
-        az[j] = (int)(v - q * (unsigned)a.D) * a.is;
-        an[j] = (int)q;
+        if (flat) {                                              // workgroup-uniform (the 1x1 convolutions of the trunk): row m of the GEMM is row m of the input -
+            ax[j] = (int)v; ay[j] = az[j] = an[j] = 0;            // decoded as x = m on a 1 x 1 x M grid (Wi_ below), the same offsets without a division
+        } else {
+            unsigned q = v / (unsigned)a.W;
+            ax[j] = (int)(v - q * (unsigned)a.W) * a.is; v = q;
+            q = v / (unsigned)a.H;
+            ay[j] = (int)(v - q * (unsigned)a.H) * a.is; v = q;
+            q = v / (unsigned)a.D;
+            az[j] = (int)(v - q * (unsigned)a.D) * a.is;
+            an[j] = (int)q;
+        }
         asrc[j] = (cp ^ ((ar[j] >> 1) & 7)) << 2;                // logical channel offset inside the 32-chunk
-    }
-    int br[BCH]; unsigned boff[BCH];
-#pragma unroll
-    for (int j = 0; j < BCH; ++j) {
-        br[j] = (tid >> 3) + RPP * j;
-        const int bsrc = (cp ^ ((br[j] >> 1) & 7)) << 2;
-        boff[j] = (n0 + br[j]) < a.Cout ? (unsigned)(((n0 + br[j]) * Cin + bsrc) * 4) : OOB;
     }
 
     // 128x128 tile (tap-inner K order, below): switching taps every K-step must be cheap. Per A row: bit t of vmask = tap t lands
     // inside the input grid; the input row of tap t is base + delta(t) with the uniform delta(t) = (dz Hi + dy) Wi + dx (LDS table),
     // so a tap switch costs a shift, a test and an add per row. The other tiles switch taps once per Cin / 32 K-steps and compute it directly.
-    constexpr bool KC_OUTER = (BM == 128 && BN == 128);
     static_assert(!RS || (!KC_OUTER && MT == 1), "the row-stage form exists on the tap-outer tiles");
     __shared__ int sdelta[KC_OUTER ? 2 * MAX_TAPS : 1];             // byte deltas of the taps for in1 / in2
     unsigned long long vmask[KC_OUTER ? ACH : 1];
@@ -302,7 +330,7 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
 #pragma unroll
             for (int j = 0; j < ACH; ++j) {
                 const int zi = az[j] + dz, yi = ay[j] + dy, xi = ax[j] + dx;
-                const bool ok = aval[j] && (unsigned)zi < (unsigned)a.Di && (unsigned)yi < (unsigned)a.Hi && (unsigned)xi < (unsigned)a.Wi;
+                const bool ok = aval[j] && (unsigned)zi < (unsigned)a.Di && (unsigned)yi < (unsigned)a.Hi && (unsigned)xi < (unsigned)Wi_;
                 vmask[j] |= (unsigned long long)ok << tt;
             }
         }
@@ -330,15 +358,14 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
 #pragma unroll
             for (int j = 0; j < ACH; ++j) {
                 const int zi = az[j] + dz, yi = ay[j] + dy, xi = ax[j] + dx;
-                const bool ok = aval[j] && (unsigned)zi < (unsigned)a.Di && (unsigned)yi < (unsigned)a.Hi && (unsigned)xi < (unsigned)a.Wi;
+                const bool ok = aval[j] && (unsigned)zi < (unsigned)a.Di && (unsigned)yi < (unsigned)a.Hi && (unsigned)xi < (unsigned)Wi_;
                 const int sp = (zi * a.Hi + yi) * a.Wi + xi;
                 eoff[j] = ok ? (unsigned)(((an[j] * (int)a.bs1r + sp) * a.ld1 + asrc[j]) * 4) : OOB;
                 eoff2[j] = ok ? (unsigned)(((an[j] * (int)a.bs2r + sp) * a.ld2 + asrc[j]) * 4) : OOB;
             }
         }
     };
-    // LDS-DMA: chunk j of this thread is row (tid >> 3) + RPP j = LDS bytes 16 tid + j NW 1024 -> per wave a lane-linear 1 KB block
-    auto issue_step = [&](int t, int kc, int buf) {
+    auto issue_a = [&](int t, int kc, int buf) {
         const int c0 = kc * BK;
         const unsigned stage = lds_wave + (unsigned)buf * (unsigned)((A_FLOATS + B_FLOATS) * 4);
         if (c0 < a.C1) {
@@ -348,10 +375,8 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
 #pragma unroll
             for (int j = 0; j < ACH; ++j) lds_dma16(w2, eoff2[j] + (unsigned)((c0 - a.C1) * 4), stage + (unsigned)(j * NW * 1024));
         }
-        const unsigned wbase = (unsigned)((t * a.Cout * Cin + c0) * 4);
-#pragma unroll
-        for (int j = 0; j < BCH; ++j) lds_dma16(ww, boff[j] + wbase, stage + (unsigned)(A_FLOATS * 4 + j * NW * 1024));
     };
+    auto issue_step = [&](int t, int kc, int buf) { issue_a(t, kc, buf); issue_b(t, kc, buf); };
     constexpr int NACC = RS == 3 ? 4 : RS ? 3 : 1;                 // accumulator sets (RS = 1, 2: the row stage frees one after point 2; RS = 3: s, d, m3, m4)
     f32x16 accs[NACC][MT][NT];
 #pragma unroll
@@ -370,10 +395,6 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
     // across the 27 taps; with the tap outer the per-tap working set is the full 1 KB rows = the whole L2 and every tap re-fetches them
     // from the fabric (ConvGRU gates launch: 502 -> 132 MB of L2 fills per launch, FETCH_SIZE). The 64-row tiles keep the tap outer:
     // they measured 3-4 % slower with the chunk outer (tools/conv_ab.py).
-    int kc, t;
-    if constexpr (KC_OUTER) { kc = s_begin / a.tpp; t = s_begin - kc * a.tpp; }
-    else { t = s_begin / kchunks; kc = s_begin - t * kchunks; }
-    t += t_lo;
     auto advance = [&]() {
         if constexpr (KC_OUTER) {
             if (++t == t_lo + a.tpp) { t = t_lo; ++kc; }
@@ -384,7 +405,7 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
     };
     if constexpr (!RS) {
         prep_tap(t);
-        issue_step(t, kc, 0);
+        issue_a(t, kc, 0);                                          // (the weight half of stage 0 is already in flight)
         lds_dma_wait();
         __syncthreads();
         FORGE_STAMP(1);
@@ -595,6 +616,67 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(const ConvArgs a) {
 
     FORGE_STAMP(2);
     // ---- epilogue: C/D layout of 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+    // Direct-store epilogue (a.fast_epi, workgroup-uniform, chosen on the host by conv_fast_epilogue_applies: identity output rows, EPI_BIAS / EPI_AFFINE_ACT,
+    // no split-K, lift or statistics): what PlaneStore does for the point forms. Stores go through a buffer descriptor of exactly the bytes
+    // ((M - 1) ldo + Cout) 4 that the launch may write, with one 32-bit byte offset per lane: rows beyond M lie beyond num_records (ldo >= Cout), columns
+    // beyond Cout start at OOB and stay in [2^31, 2^32) (ldo < 2^22: a tile's last row is at most 127 rows below) - dropped by the hardware. No row table in
+    // LDS, no barrier after the K loop, no 64-bit address and no branch per element. The residual is read through a descriptor of its own, all 16 MT NT
+    // loads of the wave ahead of its first store: each lane reads exactly the elements it writes, so an in-place residual (residual == out, ldr == ldo:
+    // the one legal overlap) sees its own values. Every launch that reaches this epilogue today has ldr == ldo (forge_conv_igemm reads the residual at the
+    // output's stride unless there is a lift or a GRU epilogue, which keep the row table); ldr stays a stride of its own here as in the row-table epilogue.
+    // Batched problems (nbat > 1, the point GEMMs) come here with EPI_BIAS only (launch_conv_tile): the residual carries no per-problem offset.
+    // The arithmetic per element is the general epilogue's, operation for operation: the stored bits are the same.
+    if (a.fast_epi) {
+        const __amdgpu_buffer_rsrc_t ro = make_rsrc(outp, ((M - 1) * a.ldo + a.Cout) * 4);
+        const unsigned row0 = (unsigned)m0 + (unsigned)(wm * (32 * MT) + 4 * half);        // this lane's first row; element (i, r) is (i 32 + (r & 3) + 8 (r >> 2)) rows below
+        const unsigned ldo4 = (unsigned)a.ldo * 4u;
+        auto direct = [&](auto EPI_TAG, auto RES_TAG) {
+            constexpr int EPI = decltype(EPI_TAG)::value;
+            constexpr bool RES = decltype(RES_TAG)::value;
+            float res[RES ? NT : 1][MT][16];
+            if constexpr (RES) {
+                const __amdgpu_buffer_rsrc_t rr = make_rsrc(a.residual, ((M - 1) * a.ldr + a.Cout) * 4);
+                const unsigned ldr4 = (unsigned)a.ldr * 4u;
+#pragma unroll
+                for (int j = 0; j < NT; ++j) {
+                    const int col = col0 + j * 32 + l31;
+                    const unsigned rb = col < a.Cout ? (row0 * (unsigned)a.ldr + (unsigned)col) * 4u : OOB;
+#pragma unroll
+                    for (int i = 0; i < MT; ++i)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            res[j][i][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rr, (int)(rb + (unsigned)(i * 32 + (r & 3) + 8 * (r >> 2)) * ldr4), 0, 0));
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                const int col = col0 + j * 32 + l31;
+                const bool cok = col < a.Cout;
+                const int colc = cok ? col : 0;
+                const float bias = a.bias ? a.bias[colc] : 0.f;
+                float sc = 1.f, sh = 0.f;
+                if (EPI == EPI_AFFINE_ACT && a.scale) { sc = a.scale[colc]; sh = a.shift[colc]; }
+                const unsigned vb = cok ? (row0 * (unsigned)a.ldo + (unsigned)col) * 4u : OOB;
+#pragma unroll
+                for (int i = 0; i < MT; ++i)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        float v = acc[i][j][r] + bias;
+                        if constexpr (EPI == EPI_AFFINE_ACT) {
+                            v = fmaf(v, sc, sh);
+                            if constexpr (RES) v += res[j][i][r];
+                            v = v > 0.f ? v : v * a.slope;
+                        }
+                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), ro, (int)(vb + (unsigned)(i * 32 + (r & 3) + 8 * (r >> 2)) * ldo4), 0, 0);
+                    }
+            }
+        };
+        if (a.epi == EPI_BIAS) direct(std::integral_constant<int, EPI_BIAS>{}, std::false_type{});
+        else if (a.residual) direct(std::integral_constant<int, EPI_AFFINE_ACT>{}, std::true_type{});
+        else direct(std::integral_constant<int, EPI_AFFINE_ACT>{}, std::false_type{});
+        FORGE_STAMP(3);
+        return;
+    }
     // The output-row mapping (identity, strided / phase remap of a transposed convolution, or the 2D->3D lift) is computed ONCE per
     // tile row by one thread (32-bit divisions) into an LDS table; the fully unrolled per-accumulator code below (the accumulators
     // must stay in registers) then holds no division and no remap branch. (Round 1 inlined three 64-bit divisions per accumulator
@@ -1135,9 +1217,30 @@ static int launch_point_form(const ConvArgs& a, int planes, size_t lds, const ch
     return 0;
 }
 
+// Which epilogue a launch of the convolution body (RS = 0) takes: true = the direct-store epilogue (see the kernel). It needs identity output rows
+// (no stride / phase remap, no lift), a plain bias or affine epilogue without split-K partials or the statistics by-product, and an output (and
+// residual) whose written byte range ((M - 1) ld + Cout) 4 fits 32-bit buffer offsets; ld >= Cout puts the rows beyond M beyond that range, and
+// ld < 2^22 keeps the offsets of a ragged tile's dropped rows (at most 127 rows further down) from wrapping round 2^32 into it.
+static bool g_conv_fast_epilogue = true;        // forge_conv_fast_epilogue(): process-wide, for A/B measurements and tests
+
+static bool conv_fast_epilogue_applies(long long M, int Cout, int ldo, int ldr, bool residual, int os, bool same_grid, int nphase, int lift, int ksplit,
+                                       bool stats, int epi) {
+    if (ksplit != 1 || os != 1 || !same_grid || nphase != 1 || lift != 0 || stats) return false;
+    if (epi != EPI_BIAS && epi != EPI_AFFINE_ACT) return false;
+    if (M < 1 || Cout < 1 || ldo < Cout || ldo >= (1 << 22) || ((M - 1) * ldo + Cout) * 4 >= (1ll << 31)) return false;
+    if (residual && epi == EPI_AFFINE_ACT && (ldr < Cout || ldr >= (1 << 22) || ((M - 1) * ldr + Cout) * 4 >= (1ll << 31))) return false;
+    return true;
+}
+
 // Launch conv_igemm_kernel with the planned tile: ceil(M / BM) x ceil(Cout / BN) workgroups per (K slice, phase, batched problem).
-static int launch_conv_tile(const ConvArgs& a, char tile, hipStream_t st, int row_stage = 0) {
+static int launch_conv_tile(const ConvArgs& args, char tile, hipStream_t st, int row_stage = 0) {
+    ConvArgs a = args;
     const long long M = (long long)a.n * a.D * a.H * a.W;
+    a.flat_rows = row_stage == 0 && a.ntaps == 1 && a.nphase == 1 && a.tap[0][0] == 0 && a.tap[0][1] == 0 && a.tap[0][2] == 0 && a.is == 1 && a.Di == a.D &&
+                  a.Hi == a.H && a.Wi == a.W && a.bs1r == (long long)a.D * a.H * a.W && (a.in2 == nullptr || a.bs2r == a.bs1r);
+    a.fast_epi = row_stage == 0 && g_conv_fast_epilogue && (a.nbat == 1 || a.epi == EPI_BIAS) &&
+                 conv_fast_epilogue_applies(M, a.Cout, a.ldo, a.ldr, a.residual != nullptr, a.os, a.Do == a.D && a.Ho == a.H && a.Wo == a.W, a.nphase, a.lift,
+                                            a.ksplit, a.stats != nullptr, a.epi);
     auto nblk = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((a.Cout + bn - 1) / bn); };
     // the forms: a.nbat = 4 point columns with four points per workgroup (RS = 1) / 16 points on the even planes (2) / on every fourth plane (3)
     if (row_stage == 1) { const size_t lds = RS_STAGES * (64 * BK + 128 * BK) * sizeof(float); return launch_point_form<1>(a, 1, lds, "forge_wino_gemm_half", st); }
@@ -1178,6 +1281,22 @@ extern "C" int forge_conv_igemm_plan(long long M, int Cout, int Cin, int ntaps, 
     return 0;
 }
 
+// The process-wide switch of the direct-store epilogue (default on) and the rule that selects it; see include/forge_hip.h. Host arithmetic only.
+extern "C" int forge_conv_fast_epilogue(int on) {
+    const int prev = g_conv_fast_epilogue;
+    if (on >= 0) g_conv_fast_epilogue = on != 0;
+    return prev;
+}
+
+extern "C" int forge_conv_igemm_epilogue(long long M, int Cout, int ldo, int ldr, int has_residual, int os, int same_grid, int nphase, int lift, int ksplit,
+                                         int has_stats, int epilogue, int* fast) {
+    FORGE_REQUIRE(fast && M > 0 && Cout > 0 && ldo > 0 && os >= 1 && nphase >= 1 && lift >= 0 && ksplit >= 1 && epilogue >= 0 && epilogue <= 3, FORGE_EINVAL,
+                  "forge_conv_igemm_epilogue: bad argument");
+    *fast = Cout > 16 && g_conv_fast_epilogue &&
+            conv_fast_epilogue_applies(M, Cout, ldo, ldr, has_residual != 0, os, same_grid != 0, nphase, lift, ksplit, has_stats != 0, epilogue);
+    return 0;
+}
+
 // Generic entry; see include/forge_hip.h for the contract.
 extern "C" int forge_conv_igemm(const float* in1, int C1, int ld1, long long bs1, const float* in2, int C2, int ld2, long long bs2,
                                 const float* wp,
@@ -1215,7 +1334,7 @@ extern "C" int forge_conv_igemm(const float* in1, int C1, int ld1, long long bs1
                   "forge_conv_igemm: an operand spans >= 2 GiB (32-bit buffer offsets); split the batch");
     a.is = is; a.Di = Di; a.Hi = Hi; a.Wi = Wi; a.residual = residual;
     a.ldr = (lift > 0 || epilogue == EPI_GRU_GATES || epilogue == EPI_GRU_OUT) ? Cout : ldo;
-    a.lift = lift; a.ws = nullptr; a.ksplit = 1; a.stats = stats;
+    a.lift = lift; a.ws = nullptr; a.ksplit = 1; a.stats = stats; a.flat_rows = a.fast_epi = 0;
     a.wp = wp; a.bias = bias; a.scale = scale; a.shift = shift; a.slope = slope;
     a.aux_h = aux_h; a.aux_z = aux_z; a.out = out; a.out2 = out2; a.out3 = out3; a.n = n; a.D = D; a.H = H; a.W = W; a.Cout = Cout; a.ldo = ldo;
     a.ntaps = ntaps; a.os = os; a.pz = pz; a.py = py; a.px = px; a.Do = Do; a.Ho = Ho; a.Wo = Wo; a.epi = epilogue;

@@ -184,7 +184,8 @@ int forge_resize_bilinear_bwd(const float* g, float* din, int P, int Hi, int Wi,
  *                               Do = D; phase p = pz*4 + py*2 + px uses taps [p*ntaps/P, (p+1)*ntaps/P)); no split-K.
  *   epilogue 0  out = acc + bias
  *            1  out = lrelu((acc + bias) * scale + shift + residual, slope)   eval-BN folded; residual
- *               [rows][ldo] nullable (ResNet shortcut); slope 1 = identity, 0 = ReLU
+ *               [rows][ldo] nullable (ResNet shortcut); slope 1 = identity, 0 = ReLU. residual may be `out` itself (in place,
+ *               element for element); no other overlap of residual and out is allowed (see forge_conv_igemm_epilogue)
  *            2  GRU gates (Cout = 2 Ch): out[m][c] = sigmoid(v_c), c < Ch (update);
  *                                        out2[m][c] = aux_h[m][c] * sigmoid(v_{Ch+c})  (h * reset)
  *            3  GRU state: hn = aux_h (1 - aux_z) + tanh(v) aux_z; out = hn;
@@ -229,6 +230,19 @@ int forge_conv_igemm(const float* in1, int C1, int ld1, long long bs1, const flo
  * caller size the split-K workspace (ksplit * M * Cout floats) and lets profilers attribute launches to kernel instantiations. */
 int forge_conv_igemm_plan(long long M, int Cout, int Cin, int ntaps, int nphase, int epilogue, int ldo, long long splitk_ws_bytes,
                           int* tile, int* ksplit);
+
+/* The two epilogues of the wide kernel (Cout > 16) behind forge_conv_igemm and forge_wino_gemm. A launch with identity output rows stores its tile
+ * directly through a 32-bit buffer descriptor of the output ("direct-store" epilogue); every other launch maps its rows through a table in LDS (the
+ * "general" epilogue). Both store the same bits. The direct-store epilogue reads `residual` ahead of its stores: `residual` may BE `out` (in place,
+ * same row stride, element for element: each lane reads exactly what it writes) - any other overlap of the two is not allowed, in either epilogue.
+ *   forge_conv_igemm_epilogue: *fast = 1 when a launch takes the direct-store epilogue. That is: the switch below is on, Cout > 16, ksplit == 1,
+ *       os == 1 with the output grid equal to the row grid (same_grid) and a single phase (nphase == 1), lift == 0, no stats, epilogue 0 or 1,
+ *       Cout <= ldo < 2^22 and ((M - 1) ldo + Cout) 4 < 2^31, and with a residual (epilogue 1) the same two conditions on ldr. Host arithmetic, no launch.
+ *   forge_conv_fast_epilogue(on): process-wide switch for A/B measurements and tests, default 1; on = 0 sends every launch through the general
+ *       epilogue, on < 0 only queries. Returns the previous setting (0 / 1), never an error. */
+int forge_conv_igemm_epilogue(long long M, int Cout, int ldo, int ldr, int has_residual, int os, int same_grid, int nphase, int lift, int ksplit,
+                              int has_stats, int epilogue, int* fast);
+int forge_conv_fast_epilogue(int on);
 
 /* ---------------------------------------------------------------------------------------------
  * a4 (inference)  the stride-1 3x3x3 convolutions of the ConvGRU fusion (models/fusion.py:29-35, 61-68, 88-95) as Winograd
