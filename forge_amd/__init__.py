@@ -36,6 +36,25 @@ def deterministic(mode=True):
     return _ctx(mode)
 
 
+def ingest_frames(frames, img_size, background="black", return_bytes=False, device=None):
+    """8-bit photographs -> (images [N,3,S,S], masks [N,1,S,S]) on the device, Pillow's Lanczos resize bit for bit: forge_amd.ingest.ingest
+    (the name `forge_amd.ingest` itself is the module)."""
+    from .ingest import ingest as _ingest
+    return _ingest(frames, img_size, background=background, return_bytes=return_bytes, device=device)
+
+
+def photos_to_sample(frames, config, t=None, background=None):
+    """The images / fg_probabilities / K_cv2 entries of the sample schema from t photographs (forge_amd/ingest.py)."""
+    from .ingest import photos_to_sample as _p2s
+    return _p2s(frames, config, t=t, background=background)
+
+
+def reconstruct_photos(model, model_gt, config, dataset, frames, **kw):
+    """demo.py's run_demo from photographs: ingest, poses, refinement, fusion, 360-degree views, optionally a coloured mesh (forge_amd/ingest.py)."""
+    from .ingest import reconstruct_photos as _rp
+    return _rp(model, model_gt, config, dataset, frames, **kw)
+
+
 def install_reference_aliases():
     """Make `from models.model import FORGE` (the import lines of kubric_train_*.py, demo.py,
     kubric_eval.py) and `from models.perceptual_loss import VGGPerceptualLoss` resolve to this package: registers forge_amd's modules under the reference's

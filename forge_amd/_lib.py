@@ -124,6 +124,10 @@ SIGNATURES = {
     "forge_mesh_emit": [_P, _P, _I, _I, _I, _I, _I, _F, _F, _P, _LL, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
     "forge_mesh_bake": [_P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _F, _F, _F, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _F, _F, _I, _F, _F, _I, _F, _P, _P, _P,
                         _P],
+    "forge_resample_taps": [_I, _I],
+    "forge_resample_coeffs": [_I, _I, _P, _P, _P],
+    "forge_resample_nearest": [_I, _I, _P],
+    "forge_ingest_rgba8": [_P, _I, _I, _I, _I, _LL, _LL, _P, _I, _P, _I, _I, _I, _I, _P, _LL, _P, _P, _P, _P],
     "forge_ncdhw_to_ndhwc": [_P, _P, _I, _I, _LL, _P],
     "forge_ndhwc_to_ncdhw": [_P, _P, _I, _I, _LL, _P],
 }

@@ -809,6 +809,56 @@ int forge_mesh_bake(const float* vertices, const float* normals, const int* coun
                     int cos_power, float z_near, float w_min, int mode, float fill, float* colors, float* weight, int* best, forge_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * h  Photographs to input tensors (csrc/ingest.hip): the `_load_frame` of dataset/kubric.py:410-445, dataset/gso.py:257-290 and
+ * dataset/omniobject3d.py:221-258 and the image loop of demo.py:236-256 - an 8-bit RGB(A) frame of any size put on a background, resized with
+ * Pillow's Image.ANTIALIAS (Lanczos, a = 3), its mask resized with Image.NEAREST, divided by 255. On 8-bit images Pillow's resampler is integer
+ * arithmetic after the coefficient table, so the result is Pillow's bit for bit (tests/golden/ingest_pillow.npz), not to a tolerance.
+ * Not covered: train.normalize_img (False in every configuration), the depth TIFFs of the Kubric loader, file decoding.
+ *
+ * One axis, n_in input and n_out output samples, float64 throughout:
+ *   scale = n_in / n_out, fs = max(scale, 1), support = 3 fs. For output i: c = (i + 0.5) scale, first = max((int)(c - support + 0.5), 0),
+ *   count = min((int)(c + support + 0.5), n_in) - first, w_j = L((j + first - c + 0.5) (1 / fs)) for j < count, with
+ *   L(x) = sinc(x) sinc(x / 3) for -3 <= x < 3, else 0; sinc(0) = 1, sinc(x) = sin(pi x) / (pi x). The w_j are divided by their sum (summed in
+ *   increasing j) unless it is 0; k_j = (int)(w_j 2^22 + 0.5) for w_j >= 0, (int)(w_j 2^22 - 0.5) otherwise ((int) truncates).
+ *   nearest: index_i = min((int)p_i, n_in - 1), p_0 = 0.5 scale, p_(i+1) = p_i + scale - the RUNNING float64 sum Pillow keeps, which differs
+ *   from floor((i + 0.5) scale) where a tap lands on an integer (6 -> 9 samples, for one).
+ * One pass over bytes: out = clamp((2^21 + sum_j k_j in[first + j]) >> 22, 0, 255), int32 accumulator, arithmetic shift, channels independent.
+ * A resize is the horizontal pass (an 8-bit image H x Wo), then the vertical pass; Pillow skips a pass whose sizes agree, which the identity
+ * table below reproduces.
+ *
+ *   forge_resample_taps     host only: K, the largest count of the axis (> 0), or FORGE_EINVAL for a non-positive size.
+ *   forge_resample_coeffs   host only: first[n_out], count[n_out], k[n_out][K] with K = forge_resample_taps(n_in, n_out), rows zero-padded.
+ *   forge_resample_nearest  host only: index[n_out].
+ *   All three write host arrays, call nothing of the GPU runtime and allocate nothing. FORGE_EINVAL: a non-positive size, a null pointer.
+ *
+ *   forge_ingest_rgba8
+ *   src      uint8 [N][H][W][C] on the device, C = 3 or 4, pixels packed; image_stride and row_stride in BYTES. Rows need no alignment.
+ *   table_x, table_y  one DEVICE int32 table per axis, n = Wo resp. Ho, K = Kx resp. Ky:  first[n] | count[n] | nearest[n] | k[K][n]  - the
+ *            coefficients TAP-MAJOR (k[j][i], the transpose of what forge_resample_coeffs writes). An axis whose sizes agree takes
+ *            first = nearest = i, count = 1, k = 2^22, K = 1: a copy. The kernels clamp first / count / nearest into the source, so a wrong
+ *            table gives wrong pixels, never an access outside src.
+ *   background  0 black: the RGB bytes are resized with alpha ignored; images = bytes / 255 times the resized mask (dataset.mask_images = True)
+ *               1 white: each channel is first put over white, t = c a + 255 (255 - a) + 128, (t + (t >> 8)) >> 8; not masked afterwards
+ *               2 premasked: RGB is zeroed where alpha == 0, then resized; not masked afterwards (demo.py:244-248)
+ *            With C = 3 there is no alpha: 1 and 2 resize the bytes as they are.
+ *   workspace  N H Wo 4 bytes, 4-byte aligned: the intermediate, one packed pixel per dword.
+ *   images   [N][3][Ho][Wo] float32: (float)byte / 255.0f, which is float32(float64(byte) / 255.0) for all 256 bytes; nullable
+ *   masks    [N][1][Ho][Wo] float32, 0 or 1: the source mask at (nearest_y[y], nearest_x[x]); C = 4: alpha > 0; C = 3: (R > 0) | (G > 0) - blue
+ *            plays no part: the third operand of np.logical_or at omniobject3d.py:228-230 is its `out=` argument; reproduced literally; nullable
+ *   bytes    [N][Ho][Wo][3] uint8, Pillow's bytes; nullable
+ * Two launches; nothing allocates, synchronises or uses atomics (graph-capturable).
+ * FORGE_EINVAL: a null src / table / workspace, a non-positive dimension or K, C outside {3, 4}, an unknown background, row_stride < W C,
+ * overlapping images, a workspace too small or unaligned. FORGE_ESHAPE: H row_stride, H Wo 4 or Ho Wo 3 beyond 2^31 - 1, or more workgroups
+ * than one launch takes.
+ */
+int forge_resample_taps(int n_in, int n_out);
+int forge_resample_coeffs(int n_in, int n_out, int* first, int* count, int* k);
+int forge_resample_nearest(int n_in, int n_out, int* index);
+int forge_ingest_rgba8(const unsigned char* src, int N, int H, int W, int C, long long image_stride, long long row_stride, const int* table_x, int Kx,
+                       const int* table_y, int Ky, int Ho, int Wo, int background, void* workspace, long long workspace_bytes, float* images,
+                       float* masks, unsigned char* bytes, forge_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * layout helpers: NCDHW <-> channels-last for callers that hold plain-contiguous volumes.
  *   src [n][C][P] -> dst [n][P][C]   (P = D*H*W)   and back.
  */
