@@ -55,6 +55,24 @@ def reconstruct_photos(model, model_gt, config, dataset, frames, **kw):
     return _rp(model, model_gt, config, dataset, frames, **kw)
 
 
+def sample_surface(meshes, n):
+    """Deterministic, area-proportional surface samples of extracted meshes (forge_amd/geometry.py)."""
+    from .geometry import sample_surface as _ss
+    return _ss(meshes, n)
+
+
+def point_metrics(a, b, **kw):
+    """Accuracy, completeness, Chamfer, Hausdorff, F-score and normal consistency between two point sets on the device (forge_amd/geometry.py)."""
+    from .geometry import point_metrics as _pm
+    return _pm(a, b, **kw)
+
+
+def mesh_metrics(pred, gt, **kw):
+    """The same metrics between surfaces: meshes sampled on the device, a ground-truth mesh or point cloud (forge_amd/geometry.py)."""
+    from .geometry import mesh_metrics as _mm
+    return _mm(pred, gt, **kw)
+
+
 def install_reference_aliases():
     """Make `from models.model import FORGE` (the import lines of kubric_train_*.py, demo.py,
     kubric_eval.py) and `from models.perceptual_loss import VGGPerceptualLoss` resolve to this package: registers forge_amd's modules under the reference's

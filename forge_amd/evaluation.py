@@ -257,3 +257,11 @@ def sync_pose(return_dict, best_canonical_id, device=None, rank_tol=1e-6):
     synced = geo_utils.mat2quat(geo_utils.get_relative_pose(poses[0], poses[1:]))
     keep = best["poses_cam"].to(device=out.device, dtype=torch.float32)
     return torch.where(status.reshape(1, 1) != 0, keep, synced), status
+
+
+def evaluate_geometry(pred_meshes, gt_meshes, transform=None, **kw):
+    """The surface metrics beside the image and pose metrics above: geometry.mesh_metrics(pred_meshes, gt_meshes, transform=transform, **kw) -
+    accuracy, completeness, Chamfer, Hausdorff, F-score and normal consistency as float64 device tensors, one entry per mesh pair. transform maps
+    the predictions (canonical frame of view 0) into the ground truth's frame. Not part of evaluate_all, whose outputs are the reference's."""
+    from . import geometry
+    return geometry.mesh_metrics(pred_meshes, gt_meshes, transform=transform, **kw)

@@ -8,7 +8,11 @@ counterpart; there is no CPU path.
 bake_vertex_colors gives those meshes their appearance (csrc/bake.hip, section g2): every vertex is projected into posed images of its volume - the
 input photographs, the model's own rendered views - and takes their colours weighted by how well it faces each camera and by the transmittance of the
 density field between it and the camera centre, so a camera that cannot see a vertex does not colour it. colored_mesh runs the whole chain from a
-fused volume: heads, extract_mesh, nvs.render_360, one bake over photographs and rendered views."""
+fused volume: heads, extract_mesh, nvs.render_360, one bake over photographs and rendered views.
+
+mesh_metrics says how good that geometry is (csrc/geomdist.hip, section g3): both surfaces are sampled deterministically (sample_surface), nearest
+neighbours are searched exactly in both directions and reduced in float64 to accuracy, completeness, Chamfer distance, Hausdorff distance, F-score
+and normal consistency (point_metrics). Mesh.from_ply / Mesh.from_obj load the ground truth."""
 import math
 from collections import namedtuple
 
@@ -95,6 +99,258 @@ class Mesh:
                 fh.writelines("v %.9g %.9g %.9g %.9g %.9g %.9g\n" % tuple(p + c) for p, c in zip(v, rgb.tolist()))
             fh.writelines("vn %.9g %.9g %.9g\n" % tuple(p) for p in n)
             fh.writelines("f %d//%d %d//%d %d//%d\n" % (a + 1, a + 1, b + 1, b + 1, c + 1, c + 1) for a, b, c in f)
+
+    @classmethod
+    def _from_arrays(cls, v, n, f, c, device):
+        import numpy as np
+        v = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3))
+        f = torch.from_numpy(np.ascontiguousarray(f, dtype=np.int32).reshape(-1, 3))
+        n = _vertex_normals(v, f) if n is None else torch.from_numpy(np.ascontiguousarray(n, dtype=np.float32).reshape(-1, 3))
+        c = None if c is None else torch.from_numpy(np.ascontiguousarray(c, dtype=np.float32).reshape(-1, 3))
+        return cls(v.to(device), n.to(device), f.to(device), None, None if c is None else c.to(device))
+
+    @classmethod
+    def from_ply(cls, path, device=None):
+        """Read a PLY (a host parser): what to_ply writes, and plain files of other tools - ASCII or binary little-endian, float or double
+        x y z, optional nx ny nz and red green blue (uchar / 255, or float), list faces of any integer type, polygons fan-triangulated, other
+        elements and properties skipped. Missing normals become area-weighted vertex normals. ValueError (naming the line) for anything else."""
+        return cls._from_arrays(*_read_ply(path), device)
+
+    @classmethod
+    def from_obj(cls, path, device=None):
+        """Read a Wavefront OBJ (a host parser): `v x y z [r g b]`, `vn`, `f` with corners i, i/t, i/t/n or i//n, negative (relative) indices,
+        polygons fan-triangulated; vt / o / g / s / usemtl / mtllib lines are skipped. A vertex takes the normal its face corners name; when
+        some corner names none, all normals are area-weighted vertex normals. ValueError (naming the line) for anything else."""
+        return cls._from_arrays(*_read_obj(path), device)
+
+
+def _vertex_normals(v, f):
+    """Area-weighted vertex normals of host tensors v [Nv,3] float32, f [Nf,3] int32: normalize(sum of cross(b - a, c - a) over the faces at a vertex)."""
+    n = torch.zeros(v.shape[0], 3, dtype=torch.float64)
+    if f.numel():
+        fl = f.long()
+        a, b, c = (v[fl[:, k]].double() for k in range(3))
+        cr = torch.linalg.cross(b - a, c - a)
+        for k in range(3):
+            n.index_add_(0, fl[:, k], cr)
+    ln = n.norm(dim=1, keepdim=True)
+    return torch.where(ln > 0, n / ln.clamp_min(1e-300), torch.zeros_like(n)).float()
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2", "int": "i4",
+              "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def _fan(polys):
+    """Polygons (index lists) -> triangles (i0, ik, ik+1)."""
+    return [(p[0], p[k], p[k + 1]) for p in polys for k in range(1, len(p) - 1)]
+
+
+def _read_ply(path):
+    import numpy as np
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    end = raw.find(b"end_header")
+    nl = raw.find(b"\n", end)
+    if end < 0 or nl < 0:
+        raise ValueError("%s: not a PLY file (no end_header line)" % path)
+    try:
+        head = raw[:end].decode("ascii").replace("\r\n", "\n").split("\n")
+    except UnicodeDecodeError:
+        raise ValueError("%s: the PLY header is not ASCII" % path) from None
+    body = raw[nl + 1:]
+    if head[0].strip() != "ply":
+        raise ValueError("%s line 1: expected 'ply', got %r" % (path, head[0]))
+    fmt, elements = None, []                       # elements: [name, count, [(kind, name, type, count type)]]
+    for ln, line in enumerate(head[1:], 2):
+        w = line.split()
+        if not w or w[0] in ("comment", "obj_info"):
+            continue
+        where = "%s line %d" % (path, ln)
+        try:
+            if w[0] == "format":
+                if w[1] not in ("ascii", "binary_little_endian"):
+                    raise ValueError("%s: format %r is not supported (ascii, binary_little_endian)" % (where, w[1]))
+                fmt = w[1]
+            elif w[0] == "element":
+                elements.append([w[1], int(w[2]), []])
+            elif w[0] == "property" and w[1] == "list":
+                elements[-1][2].append(("list", w[4], _PLY_TYPES[w[3]], _PLY_TYPES[w[2]]))
+            elif w[0] == "property":
+                elements[-1][2].append(("scalar", w[2], _PLY_TYPES[w[1]], None))
+            else:
+                raise ValueError("%s: not understood: %r" % (where, line))
+        except (IndexError, KeyError) as e:
+            raise ValueError("%s: not understood: %r (%s)" % (where, line, e)) from None
+    if fmt is None:
+        raise ValueError("%s: the PLY header has no format line" % path)
+    ascii_lines = body.decode("ascii", "replace").split("\n") if fmt == "ascii" else None
+    line_no, pos = len(head) + 1, 0                # line of the next ASCII row (1-based) / byte of the next binary row
+    verts = faces = None
+    vprops = None
+    for name, count, props in elements:
+        lists = [p for p in props if p[0] == "list"]
+        if name == "vertex" and lists:
+            raise ValueError("%s: a list property on the vertex element is not supported" % path)
+        if not lists:                              # fixed-size rows
+            dt = np.dtype([(p[1], ("<" if p[2][1] != "1" else "") + p[2]) for p in props])
+            if fmt == "ascii":
+                rows = ascii_lines[line_no - len(head) - 1:line_no - len(head) - 1 + count]
+                try:
+                    table = np.array([[float(x) for x in r.split()] for r in rows], np.float64).reshape(count, -1)
+                except ValueError:
+                    table = None
+                if table is None or len(rows) != count or table.shape[1] != len(props):
+                    bad = next((k for k, r in enumerate(rows) if len(r.split()) != len(props)), min(len(rows), count - 1) if count else 0)
+                    raise ValueError("%s line %d: expected %d numbers of element %s" % (path, line_no + bad, len(props), name))
+                line_no += count
+                cols = {p[1]: table[:, k] for k, p in enumerate(props)}
+            else:
+                if pos + count * dt.itemsize > len(body):
+                    raise ValueError("%s: truncated in element %s (%d rows of %d bytes from byte %d of the body)" % (path, name, count, dt.itemsize, pos))
+                rec = np.frombuffer(body, dt, count, pos)
+                pos += count * dt.itemsize
+                cols = {p[1]: rec[p[1]] for p in props}
+            if name == "vertex":
+                verts, vprops = cols, {p[1]: p[2] for p in props}
+            continue
+        polys = []
+        if fmt == "ascii":
+            for k in range(count):
+                w = ascii_lines[line_no - len(head) - 1 + k].split() if line_no - len(head) - 1 + k < len(ascii_lines) else []
+                at, poly = 0, None
+                try:
+                    for p in props:
+                        if p[0] == "list":
+                            m = int(w[at])
+                            vals = [int(x) for x in w[at + 1:at + 1 + m]]
+                            if len(vals) != m:
+                                raise IndexError
+                            at += 1 + m
+                            if p[1] in ("vertex_indices", "vertex_index"):
+                                poly = vals
+                        else:
+                            float(w[at])
+                            at += 1
+                except (IndexError, ValueError):
+                    raise ValueError("%s line %d: a row of element %s that does not match its properties" % (path, line_no + k, name)) from None
+                polys.append(poly)
+            line_no += count
+        else:
+            single = len(props) == 1
+            m0 = int(np.frombuffer(body, "<" + props[0][3] if props[0][3][1] != "1" else props[0][3], 1, pos)[0]) if single and count and pos < len(body) else 0
+            fast = None
+            if single and count and m0 > 0:
+                dt = np.dtype([("n", ("<" if props[0][3][1] != "1" else "") + props[0][3]), ("i", ("<" if props[0][2][1] != "1" else "") + props[0][2], (m0,))])
+                if pos + count * dt.itemsize <= len(body):
+                    rec = np.frombuffer(body, dt, count, pos)
+                    if (rec["n"] == m0).all():
+                        fast = rec["i"].astype(np.int64)
+                        pos += count * dt.itemsize
+            if fast is not None:
+                polys = fast if name == "face" and props[0][1] in ("vertex_indices", "vertex_index") else []
+            else:
+                for k in range(count):
+                    poly = None
+                    for p in props:
+                        try:
+                            if p[0] == "list":
+                                m = int(np.frombuffer(body, ("<" if p[3][1] != "1" else "") + p[3], 1, pos)[0])
+                                pos += int(p[3][1])
+                                vals = np.frombuffer(body, ("<" if p[2][1] != "1" else "") + p[2], m, pos)
+                                pos += m * int(p[2][1])
+                                if p[1] in ("vertex_indices", "vertex_index"):
+                                    poly = [int(x) for x in vals]
+                            else:
+                                np.frombuffer(body, ("<" if p[2][1] != "1" else "") + p[2], 1, pos)
+                                pos += int(p[2][1])
+                        except ValueError:
+                            raise ValueError("%s: truncated in row %d of element %s" % (path, k, name)) from None
+                    polys.append(poly)
+        if name == "face":
+            if isinstance(polys, list) and any(p is None for p in polys):
+                raise ValueError("%s: the face element has no vertex_indices list" % path)
+            faces = polys
+    if verts is None or not all(k in verts for k in "xyz"):
+        raise ValueError("%s: no vertex element with x, y, z" % path)
+    v = np.stack([verts[k] for k in "xyz"], axis=1).astype(np.float32)
+    n = np.stack([verts[k] for k in ("nx", "ny", "nz")], axis=1).astype(np.float32) if all(k in verts for k in ("nx", "ny", "nz")) else None
+    c = None
+    if all(k in verts for k in ("red", "green", "blue")):
+        c = np.stack([verts[k] for k in ("red", "green", "blue")], axis=1).astype(np.float32)
+        if vprops["red"][0] != "f":
+            c = c / np.float32(255.0)
+    if faces is None:
+        f = np.zeros((0, 3), np.int32)
+    elif isinstance(faces, np.ndarray):
+        f = faces if faces.shape[1] == 3 else np.concatenate([faces[:, [0, k, k + 1]] for k in range(1, faces.shape[1] - 1)], axis=1).reshape(-1, 3) \
+            if faces.shape[1] > 3 else np.zeros((0, 3), np.int64)
+    else:
+        f = np.array(_fan(faces), np.int64).reshape(-1, 3)
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise ValueError("%s: a face names vertex %d of %d" % (path, int(f.max() if f.max() >= v.shape[0] else f.min()), v.shape[0]))
+    return v, n, f.astype(np.int32), c
+
+
+def _read_obj(path):
+    import numpy as np
+    v, col, vn, polys, npolys = [], [], [], [], []
+    skip = {"vt", "vp", "o", "g", "s", "usemtl", "mtllib", "l", "p"}
+    with open(path, "r", errors="replace") as fh:
+        for ln, line in enumerate(fh, 1):
+            w = line.split("#", 1)[0].split()
+            if not w or w[0] in skip:
+                continue
+            where = "%s line %d" % (path, ln)
+            try:
+                if w[0] == "v":
+                    x = [float(t) for t in w[1:]]
+                    if len(x) not in (3, 4, 6, 7):
+                        raise ValueError("%d numbers after v" % len(x))
+                    v.append(x[:3])
+                    col.append(x[-3:] if len(x) >= 6 else None)
+                elif w[0] == "vn":
+                    x = [float(t) for t in w[1:]]
+                    if len(x) != 3:
+                        raise ValueError("%d numbers after vn" % len(x))
+                    vn.append(x)
+                elif w[0] == "f":
+                    if len(w) < 4:
+                        raise ValueError("a face of %d corners" % (len(w) - 1))
+                    pi, ni = [], []
+                    for t in w[1:]:
+                        parts = t.split("/")
+                        if len(parts) > 3 or not parts[0]:
+                            raise ValueError("corner %r" % t)
+                        i = int(parts[0])
+                        i = i - 1 if i > 0 else len(v) + i
+                        if i < 0 or i >= len(v) or int(parts[0]) == 0:
+                            raise ValueError("corner %r names a vertex that does not exist yet" % t)
+                        pi.append(i)
+                        if len(parts) == 3 and parts[2]:
+                            k = int(parts[2])
+                            k = k - 1 if k > 0 else len(vn) + k
+                            if k < 0 or k >= len(vn) or int(parts[2]) == 0:
+                                raise ValueError("corner %r names a normal that does not exist yet" % t)
+                            ni.append(k)
+                        else:
+                            ni.append(None)
+                    polys.append(pi)
+                    npolys.append(ni)
+                else:
+                    raise ValueError("keyword %r" % w[0])
+            except ValueError as e:
+                raise ValueError("%s: not understood: %r (%s)" % (where, line.rstrip("\n"), e)) from None
+    va = np.array(v, np.float64).reshape(-1, 3).astype(np.float32)
+    f = np.array(_fan(polys), np.int32).reshape(-1, 3)
+    n = None
+    if polys and all(k is not None for ni in npolys for k in ni):
+        n = np.zeros((len(v), 3), np.float32)
+        vna = np.array(vn, np.float64).reshape(-1, 3).astype(np.float32)
+        for pi, ni in zip(polys, npolys):
+            n[pi] = vna[ni]
+    c = np.array(col, np.float64).astype(np.float32) if col and all(x is not None for x in col) else None
+    return va, n, f, c
 
 
 def extract_mesh(density, level=0.5, volume_size=1.0, features=None, max_vertices=None, max_faces=None):
@@ -235,3 +491,110 @@ def colored_mesh(model, features_fused, K_cv2, camera_z, photos=None, photo_came
         v2v = torch.cat([torch.arange(b, dtype=torch.int32, device=dev).repeat_interleave(t), v2v])
         gain = torch.cat([torch.ones(b * t, device=dev), gain])
     return bake_vertex_colors(meshes, densities_mv, images, cams, view2vol=v2v, volume_size=volume_size, view_gain=gain, **knobs)
+
+
+# ----------------------------------------------------------------------------------------------------------------- scoring a surface
+def _pack_meshes(meshes):
+    """A list of Mesh -> the packed rows forge_surface_sample takes: (vertices [Nv,3], faces [Nf,3], counts [n,2], offsets [n,2]) on the device."""
+    meshes = list(meshes)
+    if not meshes or not all(isinstance(m, Mesh) for m in meshes):
+        raise TypeError("sample_surface: a MeshBatch or a non-empty list of Mesh")
+    dev = meshes[0].vertices.device
+    counts = torch.tensor([[int(m.vertices.shape[0]), int(m.faces.shape[0])] for m in meshes], dtype=torch.int32).reshape(len(meshes), 2)
+    offsets = torch.cumsum(counts, dim=0, dtype=torch.int32) - counts
+    vertices = torch.cat([m.vertices.to(torch.float32).reshape(-1, 3) for m in meshes]).contiguous()
+    faces = torch.cat([m.faces.to(torch.int32).reshape(-1, 3) for m in meshes]).contiguous()
+    return vertices, faces, counts.to(dev), offsets.to(dev)
+
+
+def sample_surface(meshes, n):
+    """n deterministic, area-proportional surface samples per mesh (include/forge_hip.h section g3): systematic sampling over the cumulative
+    face areas, barycentrics from the R2 low-discrepancy sequence in integer arithmetic - the same call gives the same bits everywhere.
+    meshes: a list of Mesh (packed into one launch) or the MeshBatch of extract_mesh with capacities (no host synchronisation: counts stay
+    on the device). Returns points [n_mesh,n,3], normals [n_mesh,n,3] (the face normal along the winding: outward for extracted meshes), face
+    [n_mesh,n] int32, bary [n_mesh,n,2], status [n_mesh] int32 (ops.GEOM_EMPTY for a mesh without area: its points are zero, its faces -1)."""
+    if isinstance(meshes, MeshBatch):
+        return ops.surface_sample(meshes.vertices, meshes.faces, meshes.counts, n)
+    if isinstance(meshes, Mesh):
+        meshes = [meshes]
+    vertices, faces, counts, offsets = _pack_meshes(meshes)
+    return ops.surface_sample(vertices, faces, counts, n, offsets=offsets)
+
+
+def _as_batch(t, what):
+    if not torch.is_tensor(t):
+        raise TypeError("point_metrics: %s must be a tensor" % what)
+    if t.dim() == 2:
+        t = t[None]
+    if t.dim() != 3 or t.shape[2] != 3:
+        raise ValueError("point_metrics: %s must be [N,3] or [B,N,3], got %s" % (what, tuple(t.shape)))
+    return t.to(torch.float32).contiguous()
+
+
+def _pack_transform(transform, B, dev):
+    """[4,4] or [B,4,4] -> (xf [B,12] float32 as forge_nn_points takes it, linear part [B,3,3])."""
+    T = torch.as_tensor(transform, dtype=torch.float32, device=dev)
+    if T.dim() == 2:
+        T = T[None].expand(B, 4, 4)
+    if tuple(T.shape) != (B, 4, 4):
+        raise ValueError("point_metrics: transform must be [4,4] or [%d,4,4], got %s" % (B, tuple(T.shape)))
+    return T[:, :3, :].reshape(B, 12).contiguous(), T[:, :3, :3]
+
+
+def point_metrics(a, b, normals_a=None, normals_b=None, thresholds=(0.01, 0.02, 0.05), transform=None, counts_a=None, counts_b=None):
+    """Surface metrics between point sets a [B,Na,3] (the prediction) and b [B,Nb,3] (the ground truth), [N,3] for one pair, on the device:
+    exact nearest neighbours in both directions (ops.nn_points) reduced in float64 (ops.geom_metrics). Returns a dict of float64 device tensors
+    [B]: accuracy (mean distance a -> b), completeness (b -> a), chamfer_l1 (their mean), chamfer_l2 (sum of the two mean squared distances),
+    hausdorff, normal_consistency (mean |n_a . n_b| over nearest neighbours, both directions; NaN without normals), and per threshold t
+    'precision@t', 'recall@t', 'fscore@t' (keys formatted with %g; up to 4 thresholds); 'status' [B] int32 carries ops.GEOM_EMPTY for a pair
+    with an empty side, whose means are NaN. transform ([4,4] or [B,4,4], a similarity) maps a into the frame of b before anything is measured
+    (normals_a are rotated with it); counts_a / counts_b [B] int32 device tensors limit the valid rows. Nothing is read back."""
+    if (normals_a is None) != (normals_b is None):
+        raise ValueError("point_metrics: give the normals of both sides, or of neither")
+    a, b = _as_batch(a, "a"), _as_batch(b, "b")
+    ops._require_cuda(a, b)
+    B, dev = a.shape[0], a.device
+    xf = None
+    if transform is not None:
+        xf, lin = _pack_transform(transform, B, dev)
+    if normals_a is not None:
+        normals_a, normals_b = _as_batch(normals_a, "normals_a"), _as_batch(normals_b, "normals_b")
+        if xf is not None:                         # a similarity's linear part is s R: rotate, then renormalise (a zero normal stays zero)
+            rot = normals_a @ lin.transpose(1, 2)
+            ln = rot.norm(dim=2, keepdim=True)
+            normals_a = torch.where(ln > 0, rot / ln.clamp_min(1e-30), torch.zeros_like(rot)).contiguous()
+    d2_ab, idx_ab, a_in_b = ops.nn_points(a, b, counts_a, counts_b, xf, return_transformed=True)
+    d2_ba, idx_ba = ops.nn_points(b, a_in_b, counts_b, counts_a)
+    thresholds = tuple(float(t) for t in thresholds)
+    out, status = ops.geom_metrics(d2_ab, idx_ab, d2_ba, idx_ba, normals_a, normals_b, counts_a, counts_b, thresholds)
+    res = {name: out[:, k] for k, name in enumerate(ops.GEOM_SCALARS)}
+    for name, first in ops.GEOM_PER_THRESHOLD:
+        for k, t in enumerate(thresholds):
+            res["%s@%g" % (name, t)] = out[:, first + k]
+    res["status"] = status
+    return res
+
+
+def _sampled(side, n, what):
+    """(points [B,n,3], normals or None, counts [B] int32 or None) of a Mesh, a list of Mesh, a MeshBatch or a point-cloud tensor."""
+    if torch.is_tensor(side):
+        return _as_batch(side, what), None, None
+    points, normals, _, _, status = sample_surface(side, n)
+    counts = torch.where((status & ops.GEOM_EMPTY) != 0, torch.zeros_like(status), torch.full_like(status, int(n)))      # an empty mesh has no samples
+    return points, normals, counts
+
+
+def mesh_metrics(pred, gt, n=100_000, thresholds=(0.01, 0.02, 0.05), transform=None):
+    """Chamfer distance, F-score and the other entries of point_metrics between surfaces: n samples of each side (sample_surface), then
+    point_metrics. pred / gt: a Mesh, a list of Mesh or a MeshBatch (one pair per mesh); gt may also be a point cloud [N,3] / [B,N,3], and then
+    no normal consistency is computed. transform ([4,4] or [B,4,4], a similarity) maps pred into the frame of gt: extracted meshes live in the
+    canonical world frame of view 0 (the frame VolRender takes cameras in), ground-truth meshes in their dataset's object frame, so a caller
+    scoring against ground truth passes the alignment here - nothing is estimated. With MeshBatch inputs there is no host synchronisation (an
+    empty volume shows as ops.GEOM_EMPTY in 'status' and NaN means), so the whole chain can sit in a captured graph."""
+    pa, na, ca = _sampled(pred, n, "pred")
+    pb, nb, cb = _sampled(gt, n, "gt")
+    if pa.shape[0] != pb.shape[0]:
+        raise ValueError("mesh_metrics: %d predictions against %d ground truths" % (pa.shape[0], pb.shape[0]))
+    if na is None or nb is None:
+        na = nb = None
+    return point_metrics(pa, pb, na, nb, thresholds=thresholds, transform=transform, counts_a=ca, counts_b=cb)

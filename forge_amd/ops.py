@@ -991,3 +991,130 @@ def mesh_bake(vertices, normals, counts, density, images, cam, view2vol, *, offs
                                           int(cos_power), float(z_near), float(w_min), BAKE_MODES[mode], float(fill), _lib.ptr(colors), _lib.ptr(weight),
                                           _lib.ptr(best), _lib.current_stream()), "forge_mesh_bake")
     return colors, weight, best
+
+
+# ------------------------------------------------------------------------------------------------------------------- surface metrics
+GEOM_EMPTY = 1                                                     # status bit (FORGE_GEOM_EMPTY): a mesh without area, a pair with an empty side
+GEOM_MAX_THRESHOLDS = 4
+GEOM_OUT_DOUBLES = 18
+GEOM_SCALARS = ("accuracy", "completeness", "chamfer_l1", "chamfer_l2", "hausdorff", "normal_consistency")      # out[:, 0..5]
+GEOM_PER_THRESHOLD = (("precision", 6), ("recall", 10), ("fscore", 14))                                         # out[:, first + k]
+
+
+def nn_constants():
+    """(queries per workgroup, references per LDS tile) of forge_nn_points: host only, no device is touched."""
+    L = _lib.lib()
+    return int(L.forge_nn_queries_per_block()), int(L.forge_nn_tile_points())
+
+
+def _geom_check(fn, want):
+    """want: (name, tensor or None, shape, dtype). The device of the first tensor is the device of all."""
+    dev = next(t for _, t, _, _ in want if t is not None).device
+    for name, t, shape, dt in want:
+        if t is None:
+            continue
+        if t.dtype != dt:
+            raise TypeError("%s: %s must be %s (got %s)" % (fn, name, dt, t.dtype))
+        if tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != dev:
+            raise ValueError("%s: %s must be a contiguous %s tensor on %s, got %s with strides %s on %s"
+                             % (fn, name, tuple(shape), dev, tuple(t.shape), t.stride(), t.device))
+    return dev
+
+
+@_lib.on_tensor_device
+def surface_sample(vertices, faces, counts, n_samples, offsets=None):
+    """forge_surface_sample (include/forge_hip.h section g3): n_samples deterministic, area-proportional points on each mesh. vertices
+    [n,max_vertices,3] / faces [n,max_faces,3] int32 with counts [n,2] (offsets None: every mesh owns its rows, as mesh_emit pads them) or
+    [max_vertices,3] / [max_faces,3] with offsets [n,2] (the meshes packed one after the other). Returns (points [n,n_samples,3], normals
+    [n,n_samples,3], face [n,n_samples] int32, bary [n,n_samples,2], status [n] int32 with GEOM_EMPTY for a mesh without area). Nothing is read back."""
+    tensors = (vertices, faces, counts)
+    if not all(torch.is_tensor(t) for t in tensors) or not (offsets is None or torch.is_tensor(offsets)):
+        raise TypeError("surface_sample: vertices, faces, counts (and offsets) must be tensors")
+    _require_cuda(*tensors, offsets)
+    if counts.dim() != 2 or counts.shape[0] < 1:
+        raise ValueError("surface_sample: counts must be [n,2] with n >= 1, got %s" % (tuple(counts.shape),))
+    n = int(counts.shape[0])
+    n_samples = int(n_samples)
+    if n_samples < 1:
+        raise ValueError("surface_sample: n_samples=%d must be at least 1" % n_samples)
+    lead = (n,) if offsets is None else ()
+    if vertices.dim() != len(lead) + 2 or faces.dim() != len(lead) + 2:
+        raise ValueError("surface_sample: vertices and faces must be %s, got %s and %s"
+                         % ("[%d,rows,3]" % n if offsets is None else "[rows,3] (packed: offsets given)", tuple(vertices.shape), tuple(faces.shape)))
+    mv, mf = int(vertices.shape[-2]), int(faces.shape[-2])
+    dev = _geom_check("surface_sample", [("vertices", vertices, lead + (mv, 3), torch.float32), ("faces", faces, lead + (mf, 3), torch.int32),
+                                         ("counts", counts, (n, 2), torch.int32), ("offsets", offsets, (n, 2), torch.int32)])
+    nbytes = int(_lib.lib().forge_surface_sample_workspace_bytes(n, mf, 0 if offsets is None else 1))
+    if nbytes < 0:
+        _lib.check(nbytes, "forge_surface_sample_workspace_bytes")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    points = torch.empty(n, n_samples, 3, dtype=torch.float32, device=dev)
+    normals = torch.empty(n, n_samples, 3, dtype=torch.float32, device=dev)
+    face = torch.empty(n, n_samples, dtype=torch.int32, device=dev)
+    bary = torch.empty(n, n_samples, 2, dtype=torch.float32, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().forge_surface_sample(_lib.ptr(vertices.detach()), _lib.ptr(faces), _lib.ptr(counts), _lib.ptr(offsets), n, mv, mf, n_samples,
+                                               _lib.ptr(ws), nbytes, _lib.ptr(points), _lib.ptr(normals), _lib.ptr(face), _lib.ptr(bary), _lib.ptr(status),
+                                               _lib.current_stream()), "forge_surface_sample")
+    return points, normals, face, bary, status
+
+
+@_lib.on_tensor_device
+def nn_points(q, p, q_count=None, p_count=None, xf=None, return_transformed=False):
+    """forge_nn_points (section g3): for every query q [B,Nq,3] the nearest of the references p [B,Np,3] of its pair, brute force and exact in fp32's
+    difference form. q_count / p_count [B] int32 on the device (None: all rows); xf [B,12], a row-major 3x4 (s R | t) applied to the queries on
+    load. Returns (d2 [B,Nq] float32, idx [B,Nq] int32): ties go to the lowest index; rows past q_count get (0, -1); no references: (+inf, -1).
+    return_transformed: also the queries as they were scored, [B,Nq,3] (the references of the opposite direction). Nothing is read back."""
+    if not all(torch.is_tensor(t) for t in (q, p)) or not all(t is None or torch.is_tensor(t) for t in (q_count, p_count, xf)):
+        raise TypeError("nn_points: q, p (and q_count, p_count, xf) must be tensors")
+    _require_cuda(q, p, q_count, p_count, xf)
+    if q.dim() != 3 or p.dim() != 3 or q.shape[2] != 3 or p.shape[2] != 3 or q.shape[0] != p.shape[0] or min(q.shape[:2] + p.shape[:2]) < 1:
+        raise ValueError("nn_points: q [B,Nq,3] and p [B,Np,3] with B, Nq, Np >= 1, got %s and %s" % (tuple(q.shape), tuple(p.shape)))
+    B, Nq, Np = int(q.shape[0]), int(q.shape[1]), int(p.shape[1])
+    dev = _geom_check("nn_points", [("q", q, (B, Nq, 3), torch.float32), ("p", p, (B, Np, 3), torch.float32), ("q_count", q_count, (B,), torch.int32),
+                                    ("p_count", p_count, (B,), torch.int32), ("xf", xf, (B, 12), torch.float32)])
+    d2 = torch.empty(B, Nq, dtype=torch.float32, device=dev)
+    idx = torch.empty(B, Nq, dtype=torch.int32, device=dev)
+    q_xf = torch.empty(B, Nq, 3, dtype=torch.float32, device=dev) if return_transformed else None
+    _lib.check(_lib.lib().forge_nn_points(_lib.ptr(q.detach()), _lib.ptr(p.detach()), _lib.ptr(q_count), _lib.ptr(p_count),
+                                          _lib.ptr(None if xf is None else xf.detach()), B, Nq, Np, _lib.ptr(d2), _lib.ptr(idx), _lib.ptr(q_xf), _lib.current_stream()),
+               "forge_nn_points")
+    return (d2, idx, q_xf) if return_transformed else (d2, idx)
+
+
+@_lib.on_tensor_device
+def geom_metrics(d2_ab, idx_ab, d2_ba, idx_ba, normals_a=None, normals_b=None, a_count=None, b_count=None, thresholds=()):
+    """forge_geom_metrics (section g3): the nn_points results of both directions (A against B: [B,Na]; B against A: [B,Nb]) reduced per pair in
+    float64. normals_a [B,Na,3] and normals_b [B,Nb,3]: both or neither; thresholds: up to GEOM_MAX_THRESHOLDS finite numbers (host). Returns
+    (out [B,GEOM_OUT_DOUBLES] float64, laid out as GEOM_SCALARS and GEOM_PER_THRESHOLD say, status [B] int32 with GEOM_EMPTY for a pair with an empty
+    side). Nothing is read back."""
+    import ctypes
+    tensors = (d2_ab, idx_ab, d2_ba, idx_ba)
+    if not all(torch.is_tensor(t) for t in tensors) or not all(t is None or torch.is_tensor(t) for t in (normals_a, normals_b, a_count, b_count)):
+        raise TypeError("geom_metrics: d2 / idx of both directions (and normals, counts) must be tensors")
+    _require_cuda(*tensors, normals_a, normals_b, a_count, b_count)
+    if d2_ab.dim() != 2 or d2_ba.dim() != 2 or d2_ab.shape[0] != d2_ba.shape[0] or min(tuple(d2_ab.shape) + tuple(d2_ba.shape)) < 1:
+        raise ValueError("geom_metrics: d2_ab [B,Na] and d2_ba [B,Nb] with B, Na, Nb >= 1, got %s and %s" % (tuple(d2_ab.shape), tuple(d2_ba.shape)))
+    if (normals_a is None) != (normals_b is None):
+        raise ValueError("geom_metrics: give the normals of both sides, or of neither")
+    thresholds = [float(t) for t in thresholds]
+    if len(thresholds) > GEOM_MAX_THRESHOLDS or not all(math.isfinite(t) for t in thresholds):
+        raise ValueError("geom_metrics: at most %d finite thresholds, got %r" % (GEOM_MAX_THRESHOLDS, thresholds))
+    B, Na, Nb = int(d2_ab.shape[0]), int(d2_ab.shape[1]), int(d2_ba.shape[1])
+    dev = _geom_check("geom_metrics", [("d2_ab", d2_ab, (B, Na), torch.float32), ("idx_ab", idx_ab, (B, Na), torch.int32),
+                                       ("d2_ba", d2_ba, (B, Nb), torch.float32), ("idx_ba", idx_ba, (B, Nb), torch.int32),
+                                       ("normals_a", normals_a, (B, Na, 3), torch.float32), ("normals_b", normals_b, (B, Nb, 3), torch.float32),
+                                       ("a_count", a_count, (B,), torch.int32), ("b_count", b_count, (B,), torch.int32)])
+    npart = int(_lib.lib().forge_geom_metrics_partial_doubles(B))
+    if npart < 0:
+        _lib.check(npart, "forge_geom_metrics_partial_doubles")
+    partial = torch.empty(npart, dtype=torch.float64, device=dev)
+    out = torch.empty(B, GEOM_OUT_DOUBLES, dtype=torch.float64, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    tau = (ctypes.c_double * GEOM_MAX_THRESHOLDS)(*thresholds)
+    _lib.check(_lib.lib().forge_geom_metrics(_lib.ptr(d2_ab), _lib.ptr(idx_ab), _lib.ptr(d2_ba), _lib.ptr(idx_ba),
+                                             _lib.ptr(None if normals_a is None else normals_a.detach()),
+                                             _lib.ptr(None if normals_b is None else normals_b.detach()), _lib.ptr(a_count), _lib.ptr(b_count), B, Na, Nb,
+                                             tau, len(thresholds), _lib.ptr(partial), _lib.ptr(out), _lib.ptr(status), _lib.current_stream()),
+               "forge_geom_metrics")
+    return out, status

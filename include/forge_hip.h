@@ -809,6 +809,88 @@ int forge_mesh_bake(const float* vertices, const float* normals, const int* coun
                     int cos_power, float z_near, float w_min, int mode, float fill, float* colors, float* weight, int* best, forge_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * g3  Scoring a surface against ground truth (csrc/geomdist.hip): deterministic surface samples of triangle meshes, exact nearest neighbours
+ * between two point sets, and their reduction to accuracy / completeness / Chamfer / Hausdorff / F-score / normal consistency. The reference has
+ * no counterpart. Brute force on purpose: exact, no build step, no data-dependent memory, no atomics, graph-capturable.
+ *
+ * forge_surface_sample  n_samples area-proportional points on each of n_mesh meshes, in the two row layouts of forge_mesh_emit:
+ *   vertices, faces, counts [n_mesh][2], offsets [n_mesh][2] (nullable), max_vertices, max_faces  as g1 / g2 take them: offsets == NULL: mesh v owns
+ *             rows v max_vertices .. of vertices and v max_faces .. of faces; otherwise mesh v starts at rows offsets[v] of arrays with max_vertices /
+ *             max_faces rows IN ALL. Mesh v has min(counts[v], rows left to it) vertices and faces (count_v vertices below). counts stays on the device.
+ *   area      A_f = 0.5 |cross(b - a, c - a)| of the fp32 corners a, b, c, evaluated in float64. A face with an index outside 0 .. count_v - 1 has
+ *             area 0 and is never followed.
+ *   cum       workspace[face row] (float64) = the inclusive sum of A_f over the mesh's faces, in a fixed order: with chunk = ceil(F / 256), the sum
+ *             of the chunks before the face's own (chunk sums added in increasing chunk index, each formed in increasing f) plus the running sum
+ *             within its chunk. A_total = cum[F - 1].
+ *   sample i  u_i = (i + 0.5) / n_samples A_total (float64, left to right); face = the first f with cum[f] > u_i (binary search). Systematic
+ *             sampling: face indices are non-decreasing in i, face f receives floor or ceil of n_samples A_f / A_total samples, a face of area 0
+ *             receives none.
+ *   bary      integers only: k1 = uint32(i 3242174889) >> 8, k2 = uint32(i 2447445414) >> 8 (the R2 sequence in 32-bit wrap-around arithmetic);
+ *             if k1 + k2 > 2^24: k1 = 2^24 - k1, k2 = 2^24 - k2; r1 = k1 2^-24, r2 = k2 2^-24: exact in fp32, r1, r2 >= 0, r1 + r2 <= 1.
+ *   points    [n_mesh][n_samples][3] = fma(r2, c - a, fma(r1, b - a, a)) per axis (fp32)
+ *   normals   [n_mesh][n_samples][3] = normalize(cross(b - a, c - a)) in fp32 (components fma(e1y, e2z, -(e1z e2y)), ...): the face normal along
+ *             the mesh's winding - outward for the meshes of g1; zero when the cross product is zero
+ *   face      [n_mesh][n_samples] int32;  bary [n_mesh][n_samples][2] = (r1, r2)
+ *   status    [n_mesh] int32: FORGE_GEOM_EMPTY when A_total is 0 or not finite; then points and normals are zero and face is -1 (bary is written
+ *             all the same: it does not depend on the mesh).
+ *   workspace forge_surface_sample_workspace_bytes(n_mesh, max_faces, packed = offsets != NULL) bytes, 16-byte aligned.
+ *   Two launches. FORGE_EINVAL: a null pointer (offsets excepted; vertices / faces may be null with a zero capacity), n_mesh or n_samples < 1, a
+ *   negative capacity, a workspace too small or unaligned. FORGE_ESHAPE: n_mesh > 65535, vertex / face / sample rows beyond 2^31 - 1.
+ *
+ * forge_nn_points  for each of B pairs and each query, the nearest reference:
+ *   q [B][Nq][3], p [B][Np][3] fp32; q_count [B], p_count [B] device int32, nullable (= Nq, Np), clamped into 0 .. N
+ *   xf [B][12], nullable: a row-major 3x4 (s R | t) applied to the QUERIES on load, x' = fma(m02, z, fma(m01, y, fma(m00, x, t0))) per row
+ *   d2 [B][Nq] fp32 = min over j < p_count of fma(dz, dz, fma(dy, dy, dx dx)) with dx = q'.x - p_j.x etc. in fp32;  idx [B][Nq] int32 = that j.
+ *   q_xf [B][Nq][3], nullable: the queries as they were scored (q' for every row, valid or not) - the references of the opposite direction.
+ *   Ties go to the LOWEST reference index. Rows at or past q_count: d2 = 0, idx = -1. p_count = 0: d2 = +inf, idx = -1. A candidate wins only
+ *   through `d2_j < best` (best starts at +inf), so a NaN coordinate never wins; a query with no winning reference at all keeps d2 = +inf, idx = -1.
+ *   The DIFFERENCE form is deliberate, and not |q|^2 + |p|^2 - 2 q.p on the matrix cores: between two samplings of nearly the same surface - the
+ *   regime the metric exists to measure - d2 ~ 1e-6 stands against terms ~ 0.25, and the expanded form cancels to nothing in fp32, while the
+ *   difference form keeps a relative error of a few 2^-24 at any distance.
+ *   One launch, grid (query blocks of forge_nn_queries_per_block(), pairs), references walked in LDS tiles of forge_nn_tile_points(); no split over
+ *   the references, so no merge. FORGE_EINVAL: null q / p / d2 / idx, B, Nq or Np < 1. FORGE_ESHAPE: B > 65535, Nq or Np within a tile of 2^31.
+ *
+ * forge_geom_metrics  the distances of both directions reduced per pair, float64 throughout, d = sqrt((double)d2):
+ *   d2_ab, idx_ab [B][Na] (queries A against references B), d2_ba, idx_ba [B][Nb]; normals_a [B][Na][3], normals_b [B][Nb][3]: both or neither;
+ *   a_count, b_count [B] nullable as above; tau: n_tau <= FORGE_GEOM_MAX_THRESHOLDS finite thresholds, a HOST array read before the launch.
+ *   Per direction over the count's valid rows: mean d, mean d2, max d, the fraction with d < tau_k, and the mean of |n_from[i] . n_to[idx[i]]| (an
+ *   fma chain z, y, x in float64; rows with idx = -1 add 0). Per-workgroup partials (fixed tree) are summed in workgroup order by the second launch.
+ *   out [B][FORGE_GEOM_OUT_DOUBLES]: ACCURACY = mean d of A -> B, COMPLETENESS = mean d of B -> A, CHAMFER_L1 = their mean, CHAMFER_L2 = the sum of
+ *   the two mean d2, HAUSDORFF = the larger max, NORMAL_CONSISTENCY = the mean of the two directions (NaN without normals), then per threshold k
+ *   PRECISION + k (A -> B), RECALL + k (B -> A), FSCORE + k = 2 P R / (P + R), 0 when P + R = 0 (NaN for k >= n_tau).
+ *   status [B]: FORGE_GEOM_EMPTY when either count is 0; the means of an empty side are NaN (0 / 0) - never a trap, never a host check.
+ *   partial: forge_geom_metrics_partial_doubles(B) doubles. Two launches.
+ *   FORGE_EINVAL: a null pointer (normals, counts excepted; tau with n_tau = 0), normals of one side only, B, Na or Nb < 1, n_tau outside 0 .. 4, a
+ *   threshold that is not finite, partial or out not 8-byte aligned. FORGE_ESHAPE: B > 65535.
+ * Nothing allocates, synchronises or reads the environment; every entry takes the stream; every output bit is reproducible.
+ */
+#define FORGE_GEOM_EMPTY 1              /* status bit: a mesh without area (forge_surface_sample), a pair with an empty side (forge_geom_metrics) */
+#define FORGE_GEOM_MAX_THRESHOLDS 4
+#define FORGE_GEOM_ACCURACY 0
+#define FORGE_GEOM_COMPLETENESS 1
+#define FORGE_GEOM_CHAMFER_L1 2
+#define FORGE_GEOM_CHAMFER_L2 3
+#define FORGE_GEOM_HAUSDORFF 4
+#define FORGE_GEOM_NORMAL_CONSISTENCY 5
+#define FORGE_GEOM_PRECISION 6
+#define FORGE_GEOM_RECALL 10
+#define FORGE_GEOM_FSCORE 14
+#define FORGE_GEOM_OUT_DOUBLES 18
+int forge_nn_queries_per_block(void);
+int forge_nn_tile_points(void);
+int forge_geom_scan_threads(void);
+long long forge_surface_sample_workspace_bytes(int n_mesh, int max_faces, int packed);
+int forge_surface_sample(const float* vertices, const int* faces, const int* counts, const int* offsets, int n_mesh, int max_vertices, int max_faces,
+                         int n_samples, void* workspace, long long workspace_bytes, float* points, float* normals, int* face, float* bary,
+                         int* status, forge_stream_t stream);
+int forge_nn_points(const float* q, const float* p, const int* q_count, const int* p_count, const float* xf, int B, int Nq, int Np, float* d2,
+                    int* idx, float* q_xf, forge_stream_t stream);
+long long forge_geom_metrics_partial_doubles(int B);
+int forge_geom_metrics(const float* d2_ab, const int* idx_ab, const float* d2_ba, const int* idx_ba, const float* normals_a, const float* normals_b,
+                       const int* a_count, const int* b_count, int B, int Na, int Nb, const double* tau, int n_tau, double* partial, double* out,
+                       int* status, forge_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * h  Photographs to input tensors (csrc/ingest.hip): the `_load_frame` of dataset/kubric.py:410-445, dataset/gso.py:257-290 and
  * dataset/omniobject3d.py:221-258 and the image loop of demo.py:236-256 - an 8-bit RGB(A) frame of any size put on a background, resized with
  * Pillow's Image.ANTIALIAS (Lanczos, a = 3), its mask resized with Image.NEAREST, divided by 255. On 8-bit images Pillow's resampler is integer
