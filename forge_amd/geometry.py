@@ -12,7 +12,13 @@ fused volume: heads, extract_mesh, nvs.render_360, one bake over photographs and
 
 mesh_metrics says how good that geometry is (csrc/geomdist.hip, section g3): both surfaces are sampled deterministically (sample_surface), nearest
 neighbours are searched exactly in both directions and reduced in float64 to accuracy, completeness, Chamfer distance, Hausdorff distance, F-score
-and normal consistency (point_metrics). Mesh.from_ply / Mesh.from_obj load the ground truth."""
+and normal consistency (point_metrics). Mesh.from_ply / Mesh.from_obj load the ground truth.
+
+label_components and keep_components say which voxels belong to the object (csrc/components.hip, section g4): a few-view reconstruction emits the
+object plus small detached blobs - floaters - and every stage above pays for them (extra shells, volume, samples, occluders). Components are
+taken under the adjacency of the very lattice extract_mesh marches over, so dropping a component removes exactly one closed shell and leaves
+every other vertex and face of the mesh bit for bit as it was. extract_mesh(components=...) and colored_mesh(components=...) clean the volume
+first."""
 import math
 from collections import namedtuple
 
@@ -24,6 +30,12 @@ MeshBatch = namedtuple("MeshBatch", "vertices normals faces features counts stat
 MeshBatch.__doc__ = """extract_mesh with capacities: padded device tensors of the whole batch. vertices / normals [n,max_vertices,3] float32,
 faces [n,max_faces,3] int32, features [n,max_vertices,C] or None, counts [n,2] int32 (the vertices and triangles each volume NEEDS), status [n] int32
 (ops.MESH_OVERFLOW where the need exceeds a capacity: what was written is then the prefix of the full result). Rows past a volume's count are zero."""
+
+Components = namedtuple("Components", "labels counts sizes bbox centroid status")
+Components.__doc__ = """label_components: labels [n,D,H,W] int32 (0 outside, 1 .. K inside, numbered by the component's lowest linear index), counts [n]
+int32 (the components each volume HAS), and per component in label order, Kmax rows per volume: sizes [n,Kmax] int32 (voxels), bbox [n,Kmax,6] int32
+(x0, y0, z0, x1, y1, z1 voxel indices, inclusive), centroid [n,Kmax,3] float64 (x, y, z in the mesh's world frame), status [n] int32
+(ops.COMPONENTS_OVERFLOW where a volume has more than Kmax components: the rows are then the first Kmax). Rows past a volume's count are zero."""
 
 
 class Mesh:
@@ -353,15 +365,66 @@ def _read_obj(path):
     return va, n, f, c
 
 
-def extract_mesh(density, level=0.5, volume_size=1.0, features=None, max_vertices=None, max_faces=None):
+def label_components(density, level=0.5, max_components=None, volume_size=1.0):
+    """The connected components of `density > level` of density [n,1,D,H,W] (float32, on the device) under the Kuhn adjacency (include/forge_hip.h
+    section g4: the 6 axis neighbours, the same-sign face diagonals and the same-sign body diagonal - the lattice edges extract_mesh marches over),
+    as a Components tuple. Everything is integer arithmetic on the device and reproducible bit for bit; centroid is derived here in float64,
+    per axis (coord_sum / size - 0.5 (N - 1)) (volume_size / N): the world frame of extract_mesh's vertices GIVEN THE SAME volume_size - it is
+    not taken from anywhere else, so a caller who passes config.render.volume_size to extract_mesh must pass it here too, or the centroids
+    live in the frame of a unit volume.
+
+    Without max_components: one read-back of the per-volume counts (the only host synchronisation) and exactly max(counts) rows. With
+    max_components: no synchronisation at all; the call can sit inside a captured graph."""
+    labels, counts, ws = ops.components_label(density, level)
+    kmax = int(counts.max()) if max_components is None else int(max_components)          # the one synchronisation
+    sizes, bbox, coord_sum, status = ops.components_stats(density, ws, kmax)
+    D, H, W = (int(s) for s in density.shape[2:])
+    mean = coord_sum.to(torch.float64) / sizes.to(torch.float64)[..., None]
+    # per axis with Python scalars: they travel as kernel arguments, so nothing is copied from the host (a tensor built from a list would be)
+    world = torch.stack([(mean[..., a] - 0.5 * (N - 1)) * (float(volume_size) / N) for a, N in enumerate((W, H, D))], dim=-1)
+    centroid = torch.where(sizes[..., None] > 0, world, torch.zeros_like(world))
+    return Components(labels, counts, sizes, bbox, centroid, status)
+
+
+def keep_components(density, level=0.5, keep="largest", min_voxels=1, min_fraction=0.0):
+    """density [n,1,D,H,W] with its floaters removed: the inside voxels (d > level) of dropped components become +0.0, every other voxel keeps
+    its bits. A component passes when it has at least min_voxels voxels and at least ceil(min_fraction * L) of them, L the size of its volume's
+    largest component; keep="all" keeps every passing component, keep="largest" only the largest passing one (ties: the lowest label, i.e. the
+    component that comes first in linear voxel order). A volume without inside voxels is copied. Never synchronises; graph-capturable.
+    extract_mesh of the result at any level >= `level` is an ordered sub-mesh of extract_mesh of the input: same vertices, same faces, fewer."""
+    if keep not in ("largest", "all"):
+        raise ValueError("keep_components: keep=%r must be 'largest' or 'all'" % (keep,))
+    _, _, ws = ops.components_label(density, level, want_labels=False)
+    return ops.components_select(density, ws, keep_largest=keep == "largest", min_voxels=min_voxels, min_fraction=min_fraction)
+
+
+def _clean(fn, density, level, components):
+    """The `components` argument of extract_mesh / colored_mesh: "largest" or a dict of keep_components arguments -> the cleaned density."""
+    if isinstance(components, str):
+        components = {"keep": components}
+    if not isinstance(components, dict):
+        raise TypeError("%s: components must be None, 'largest' / 'all' or a dict of keep_components arguments, got %r" % (fn, components))
+    kw = dict(components)
+    label_level = float(kw.pop("level", level))
+    if not label_level <= float(level):
+        raise ValueError("%s: components are labelled at level %g above the extraction level %g: the cleaned mesh would not be a sub-mesh of "
+                         "the original (label at or below the extraction level)" % (fn, label_level, float(level)))
+    return keep_components(density, level=label_level, **kw)
+
+
+def extract_mesh(density, level=0.5, volume_size=1.0, features=None, max_vertices=None, max_faces=None, components=None):
     """Iso-surface `density = level` of density [n,1,D,H,W] (float32, on the device) as triangle meshes; features [n,C,D,H,W] (channels-last,
     C % 4 == 0), when given, are interpolated onto the vertices. volume_size is config.render.volume_size. level must be finite and > 0.
+    components: None (the volume as it is), "largest" or a dict of keep_components arguments (keep, min_voxels, min_fraction, level): the volume
+    is first cleaned of its floaters, labelled at components["level"] (default: `level`; it must not exceed `level`), which never synchronises.
 
     Without capacities: one read-back of the per-volume counts (the only host synchronisation), exact allocation, a list of n Mesh (an empty
     surface gives empty tensors). With max_vertices and max_faces: no synchronisation at all - a MeshBatch of padded tensors with device counts
     and status, which can sit inside a captured graph. The order of vertices and triangles is specified (include/forge_hip.h) and reproducible."""
     if (max_vertices is None) != (max_faces is None):
         raise ValueError("extract_mesh: give both max_vertices and max_faces, or neither")
+    if components is not None:
+        density = _clean("extract_mesh", density, level, components)
     counts, ws = ops.mesh_count(density, level)
     n = density.shape[0]
     if max_vertices is not None:
@@ -460,17 +523,22 @@ def bake_vertex_colors(meshes, density, images, cameras, view2vol=None, volume_s
 
 
 @torch.no_grad()
-def colored_mesh(model, features_fused, K_cv2, camera_z, photos=None, photo_cameras=None, level=0.5, n_views=28, render_gain=0.05, **knobs):
+def colored_mesh(model, features_fused, K_cv2, camera_z, photos=None, photo_cameras=None, level=0.5, n_views=28, render_gain=0.05, components=None,
+                 **knobs):
     """From a fused volume to coloured meshes: features_fused [b,128,d,d,d] (encoder_3d.fuse) -> both heads -> extract_mesh(density, level) ->
     nvs.render_360 (n_views rendered views per scene) -> ONE bake over the photographs (gain 1) followed by the rendered views (gain render_gain),
     so a region no photograph sees takes the model's own rendering. photos [b,t,3,Hi,Wi] with photo_cameras, the {'R','T','K'} dict of their b t
     (refined) cameras, scene-major, K_cv2-style intrinsics in pixels of the photographs - exactly what `model.render` would be given; K_cv2 [3,3]
     the intrinsics of the rendered views (config.dataset.img_size). The 360-degree path hands PyTorch3D-convention (R, T) to the renderer as if
     they were OpenCV extrinsics (nvs.py); the bake is given the same (R, T) and inverts the same mapping, so the quirk cancels.
+    components (None, "largest" or a dict, as extract_mesh takes it): the density is cleaned of its floaters once, and the cleaned volume is what
+    is extracted, rendered and used for the bake's transmittance - removed floaters neither occlude nor get painted into the rendered views.
     Returns what bake_vertex_colors returns for a list: (meshes, [(weight, best) per mesh])."""
     from . import nvs
     features_mv, densities_mv = model.encoder_3d.heads(features_fused)
     densities_mv = densities_mv.contiguous()
+    if components is not None:
+        densities_mv = _clean("colored_mesh", densities_mv, level, components)
     volume_size = model.render.volume_physical_size
     b, dev = densities_mv.shape[0], densities_mv.device
     meshes = extract_mesh(densities_mv, level=level, volume_size=volume_size)

@@ -1118,3 +1118,106 @@ def geom_metrics(d2_ab, idx_ab, d2_ba, idx_ba, normals_a=None, normals_b=None, a
                                              tau, len(thresholds), _lib.ptr(partial), _lib.ptr(out), _lib.ptr(status), _lib.current_stream()),
                "forge_geom_metrics")
     return out, status
+
+
+# ---------------------------------------------------------------------------------------------------------------- connected components
+COMPONENTS_OVERFLOW = 1                                            # status bit of forge_components_stats (FORGE_COMPONENTS_OVERFLOW)
+
+
+def components_tile():
+    """T, the edge of the cubic tile one workgroup of forge_components_label unions in LDS (host only, no device is touched)."""
+    return int(_lib.lib().forge_components_tile())
+
+
+def _components_inputs(fn, density, level=None):
+    """Shape, dtype, layout and level first, the device last (the caller's _require_cuda): a wrong argument is named as what it is on any device."""
+    if not torch.is_tensor(density):
+        raise TypeError("%s: density must be a tensor" % fn)
+    if density.dim() != 5 or density.shape[1] != 1:
+        raise ValueError("%s: density must be [n,1,D,H,W] (encoder_3d.get_density3D), got %s" % (fn, tuple(density.shape)))
+    if density.dtype != torch.float32:
+        raise TypeError("%s: float32 density (got %s)" % (fn, density.dtype))
+    if not density.is_contiguous():
+        raise ValueError("%s: density must be contiguous (strides %s)" % (fn, density.stride()))
+    n, _, D, H, W = (int(s) for s in density.shape)
+    if n < 1:
+        raise ValueError("%s: empty batch" % fn)
+    if level is not None:
+        level = float(level)
+        if not (level > 0.0 and math.isfinite(level)):
+            raise ValueError("%s: level=%r must be finite and > 0" % (fn, level))
+    return n, D, H, W, level
+
+
+def _components_ws_bytes(n, D, H, W):
+    b = int(_lib.lib().forge_components_workspace_bytes(n, D, H, W))
+    if b < 0:
+        _lib.check(b, "forge_components_workspace_bytes")
+    return b
+
+
+def _components_workspace(fn, workspace, density, nbytes):
+    if not torch.is_tensor(workspace):
+        raise TypeError("%s: workspace must be a tensor" % fn)
+    if workspace.dtype != torch.uint8 or workspace.numel() < nbytes or not workspace.is_contiguous() or workspace.device != density.device:
+        raise ValueError("%s: workspace is not the one components_label returned for this shape" % fn)
+
+
+@_lib.on_tensor_device
+def components_label(density, level=0.5, want_labels=True):
+    """forge_components_label (include/forge_hip.h section g4): the connected components of `density > level` under the Kuhn adjacency. Returns
+    (labels [n,D,H,W] int32 or None, counts [n] int32 on the device, workspace): the workspace (uint8) goes to components_stats and
+    components_select together with the same density. Nothing is read back."""
+    n, D, H, W, level = _components_inputs("components_label", density, level)
+    _require_cuda(density)
+    nbytes = _components_ws_bytes(n, D, H, W)
+    dev = density.device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    labels = torch.empty(n, D, H, W, dtype=torch.int32, device=dev) if want_labels else None
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().forge_components_label(_lib.ptr(density.detach()), n, D, H, W, level, _lib.ptr(ws), nbytes, _lib.ptr(labels), _lib.ptr(counts),
+                                                 _lib.current_stream()), "forge_components_label")
+    return labels, counts, ws
+
+
+@_lib.on_tensor_device
+def components_stats(density, workspace, max_components):
+    """forge_components_stats after components_label(density, ...): per component, in label order, with max_components rows per volume:
+    (sizes [n,Kmax] int32, bbox [n,Kmax,6] int32 = x0, y0, z0, x1, y1, z1 inclusive, coord_sum [n,Kmax,3] int64, status [n] int32 with
+    COMPONENTS_OVERFLOW where a volume has more components than rows). Rows past a volume's count are zero. Nothing is read back."""
+    n, D, H, W, _ = _components_inputs("components_stats", density)
+    kmax = int(max_components)
+    if kmax < 0:
+        raise ValueError("components_stats: max_components=%d must not be negative" % kmax)
+    nbytes = _components_ws_bytes(n, D, H, W)
+    _components_workspace("components_stats", workspace, density, nbytes)
+    _require_cuda(density, workspace)
+    dev = density.device
+    sizes = torch.empty(n, kmax, dtype=torch.int32, device=dev)
+    bbox = torch.empty(n, kmax, 6, dtype=torch.int32, device=dev)
+    coord_sum = torch.empty(n, kmax, 3, dtype=torch.int64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    nz = kmax > 0
+    _lib.check(_lib.lib().forge_components_stats(_lib.ptr(workspace), nbytes, n, D, H, W, kmax, _lib.ptr(sizes if nz else None), _lib.ptr(bbox if nz else None),
+                                                 _lib.ptr(coord_sum if nz else None), _lib.ptr(status), _lib.current_stream()), "forge_components_stats")
+    return sizes, bbox, coord_sum, status
+
+
+@_lib.on_tensor_device
+def components_select(density, workspace, keep_largest=True, min_voxels=1, min_fraction=0.0):
+    """forge_components_select after components_label(density, ...): the density with the inside voxels of removed components set to +0.0 and every
+    other voxel's bits copied. A component passes with size >= min_voxels and size >= ceil(min_fraction * largest size of its volume);
+    keep_largest keeps only the largest passing one (ties: the lowest label). Nothing is read back."""
+    n, D, H, W, _ = _components_inputs("components_select", density)
+    min_voxels, min_fraction = int(min_voxels), float(min_fraction)
+    if min_voxels < 1:
+        raise ValueError("components_select: min_voxels=%d must be at least 1" % min_voxels)
+    if not 0.0 <= min_fraction <= 1.0:
+        raise ValueError("components_select: min_fraction=%r must lie in [0, 1]" % min_fraction)
+    nbytes = _components_ws_bytes(n, D, H, W)
+    _components_workspace("components_select", workspace, density, nbytes)
+    _require_cuda(density, workspace)
+    out = torch.empty_like(density)
+    _lib.check(_lib.lib().forge_components_select(_lib.ptr(density.detach()), n, D, H, W, _lib.ptr(workspace), nbytes, 1 if keep_largest else 0, min_voxels,
+                                                  min_fraction, _lib.ptr(out), _lib.current_stream()), "forge_components_select")
+    return out

@@ -891,6 +891,58 @@ int forge_geom_metrics(const float* d2_ab, const int* idx_ab, const float* d2_ba
                        int* status, forge_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * g4  Connected components of density volumes, and dropping the floaters (csrc/components.hip): which voxels belong to the object. A few-view
+ * reconstruction emits the object plus small detached blobs; every stage of g1 - g3 pays for them. The reference has no counterpart.
+ *   density  [n][D][H][W] float32, as in g1;  level finite and > 0; a voxel is INSIDE iff d > level (strict, an fp32 compare - the one g1 makes):
+ *            NaN is outside, +inf is inside.
+ *   adjacency  two inside voxels are neighbours iff their index difference (dx, dy, dz) is non-zero and has all three components in {0, +1} or all
+ *            three in {0, -1}: 14 neighbours - the 6 axis neighbours, the three same-sign face diagonals, the same-sign body diagonal and their
+ *            negatives; (+1, -1, 0) is NOT a neighbour. These are exactly the lattice edges g1 marches over (offset codes 1..7 of its case table).
+ *            Nothing is adjacent across the volume border, across rows, or across the volumes of a batch.
+ *   Why this adjacency: a component is then exactly one solid region of the surface of g1. Set the inside voxels of some components to zero and
+ *   leave every other voxel as it is: no lattice edge joins a kept inside voxel to a removed one, so the mesh g1 extracts at any level >= this
+ *   level is an ordered sub-mesh of the original - the same vertices bit for bit in the same relative order, the original faces filtered and
+ *   re-indexed in the same order. (Normals may differ within two voxels of a removed voxel: the gradient stencil reads it.)
+ *   labels   [n][D][H][W] int32: 0 outside, 1 .. K_v inside; the components of a volume are numbered by their LOWEST linear index
+ *            (z H + y) W + x, ascending. Labels need no capacity.
+ *   counts   [n] int32 = K_v
+ *   statistics, integers, in label order, rows of capacity max_components (Kmax) per volume; rows at or past K_v are zero:
+ *            sizes [n][Kmax] int32 voxel counts;  bbox [n][Kmax][6] int32 = x0, y0, z0, x1, y1, z1 inclusive;
+ *            coord_sum [n][Kmax][3] int64 = the sums of the x, y, z indices (centroid = coord_sum / size, exact in the caller's float64);
+ *            status [n] int32 = FORGE_COMPONENTS_OVERFLOW where K_v > Kmax: the rows are then the first Kmax components.
+ *   selection  out [n][1][D][H][W] float32. With L_v the largest size in volume v, a component PASSES iff size >= min_voxels and
+ *            size >= thr_v, thr_v = (int)ceil((double)min_fraction * (double)L_v): float64, L_v converts exactly, ONE rounding in the product,
+ *            ceil exact. keep_largest = 0: every passing component is kept. keep_largest = 1: only one, the passing component of largest size,
+ *            ties to the lowest label (it is the largest component of the volume, kept iff L_v >= min_voxels). out = the density's bits for
+ *            outside voxels and for inside voxels of kept components (NaN payloads and signed zeros survive), +0.0f for inside voxels of removed
+ *            components. A volume without inside voxels is copied. Selection needs no component capacity and no read-back: sizes live at the
+ *            component's root voxel in the workspace.
+ *
+ *   forge_components_tile             host only: T, the edge of the cubic tile one workgroup labels in LDS (tile seams are where tests look).
+ *   forge_components_workspace_bytes  bytes of the workspace (16-byte aligned) shared by the calls below; negative FORGE_E* for bad extents.
+ *   forge_components_label   labels the volumes into the workspace, writes counts and, when labels != NULL, labels. Five launches, six with labels.
+ *   forge_components_stats   after forge_components_label on the same workspace and extents: the statistics. Two launches. max_components = 0
+ *                            writes status only (sizes, bbox, coord_sum may then be null).
+ *   forge_components_select  after forge_components_label on the same workspace, extents and density: writes out. Two launches. out may not
+ *                            alias density.
+ * Union-find with parent[x] <= x, tile-local in LDS, then across tile faces by agent-scope fetch_min; every walk moves to a strictly smaller
+ * index, no kernel waits for another workgroup. Integer atomics only (add, min, max on int32 / int64): every output bit is reproducible.
+ * Nothing allocates, synchronises or reads the environment; every entry takes the stream and may sit in a captured graph.
+ * FORGE_EINVAL: a null pointer (labels excepted), level <= 0 or not finite, an extent or n < 1, a workspace too small or unaligned,
+ * max_components < 0, keep_largest outside {0, 1}, min_voxels < 1, min_fraction outside [0, 1] (NaN included).
+ * FORGE_ESHAPE: D H W >= 2^31 - 1 (indices are 32-bit), n > 65535, n max_components > 2^31 - 1.
+ */
+#define FORGE_COMPONENTS_OVERFLOW 1   /* status bit of forge_components_stats: the volume has more components than max_components */
+int forge_components_tile(void);
+long long forge_components_workspace_bytes(int n, int D, int H, int W);
+int forge_components_label(const float* density, int n, int D, int H, int W, float level, void* workspace, long long workspace_bytes, int* labels,
+                           int* counts, forge_stream_t stream);
+int forge_components_stats(const void* workspace, long long workspace_bytes, int n, int D, int H, int W, int max_components, int* sizes, int* bbox,
+                           long long* coord_sum, int* status, forge_stream_t stream);
+int forge_components_select(const float* density, int n, int D, int H, int W, void* workspace, long long workspace_bytes, int keep_largest,
+                            int min_voxels, double min_fraction, float* out, forge_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * h  Photographs to input tensors (csrc/ingest.hip): the `_load_frame` of dataset/kubric.py:410-445, dataset/gso.py:257-290 and
  * dataset/omniobject3d.py:221-258 and the image loop of demo.py:236-256 - an 8-bit RGB(A) frame of any size put on a background, resized with
  * Pillow's Image.ANTIALIAS (Lanczos, a = 3), its mask resized with Image.NEAREST, divided by 255. On 8-bit images Pillow's resampler is integer
