@@ -21,9 +21,7 @@
 // launch is bound by instruction issue, not by the caches: 3.39 ms on 1024 SIMDs at 2.4 GHz and two cycles per wave64 instruction is about 1700
 // issued instructions per wave and view, and the kernel is about 1000 instructions long with 24 correctly rounded divisions - the set-up per view
 // (projection, facing, interval) and, per marched sample, three divisions and the index arithmetic of the 8 taps.
-#include <cmath>
-
-#include "common.h"
+#include "geom_common.h"
 
 namespace forge {
 
@@ -32,7 +30,7 @@ constexpr int BAKE_GROUP = 8;                             // lanes per vertex
 constexpr int BAKE_ROWS = BAKE_THREADS / BAKE_GROUP;      // vertices per workgroup
 
 struct BakeParams {
-    int n, max_vertices, packed;      // packed 0: volume v owns rows v max_vertices ..; 1: volume v starts at offsets[v][0], max_vertices rows in all
+    int n, max_vertices;              // rows per volume (offsets == nullptr) or in all (packed), see row_span
     int D, H, W;
     float hx, hy, hz;
     int C, Hi, Wi, V;
@@ -116,11 +114,10 @@ __global__ __launch_bounds__(BAKE_THREADS) void mesh_bake_kernel(const float* __
     const int vol = blockIdx.y;
     const int j = threadIdx.x & (BAKE_GROUP - 1);
     const long long local = (long long)blockIdx.x * BAKE_ROWS + (threadIdx.x / BAKE_GROUP);
-    const long long row0 = p.packed ? (long long)offsets[2 * vol] : (long long)vol * p.max_vertices;
-    const long long room = p.packed ? (long long)p.max_vertices - row0 : (long long)p.max_vertices;       // rows this volume may use
-    const long long have = min((long long)counts[2 * vol], max(room, 0ll));
+    const RowSpan span = mesh_spans(offsets, vol, p.max_vertices, 0).v;                                   // the faces' capacity plays no part here
+    const long long have = min((long long)counts[2 * vol], span.room);                                    // a negative offset of either array: none
     if (local >= have) return;                                                                            // the whole group leaves together
-    const long long row = row0 + local;
+    const long long row = span.row0 + local;
 
     const float px = vertices[row * 3], py = vertices[row * 3 + 1], pz = vertices[row * 3 + 2];
     const float nx = normals[row * 3], ny = normals[row * 3 + 1], nz = normals[row * 3 + 2];
@@ -218,8 +215,9 @@ extern "C" int forge_mesh_bake(const float* vertices, const float* normals, cons
                                float offset, int cos_power, float z_near, float w_min, int mode, float fill, float* colors, float* weight, int* best,
                                forge_stream_t stream) {
     using namespace forge;
-    FORGE_REQUIRE(n >= 1 && D >= 1 && H >= 1 && W >= 1 && Hi >= 1 && Wi >= 1, FORGE_EINVAL, "forge_mesh_bake: n=%d D=%d H=%d W=%d Hi=%d Wi=%d must be positive",
-                  n, D, H, W, Hi, Wi);
+    const int rc = volume_dims_ok("forge_mesh_bake", n, D, H, W, 0, 0x7fffffffll);
+    if (rc != 0) return rc;
+    FORGE_REQUIRE(Hi >= 1 && Wi >= 1, FORGE_EINVAL, "forge_mesh_bake: Hi=%d Wi=%d must be positive", Hi, Wi);
     FORGE_REQUIRE(max_vertices >= 0, FORGE_EINVAL, "forge_mesh_bake: max_vertices=%d must not be negative", max_vertices);
     FORGE_REQUIRE(V >= 1 && S >= 1, FORGE_EINVAL, "forge_mesh_bake: V=%d and S=%d must be at least 1", V, S);
     FORGE_REQUIRE(step > 0.f && std::isfinite(step), FORGE_EINVAL, "forge_mesh_bake: step=%g must be finite and > 0", (double)step);
@@ -231,16 +229,14 @@ extern "C" int forge_mesh_bake(const float* vertices, const float* normals, cons
     FORGE_REQUIRE(cos_power >= 1 && cos_power <= 8, FORGE_EINVAL, "forge_mesh_bake: cos_power=%d outside 1 .. 8", cos_power);
     FORGE_REQUIRE(mode == 0 || mode == 1, FORGE_EINVAL, "forge_mesh_bake: mode=%d (0 blend, 1 best view)", mode);
     FORGE_REQUIRE(C >= 1 && C <= 4, FORGE_ESHAPE, "forge_mesh_bake: C=%d image channels outside 1 .. 4", C);
-    FORGE_REQUIRE((long long)D * H * W <= 0x7fffffffll && (long long)Hi * Wi <= 0x7fffffffll, FORGE_ESHAPE,
-                  "forge_mesh_bake: a volume of %d x %d x %d voxels or an image of %d x %d pixels is beyond 32-bit indices", D, H, W, Hi, Wi);
-    FORGE_REQUIRE(n <= 65535, FORGE_ESHAPE, "forge_mesh_bake: n=%d volumes in one call (at most 65535)", n);
+    FORGE_REQUIRE((long long)Hi * Wi <= 0x7fffffffll, FORGE_ESHAPE, "forge_mesh_bake: an image of %d x %d pixels is beyond 32-bit indices", Hi, Wi);
     FORGE_REQUIRE(V <= 0x7fffffff / 16, FORGE_ESHAPE, "forge_mesh_bake: V=%d views beyond 32-bit camera offsets", V);
     FORGE_REQUIRE(offsets != nullptr || (long long)n * max_vertices <= 0x7fffffffll, FORGE_ESHAPE, "forge_mesh_bake: n * max_vertices beyond 2^31 - 1 rows");
     FORGE_REQUIRE(counts && density && images && cam && view2vol, FORGE_EINVAL, "forge_mesh_bake: null pointer");
     if (max_vertices == 0) return 0;                          // zero rows: nothing to launch
     FORGE_REQUIRE(vertices && normals && colors && weight && best, FORGE_EINVAL, "forge_mesh_bake: null pointer (rows) with max_vertices=%d", max_vertices);
     BakeParams p;
-    p.n = n; p.max_vertices = max_vertices; p.packed = offsets != nullptr ? 1 : 0;
+    p.n = n; p.max_vertices = max_vertices;
     p.D = D; p.H = H; p.W = W;
     p.hx = hx; p.hy = hy; p.hz = hz;
     p.C = C; p.Hi = Hi; p.Wi = Wi; p.V = V;

@@ -38,9 +38,8 @@
 // These byte counts size the workspace traffic; they are not a roofline the kernels approach: cc_seam launches a thread per voxel though only
 // tile-face voxels work, the per-wave grouping takes up to 64 passes on dusty fields, and at 64^3 .. 8 x 128^3 the launches are latency-bound.
 #include <climits>
-#include <cmath>
 
-#include "common.h"
+#include "geom_common.h"
 
 namespace forge {
 
@@ -210,30 +209,9 @@ __global__ __launch_bounds__(CC_THREADS) void cc_flatten(const int* __restrict__
 
 // partial[vol][0..nblk) -> its exclusive scan in place; counts[vol] = vols[vol].K = the total
 __global__ __launch_bounds__(CC_SCAN_THREADS) void cc_scan(int* __restrict__ partial, int nblk, int* __restrict__ counts, CcVol* __restrict__ vols) {
-    __shared__ int wsum[CC_SCAN_THREADS / 64];
-    __shared__ int carry_s;
-    const int vol = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int* p = partial + (long long)vol * nblk;
-    int carry = 0;
-    for (int base = 0; base < nblk; base += CC_SCAN_THREADS) {
-        const int i = base + tid;
-        const int own = i < nblk ? p[i] : 0;
-        int v = own;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(v, o, 64);
-            if (lane >= o) v += u;
-        }
-        if (lane == 63) wsum[wave] = v;
-        __syncthreads();
-        int before = carry;
-        for (int w = 0; w < wave; ++w) before += wsum[w];
-        if (i < nblk) p[i] = before + v - own;
-        if (tid == CC_SCAN_THREADS - 1) carry_s = before + v;
-        __syncthreads();
-        carry = carry_s;
-    }
-    if (tid == 0) {
+    const int vol = blockIdx.x;
+    const int carry = block_exclusive_scan_inplace<int, CC_SCAN_THREADS>(partial + (long long)vol * nblk, nblk);
+    if (threadIdx.x == 0) {
         counts[vol] = carry;
         vols[vol].K = carry;
     }
@@ -266,9 +244,8 @@ __global__ __launch_bounds__(CC_THREADS) void cc_rank(const int* __restrict__ ro
     }
     __syncthreads();
     if (is_root) {
-        int before = partial[(long long)vol * g.nblk + blockIdx.x] + before_lane;
-        for (int w = 0; w < wave; ++w) before += wsum[w];
-        rank[base + lin64] = before;                 // the root's own parent slot: the forest is not read again
+        // the root's own parent slot: the forest is not read again
+        rank[base + lin64] = waves_before(wsum, wave, partial[(long long)vol * g.nblk + blockIdx.x] + before_lane);
     }
     if (tid == 0) {
         unsigned long long m = 0ull;
@@ -396,36 +373,21 @@ __global__ __launch_bounds__(CC_THREADS) void cc_select(const unsigned* __restri
     out[at] = keep ? bits : 0u;
 }
 
-static long long cc_align(long long b) { return (b + 255) & ~255ll; }
-
 // workspace of n volumes: parent / rank [n][V] int32 | root [n][V] int32 | size [n][V] int32 | partial [n][nblk] int32 | pmax [n][nblk] uint64 |
 // vols [n] CcVol
 static int cc_grid(int n, int D, int H, int W, CcGrid& g, long long (&off)[7], const char* fn) {
-    FORGE_REQUIRE(n >= 1 && D >= 1 && H >= 1 && W >= 1, FORGE_EINVAL, "%s: n=%d D=%d H=%d W=%d must be positive", fn, n, D, H, W);
-    const long long hw = (long long)H * W;
-    FORGE_REQUIRE(hw < 0x7fffffffll && (long long)D * hw < 0x7fffffffll, FORGE_ESHAPE, "%s: D H W = %d x %d x %d voxels per volume: indices are 32-bit (below 2^31 - 1)",
-                  fn, D, H, W);
-    FORGE_REQUIRE(n <= 65535, FORGE_ESHAPE, "%s: n=%d volumes in one call (at most 65535)", fn, n);
-    const long long V = (long long)D * hw;
+    const int rc = volume_dims_ok(fn, n, D, H, W, 0, 0x7fffffffll - 1);      // voxels: indices are 32-bit, below 2^31 - 1
+    if (rc != 0) return rc;
+    const long long V = (long long)D * H * W;
     g.D = D; g.H = H; g.W = W;
     g.V = (int)V;
     g.nblk = (int)((V + CC_THREADS - 1) / CC_THREADS);
-    g.tw = (W + CC_T - 1) / CC_T;
-    g.th = (H + CC_T - 1) / CC_T;
-    g.ntile = g.tw * g.th * ((D + CC_T - 1) / CC_T);
-    off[0] = 0;
-    off[1] = off[0] + cc_align((long long)n * V * 4);
-    off[2] = off[1] + cc_align((long long)n * V * 4);
-    off[3] = off[2] + cc_align((long long)n * V * 4);
-    off[4] = off[3] + cc_align((long long)n * g.nblk * 4);
-    off[5] = off[4] + cc_align((long long)n * g.nblk * 8);
-    off[6] = off[5] + cc_align((long long)n * (long long)sizeof(CcVol));
-    return 0;
-}
-
-static int cc_workspace(const void* workspace, long long workspace_bytes, const long long (&off)[7], const char* fn) {
-    FORGE_REQUIRE(workspace_bytes >= off[6], FORGE_EINVAL, "%s: workspace of %lld bytes, %lld needed", fn, workspace_bytes, off[6]);
-    FORGE_REQUIRE(((unsigned long long)workspace & 15ull) == 0, FORGE_EINVAL, "%s: workspace must be 16-byte aligned", fn);
+    g.tw = (W - 1) / CC_T + 1;                  // extents are >= 1; W + CC_T - 1 would overflow for W near 2^31
+    g.th = (H - 1) / CC_T + 1;
+    g.ntile = g.tw * g.th * ((D - 1) / CC_T + 1);
+    ws_layout({(long long)n * V * 4, (long long)n * V * 4, (long long)n * V * 4, (long long)n * g.nblk * 4, (long long)n * g.nblk * 8,
+               (long long)n * (long long)sizeof(CcVol)},
+              off);
     return 0;
 }
 
@@ -445,12 +407,12 @@ extern "C" int forge_components_label(const float* density, int n, int D, int H,
                                       int* labels, int* counts, forge_stream_t stream) {
     using namespace forge;
     FORGE_REQUIRE(density && workspace && counts, FORGE_EINVAL, "forge_components_label: null pointer");
-    FORGE_REQUIRE(level > 0.f && std::isfinite(level), FORGE_EINVAL, "forge_components_label: level=%g must be finite and > 0", (double)level);
+    FORGE_REQUIRE(level_ok(level), FORGE_EINVAL, "forge_components_label: level=%g must be finite and > 0", (double)level);
     CcGrid g;
     long long off[7];
     int rc = cc_grid(n, D, H, W, g, off, "forge_components_label");
     if (rc != 0) return rc;
-    rc = cc_workspace(workspace, workspace_bytes, off, "forge_components_label");
+    rc = workspace_ok("forge_components_label", workspace, workspace_bytes, off[6]);
     if (rc != 0) return rc;
     char* ws = (char*)workspace;
     int* parent = (int*)(ws + off[0]);
@@ -489,7 +451,7 @@ extern "C" int forge_components_stats(const void* workspace, long long workspace
     long long off[7];
     int rc = cc_grid(n, D, H, W, g, off, "forge_components_stats");
     if (rc != 0) return rc;
-    rc = cc_workspace(workspace, workspace_bytes, off, "forge_components_stats");
+    rc = workspace_ok("forge_components_stats", workspace, workspace_bytes, off[6]);
     if (rc != 0) return rc;
     FORGE_REQUIRE((long long)n * max_components <= 0x7fffffffll, FORGE_ESHAPE, "forge_components_stats: n * max_components beyond 2^31 - 1 rows");
     FORGE_REQUIRE(((unsigned long long)coord_sum & 7ull) == 0, FORGE_EINVAL, "forge_components_stats: coord_sum must be 8-byte aligned");
@@ -521,7 +483,7 @@ extern "C" int forge_components_select(const float* density, int n, int D, int H
     long long off[7];
     int rc = cc_grid(n, D, H, W, g, off, "forge_components_select");
     if (rc != 0) return rc;
-    rc = cc_workspace(workspace, workspace_bytes, off, "forge_components_select");
+    rc = workspace_ok("forge_components_select", workspace, workspace_bytes, off[6]);
     if (rc != 0) return rc;
     char* ws = (char*)workspace;
     const int* root = (const int*)(ws + off[1]);

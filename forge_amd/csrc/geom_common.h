@@ -1,0 +1,142 @@
+// geom_common.h — what mesh.hip, bake.hip, geomdist.hip, components.hip and metrics.hip share, written once (header only: no translation unit).
+//   wave / block primitives   wave_inclusive_scan, wave_sum, waves_before, block_exclusive_scan_inplace (integer scans: any order gives the same bits)
+//   row spans                 row_span, mesh_spans: the rows of a padded or packed mesh array that one volume owns (forge_hip.h sections g1, g2, g3)
+//   fixed-tree reductions     block_reduce256 / block_sum256 / block_max256: float64, ONE tree, so every caller keeps its bits
+//   host side                 ws_align, ws_layout, volume_dims_ok, workspace_ok, level_ok: the argument checks of the workspace entry points
+#pragma once
+#include <cmath>
+
+#include "common.h"
+
+namespace forge {
+
+// ------------------------------------------------------------------------------------------------------------------ wave and block primitives
+// inclusive scan over the lanes of a wave64: the shuffle-up ladder
+template <class T>
+__device__ __forceinline__ T wave_inclusive_scan(T v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T u = __shfl_up(v, o, 64);
+        if (lane >= o) v += u;
+    }
+    return v;
+}
+
+// sum over the lanes of a wave64, valid in lane 0: the shuffle-down ladder
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+
+// start + the totals of the waves before `wave` (wsum[w] = total of wave w, in LDS, complete)
+template <class T>
+__device__ __forceinline__ T waves_before(const T* wsum, int wave, T start) {
+    for (int w = 0; w < wave; ++w) start += wsum[w];
+    return start;
+}
+
+// p[0..n) -> its exclusive scan in place, by one workgroup of THREADS threads: chunks of THREADS elements with a running carry through LDS.
+// Every thread of the workgroup must call it; every thread gets the total.
+template <class T, int THREADS>
+__device__ __forceinline__ T block_exclusive_scan_inplace(T* p, int n) {
+    __shared__ T wsum[THREADS / 64];
+    __shared__ T carry_s;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    T carry = 0;
+    for (int base = 0; base < n; base += THREADS) {
+        const int i = base + tid;
+        const T own = i < n ? p[i] : T(0);
+        const T v = wave_inclusive_scan(own, lane);
+        if (lane == 63) wsum[wave] = v;
+        __syncthreads();
+        const T before = waves_before(wsum, wave, carry);
+        if (i < n) p[i] = before + v - own;
+        if (tid == THREADS - 1) carry_s = before + v;
+        __syncthreads();
+        carry = carry_s;
+    }
+    return carry;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------- row spans
+// The rows of a mesh array (vertices: col 0, faces: col 1) that volume `vol` owns: rows row0 .. row0 + room - 1.
+//   offsets == nullptr (padded): every volume owns max_rows rows, volume v from row v max_rows;
+//   offsets != nullptr (packed): the array has max_rows rows in all and volume v starts at offsets[v][col]; room is what is left from there
+//   (not positive when the volume starts at or past the end). A NEGATIVE offset is never followed: room 0, the volume touches nothing.
+struct RowSpan {
+    long long row0, room;
+};
+
+__device__ __forceinline__ RowSpan row_span(const int* __restrict__ offsets, int vol, int col, long long max_rows) {
+    if (offsets == nullptr) return {(long long)vol * max_rows, max_rows};
+    const long long row0 = offsets[2 * vol + col];
+    return {row0, row0 < 0 ? 0ll : max_rows - row0};
+}
+
+// Both spans of a mesh (vertex rows, face rows). A negative offset of EITHER array empties both: the volume touches no row of any array.
+struct MeshSpans {
+    RowSpan v, f;
+};
+
+__device__ __forceinline__ MeshSpans mesh_spans(const int* __restrict__ offsets, int vol, long long max_vertices, long long max_faces) {
+    MeshSpans s = {row_span(offsets, vol, 0, max_vertices), row_span(offsets, vol, 1, max_faces)};
+    if (s.v.row0 < 0 || s.f.row0 < 0) s.v.room = s.f.room = 0;
+    return s;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ fixed-tree reductions
+// One double per thread of a 256-thread workgroup, combined by the fixed tree red[t] = op(red[t], red[t + s]), s = 128 .. 1; valid in thread 0.
+// A caller that reduces several values through the same `red` back to back puts a __syncthreads() before each (geomdist.hip does).
+template <class Op>
+__device__ __forceinline__ double block_reduce256(double v, double* red, Op op) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] = op(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    return red[0];
+}
+
+__device__ __forceinline__ double block_sum256(double v, double* red) {
+    return block_reduce256(v, red, [](double a, double b) { return a + b; });
+}
+
+__device__ __forceinline__ double block_max256(double v, double* red) {
+    return block_reduce256(v, red, [](double a, double b) { return fmax(a, b); });
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------ host side
+inline long long ws_align(long long b) { return (b + 255) & ~255ll; }
+
+// off[0] = 0, off[k + 1] = off[k] + ws_align(bytes[k]): the sections of a workspace, each 256-byte aligned; off[N] is the size
+template <int N>
+inline void ws_layout(const long long (&bytes)[N], long long (&off)[N + 1]) {
+    off[0] = 0;
+    for (int k = 0; k < N; ++k) off[k + 1] = off[k] + ws_align(bytes[k]);
+}
+
+// what every volume entry point requires: positive extents, at most max_points grid points (D + pad)(H + pad)(W + pad) per volume (the caller's
+// own bound: its indices are 32-bit; max_points <= 2^31, so no product here overflows), at most 65535 volumes (the grid's y extent)
+inline int volume_dims_ok(const char* fn, int n, int D, int H, int W, int pad, long long max_points) {
+    FORGE_REQUIRE(n >= 1 && D >= 1 && H >= 1 && W >= 1, FORGE_EINVAL, "%s: n=%d D=%d H=%d W=%d must be positive", fn, n, D, H, W);
+    const long long hw = ((long long)H + pad) * ((long long)W + pad);
+    FORGE_REQUIRE(hw <= max_points && ((long long)D + pad) * hw <= max_points, FORGE_ESHAPE,
+                  "%s: D H W = %d x %d x %d: per-volume indices are 32-bit (at most %lld grid points of (D+%d)(H+%d)(W+%d))", fn, D, H, W, max_points, pad, pad,
+                  pad);
+    FORGE_REQUIRE(n <= 65535, FORGE_ESHAPE, "%s: n=%d volumes in one call (at most 65535)", fn, n);
+    return 0;
+}
+
+inline int workspace_ok(const char* fn, const void* workspace, long long bytes, long long need) {
+    FORGE_REQUIRE(bytes >= need, FORGE_EINVAL, "%s: workspace of %lld bytes, %lld needed", fn, bytes, need);
+    FORGE_REQUIRE(((unsigned long long)workspace & 15ull) == 0, FORGE_EINVAL, "%s: workspace must be 16-byte aligned", fn);
+    return 0;
+}
+
+// a level the zero shell lies strictly below
+inline bool level_ok(float level) { return level > 0.f && std::isfinite(level); }
+
+}  // namespace forge

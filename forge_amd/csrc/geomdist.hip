@@ -25,9 +25,7 @@
 // 62 % of 1024 SIMDs x 32 lanes x 2.4 GHz; chunked torch.cdist + min takes 47.0 and 396 ms.
 // The difference form (q - p)^2 is deliberate (see g3): |q|^2 + |p|^2 - 2 q.p on the matrix cores cancels to nothing exactly where the metric is
 // used, between two samplings of nearly the same surface.
-#include <cmath>
-
-#include "common.h"
+#include "geom_common.h"
 
 namespace forge {
 
@@ -53,14 +51,11 @@ struct MeshRows {
 
 // rows of mesh v: first vertex / face row and how many of each are valid (a mesh that overflowed its capacity keeps the prefix that fitted)
 __device__ __forceinline__ void mesh_rows(const MeshRows& m, int v, long long& v0, long long& f0, int& nv, int& nf) {
-    const bool packed = m.offsets != nullptr;
-    v0 = packed ? (long long)m.offsets[2 * v] : (long long)v * m.max_vertices;
-    f0 = packed ? (long long)m.offsets[2 * v + 1] : (long long)v * m.max_faces;
-    const long long room_v = packed ? (long long)m.max_vertices - v0 : (long long)m.max_vertices;
-    const long long room_f = packed ? (long long)m.max_faces - f0 : (long long)m.max_faces;
-    nv = (int)max(min((long long)m.counts[2 * v], room_v), 0ll);
-    nf = (int)max(min((long long)m.counts[2 * v + 1], room_f), 0ll);
-    if (v0 < 0 || f0 < 0) nv = nf = 0;             // a negative offset is never followed
+    const MeshSpans s = mesh_spans(m.offsets, v, m.max_vertices, m.max_faces);      // a negative offset of either array: the mesh is never followed
+    v0 = s.v.row0;
+    f0 = s.f.row0;
+    nv = (int)max(min((long long)m.counts[2 * v], s.v.room), 0ll);
+    nf = (int)max(min((long long)m.counts[2 * v + 1], s.f.room), 0ll);
 }
 
 // A_f in float64 from the fp32 corners: 0.5 |cross(b - a, c - a)|; 0 for a face with an index outside 0 .. nv - 1
@@ -265,29 +260,6 @@ struct GeomTau {
     int n;
 };
 
-// fixed-tree reductions of one double per thread of a 256-thread workgroup; the result is valid in thread 0
-__device__ __forceinline__ double geom_block_sum(double v, double* red) {
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
-__device__ __forceinline__ double geom_block_max(double v, double* red) {
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
-    return red[0];
-}
-
 // grid (GEOM_BLOCKS, 2, B): direction 0 scores A -> B (rows of A, normals of B gathered through idx), direction 1 B -> A.
 // partial[((b 2 + dir) GEOM_BLOCKS + block) 8 + ..] = sum d | sum d^2 | max d | count(d < tau_k), k = 0..3 | sum |n_from . n_to[idx]|
 __global__ __launch_bounds__(256) void geom_partial_kernel(const float* __restrict__ d2_ab, const int* __restrict__ idx_ab,
@@ -320,11 +292,14 @@ __global__ __launch_bounds__(256) void geom_partial_kernel(const float* __restri
     }
     __shared__ double red[256];
     double* out = partial + (((long long)b * 2 + dir) * GEOM_BLOCKS + blockIdx.x) * GEOM_PARTIAL;
-    const double r0 = geom_block_sum(sd, red), r1 = geom_block_sum(sd2, red), r2 = geom_block_max(md, red);
+    // `red` is reused back to back: the barrier before each reduction lets every thread finish with the previous one
+    auto sum = [&](double v) { __syncthreads(); return block_sum256(v, red); };
+    auto maxi = [&](double v) { __syncthreads(); return block_max256(v, red); };
+    const double r0 = sum(sd), r1 = sum(sd2), r2 = maxi(md);
     double rc[FORGE_GEOM_MAX_THRESHOLDS];
 #pragma unroll
-    for (int k = 0; k < FORGE_GEOM_MAX_THRESHOLDS; ++k) rc[k] = geom_block_sum(cnt[k], red);
-    const double r7 = geom_block_sum(sn, red);
+    for (int k = 0; k < FORGE_GEOM_MAX_THRESHOLDS; ++k) rc[k] = sum(cnt[k]);
+    const double r7 = sum(sn);
     if (threadIdx.x == 0) {
         out[0] = r0;
         out[1] = r1;
@@ -400,8 +375,8 @@ extern "C" int forge_surface_sample(const float* vertices, const int* faces, con
     FORGE_REQUIRE((vertices || max_vertices == 0) && (faces || max_faces == 0), FORGE_EINVAL,
                   "forge_surface_sample: null pointer (rows) with capacities (%d, %d)", max_vertices, max_faces);
     const long long need = forge_surface_sample_workspace_bytes(n_mesh, max_faces, offsets != nullptr);
-    FORGE_REQUIRE(workspace_bytes >= need && ((unsigned long long)workspace & 15ull) == 0, FORGE_EINVAL,
-                  "forge_surface_sample: workspace of %lld bytes at %p; %lld bytes, 16-byte aligned, are needed", workspace_bytes, workspace, need);
+    const int rc = workspace_ok("forge_surface_sample", workspace, workspace_bytes, need);
+    if (rc != 0) return rc;
     MeshRows m;
     m.vertices = vertices; m.faces = faces; m.counts = counts; m.offsets = offsets;
     m.max_vertices = max_vertices; m.max_faces = max_faces;

@@ -14,9 +14,7 @@
 // Traffic at 129^3 cells: classify reads the density once (the 8 corner loads of neighbouring threads hit L1 / L2) and writes the 4-byte record
 // of each cell (it shares an 8-byte slot with the vertex offset); apply reads the record and writes the two offsets of the cells that emit;
 // vertex emission reads the slot, face emission the record, and after that only the surface's neighbourhood.
-#include <cmath>
-
-#include "common.h"
+#include "geom_common.h"
 
 namespace forge {
 
@@ -98,22 +96,6 @@ __device__ __forceinline__ float mesh_field(const float* __restrict__ d, const M
     return in ? d[((long long)z * g.H + y) * g.W + x] : 0.f;
 }
 
-// sum over the workgroup of a value < 2^16 per thread pair (vertices low half, triangles high half): wave64 shuffles, then LDS
-__device__ __forceinline__ unsigned mesh_wave_sum(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ unsigned mesh_wave_inclusive(unsigned v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned u = __shfl_up(v, o, 64);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(MESH_THREADS) void mesh_classify(const float* __restrict__ density, float level, MeshGrid g, uint2* __restrict__ cell,
                                                               unsigned long long* __restrict__ partial) {
     __shared__ unsigned wsum[MESH_THREADS / 64];
@@ -143,7 +125,7 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_classify(const float* __res
         cell[(long long)vol * g.cells + lin].x = mask | ntri << 8 | inside << 16;
         packed = (unsigned)__popc(mask) | ntri << 16;
     }
-    const unsigned s = mesh_wave_sum(packed);
+    const unsigned s = wave_sum(packed);            // < 2^16 per thread and half (vertices low, triangles high): no carry between the halves
     if ((tid & 63) == 0) wsum[tid >> 6] = s;
     __syncthreads();
     if (tid == 0) {
@@ -156,30 +138,9 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_classify(const float* __res
 
 // partial[vol][0..nblk) (vertices low word, triangles high word) -> its exclusive scan in place; counts[vol] = the totals
 __global__ __launch_bounds__(MESH_SCAN_THREADS) void mesh_scan(unsigned long long* __restrict__ partial, int nblk, int* __restrict__ counts) {
-    __shared__ unsigned long long wsum[MESH_SCAN_THREADS / 64];
-    __shared__ unsigned long long carry_s;
-    const int vol = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    unsigned long long* p = partial + (long long)vol * nblk;
-    unsigned long long carry = 0;
-    for (int base = 0; base < nblk; base += MESH_SCAN_THREADS) {
-        const int i = base + tid;
-        const unsigned long long own = i < nblk ? p[i] : 0ull;
-        unsigned long long v = own;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long u = __shfl_up(v, o, 64);
-            if (lane >= o) v += u;
-        }
-        if (lane == 63) wsum[wave] = v;
-        __syncthreads();
-        unsigned long long before = carry;
-        for (int w = 0; w < wave; ++w) before += wsum[w];
-        if (i < nblk) p[i] = before + v - own;
-        if (tid == MESH_SCAN_THREADS - 1) carry_s = before + v;
-        __syncthreads();
-        carry = carry_s;
-    }
-    if (tid == 0) {
+    const int vol = blockIdx.x;
+    const unsigned long long carry = block_exclusive_scan_inplace<unsigned long long, MESH_SCAN_THREADS>(partial + (long long)vol * nblk, nblk);
+    if (threadIdx.x == 0) {
         counts[2 * vol] = (int)(unsigned)(carry & 0xffffffffull);
         counts[2 * vol + 1] = (int)(unsigned)(carry >> 32);
     }
@@ -196,11 +157,10 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_apply(uint2* __restrict__ c
         const unsigned rec = cell[at].x;
         own = (unsigned)__popc(mesh_rec_mask(rec)) | mesh_rec_ntri(rec) << 16;
     }
-    const unsigned inc = mesh_wave_inclusive(own, lane);
+    const unsigned inc = wave_inclusive_scan(own, lane);
     if (lane == 63) wsum[wave] = inc;
     __syncthreads();
-    unsigned before = 0;
-    for (int w = 0; w < wave; ++w) before += wsum[w];
+    const unsigned before = waves_before(wsum, wave, 0u);
     if (lin < g.cells && own != 0u) {            // offsets of cells that emit nothing are never read
         const unsigned long long po = partial[(long long)vol * g.nblk + blockIdx.x];
         const unsigned ex = before + inc - own;
@@ -213,8 +173,7 @@ struct MeshEmit {
     float level;
     float ex, ey, ez;                // world half extents e = 0.5 (N - 1) volume_size / N of W, H, D
     float dx, dy, dz;                // max(N - 1, 1) of W, H, D
-    int max_vertices, max_faces;     // rows of the output arrays available to ...
-    int packed;                      // ... 0: each volume (volume v starts at row v * max); 1: all volumes together (volume v starts at offsets[v])
+    int max_vertices, max_faces;     // rows of the output arrays: per volume (offsets == nullptr) or in all (packed), see row_span
     int C;
 };
 
@@ -238,13 +197,10 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_vertices(const float* __res
                                                               float* __restrict__ normals, float* __restrict__ vfeat, int* __restrict__ status) {
     const int vol = blockIdx.y;
     const int lin = blockIdx.x * MESH_THREADS + threadIdx.x;
-    const long long row0 = p.packed ? (long long)offsets[2 * vol] : (long long)vol * p.max_vertices;
-    const long long rows = p.packed ? (long long)p.max_vertices : row0 + p.max_vertices;       // first row this volume may not write
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const long long f0 = p.packed ? (long long)offsets[2 * vol + 1] : (long long)vol * p.max_faces;
-        const long long fend = p.packed ? (long long)p.max_faces : f0 + p.max_faces;
-        status[vol] = (row0 + counts[2 * vol] > rows || f0 + counts[2 * vol + 1] > fend) ? FORGE_MESH_OVERFLOW : 0;
-    }
+    const MeshSpans spans = mesh_spans(offsets, vol, p.max_vertices, p.max_faces);
+    const RowSpan span = spans.v;
+    const long long rows = span.row0 + span.room;                                              // first row this volume may not write
+    if (blockIdx.x == 0 && threadIdx.x == 0) status[vol] = (counts[2 * vol] > span.room || counts[2 * vol + 1] > spans.f.room) ? FORGE_MESH_OVERFLOW : 0;
     if (lin >= g.cells) return;
     const uint2 rc = cell[(long long)vol * g.cells + lin];
     const unsigned mask = mesh_rec_mask(rc.x);
@@ -256,7 +212,7 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_vertices(const float* __res
     const float d0 = mesh_field(d, g, z0, y0, x0);
     float g0[3];
     mesh_gradient(d, g, z0, y0, x0, g0);
-    long long row = row0 + rc.y;
+    long long row = span.row0 + rc.y;
     for (int k = 0; k < 7; ++k) {
         if (!((mask >> k) & 1u)) continue;
         if (row >= rows) return;                               // capacity reached: rows ascend with k
@@ -309,9 +265,9 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_faces(const uint2* __restri
     const unsigned rec = cv[lin].x;
     if (mesh_rec_ntri(rec) == 0u) return;
     const unsigned inside = mesh_rec_inside(rec);
-    const long long row0 = p.packed ? (long long)offsets[2 * vol + 1] : (long long)vol * p.max_faces;
-    const long long rows = p.packed ? (long long)p.max_faces : row0 + p.max_faces;
-    long long row = row0 + toff[(long long)vol * g.cells + lin];
+    const RowSpan span = mesh_spans(offsets, vol, p.max_vertices, p.max_faces).f;
+    const long long rows = span.row0 + span.room;
+    long long row = span.row0 + toff[(long long)vol * g.cells + lin];
     for (int q = 0; q < 6; ++q) {
         const unsigned tc = MESH_TET_DEV[q];
         const unsigned m = ((inside >> (tc & 7u)) & 1u) | ((inside >> ((tc >> 8) & 7u)) & 1u) << 1 | ((inside >> ((tc >> 16) & 7u)) & 1u) << 2 |
@@ -341,26 +297,17 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_faces(const uint2* __restri
     }
 }
 
-static long long mesh_align(long long b) { return (b + 255) & ~255ll; }
-
 // workspace of n volumes: cell records [n][cells] uint2 | triangle offsets [n][cells] uint32 | partials [n][nblk] uint64
 static int mesh_grid(int n, int D, int H, int W, MeshGrid& g, long long (&off)[4], const char* fn) {
-    FORGE_REQUIRE(n >= 1 && D >= 1 && H >= 1 && W >= 1, FORGE_EINVAL, "%s: n=%d D=%d H=%d W=%d must be positive", fn, n, D, H, W);
+    const int rc = volume_dims_ok(fn, n, D, H, W, 1, MESH_MAX_CELLS);       // cells, 12 triangles each: vertex and triangle offsets are 32-bit
+    if (rc != 0) return rc;
     const long long cells = ((long long)D + 1) * ((long long)H + 1) * ((long long)W + 1);
-    FORGE_REQUIRE(cells <= MESH_MAX_CELLS, FORGE_ESHAPE, "%s: %lld cells per volume: vertex and triangle offsets are 32-bit (at most %lld cells)", fn, cells,
-                  MESH_MAX_CELLS);
-    FORGE_REQUIRE(n <= 65535, FORGE_ESHAPE, "%s: n=%d volumes in one call (at most 65535)", fn, n);
     g.D = D; g.H = H; g.W = W; g.Hc = H + 1; g.Wc = W + 1;
     g.cells = (int)cells;
     g.nblk = (int)((cells + MESH_THREADS - 1) / MESH_THREADS);
-    off[0] = 0;
-    off[1] = off[0] + mesh_align((long long)n * cells * 8);
-    off[2] = off[1] + mesh_align((long long)n * cells * 4);
-    off[3] = off[2] + mesh_align((long long)n * g.nblk * 8);
+    ws_layout({(long long)n * cells * 8, (long long)n * cells * 4, (long long)n * g.nblk * 8}, off);
     return 0;
 }
-
-static bool mesh_level_ok(float level) { return level > 0.f && std::isfinite(level); }
 
 }  // namespace forge
 
@@ -393,13 +340,12 @@ extern "C" int forge_mesh_count(const float* density, int n, int D, int H, int W
                                 forge_stream_t stream) {
     using namespace forge;
     FORGE_REQUIRE(density && workspace && counts, FORGE_EINVAL, "forge_mesh_count: null pointer");
-    FORGE_REQUIRE(mesh_level_ok(level), FORGE_EINVAL, "forge_mesh_count: level=%g must be finite and > 0 (the virtual shell is zero)", (double)level);
+    FORGE_REQUIRE(level_ok(level), FORGE_EINVAL, "forge_mesh_count: level=%g must be finite and > 0 (the virtual shell is zero)", (double)level);
     MeshGrid g;
     long long off[4];
-    const int rc = mesh_grid(n, D, H, W, g, off, "forge_mesh_count");
+    int rc = mesh_grid(n, D, H, W, g, off, "forge_mesh_count");
+    if (rc == 0) rc = workspace_ok("forge_mesh_count", workspace, workspace_bytes, off[3]);
     if (rc != 0) return rc;
-    FORGE_REQUIRE(workspace_bytes >= off[3], FORGE_EINVAL, "forge_mesh_count: workspace of %lld bytes, %lld needed", workspace_bytes, off[3]);
-    FORGE_REQUIRE(((unsigned long long)workspace & 15ull) == 0, FORGE_EINVAL, "forge_mesh_count: workspace must be 16-byte aligned");
     char* ws = (char*)workspace;
     uint2* cell = (uint2*)(ws + off[0]);
     unsigned* toff = (unsigned*)(ws + off[1]);
@@ -423,7 +369,7 @@ extern "C" int forge_mesh_emit(const float* density, const float* features, int 
                   max_faces);
     FORGE_REQUIRE((vertices && normals) || max_vertices == 0, FORGE_EINVAL, "forge_mesh_emit: null vertices / normals with max_vertices=%d", max_vertices);
     FORGE_REQUIRE(faces || max_faces == 0, FORGE_EINVAL, "forge_mesh_emit: null faces with max_faces=%d", max_faces);
-    FORGE_REQUIRE(mesh_level_ok(level), FORGE_EINVAL, "forge_mesh_emit: level=%g must be finite and > 0 (the virtual shell is zero)", (double)level);
+    FORGE_REQUIRE(level_ok(level), FORGE_EINVAL, "forge_mesh_emit: level=%g must be finite and > 0 (the virtual shell is zero)", (double)level);
     FORGE_REQUIRE(volume_size > 0.f && std::isfinite(volume_size), FORGE_EINVAL, "forge_mesh_emit: volume_size=%g must be finite and > 0", (double)volume_size);
     if (features != nullptr) {
         FORGE_REQUIRE(C >= 4 && C % 4 == 0, FORGE_ESHAPE, "forge_mesh_emit: C=%d must be a positive multiple of 4 (float4 rows)", C);
@@ -433,9 +379,9 @@ extern "C" int forge_mesh_emit(const float* density, const float* features, int 
     }
     MeshGrid g;
     long long off[4];
-    const int rc = mesh_grid(n, D, H, W, g, off, "forge_mesh_emit");
+    int rc = mesh_grid(n, D, H, W, g, off, "forge_mesh_emit");
+    if (rc == 0) rc = workspace_ok("forge_mesh_emit", workspace, workspace_bytes, off[3]);
     if (rc != 0) return rc;
-    FORGE_REQUIRE(workspace_bytes >= off[3], FORGE_EINVAL, "forge_mesh_emit: workspace of %lld bytes, %lld needed", workspace_bytes, off[3]);
     FORGE_REQUIRE(offsets != nullptr || ((long long)n * max_vertices <= 0x7fffffffll && (long long)n * max_faces <= 0x7fffffffll), FORGE_ESHAPE,
                   "forge_mesh_emit: n * max_vertices or n * max_faces beyond 2^31 - 1 rows");
     const char* ws = (const char*)workspace;
@@ -453,7 +399,6 @@ extern "C" int forge_mesh_emit(const float* density, const float* features, int 
     p.dx = den[0]; p.dy = den[1]; p.dz = den[2];
     p.max_vertices = max_vertices;
     p.max_faces = max_faces;
-    p.packed = offsets != nullptr ? 1 : 0;
     p.C = features != nullptr ? C : 0;
     const dim3 grid(g.nblk, n);
     if (features != nullptr)

@@ -2,9 +2,7 @@
 // (skimage's peak_signal_noise_ratio / structural_similarity as the reference calls them) and the per-tap distance of LPIPS-VGG (lpips 0.1).
 // LPIPS's VGG-16 trunk runs on the convolution entries (forge_amd/perceptual.py); these kernels are the rest.
 // Deterministic: no atomics; every reduction is a fixed LDS tree per workgroup into a slab, summed in a fixed order by a finalize launch.
-#include <cmath>
-
-#include "common.h"
+#include "geom_common.h"
 
 namespace forge {
 
@@ -17,17 +15,6 @@ struct ImgSrc {
     const float* p;
     long long sn, sc, sh, sw;            // element strides of the [N][C][H][W] view
 };
-
-// fixed-tree sum of one double per thread of a 256-thread workgroup; the result is valid in thread 0
-__device__ __forceinline__ double block_sum256(double v, double* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    return red[0];
-}
 
 // partial[n][blockIdx.x] = sum of (a - b)^2 over the elements of image n that workgroup (blockIdx.x, n) visits; the difference and its square in
 // float64 (exact for float32 inputs up to the square's rounding), as skimage forms them

@@ -365,6 +365,43 @@ def _read_obj(path):
     return va, n, f, c
 
 
+def _exclusive_offsets(counts):
+    """counts [n,2] int32 -> the row each mesh starts at when the meshes are packed one after the other (same device, no synchronisation)."""
+    return (torch.cumsum(counts, dim=0, dtype=torch.int32) - counts).contiguous()
+
+
+def _pack_rows(meshes, fn, fields, cast=False):
+    """A list of Mesh -> the packed rows the kernels take: ([one [rows,3] array per name in fields], counts [n,2], offsets [n,2]) on the meshes'
+    device, and the host list of (vertices, faces) per mesh that counts was built from. cast: rows become float32 (faces: int32) [rows,3]
+    whatever the meshes hold; otherwise they are concatenated as they are and the kernel wrapper judges them."""
+    meshes = list(meshes)
+    if not meshes or not all(isinstance(m, Mesh) for m in meshes):
+        raise TypeError("%s: a MeshBatch or a non-empty list of Mesh" % fn)
+    dev = meshes[0].vertices.device
+    sizes = [(int(m.vertices.shape[0]), int(m.faces.shape[0])) for m in meshes]
+    counts = torch.tensor(sizes, dtype=torch.int32).reshape(len(meshes), 2)
+    packed = []
+    for name in fields:
+        arrays = [getattr(m, name) for m in meshes]
+        if cast:
+            dtype = torch.int32 if name == "faces" else torch.float32
+            arrays = [a.to(dtype).reshape(-1, 3) for a in arrays]
+        packed.append(torch.cat(arrays).contiguous())
+    both = torch.stack([counts, _exclusive_offsets(counts)]).to(dev)      # counts and offsets travel in ONE host-to-device copy
+    return packed, both[0], both[1], sizes
+
+
+def _split_rows(sizes, columns, *arrays):
+    """Packed rows back per mesh. sizes: (vertices, faces) per mesh; array k follows column columns[k] of it (0: vertex rows, 1: face rows).
+    Returns, per mesh, the list of its rows of every array (None stays None)."""
+    out, v0, f0 = [], 0, 0
+    for nv, nf in sizes:
+        lo, hi = (v0, f0), (v0 + nv, f0 + nf)
+        out.append([None if a is None else a[lo[c]:hi[c]] for a, c in zip(arrays, columns)])
+        v0, f0 = hi
+    return out
+
+
 def label_components(density, level=0.5, max_components=None, volume_size=1.0):
     """The connected components of `density > level` of density [n,1,D,H,W] (float32, on the device) under the Kuhn adjacency (include/forge_hip.h
     section g4: the 6 axis neighbours, the same-sign face diagonals and the same-sign body diagonal - the lattice edges extract_mesh marches over),
@@ -435,19 +472,13 @@ def extract_mesh(density, level=0.5, volume_size=1.0, features=None, max_vertice
                None if features is None else torch.zeros(n, mv, C, device=dev))
         v, nr, f, vf, status = ops.mesh_emit(density, ws, counts, mv, mf, level, volume_size, features, out=out)
         return MeshBatch(v, nr, f, vf, counts, status)
-    ends = torch.cumsum(counts, dim=0, dtype=torch.int32)
-    offsets = (ends - counts).contiguous()
+    offsets = _exclusive_offsets(counts)
     host = counts.cpu()                                           # the one synchronisation
     total_v, total_f = (int(x) for x in host.sum(dim=0, dtype=torch.int64))
     if max(total_v, total_f) > 2 ** 31 - 1:
         raise ValueError("extract_mesh: %d vertices and %d triangles in one batch exceed int32 rows; extract fewer volumes per call" % (total_v, total_f))
     v, nr, f, vf, _ = ops.mesh_emit(density, ws, counts, total_v, total_f, level, volume_size, features, offsets=offsets)
-    meshes, v0, f0 = [], 0, 0
-    for nv, nf in host.tolist():
-        meshes.append(Mesh(v[v0:v0 + nv], nr[v0:v0 + nv], f[f0:f0 + nf], None if vf is None else vf[v0:v0 + nv]))
-        v0 += nv
-        f0 += nf
-    return meshes
+    return [Mesh(*rows) for rows in _split_rows(host.tolist(), (0, 0, 1, 0), v, nr, f, vf)]
 
 
 def pack_bake_cameras(cameras, image_hw, img_size=None, device=None):
@@ -509,17 +540,10 @@ def bake_vertex_colors(meshes, density, images, cameras, view2vol=None, volume_s
     meshes = list(meshes)
     if len(meshes) != n:
         raise ValueError("bake_vertex_colors: %d meshes for %d volumes" % (len(meshes), n))
-    sizes = [[int(m.vertices.shape[0]), int(m.faces.shape[0])] for m in meshes]
-    counts = torch.tensor(sizes, dtype=torch.int32).reshape(n, 2)
-    offsets = (torch.cumsum(counts, dim=0, dtype=torch.int32) - counts).to(dev)
-    colors, weight, best = ops.mesh_bake(torch.cat([m.vertices for m in meshes]).contiguous(), torch.cat([m.normals for m in meshes]).contiguous(),
-                                         counts.to(dev), density, images, cam, view2vol, offsets=offsets, **kw)
-    out, extras, v0 = [], [], 0
-    for m, (nv, _) in zip(meshes, sizes):
-        out.append(Mesh(m.vertices, m.normals, m.faces, m.features, colors[v0:v0 + nv]))
-        extras.append((weight[v0:v0 + nv], best[v0:v0 + nv]))
-        v0 += nv
-    return out, extras
+    (vertices, normals), counts, offsets, sizes = _pack_rows(meshes, "bake_vertex_colors", ("vertices", "normals"))
+    baked = ops.mesh_bake(vertices, normals, counts, density, images, cam, view2vol, offsets=offsets, **kw)
+    rows = _split_rows(sizes, (0, 0, 0), *baked)
+    return [Mesh(m.vertices, m.normals, m.faces, m.features, c) for m, (c, _, _) in zip(meshes, rows)], [(w, b) for _, w, b in rows]
 
 
 @torch.no_grad()
@@ -562,19 +586,6 @@ def colored_mesh(model, features_fused, K_cv2, camera_z, photos=None, photo_came
 
 
 # ----------------------------------------------------------------------------------------------------------------- scoring a surface
-def _pack_meshes(meshes):
-    """A list of Mesh -> the packed rows forge_surface_sample takes: (vertices [Nv,3], faces [Nf,3], counts [n,2], offsets [n,2]) on the device."""
-    meshes = list(meshes)
-    if not meshes or not all(isinstance(m, Mesh) for m in meshes):
-        raise TypeError("sample_surface: a MeshBatch or a non-empty list of Mesh")
-    dev = meshes[0].vertices.device
-    counts = torch.tensor([[int(m.vertices.shape[0]), int(m.faces.shape[0])] for m in meshes], dtype=torch.int32).reshape(len(meshes), 2)
-    offsets = torch.cumsum(counts, dim=0, dtype=torch.int32) - counts
-    vertices = torch.cat([m.vertices.to(torch.float32).reshape(-1, 3) for m in meshes]).contiguous()
-    faces = torch.cat([m.faces.to(torch.int32).reshape(-1, 3) for m in meshes]).contiguous()
-    return vertices, faces, counts.to(dev), offsets.to(dev)
-
-
 def sample_surface(meshes, n):
     """n deterministic, area-proportional surface samples per mesh (include/forge_hip.h section g3): systematic sampling over the cumulative
     face areas, barycentrics from the R2 low-discrepancy sequence in integer arithmetic - the same call gives the same bits everywhere.
@@ -585,7 +596,7 @@ def sample_surface(meshes, n):
         return ops.surface_sample(meshes.vertices, meshes.faces, meshes.counts, n)
     if isinstance(meshes, Mesh):
         meshes = [meshes]
-    vertices, faces, counts, offsets = _pack_meshes(meshes)
+    (vertices, faces), counts, offsets, _ = _pack_rows(meshes, "sample_surface", ("vertices", "faces"), cast=True)
     return ops.surface_sample(vertices, faces, counts, n, offsets=offsets)
 
 

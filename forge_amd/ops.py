@@ -834,49 +834,96 @@ def mesh_case_table():
     return _mesh_table
 
 
-def _mesh_inputs(density, features, level):
-    if not torch.is_tensor(density) or (features is not None and not torch.is_tensor(features)):
-        raise TypeError("mesh: density (and features) must be tensors")
-    _require_cuda(density, features)
+def _check_tensors(fn, want, dev=None):
+    """The one tensor-table check of the geometry wrappers. want: (name, tensor or None, shape, dtype). An int in place of a shape asks for a
+    1-D tensor of at least that many elements, which may not be None (a workspace). Without dev, the device of the first tensor is the device
+    of all. Returns that device."""
+    if dev is None:
+        dev = next(t for _, t, _, _ in want if t is not None).device
+    for name, t, shape, dt in want:
+        least = shape if isinstance(shape, int) else None
+        if t is None and least is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a tensor" % (fn, name))
+        if t.dtype != dt:
+            raise TypeError("%s: %s must be %s (got %s)" % (fn, name, dt, t.dtype))
+        if (t.shape != shape if least is None else t.dim() != 1 or t.shape[0] < least) or not t.is_contiguous() or t.device != dev:
+            raise ValueError("%s: %s must be a contiguous %s tensor on %s, got %s with strides %s on %s"
+                             % (fn, name, tuple(shape) if least is None else "1-D, %d elements or more," % least, dev, tuple(t.shape), t.stride(), t.device))
+    return dev
+
+
+def _out_or_empty(fn, out, specs, dev):
+    """The `out=` argument: specs is a list of (shape, dtype) or None (no such output). out None: fresh tensors; else out's tensors, checked."""
+    if out is None:
+        return [None if sp is None else torch.empty(sp[0], dtype=sp[1], device=dev) for sp in specs]
+    for t, sp in zip(out, specs):
+        if sp is not None and (not isinstance(t, torch.Tensor) or t.shape != sp[0] or t.dtype != sp[1] or not t.is_contiguous() or t.device != dev):
+            raise ValueError("%s: every out tensor must be contiguous, here %s of shape %s on %s" % (fn, sp[1], tuple(sp[0]), dev))
+    return [None if sp is None else t for t, sp in zip(out, specs)]
+
+
+def _density_volume(fn, density, level=None):
+    """density is a contiguous float32 [n,1,D,H,W] with n >= 1, level (when given) finite and > 0 -> (n, D, H, W, level). Shape, dtype, layout and
+    level only: the device comes last (the caller's _require_cuda), so a wrong argument is named as what it is on any machine."""
+    if not isinstance(density, torch.Tensor):
+        raise TypeError("%s: density must be a tensor" % fn)
     if density.dim() != 5 or density.shape[1] != 1:
-        raise ValueError("mesh: density must be [n,1,D,H,W] (encoder_3d.get_density3D), got %s" % (tuple(density.shape),))
+        raise ValueError("%s: density must be [n,1,D,H,W] (encoder_3d.get_density3D), got %s" % (fn, tuple(density.shape)))
     if density.dtype != torch.float32:
-        raise TypeError("mesh: float32 density (got %s)" % density.dtype)
+        raise TypeError("%s: float32 density (got %s)" % (fn, density.dtype))
     if not density.is_contiguous():
-        raise ValueError("mesh: density must be contiguous (strides %s)" % (density.stride(),))
-    n, _, D, H, W = (int(s) for s in density.shape)
+        raise ValueError("%s: density must be contiguous (strides %s)" % (fn, density.stride()))
+    n, _, D, H, W = density.shape
     if n < 1:
-        raise ValueError("mesh: empty batch")
-    level = float(level)
-    if not (level > 0.0 and math.isfinite(level)):
-        raise ValueError("mesh: level=%r must be finite and > 0 (the virtual shell around the volume is zero)" % level)
-    C = 0
-    if features is not None:
-        if features.dim() != 5 or features.shape[0] != n or tuple(features.shape[2:]) != (D, H, W) or features.device != density.device:
-            raise ValueError("mesh: features must be [%d,C,%d,%d,%d] on the density's device, got %s" % (n, D, H, W, tuple(features.shape)))
-        if features.dtype != torch.float32:
-            raise TypeError("mesh: float32 features (got %s)" % features.dtype)
-        C = int(features.shape[1])
-        if C < 4 or C % 4:
-            raise ValueError("mesh: C=%d feature channels must be a positive multiple of 4" % C)
-        if not features.permute(0, 2, 3, 4, 1).is_contiguous():
-            raise ValueError("mesh: features must be channels-last (torch.channels_last_3d; ops.to_channels_last_3d), got strides %s" % (features.stride(),))
-    return n, C, D, H, W, level
+        raise ValueError("%s: empty batch" % fn)
+    if level is not None:
+        level = float(level)
+        if not (level > 0.0 and math.isfinite(level)):
+            raise ValueError("%s: level=%r must be finite and > 0 (the virtual shell around the volume is zero)" % (fn, level))
+    return n, D, H, W, level
 
 
-def _mesh_ws_bytes(n, D, H, W):
-    b = int(_lib.lib().forge_mesh_workspace_bytes(n, D, H, W))
+def _size_query(name, *args):
+    """A host-side size query of the library: a negative result is an error code, raised with the library's message."""
+    b = int(getattr(_lib.lib(), name)(*args))
     if b < 0:
-        _lib.check(b, "forge_mesh_workspace_bytes")
+        _lib.check(b, name)
     return b
+
+
+def _row_lead(n, offsets):
+    """Leading dimensions of mesh rows: [n, rows, ...] padded (offsets None), [rows, ...] packed."""
+    return (n,) if offsets is None else ()
+
+
+def _mesh_features(fn, features, density):
+    """features [n,C,D,H,W], channels-last float32 on the density's device, C a positive multiple of 4 -> C (0 without features)."""
+    if features is None:
+        return 0
+    if not torch.is_tensor(features):
+        raise TypeError("%s: features must be a tensor" % fn)
+    n, _, D, H, W = density.shape
+    if features.dim() != 5 or features.shape[0] != n or tuple(features.shape[2:]) != (D, H, W) or features.device != density.device:
+        raise ValueError("%s: features must be [%d,C,%d,%d,%d] on the density's device, got %s" % (fn, n, D, H, W, tuple(features.shape)))
+    if features.dtype != torch.float32:
+        raise TypeError("%s: float32 features (got %s)" % (fn, features.dtype))
+    C = int(features.shape[1])
+    if C < 4 or C % 4:
+        raise ValueError("%s: C=%d feature channels must be a positive multiple of 4" % (fn, C))
+    if not features.permute(0, 2, 3, 4, 1).is_contiguous():
+        raise ValueError("%s: features must be channels-last (torch.channels_last_3d; ops.to_channels_last_3d), got strides %s" % (fn, features.stride()))
+    return C
 
 
 @_lib.on_tensor_device
 def mesh_count(density, level=0.5):
     """forge_mesh_count: classify the cells of density [n,1,D,H,W] and scan. Returns (counts [n,2] int32 on the device: vertices and triangles
     per volume, workspace): the workspace goes to mesh_emit together with the same density and level. Nothing is read back."""
-    n, _, D, H, W, level = _mesh_inputs(density, None, level)
-    nbytes = _mesh_ws_bytes(n, D, H, W)
+    n, D, H, W, level = _density_volume("mesh_count", density, level)
+    _require_cuda(density)
+    nbytes = _size_query("forge_mesh_workspace_bytes", n, D, H, W)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=density.device)
     counts = torch.empty(n, 2, dtype=torch.int32, device=density.device)
     _lib.check(_lib.lib().forge_mesh_count(_lib.ptr(density.detach()), n, D, H, W, level, _lib.ptr(ws), nbytes, _lib.ptr(counts), _lib.current_stream()),
@@ -892,35 +939,20 @@ def mesh_emit(density, workspace, counts, max_vertices, max_faces, level=0.5, vo
     max_faces rows in all: vertices [max_vertices,3], ... Rows that no vertex or triangle lands in are left as they were. status carries
     MESH_OVERFLOW for a volume that did not fit; what fitted is the prefix of the full result. out: (vertices, normals, faces, features or None)
     to write into, instead of fresh tensors. Nothing is read back."""
-    n, C, D, H, W, level = _mesh_inputs(density, features, level)
+    n, D, H, W, level = _density_volume("mesh_emit", density, level)
+    C = _mesh_features("mesh_emit", features, density)
     max_vertices, max_faces = int(max_vertices), int(max_faces)
     if max_vertices < 0 or max_faces < 0:
         raise ValueError("mesh_emit: negative capacity (%d, %d)" % (max_vertices, max_faces))
-    nbytes = _mesh_ws_bytes(n, D, H, W)
-    _require_cuda(workspace, counts, offsets)
-    if workspace.dtype != torch.uint8 or workspace.numel() < nbytes or not workspace.is_contiguous():
-        raise ValueError("mesh_emit: workspace is not the one mesh_count returned for this shape")
-    for name, t in (("counts", counts), ("offsets", offsets)):
-        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (n, 2) or not t.is_contiguous()):
-            raise ValueError("mesh_emit: %s must be a contiguous int32 [%d,2] tensor" % (name, n))
+    nbytes = _size_query("forge_mesh_workspace_bytes", n, D, H, W)
     dev = density.device
-    lead = (n,) if offsets is None else ()
-    shapes = (lead + (max_vertices, 3), lead + (max_vertices, 3), lead + (max_faces, 3), lead + (max_vertices, C))
-    if out is None:
-        vertices = torch.empty(shapes[0], dtype=torch.float32, device=dev)
-        normals = torch.empty(shapes[1], dtype=torch.float32, device=dev)
-        faces = torch.empty(shapes[2], dtype=torch.int32, device=dev)
-        vfeat = torch.empty(shapes[3], dtype=torch.float32, device=dev) if features is not None else None
-    else:
-        vertices, normals, faces, vfeat = out
-        want = [(vertices, shapes[0], torch.float32), (normals, shapes[1], torch.float32), (faces, shapes[2], torch.int32)]
-        if features is not None:
-            want.append((vfeat, shapes[3], torch.float32))
-        else:
-            vfeat = None
-        for t, shape, dt in want:
-            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev:
-                raise ValueError("mesh_emit: every out tensor must be contiguous, here %s of shape %s on %s" % (dt, shape, dev))
+    _check_tensors("mesh_emit", [("workspace", workspace, nbytes, torch.uint8), ("counts", counts, (n, 2), torch.int32),
+                                 ("offsets", offsets, (n, 2), torch.int32)], dev)
+    lead = _row_lead(n, offsets)
+    vrows = (lead + (max_vertices, 3), torch.float32)
+    specs = [vrows, vrows, (lead + (max_faces, 3), torch.int32), None if features is None else (lead + (max_vertices, C), torch.float32)]
+    _require_cuda(density, features, workspace, counts, offsets)
+    vertices, normals, faces, vfeat = _out_or_empty("mesh_emit", out, specs, dev)
     status = torch.empty(n, dtype=torch.int32, device=dev)
     _lib.check(_lib.lib().forge_mesh_emit(_lib.ptr(density.detach()), _lib.ptr(None if features is None else features.detach()), n, C, D, H, W, level,
                                           float(volume_size), _lib.ptr(workspace), nbytes, _lib.ptr(counts), _lib.ptr(offsets), max_vertices, max_faces,
@@ -946,14 +978,9 @@ def mesh_bake(vertices, normals, counts, density, images, cam, view2vol, *, offs
     tensors = (vertices, normals, counts, density, images, cam, view2vol)
     if not all(torch.is_tensor(t) for t in tensors) or not all(t is None or torch.is_tensor(t) for t in (offsets, view_weight, view_gain)):
         raise TypeError("mesh_bake: vertices, normals, counts, density, images, cam, view2vol (and offsets, view_weight, view_gain) must be tensors")
-    _require_cuda(*tensors, offsets, view_weight, view_gain)
+    n, D, H, W, _ = _density_volume("mesh_bake", density)
     dev = density.device
-    if density.dim() != 5 or density.shape[1] != 1:
-        raise ValueError("mesh_bake: density must be [n,1,D,H,W] (encoder_3d.get_density3D), got %s" % (tuple(density.shape),))
-    n, _, D, H, W = (int(s) for s in density.shape)
-    if n < 1:
-        raise ValueError("mesh_bake: empty batch")
-    lead = (n,) if offsets is None else ()
+    lead = _row_lead(n, offsets)
     if vertices.dim() != len(lead) + 2 or tuple(vertices.shape[:len(lead)]) != lead or vertices.shape[-1] != 3 or normals.shape != vertices.shape:
         raise ValueError("mesh_bake: vertices and normals must both be %s, got %s and %s"
                          % ("[%d,max_vertices,3]" % n if offsets is None else "[max_vertices,3] (packed: offsets given)", tuple(vertices.shape), tuple(normals.shape)))
@@ -961,30 +988,17 @@ def mesh_bake(vertices, normals, counts, density, images, cam, view2vol, *, offs
     if images.dim() != 4 or not 1 <= images.shape[1] <= 4 or images.shape[0] < 1:
         raise ValueError("mesh_bake: images must be [V,C,Hi,Wi] with C in 1..4 and V >= 1, got %s" % (tuple(images.shape),))
     V, C, Hi, Wi = (int(s) for s in images.shape)
-    want = [("vertices", vertices, vertices.shape, torch.float32), ("normals", normals, vertices.shape, torch.float32),
-            ("counts", counts, (n, 2), torch.int32), ("offsets", offsets, (n, 2), torch.int32), ("density", density, density.shape, torch.float32),
-            ("images", images, images.shape, torch.float32), ("cam", cam, (V, 16), torch.float32), ("view2vol", view2vol, (V,), torch.int32),
-            ("view_weight", view_weight, (V, Hi, Wi), torch.float32), ("view_gain", view_gain, (V,), torch.float32)]
-    for name, t, shape, dt in want:
-        if t is None:
-            continue
-        if t.dtype != dt:
-            raise TypeError("mesh_bake: %s must be %s (got %s)" % (name, dt, t.dtype))
-        if tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != dev:
-            raise ValueError("mesh_bake: %s must be a contiguous %s tensor on %s, got %s with strides %s on %s"
-                             % (name, tuple(shape), dev, tuple(t.shape), t.stride(), t.device))
+    _check_tensors("mesh_bake", [("vertices", vertices, vertices.shape, torch.float32), ("normals", normals, vertices.shape, torch.float32),
+                                 ("counts", counts, (n, 2), torch.int32), ("offsets", offsets, (n, 2), torch.int32),
+                                 ("images", images, images.shape, torch.float32), ("cam", cam, (V, 16), torch.float32),
+                                 ("view2vol", view2vol, (V,), torch.int32), ("view_weight", view_weight, (V, Hi, Wi), torch.float32),
+                                 ("view_gain", view_gain, (V,), torch.float32)], dev)
     if mode not in BAKE_MODES:
         raise ValueError("mesh_bake: mode=%r (one of %s)" % (mode, sorted(BAKE_MODES)))
     hx, hy, hz = (float(h) for h in half)
+    _require_cuda(*tensors, offsets, view_weight, view_gain)
     rows = lead + (max_vertices,)
-    shapes = ((rows + (C,), torch.float32), (rows, torch.float32), (rows, torch.int32))
-    if out is None:
-        colors, weight, best = (torch.empty(s, dtype=dt, device=dev) for s, dt in shapes)
-    else:
-        colors, weight, best = out
-        for t, (shape, dt) in zip(out, shapes):
-            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev:
-                raise ValueError("mesh_bake: every out tensor must be contiguous, here %s of shape %s on %s" % (dt, shape, dev))
+    colors, weight, best = _out_or_empty("mesh_bake", out, [(rows + (C,), torch.float32), (rows, torch.float32), (rows, torch.int32)], dev)
     _lib.check(_lib.lib().forge_mesh_bake(_lib.ptr(vertices.detach()), _lib.ptr(normals.detach()), _lib.ptr(counts), _lib.ptr(offsets), n, max_vertices,
                                           _lib.ptr(density.detach()), D, H, W, hx, hy, hz, _lib.ptr(images.detach()), _lib.ptr(view_weight), C, Hi, Wi,
                                           _lib.ptr(cam.detach()), _lib.ptr(view2vol), _lib.ptr(view_gain), V, int(S), float(step), float(offset),
@@ -1007,20 +1021,6 @@ def nn_constants():
     return int(L.forge_nn_queries_per_block()), int(L.forge_nn_tile_points())
 
 
-def _geom_check(fn, want):
-    """want: (name, tensor or None, shape, dtype). The device of the first tensor is the device of all."""
-    dev = next(t for _, t, _, _ in want if t is not None).device
-    for name, t, shape, dt in want:
-        if t is None:
-            continue
-        if t.dtype != dt:
-            raise TypeError("%s: %s must be %s (got %s)" % (fn, name, dt, t.dtype))
-        if tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != dev:
-            raise ValueError("%s: %s must be a contiguous %s tensor on %s, got %s with strides %s on %s"
-                             % (fn, name, tuple(shape), dev, tuple(t.shape), t.stride(), t.device))
-    return dev
-
-
 @_lib.on_tensor_device
 def surface_sample(vertices, faces, counts, n_samples, offsets=None):
     """forge_surface_sample (include/forge_hip.h section g3): n_samples deterministic, area-proportional points on each mesh. vertices
@@ -1037,16 +1037,14 @@ def surface_sample(vertices, faces, counts, n_samples, offsets=None):
     n_samples = int(n_samples)
     if n_samples < 1:
         raise ValueError("surface_sample: n_samples=%d must be at least 1" % n_samples)
-    lead = (n,) if offsets is None else ()
+    lead = _row_lead(n, offsets)
     if vertices.dim() != len(lead) + 2 or faces.dim() != len(lead) + 2:
         raise ValueError("surface_sample: vertices and faces must be %s, got %s and %s"
                          % ("[%d,rows,3]" % n if offsets is None else "[rows,3] (packed: offsets given)", tuple(vertices.shape), tuple(faces.shape)))
     mv, mf = int(vertices.shape[-2]), int(faces.shape[-2])
-    dev = _geom_check("surface_sample", [("vertices", vertices, lead + (mv, 3), torch.float32), ("faces", faces, lead + (mf, 3), torch.int32),
+    dev = _check_tensors("surface_sample", [("vertices", vertices, lead + (mv, 3), torch.float32), ("faces", faces, lead + (mf, 3), torch.int32),
                                          ("counts", counts, (n, 2), torch.int32), ("offsets", offsets, (n, 2), torch.int32)])
-    nbytes = int(_lib.lib().forge_surface_sample_workspace_bytes(n, mf, 0 if offsets is None else 1))
-    if nbytes < 0:
-        _lib.check(nbytes, "forge_surface_sample_workspace_bytes")
+    nbytes = _size_query("forge_surface_sample_workspace_bytes", n, mf, 0 if offsets is None else 1)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     points = torch.empty(n, n_samples, 3, dtype=torch.float32, device=dev)
     normals = torch.empty(n, n_samples, 3, dtype=torch.float32, device=dev)
@@ -1071,7 +1069,7 @@ def nn_points(q, p, q_count=None, p_count=None, xf=None, return_transformed=Fals
     if q.dim() != 3 or p.dim() != 3 or q.shape[2] != 3 or p.shape[2] != 3 or q.shape[0] != p.shape[0] or min(q.shape[:2] + p.shape[:2]) < 1:
         raise ValueError("nn_points: q [B,Nq,3] and p [B,Np,3] with B, Nq, Np >= 1, got %s and %s" % (tuple(q.shape), tuple(p.shape)))
     B, Nq, Np = int(q.shape[0]), int(q.shape[1]), int(p.shape[1])
-    dev = _geom_check("nn_points", [("q", q, (B, Nq, 3), torch.float32), ("p", p, (B, Np, 3), torch.float32), ("q_count", q_count, (B,), torch.int32),
+    dev = _check_tensors("nn_points", [("q", q, (B, Nq, 3), torch.float32), ("p", p, (B, Np, 3), torch.float32), ("q_count", q_count, (B,), torch.int32),
                                     ("p_count", p_count, (B,), torch.int32), ("xf", xf, (B, 12), torch.float32)])
     d2 = torch.empty(B, Nq, dtype=torch.float32, device=dev)
     idx = torch.empty(B, Nq, dtype=torch.int32, device=dev)
@@ -1101,13 +1099,11 @@ def geom_metrics(d2_ab, idx_ab, d2_ba, idx_ba, normals_a=None, normals_b=None, a
     if len(thresholds) > GEOM_MAX_THRESHOLDS or not all(math.isfinite(t) for t in thresholds):
         raise ValueError("geom_metrics: at most %d finite thresholds, got %r" % (GEOM_MAX_THRESHOLDS, thresholds))
     B, Na, Nb = int(d2_ab.shape[0]), int(d2_ab.shape[1]), int(d2_ba.shape[1])
-    dev = _geom_check("geom_metrics", [("d2_ab", d2_ab, (B, Na), torch.float32), ("idx_ab", idx_ab, (B, Na), torch.int32),
+    dev = _check_tensors("geom_metrics", [("d2_ab", d2_ab, (B, Na), torch.float32), ("idx_ab", idx_ab, (B, Na), torch.int32),
                                        ("d2_ba", d2_ba, (B, Nb), torch.float32), ("idx_ba", idx_ba, (B, Nb), torch.int32),
                                        ("normals_a", normals_a, (B, Na, 3), torch.float32), ("normals_b", normals_b, (B, Nb, 3), torch.float32),
                                        ("a_count", a_count, (B,), torch.int32), ("b_count", b_count, (B,), torch.int32)])
-    npart = int(_lib.lib().forge_geom_metrics_partial_doubles(B))
-    if npart < 0:
-        _lib.check(npart, "forge_geom_metrics_partial_doubles")
+    npart = _size_query("forge_geom_metrics_partial_doubles", B)
     partial = torch.empty(npart, dtype=torch.float64, device=dev)
     out = torch.empty(B, GEOM_OUT_DOUBLES, dtype=torch.float64, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev)
@@ -1129,48 +1125,14 @@ def components_tile():
     return int(_lib.lib().forge_components_tile())
 
 
-def _components_inputs(fn, density, level=None):
-    """Shape, dtype, layout and level first, the device last (the caller's _require_cuda): a wrong argument is named as what it is on any device."""
-    if not torch.is_tensor(density):
-        raise TypeError("%s: density must be a tensor" % fn)
-    if density.dim() != 5 or density.shape[1] != 1:
-        raise ValueError("%s: density must be [n,1,D,H,W] (encoder_3d.get_density3D), got %s" % (fn, tuple(density.shape)))
-    if density.dtype != torch.float32:
-        raise TypeError("%s: float32 density (got %s)" % (fn, density.dtype))
-    if not density.is_contiguous():
-        raise ValueError("%s: density must be contiguous (strides %s)" % (fn, density.stride()))
-    n, _, D, H, W = (int(s) for s in density.shape)
-    if n < 1:
-        raise ValueError("%s: empty batch" % fn)
-    if level is not None:
-        level = float(level)
-        if not (level > 0.0 and math.isfinite(level)):
-            raise ValueError("%s: level=%r must be finite and > 0" % (fn, level))
-    return n, D, H, W, level
-
-
-def _components_ws_bytes(n, D, H, W):
-    b = int(_lib.lib().forge_components_workspace_bytes(n, D, H, W))
-    if b < 0:
-        _lib.check(b, "forge_components_workspace_bytes")
-    return b
-
-
-def _components_workspace(fn, workspace, density, nbytes):
-    if not torch.is_tensor(workspace):
-        raise TypeError("%s: workspace must be a tensor" % fn)
-    if workspace.dtype != torch.uint8 or workspace.numel() < nbytes or not workspace.is_contiguous() or workspace.device != density.device:
-        raise ValueError("%s: workspace is not the one components_label returned for this shape" % fn)
-
-
 @_lib.on_tensor_device
 def components_label(density, level=0.5, want_labels=True):
     """forge_components_label (include/forge_hip.h section g4): the connected components of `density > level` under the Kuhn adjacency. Returns
     (labels [n,D,H,W] int32 or None, counts [n] int32 on the device, workspace): the workspace (uint8) goes to components_stats and
     components_select together with the same density. Nothing is read back."""
-    n, D, H, W, level = _components_inputs("components_label", density, level)
+    n, D, H, W, level = _density_volume("components_label", density, level)
     _require_cuda(density)
-    nbytes = _components_ws_bytes(n, D, H, W)
+    nbytes = _size_query("forge_components_workspace_bytes", n, D, H, W)
     dev = density.device
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     labels = torch.empty(n, D, H, W, dtype=torch.int32, device=dev) if want_labels else None
@@ -1185,12 +1147,12 @@ def components_stats(density, workspace, max_components):
     """forge_components_stats after components_label(density, ...): per component, in label order, with max_components rows per volume:
     (sizes [n,Kmax] int32, bbox [n,Kmax,6] int32 = x0, y0, z0, x1, y1, z1 inclusive, coord_sum [n,Kmax,3] int64, status [n] int32 with
     COMPONENTS_OVERFLOW where a volume has more components than rows). Rows past a volume's count are zero. Nothing is read back."""
-    n, D, H, W, _ = _components_inputs("components_stats", density)
+    n, D, H, W, _ = _density_volume("components_stats", density)
     kmax = int(max_components)
     if kmax < 0:
         raise ValueError("components_stats: max_components=%d must not be negative" % kmax)
-    nbytes = _components_ws_bytes(n, D, H, W)
-    _components_workspace("components_stats", workspace, density, nbytes)
+    nbytes = _size_query("forge_components_workspace_bytes", n, D, H, W)
+    _check_tensors("components_stats", [("workspace", workspace, nbytes, torch.uint8)], density.device)
     _require_cuda(density, workspace)
     dev = density.device
     sizes = torch.empty(n, kmax, dtype=torch.int32, device=dev)
@@ -1208,14 +1170,14 @@ def components_select(density, workspace, keep_largest=True, min_voxels=1, min_f
     """forge_components_select after components_label(density, ...): the density with the inside voxels of removed components set to +0.0 and every
     other voxel's bits copied. A component passes with size >= min_voxels and size >= ceil(min_fraction * largest size of its volume);
     keep_largest keeps only the largest passing one (ties: the lowest label). Nothing is read back."""
-    n, D, H, W, _ = _components_inputs("components_select", density)
+    n, D, H, W, _ = _density_volume("components_select", density)
     min_voxels, min_fraction = int(min_voxels), float(min_fraction)
     if min_voxels < 1:
         raise ValueError("components_select: min_voxels=%d must be at least 1" % min_voxels)
     if not 0.0 <= min_fraction <= 1.0:
         raise ValueError("components_select: min_fraction=%r must lie in [0, 1]" % min_fraction)
-    nbytes = _components_ws_bytes(n, D, H, W)
-    _components_workspace("components_select", workspace, density, nbytes)
+    nbytes = _size_query("forge_components_workspace_bytes", n, D, H, W)
+    _check_tensors("components_select", [("workspace", workspace, nbytes, torch.uint8)], density.device)
     _require_cuda(density, workspace)
     out = torch.empty_like(density)
     _lib.check(_lib.lib().forge_components_select(_lib.ptr(density.detach()), n, D, H, W, _lib.ptr(workspace), nbytes, 1 if keep_largest else 0, min_voxels,

@@ -754,7 +754,8 @@ int forge_pose_sync(const float* P, const float* conf, const int* pairs, int B, 
  *                            vertex_features and rows v max_faces .. of faces. offsets != NULL (device int32 [n][2], the exclusive scan of counts
  *                            over volumes): volume v starts at row offsets[v] of arrays with max_vertices / max_faces rows IN ALL. Rows past
  *                            the capacity are never written; status[v] (device int32) = FORGE_MESH_OVERFLOW when volume v did not fit, else 0;
- *                            the rows that did fit are the prefix of the full result. Two launches.
+ *                            the rows that did fit are the prefix of the full result. A NEGATIVE offsets[v][0] or offsets[v][1] is never followed: volume v
+ *                            writes nothing, to any array, and reports FORGE_MESH_OVERFLOW if it had anything to emit. Two launches.
  * Nothing allocates, synchronises or reads the environment: both calls may sit in a captured graph.
  * FORGE_EINVAL: null pointer, level <= 0 or not finite, volume_size <= 0 or not finite, an extent or n < 1, a workspace too small or unaligned,
  * negative capacities. FORGE_ESHAPE: C % 4 != 0, more than (2^31 - 1) / 12 cells per volume (per-volume offsets are 32-bit), n > 65535.
@@ -776,7 +777,8 @@ int forge_mesh_emit(const float* density, const float* features, int n, int C, i
  *   vertices, normals  the rows forge_mesh_emit wrote; counts [n][2], offsets [n][2] (nullable) and max_vertices select the same two row layouts:
  *                      offsets == NULL: volume k owns rows k max_vertices .. (k+1) max_vertices - 1; otherwise volume k starts at row offsets[k][0]
  *                      of arrays with max_vertices rows IN ALL. Volume k has min(counts[k][0], rows left to it) rows: a volume that overflowed bakes
- *                      the prefix that fitted. Rows past that are never written.
+ *                      the prefix that fitted. Rows past that are never written. A negative offsets[k][0] or offsets[k][1] is never followed: volume k
+ *                      has no rows, nothing of it is read or written (as in g1 and g3).
  *   density  [n][D][H][W]; hx, hy, hz the half extents of W, H, D as forge_render_fwd takes them (finite, > 0)
  *   images   [V][C][Hi][Wi] planar, C in 1 .. 4; view_weight [V][Hi][Wi], nullable (= 1): a per-pixel confidence or foreground map
  *   cam      [V][16]: R[9] row-major (OpenCV world->camera, x_cam = R p + T), T[3], fx, fy, cx, cy in pixels OF THE GIVEN IMAGES (not the
