@@ -132,6 +132,10 @@ SIGNATURES = {
     "forge_nn_points": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     "forge_geom_metrics_partial_doubles": [_I],
     "forge_geom_metrics": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P],
+    "forge_align_blocks": [],
+    "forge_align_partial_doubles": [_I],
+    "forge_align_step": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _D, _D, _D, _D, _P, _P, _P, _P, _P],
+    "forge_align_select": [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
     "forge_components_tile": [],
     "forge_components_workspace_bytes": [_I, _I, _I, _I],
     "forge_components_label": [_P, _I, _I, _I, _I, _F, _P, _LL, _P, _P, _P],
@@ -149,7 +153,7 @@ SIGNATURES = {
 _LL_RESULTS = ("forge_render_bwd_ws_bytes", "forge_conv_wgrad_det_ws_bytes", "forge_wino_wgrad_det_ws_bytes",     # byte counts: long long results
                "forge_conv_direct_wgrad_det_ws_bytes", "forge_rotate_bwd_det_ws_bytes", "forge_rotate_bwd_slots_det_ws_bytes",
                "forge_token_linear_bwd_ws_bytes", "forge_layer_norm_bwd_ws_bytes", "forge_mesh_workspace_bytes", "forge_surface_sample_workspace_bytes",
-               "forge_geom_metrics_partial_doubles", "forge_components_workspace_bytes")
+               "forge_geom_metrics_partial_doubles", "forge_components_workspace_bytes", "forge_align_partial_doubles")
 
 
 def lib():

@@ -1,4 +1,4 @@
-// geom_common.h — what mesh.hip, bake.hip, geomdist.hip, components.hip and metrics.hip share, written once (header only: no translation unit).
+// geom_common.h — what mesh.hip, bake.hip, geomdist.hip, components.hip, align.hip and metrics.hip share, written once (header only: no translation unit).
 //   wave / block primitives   wave_inclusive_scan, wave_sum, waves_before, block_exclusive_scan_inplace (integer scans: any order gives the same bits)
 //   row spans                 row_span, mesh_spans: the rows of a padded or packed mesh array that one volume owns (forge_hip.h sections g1, g2, g3)
 //   fixed-tree reductions     block_reduce256 / block_sum256 / block_max256: float64, ONE tree, so every caller keeps its bits

@@ -259,9 +259,11 @@ def sync_pose(return_dict, best_canonical_id, device=None, rank_tol=1e-6):
     return torch.where(status.reshape(1, 1) != 0, keep, synced), status
 
 
-def evaluate_geometry(pred_meshes, gt_meshes, transform=None, **kw):
-    """The surface metrics beside the image and pose metrics above: geometry.mesh_metrics(pred_meshes, gt_meshes, transform=transform, **kw) -
-    accuracy, completeness, Chamfer, Hausdorff, F-score and normal consistency as float64 device tensors, one entry per mesh pair. transform maps
-    the predictions (canonical frame of view 0) into the ground truth's frame. Not part of evaluate_all, whose outputs are the reference's."""
+def evaluate_geometry(pred_meshes, gt_meshes, transform=None, align=None, **kw):
+    """The surface metrics beside the image and pose metrics above: geometry.mesh_metrics(pred_meshes, gt_meshes, transform=transform, align=align,
+    **kw) - accuracy, completeness, Chamfer, Hausdorff, F-score and normal consistency as float64 device tensors, one entry per mesh pair.
+    transform maps the predictions (canonical frame of view 0) into the ground truth's frame; where nobody knows it (predicted poses, photographs,
+    meshes in their own object frame), align="icp" or a dict of geometry.align_points keywords estimates it on the device first and returns it
+    under 'alignment'. Not part of evaluate_all, whose outputs are the reference's."""
     from . import geometry
-    return geometry.mesh_metrics(pred_meshes, gt_meshes, transform=transform, **kw)
+    return geometry.mesh_metrics(pred_meshes, gt_meshes, transform=transform, align=align, **kw)

@@ -18,7 +18,11 @@ label_components and keep_components say which voxels belong to the object (csrc
 object plus small detached blobs - floaters - and every stage above pays for them (extra shells, volume, samples, occluders). Components are
 taken under the adjacency of the very lattice extract_mesh marches over, so dropping a component removes exactly one closed shell and leaves
 every other vertex and face of the mesh bit for bit as it was. extract_mesh(components=...) and colored_mesh(components=...) clean the volume
-first."""
+first.
+
+align_points, align_meshes and fit_similarity find the similarity between a prediction and its ground truth when nobody knows it (csrc/align.hip,
+section g5): ICP on the exact nearest-neighbour search above with a closed-form float64 update per iteration, several starts in one batch,
+nothing read back; mesh_metrics(align="icp") scores under what they find."""
 import math
 from collections import namedtuple
 
@@ -663,17 +667,160 @@ def _sampled(side, n, what):
     return points, normals, counts
 
 
-def mesh_metrics(pred, gt, n=100_000, thresholds=(0.01, 0.02, 0.05), transform=None):
+def mesh_metrics(pred, gt, n=100_000, thresholds=(0.01, 0.02, 0.05), transform=None, align=None):
     """Chamfer distance, F-score and the other entries of point_metrics between surfaces: n samples of each side (sample_surface), then
     point_metrics. pred / gt: a Mesh, a list of Mesh or a MeshBatch (one pair per mesh); gt may also be a point cloud [N,3] / [B,N,3], and then
     no normal consistency is computed. transform ([4,4] or [B,4,4], a similarity) maps pred into the frame of gt: extracted meshes live in the
     canonical world frame of view 0 (the frame VolRender takes cameras in), ground-truth meshes in their dataset's object frame, so a caller
-    scoring against ground truth passes the alignment here - nothing is estimated. With MeshBatch inputs there is no host synchronisation (an
-    empty volume shows as ops.GEOM_EMPTY in 'status' and NaN means), so the whole chain can sit in a captured graph."""
+    scoring against ground truth passes the alignment here - with align=None nothing is estimated. align="icp", or a dict of align_points
+    keywords (and 'n', the samples per side of the alignment, default 20 000): align_meshes runs first on its own smaller sample, started from
+    `transform` (its `init`), the float32 of what it finds is the transform everything is measured under, and the Alignment is returned under
+    'alignment'. With MeshBatch inputs there is no host synchronisation (an empty volume shows as ops.GEOM_EMPTY in 'status' and NaN means), so
+    the whole chain can sit in a captured graph."""
+    alignment = None
+    if align is not None:
+        if not (align == "icp" or isinstance(align, dict)):
+            raise ValueError("mesh_metrics: align must be None, 'icp' or a dict of align_points keywords, got %r" % (align,))
+        kw = dict(align) if isinstance(align, dict) else {}
+        if transform is not None:
+            kw.setdefault("init", transform)
+        alignment = align_meshes(pred, gt, **kw)
+        transform = alignment.transform.to(torch.float32)
     pa, na, ca = _sampled(pred, n, "pred")
     pb, nb, cb = _sampled(gt, n, "gt")
     if pa.shape[0] != pb.shape[0]:
         raise ValueError("mesh_metrics: %d predictions against %d ground truths" % (pa.shape[0], pb.shape[0]))
     if na is None or nb is None:
         na = nb = None
-    return point_metrics(pa, pb, na, nb, thresholds=thresholds, transform=transform, counts_a=ca, counts_b=cb)
+    res = point_metrics(pa, pb, na, nb, thresholds=thresholds, transform=transform, counts_a=ca, counts_b=cb)
+    if alignment is not None:
+        res["alignment"] = alignment
+    return res
+
+
+# ------------------------------------------------------------------------------------------------------------ aligning to ground truth
+Alignment = namedtuple("Alignment", "transform scale rmse inliers iterations start status")
+Alignment.__doc__ = """fit_similarity / align_points / align_meshes, device tensors, one entry per pair: transform [B,4,4] float64 (s R | t over 0 0 0 1:
+maps a into the frame of b), scale [B] float64, rmse [B] float64 (root mean square distance of the inliers under `transform`; for a pair that
+CONVERGED, under the transform that came INTO its last update, which is `transform` itself with tol = 0 and within tol per entry of it otherwise:
+a frozen pair is not measured again - the starts of a multi-start run are compared by scores taken the same way), inliers [B] int32,
+iterations [B] int32 (updates made before the pair converged or the budget ran out), start [B] int32 (the start that won; 0 without starts; -1 if
+none could be fitted), status [B] int32 (ops.ALIGN_EMPTY: fewer than 3 matched points, the transform is the start; ops.ALIGN_RANK: the matched
+points are collinear; ops.ALIGN_NONFINITE: rows with NaN / inf were skipped; ops.ALIGN_CONVERGED: the last update moved no entry by more than tol)."""
+
+
+def rotation_starts(kind="cube"):
+    """Start rotations for align_points(starts=...), [K,3,3] float64 on the host. "cube": the 24 proper signed permutation matrices (the
+    rotations of a cube), the identity first - every rotation is within 62.8 degrees of one of them."""
+    if kind != "cube":
+        raise ValueError("rotation_starts: kind must be 'cube', got %r" % (kind,))
+    import itertools
+    out = []
+    for perm in itertools.permutations(range(3)):
+        for signs in itertools.product((1.0, -1.0), repeat=3):
+            m = torch.zeros(3, 3, dtype=torch.float64)
+            for r in range(3):
+                m[r, perm[r]] = signs[r]
+            parity = 1.0 if perm in ((0, 1, 2), (1, 2, 0), (2, 0, 1)) else -1.0
+            if parity * signs[0] * signs[1] * signs[2] > 0:
+                out.append(m)
+    return torch.stack(out)
+
+
+def _align_counts(counts, B, N, dev, what):
+    if counts is None:
+        return torch.full((B,), int(N), dtype=torch.int32, device=dev)
+    if not torch.is_tensor(counts) or counts.dtype != torch.int32 or tuple(counts.shape) != (B,):
+        raise ValueError("align_points: %s must be an int32 tensor [%d]" % (what, B))
+    return counts.contiguous()
+
+
+def _alignment(state, status, K):
+    T, _, best, st, stat = ops.align_select(state, status, K)
+    return Alignment(T, st[:, ops.ALIGN_SCALE], st[:, ops.ALIGN_RMSE], st[:, ops.ALIGN_N_IN].to(torch.int32),
+                     st[:, ops.ALIGN_ITERATIONS].to(torch.int32), best, stat)
+
+
+def _centroids(x, counts):
+    """[B,3] float64: the mean of the valid rows, from forge_align_step's own moments (a statistics-only step of x against itself), so the bits
+    are the kernels' and not a torch reduction's. NaN for a pair without rows."""
+    state, xf, status = ops.align_state(None, x.shape[0], x.device)
+    ops.align_step(x, x, state, xf, status, q_count=counts, p_count=counts, update=False)
+    return state[:, ops.ALIGN_CQ:ops.ALIGN_CQ + 3]
+
+
+def fit_similarity(a, b, with_scale=True, counts=None):
+    """The least-squares similarity (Umeyama; a rigid motion with with_scale=False) that maps a [B,N,3] onto b [B,N,3] when row i of a IS row i
+    of b - known correspondences, for one: predicted camera centres against ground-truth ones. One ops.align_step in closed form (float64
+    moments, the SO(3) projection of pose synchronisation), then the residuals under the fitted transform for rmse. counts [B] int32 on the
+    device limits the valid rows. Returns an Alignment; nothing is read back. The residuals behind rmse are formed by torch (float64, elementwise
+    and a 3-term sum per row) and reduced by a statistics-only align_step: the fit's bits are the kernels' own, rmse's last bits are torch's."""
+    a, b = _as_batch(a, "a"), _as_batch(b, "b")
+    ops._require_cuda(a, b)
+    if a.shape[0] != b.shape[0]:
+        raise ValueError("fit_similarity: %d sets against %d" % (a.shape[0], b.shape[0]))
+    B, dev, n = a.shape[0], a.device, min(a.shape[1], b.shape[1])
+    state, xf, status = ops.align_state(None, B, dev)
+    ops.align_step(a, b, state, xf, status, q_count=counts, p_count=counts, with_scale=with_scale)
+    T = state[:, ops.ALIGN_T:ops.ALIGN_T + 12].view(B, 3, 4)
+    r = a[:, :n].double() @ T[:, :, :3].transpose(1, 2) + T[:, None, :, 3] - b[:, :n].double()
+    d2 = torch.zeros(B, a.shape[1], dtype=torch.float32, device=dev)
+    d2[:, :n] = (r * r).sum(dim=2).to(torch.float32)
+    status.bitwise_and_(~ops.ALIGN_CONVERGED)      # a fit that happens to be the identity is measured like any other
+    ops.align_step(a, b, state, xf, status, d2=d2, q_count=counts, p_count=counts, update=False)
+    return _alignment(state, status, 1)
+
+
+def align_points(a, b, iterations=32, with_scale=False, init=None, starts=None, reject=0.0, reject_floor=0.0, tol=0.0, counts_a=None, counts_b=None):
+    """ICP on the device (include/forge_hip.h section g5): the similarity that maps the points a [B,Na,3] onto the points b [B,Nb,3] ([N,3] for one
+    pair) when nobody knows which point matches which. Every iteration is one exact nearest-neighbour search of a, under the current transform,
+    in b (ops.nn_points) and one closed-form update from float64 moments (ops.align_step); after `iterations` updates one more search measures
+    rmse and inliers under the final transform. A pair whose update moves no entry of the transform by more than tol is frozen on the device and
+    searches nothing from then on; nothing is read back, so the result depends on the inputs and the budget alone and the call can be captured.
+      with_scale    estimate the scale too (a similarity), else a rigid motion
+      init          [4,4] or [B,4,4]: where to start (None: the identity). ICP finds the nearest local minimum: beyond about 45 degrees give starts.
+      starts        [K,3,3] or [K,4,4] rotations (rotation_starts("cube")): each is tried with the centroid of a placed on the centroid of b, as
+                    B K pairs in one batch, and the start with the lowest mean squared distance wins (the lowest index on a tie)
+      reject        > 0: from the second iteration on, matches farther than reject x the inliers' rms distance of the previous iteration (but
+                    never nearer than reject_floor) are left out of the fit - floaters, parts the other side does not have
+      counts_a, counts_b  [B] int32 on the device: the valid rows
+    Returns an Alignment."""
+    a, b = _as_batch(a, "a"), _as_batch(b, "b")
+    ops._require_cuda(a, b)
+    if a.shape[0] != b.shape[0]:
+        raise ValueError("align_points: %d sets against %d" % (a.shape[0], b.shape[0]))
+    iterations = int(iterations)
+    if iterations < 0:
+        raise ValueError("align_points: iterations=%d must not be negative" % iterations)
+    B, dev, K = a.shape[0], a.device, 1
+    ca, cb = _align_counts(counts_a, B, a.shape[1], dev, "counts_a"), _align_counts(counts_b, B, b.shape[1], dev, "counts_b")
+    if starts is not None:
+        if init is not None:
+            raise ValueError("align_points: give init or starts, not both")
+        R = torch.as_tensor(starts, dtype=torch.float64, device=dev)
+        if R.dim() != 3 or R.shape[0] < 1 or tuple(R.shape[1:]) not in ((3, 3), (4, 4)):
+            raise ValueError("align_points: starts must be [K,3,3] or [K,4,4], got %s" % (tuple(R.shape),))
+        R, K = R[:, :3, :3], int(R.shape[0])
+        ma, mb = _centroids(a, ca), _centroids(b, cb)
+        Ra = R[None, :, :, 0] * ma[:, None, 0:1] + R[None, :, :, 1] * ma[:, None, 1:2] + R[None, :, :, 2] * ma[:, None, 2:3]       # [B,K,3], left to right
+        init = torch.cat([R[None].expand(B, K, 3, 3), (mb[:, None, :] - Ra)[..., None]], dim=3).reshape(B * K, 3, 4)
+        a, b = (x[:, None].expand(B, K, x.shape[1], 3).contiguous().view(B * K, x.shape[1], 3) for x in (a, b))     # pair b's K starts: rows b K .. b K + K - 1
+        ca, cb = (c[:, None].expand(B, K).contiguous().view(B * K) for c in (ca, cb))
+    state, xf, status = ops.align_state(init, B * K, dev)
+    none = torch.zeros_like(ca)
+    for it in range(iterations + 1):               # the last one measures
+        active = torch.where((status & ops.ALIGN_CONVERGED) != 0, none, ca)       # a frozen pair searches nothing
+        d2, idx = ops.nn_points(a, b, active, cb, xf)
+        ops.align_step(a, b, state, xf, status, idx=idx, d2=d2, q_count=ca, p_count=cb, with_scale=with_scale, update=it < iterations, reject=reject,
+                       reject_floor=reject_floor, tol=tol)
+    return _alignment(state, status, K)
+
+
+def align_meshes(pred, gt, n=20_000, **kw):
+    """align_points between n surface samples of each side (sample_surface): pred / gt as mesh_metrics takes them (gt may be a point cloud). An
+    empty mesh has no samples, and its pair comes back with ops.ALIGN_EMPTY and the start as its transform. kw: the keywords of align_points."""
+    pa, _, ca = _sampled(pred, n, "pred")
+    pb, _, cb = _sampled(gt, n, "gt")
+    if pa.shape[0] != pb.shape[0]:
+        raise ValueError("align_meshes: %d predictions against %d ground truths" % (pa.shape[0], pb.shape[0]))
+    return align_points(pa, pb, counts_a=ca, counts_b=cb, **kw)

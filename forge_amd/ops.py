@@ -1116,6 +1116,99 @@ def geom_metrics(d2_ab, idx_ab, d2_ba, idx_ba, normals_a=None, normals_b=None, a
     return out, status
 
 
+# ------------------------------------------------------------------------------------------------------------------------- alignment
+ALIGN_EMPTY, ALIGN_RANK, ALIGN_NONFINITE, ALIGN_CONVERGED = 1, 2, 4, 8      # status bits (FORGE_ALIGN_*)
+ALIGN_STATE_DOUBLES = 29
+ALIGN_T, ALIGN_SCALE, ALIGN_RMSE, ALIGN_N_IN, ALIGN_N_VALID, ALIGN_CUT2, ALIGN_DELTA, ALIGN_ITERATIONS, ALIGN_SV, ALIGN_SCORE, ALIGN_CQ, ALIGN_CP = (
+    0, 12, 13, 14, 15, 16, 17, 18, 19, 22, 23, 26)                           # columns of a state row (FORGE_ALIGN_*)
+ALIGN_RANK_TOL = 1e-6
+
+
+def align_blocks():
+    """Workgroups per pair of forge_align_step's moments pass: host only, no device is touched."""
+    return int(_lib.lib().forge_align_blocks())
+
+
+def align_state(init, B, device):
+    """The first state of forge_align_step (section g5) for B pairs, built on the device: T = init ([4,4], [3,4], [B,4,4] or [B,3,4], a similarity;
+    None: the identity), SCALE = the length of T's first row, CUT2 = +inf (nothing is rejected in the first step), DELTA = +inf, RMSE = SCORE = NaN
+    (a start that was never stepped never wins align_select), everything else 0. Returns (state [B,ALIGN_STATE_DOUBLES] float64, xf [B,12] float32,
+    status [B] int32, zero). Nothing is read back."""
+    B = int(B)
+    if B < 1:
+        raise ValueError("align_state: B=%d must be at least 1" % B)
+    if init is None:
+        T = torch.eye(4, dtype=torch.float64, device=device)[:3].expand(B, 3, 4)
+    else:
+        T = torch.as_tensor(init, device=device).to(torch.float64)
+        if T.dim() == 2:
+            T = T[None].expand(B, *T.shape)
+        if T.dim() != 3 or T.shape[0] != B or tuple(T.shape[1:]) not in ((4, 4), (3, 4)):
+            raise ValueError("align_state: init must be [4,4], [3,4], [%d,4,4] or [%d,3,4], got %s" % (B, B, tuple(T.shape)))
+        T = T[:, :3, :]
+    state = torch.zeros(B, ALIGN_STATE_DOUBLES, dtype=torch.float64, device=device)
+    state[:, ALIGN_T:ALIGN_T + 12] = T.reshape(B, 12)
+    state[:, ALIGN_SCALE] = (T[:, 0, 0] * T[:, 0, 0] + T[:, 0, 1] * T[:, 0, 1] + T[:, 0, 2] * T[:, 0, 2]).sqrt()
+    state[:, ALIGN_CUT2] = math.inf
+    state[:, ALIGN_DELTA] = math.inf
+    state[:, ALIGN_RMSE] = math.nan
+    state[:, ALIGN_SCORE] = math.nan
+    return state, state[:, ALIGN_T:ALIGN_T + 12].to(torch.float32).contiguous(), torch.zeros(B, dtype=torch.int32, device=device)
+
+
+@_lib.on_tensor_device
+def align_step(q, p, state, xf, status, idx=None, d2=None, q_count=None, p_count=None, with_scale=False, update=True, reject=0.0, reject_floor=0.0,
+               tol=0.0, rank_tol=ALIGN_RANK_TOL, clamp2=math.inf):
+    """forge_align_step (section g5): one least-squares update of the similarity q -> p per pair, IN PLACE on state [B,ALIGN_STATE_DOUBLES] float64,
+    xf [B,12] float32 and status [B] int32 (align_state makes the first ones). q [B,Nq,3], p [B,Np,3] float32; idx [B,Nq] int32 and d2 [B,Nq]
+    float32 as nn_points returns them (idx None: row i matches row i; d2 None: zeros); q_count / p_count [B] int32 on the device. update False:
+    statistics only. A pair whose status carries ALIGN_CONVERGED is left as it is. Returns (state, xf, status), the same tensors. Nothing is
+    read back."""
+    tensors = (q, p, state, xf, status)
+    if not all(torch.is_tensor(t) for t in tensors) or not all(t is None or torch.is_tensor(t) for t in (idx, d2, q_count, p_count)):
+        raise TypeError("align_step: q, p, state, xf, status (and idx, d2, q_count, p_count) must be tensors")
+    _require_cuda(*tensors, idx, d2, q_count, p_count)
+    if q.dim() != 3 or p.dim() != 3 or q.shape[2] != 3 or p.shape[2] != 3 or q.shape[0] != p.shape[0] or min(q.shape[:2] + p.shape[:2]) < 1:
+        raise ValueError("align_step: q [B,Nq,3] and p [B,Np,3] with B, Nq, Np >= 1, got %s and %s" % (tuple(q.shape), tuple(p.shape)))
+    B, Nq, Np = int(q.shape[0]), int(q.shape[1]), int(p.shape[1])
+    dev = _check_tensors("align_step", [("q", q, (B, Nq, 3), torch.float32), ("p", p, (B, Np, 3), torch.float32),
+                                     ("state", state, (B, ALIGN_STATE_DOUBLES), torch.float64), ("xf", xf, (B, 12), torch.float32),
+                                     ("status", status, (B,), torch.int32), ("idx", idx, (B, Nq), torch.int32), ("d2", d2, (B, Nq), torch.float32),
+                                     ("q_count", q_count, (B,), torch.int32), ("p_count", p_count, (B,), torch.int32)])
+    scalars = [float(v) for v in (reject, reject_floor, tol, rank_tol, clamp2)]
+    if not all(math.isfinite(v) and v >= 0.0 for v in scalars[:3]) or not 0.0 <= scalars[3] < 1.0 or not scalars[4] >= 0.0:
+        raise ValueError("align_step: reject, reject_floor, tol >= 0 and finite, rank_tol in [0, 1), clamp2 >= 0; got %r" % (scalars,))
+    npart = _size_query("forge_align_partial_doubles", B)
+    partial = torch.empty(npart, dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().forge_align_step(_lib.ptr(q.detach()), _lib.ptr(p.detach()), _lib.ptr(q_count), _lib.ptr(p_count), _lib.ptr(idx), _lib.ptr(d2),
+                                           B, Nq, Np, 1 if with_scale else 0, 1 if update else 0, *scalars, _lib.ptr(partial), _lib.ptr(state),
+                                           _lib.ptr(xf), _lib.ptr(status), _lib.current_stream()), "forge_align_step")
+    return state, xf, status
+
+
+@_lib.on_tensor_device
+def align_select(state, status, K):
+    """forge_align_select (section g5): state [B*K,ALIGN_STATE_DOUBLES] and status [B*K], pair b's K starts in rows b K .. b K + K - 1 -> the start
+    of lowest SCORE per pair (the lowest index on a tie; NaN, +inf and a start with ALIGN_EMPTY never win). Returns (T [B,4,4] float64, xf [B,12]
+    float32, best [B] int32 (-1: none won, start 0 is reported), state [B,ALIGN_STATE_DOUBLES], status [B]). Nothing is read back."""
+    if not torch.is_tensor(state) or not torch.is_tensor(status):
+        raise TypeError("align_select: state and status must be tensors")
+    _require_cuda(state, status)
+    K = int(K)
+    if K < 1 or state.dim() != 2 or state.shape[0] < K or state.shape[0] % K:
+        raise ValueError("align_select: state must be [B*K,%d] with K=%d >= 1, got %s" % (ALIGN_STATE_DOUBLES, K, tuple(state.shape)))
+    B = int(state.shape[0]) // K
+    dev = _check_tensors("align_select", [("state", state, (B * K, ALIGN_STATE_DOUBLES), torch.float64), ("status", status, (B * K,), torch.int32)])
+    T = torch.empty(B, 4, 4, dtype=torch.float64, device=dev)
+    xf = torch.empty(B, 12, dtype=torch.float32, device=dev)
+    best = torch.empty(B, dtype=torch.int32, device=dev)
+    state_out = torch.empty(B, ALIGN_STATE_DOUBLES, dtype=torch.float64, device=dev)
+    status_out = torch.empty(B, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().forge_align_select(_lib.ptr(state), _lib.ptr(status), B, K, _lib.ptr(T), _lib.ptr(xf), _lib.ptr(best), _lib.ptr(state_out),
+                                             _lib.ptr(status_out), _lib.current_stream()), "forge_align_select")
+    return T, xf, best, state_out, status_out
+
+
 # ---------------------------------------------------------------------------------------------------------------- connected components
 COMPONENTS_OVERFLOW = 1                                            # status bit of forge_components_stats (FORGE_COMPONENTS_OVERFLOW)
 

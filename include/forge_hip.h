@@ -945,6 +945,85 @@ int forge_components_select(const float* density, int n, int D, int H, int W, vo
                             int min_voxels, double min_fraction, float* out, forge_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * g5  Aligning a prediction to ground truth (csrc/align.hip): the similarity q -> p that g3's `xf` takes, ESTIMATED - the closed-form least-squares
+ * fit (Umeyama; Kabsch without scale) from float64 moments, as one update of an ICP whose correspondences are forge_nn_points', and the choice among
+ * several starts. The reference has no counterpart. No atomics, no allocation, nothing read back; every output bit is reproducible and independent
+ * of the batch; the rotation is csrc/so3.h's projection onto SO(3), U diag(1, 1, det) V^T - the one forge_pose_sync uses.
+ *
+ * forge_align_step  one update per pair, two launches:
+ *   q [B][Nq][3], p [B][Np][3] fp32; q_count, p_count [B] device int32, nullable (= Nq, Np), clamped into 0 .. N as in g3
+ *   idx [B][Nq] int32, nullable: row i of q matches row idx[i] of p; an idx outside 0 .. p_count - 1 skips the row and is never followed.
+ *            Rows i < q_count are looked at. NULL: row i matches row i (known correspondences), rows i < min(q_count, p_count).
+ *   d2  [B][Nq] fp32, nullable (NULL counts as 0): the squared distance of the match under the CURRENT transform (forge_nn_points' d2). Used for
+ *            rejection and residuals only, never for the fit.
+ *   state [B][FORGE_ALIGN_STATE_DOUBLES] float64, in and out:  T (12: row-major 3x4, s R | t, maps q to p) | SCALE s | RMSE | N_IN | N_VALID | CUT2 |
+ *            DELTA | ITERATIONS | SV (3: singular values of H, descending) | SCORE | CQ (3) | CP (3): the centroids of the inliers' q and p
+ *   xf [B][12] fp32, out: T rounded to nearest - the `xf` of the next forge_nn_points;   status [B] int32, in and out (bits below)
+ *   host scalars: with_scale, update (0 or 1); reject, reject_floor, tol >= 0 and finite; rank_tol in [0, 1); clamp2 >= 0, may be +inf
+ *   partial: forge_align_partial_doubles(B) doubles of work space.
+ *   Launch 1, grid (forge_align_blocks(), B) x 256 threads, each striding over the rows. A row is VALID when it is matched and none of its six
+ *   coordinates is infinite or NaN and its d2 is not NaN (else it is skipped and FORGE_ALIGN_NONFINITE is set); a valid row is an INLIER when
+ *   !(d2 > CUT2), CUT2 from the incoming state. Values are widened to float64 on load. Per workgroup: n_in, n_valid, sum q (the RAW q, not the
+ *   transformed one), sum p, sum p_r q_c (9: per thread acc = fma(p_r, q_c, acc) in row order), sum |q|^2 (fma(qz, qz, fma(qy, qy, qx qx)) per row) and
+ *   sum d2 over the inliers, sum min(d2, clamp2) over the valid rows; each combined over the workgroup by ONE fixed tree (red[t] += red[t + s],
+ *   s = 128 .. 1).
+ *   The moments are those of the untransformed q: every step solves for the whole transform q -> p, so nothing is composed in fp32 and no error
+ *   accumulates over the iterations of an ICP. One-pass raw moments suffice: coordinates are O(1) and n <= 2^20, so float64 leaves about
+ *   n 2^-53 ~ 1e-10 absolute on sums whose centred values are about 0.05 n - nine digits of H survive the subtraction.
+ *   Launch 2, one workgroup per pair: the partials are added in workgroup order, then one thread solves, every expression left to right:
+ *     H_rc = sum p_r q_c - (sum p_r)(sum q_c) / n;  v_q = sum |q|^2 - |sum q|^2 / n  (n = n_in);  (R, SV) = projection of H onto SO(3)
+ *     s = (sum_rc R_rc H_rc) / v_q with_scale and v_q > 0, else 1;  T = (s R | CP - s R CQ);  RMSE = sqrt(sum d2 / n_in);
+ *     SCORE = sum min(d2, clamp2) / n_valid;  CUT2 = max(reject^2 sum d2 / n_in, reject_floor^2) for reject > 0, else +inf;
+ *     DELTA = max |T_new - T_old| over the 12 entries (NaN if any is);  ITERATIONS += 1.
+ *   RMSE, N_IN, N_VALID, SCORE, CQ and CP describe the INCOMING transform (they come from the incoming d2), T and SV the outgoing one.
+ *   update = 0: statistics only - RMSE, N_IN, N_VALID, SCORE, CQ, CP are written, everything else stands (xf is rewritten from T).
+ *   status: FORGE_ALIGN_EMPTY     n_in < 3: T, SCALE, SV and CUT2 are kept, DELTA = 0, and the pair does not count as converged
+ *           FORGE_ALIGN_RANK      SV[1] / SV[0] < rank_tol or SV[0] = 0: the matched points are collinear; T is written all the same - a proper
+ *                                 rotation that fits the line, its turn about the line arbitrary
+ *           FORGE_ALIGN_NONFINITE a row was skipped for a non-finite value
+ *           FORGE_ALIGN_CONVERGED DELTA <= tol
+ *   update = 1 writes all four bits afresh; update = 0 keeps RANK and CONVERGED and writes the other two. A pair that ENTERS with CONVERGED set
+ *   is frozen, whatever `update` is: neither launch reads its rows, state and status stand, xf is rewritten from T. Its RMSE, N_IN, N_VALID and
+ *   SCORE therefore stay those of the step that converged, which describe the transform that came INTO that step: the final T itself when
+ *   tol = 0 (DELTA = 0), a transform within tol per entry of it otherwise. forge_align_select compares such scores as they stand. The result of a loop of
+ *   searches and steps is then a function of the inputs and the iteration budget alone - no host decision, so the loop can be captured.
+ *   FORGE_EINVAL: a null q / p / partial / state / xf / status, B, Nq or Np < 1, with_scale or update outside {0, 1}, reject, reject_floor or tol
+ *   negative or not finite, rank_tol outside [0, 1), clamp2 negative or NaN, partial or state not 8-byte aligned. FORGE_ESHAPE: B > 65535, Nq or
+ *   Np within a launch's stride of 2^31.
+ *
+ * forge_align_select  state [B][K][FORGE_ALIGN_STATE_DOUBLES], status [B][K]: K starts per pair. best [B] int32 = the k of the lowest SCORE: the
+ *   compare is a strict `<` in increasing k from +inf, so the lowest index wins a tie and NaN (and +inf) never wins; a start with EMPTY set never
+ *   wins. T [B][4][4] float64 (bottom row 0 0 0 1), xf [B][12] fp32, state_out [B][FORGE_ALIGN_STATE_DOUBLES], status_out [B]: of the winner.
+ *   best = -1 if none won: start 0 is then what is written. One launch.
+ *   FORGE_EINVAL: a null pointer, B or K < 1, state, T or state_out not 8-byte aligned. FORGE_ESHAPE: B > 65535, B K beyond 32-bit rows.
+ * Nothing allocates, synchronises or reads the environment; every entry takes the stream and may sit in a captured graph.
+ */
+#define FORGE_ALIGN_EMPTY 1
+#define FORGE_ALIGN_RANK 2
+#define FORGE_ALIGN_NONFINITE 4
+#define FORGE_ALIGN_CONVERGED 8
+#define FORGE_ALIGN_T 0
+#define FORGE_ALIGN_SCALE 12
+#define FORGE_ALIGN_RMSE 13
+#define FORGE_ALIGN_N_IN 14
+#define FORGE_ALIGN_N_VALID 15
+#define FORGE_ALIGN_CUT2 16
+#define FORGE_ALIGN_DELTA 17
+#define FORGE_ALIGN_ITERATIONS 18
+#define FORGE_ALIGN_SV 19
+#define FORGE_ALIGN_SCORE 22
+#define FORGE_ALIGN_CQ 23
+#define FORGE_ALIGN_CP 26
+#define FORGE_ALIGN_STATE_DOUBLES 29
+int forge_align_blocks(void);
+long long forge_align_partial_doubles(int B);
+int forge_align_step(const float* q, const float* p, const int* q_count, const int* p_count, const int* idx, const float* d2, int B, int Nq, int Np,
+                     int with_scale, int update, double reject, double reject_floor, double tol, double rank_tol, double clamp2, double* partial,
+                     double* state, float* xf, int* status, forge_stream_t stream);
+int forge_align_select(const double* state, const int* status, int B, int K, double* T, float* xf, int* best, double* state_out, int* status_out,
+                       forge_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * h  Photographs to input tensors (csrc/ingest.hip): the `_load_frame` of dataset/kubric.py:410-445, dataset/gso.py:257-290 and
  * dataset/omniobject3d.py:221-258 and the image loop of demo.py:236-256 - an 8-bit RGB(A) frame of any size put on a background, resized with
  * Pillow's Image.ANTIALIAS (Lanczos, a = 3), its mask resized with Image.NEAREST, divided by 255. On 8-bit images Pillow's resampler is integer
