@@ -4,6 +4,7 @@ Host-side plumbing only: layout checks, output allocation, stream hand-off, auto
 All arithmetic of the hot path happens in forge_amd/csrc/*.hip. There is no CPU implementation
 here: calling these ops with CPU tensors (or without the built library) raises.
 """
+import ctypes
 import math
 import os
 
@@ -174,12 +175,9 @@ class _RenderRays(torch.autograd.Function):
         dfeat = _empty_like_cl(feat_cl)
         ddens = torch.empty_like(dens_c)
         dcam = torch.empty_like(cam_c) if ctx.needs_input_grad[2] else None        # pose refinement / joint training
-        L = _lib.lib()
-        ws_bytes = L.forge_render_bwd_ws_bytes(V, C, Hr, Wr, S, 0 if dcam is None else 1)
-        if ws_bytes < 0:
-            raise RuntimeError("forge_amd: forge_render_bwd_ws_bytes rejected V=%d C=%d Hr=%d Wr=%d S=%d" % (V, C, Hr, Wr, S))
+        ws_bytes = _lib.size_query("forge_render_bwd_ws_bytes", V, C, Hr, Wr, S, 0 if dcam is None else 1)
         ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=feat_cl.device)   # per-sample (dL/dd_s, T_s d_s) of every ray: 8 V Hr Wr S bytes
-        _lib.check(L.forge_render_bwd(
+        _lib.check(_lib.lib().forge_render_bwd(
             _lib.ptr(feat_cl), _lib.ptr(dens_c), _lib.ptr(cam_c), _lib.ptr(view2vol),
             _lib.ptr(g_feat), _lib.ptr(g_opac), _lib.ptr(g_depth), _lib.ptr(dfeat), _lib.ptr(ddens), _lib.ptr(dcam),
             V, nvol, C, D, H, W, Hr, Wr, S, zmin, zmax, half[0], half[1], half[2], _lib.ptr(ws), ws_bytes, _lib.current_stream()),
@@ -226,14 +224,67 @@ def resize_bilinear(x, Ho, Wo):
     return _ResizeBilinear.apply(x, int(Ho), int(Wo))
 
 
-def attention_applies(q, k, v):
-    """forge_attention_fwd's domain: fp32 on the MI355X, no autograd graph wanted, one head of 64 channels, token counts multiples of 64,
-    q / k [B,N,64] and v [B,Nk,64] or [1,Nk,64] (shared)."""
+class _Switch:
+    """An opt-in path: off unless `env` is "1" (read once, at import) or the public function named `setter` turned it on."""
+
+    def __init__(self, env, setter):
+        self.on, self.setter = os.environ.get(env, "0") == "1", setter
+
+    def set(self, flag):
+        if not isinstance(flag, bool):
+            raise TypeError("%s takes True or False (got %r)" % (self.setter, flag))
+        prev, self.on = self.on, flag
+        return prev
+
+
+def _finite_scalar(x, lo, strict):
+    """x is a finite int or float (never a bool), above lo (strict) or at least lo."""
+    return isinstance(x, (int, float)) and not isinstance(x, bool) and math.isfinite(x) and (x > lo if strict else x >= lo)
+
+
+def _tensor_desc(t):
+    """A tensor as this family's error messages show it; anything else by its repr."""
+    return "%s %s strides %s %s" % (tuple(t.shape), str(t.dtype).replace("torch.", ""), tuple(t.stride()), t.device) if torch.is_tensor(t) else repr(t)
+
+
+def _empty_f32(dev, *shape):
+    """An fp32 tensor that a kernel writes in full: no zero-fill."""
+    return torch.empty(*shape, dtype=torch.float32, device=dev)
+
+
+def _bwd_workspace(query, dev, *args):
+    """(workspace, its byte count) of a backward entry, sized by the entry's host size query; never an empty allocation."""
+    nbytes = _lib.size_query(query, *args)
+    return _empty_f32(dev, max(nbytes // 4, 4)), nbytes
+
+
+def _attention_domain(q, k, v):
+    """What forge_attention_fwd / _fwd_lse / _bwd take (attention_applies' docstring), whatever the grad mode."""
     return (q.is_cuda and k.device == q.device and v.device == q.device                 # raw pointers go to the kernel: all three on q's HIP device
-            and q.dtype == torch.float32 and k.dtype == torch.float32 and v.dtype == torch.float32 and not torch.is_grad_enabled()
+            and q.dtype == torch.float32 and k.dtype == torch.float32 and v.dtype == torch.float32
             and q.dim() == 3 and k.dim() == 3 and v.dim() == 3 and q.shape[-1] == 64 and k.shape[-1] == 64 and v.shape[-1] == 64
             and q.shape[0] == k.shape[0] and v.shape[0] in (1, q.shape[0]) and v.shape[1] == k.shape[1]
             and q.shape[1] % 64 == 0 and k.shape[1] % 64 == 0 and q.shape[1] > 0 and k.shape[1] > 0)
+
+
+def attention_applies(q, k, v):
+    """forge_attention_fwd's domain: fp32 on the MI355X, no autograd graph wanted, one head of 64 channels, token counts multiples of 64,
+    q / k [B,N,64] and v [B,Nk,64] or [1,Nk,64] (shared)."""
+    return _attention_domain(q, k, v) and not torch.is_grad_enabled()
+
+
+def _sh_forward(q, k, v, want_lse):
+    """One forge_attention_fwd launch, or with want_lse one forge_attention_fwd_lse launch. Returns (out, lse or None, the contiguous operands,
+    v_rows): v_rows is the kernels' batch stride of v in rows, 0 for a value table shared by the batch."""
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    B, Nq, d = q.shape
+    Nk = k.shape[1]
+    v_rows = 0 if v.shape[0] == 1 and B > 1 else Nk
+    out = _empty_f32(q.device, B, Nq, d)
+    lse = _empty_f32(q.device, B, Nq) if want_lse else None
+    entry, outs = ("forge_attention_fwd_lse", (_lib.ptr(out), _lib.ptr(lse))) if want_lse else ("forge_attention_fwd", (_lib.ptr(out),))
+    _lib.check(getattr(_lib.lib(), entry)(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), v_rows, *outs, B, Nq, Nk, d, _lib.current_stream()), entry)
+    return out, lse, (q, k, v), v_rows
 
 
 @_lib.on_tensor_device
@@ -243,49 +294,34 @@ def attention(q, k, v):
     if not attention_applies(q, k, v):
         raise RuntimeError("forge_amd: ops.attention needs fp32 [B,N,64] tensors on the MI355X with token counts that are multiples of 64, outside autograd "
                            "(got q %s, k %s, v %s, grad mode %s)" % (tuple(q.shape), tuple(k.shape), tuple(v.shape), torch.is_grad_enabled()))
-    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-    B, Nq, d = q.shape
-    Nk = k.shape[1]
-    out = torch.empty(B, Nq, d, dtype=torch.float32, device=q.device)
-    _lib.check(_lib.lib().forge_attention_fwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), 0 if v.shape[0] == 1 and B > 1 else Nk, _lib.ptr(out), B, Nq, Nk, d,
-                                              _lib.current_stream()), "forge_attention_fwd")
-    return out
+    return _sh_forward(q, k, v, False)[0]
 
 
 # ---- differentiable attention (training), opt-in: forge_attention_fwd_lse / forge_attention_bwd. Off by default - with the switch off nothing
 # in the package calls the two entry points and every training attention stays on torch's differentiable ops, bit for bit as before.
-_attention_training = os.environ.get("FORGE_ATTENTION_TRAIN", "0") == "1"          # read once, at import
+_attention_training = _Switch("FORGE_ATTENTION_TRAIN", "set_attention_training")
 
 
 def set_attention_training(flag):
     """True: attentions inside an autograd graph run ops.attention_train (where attention_train_applies holds); False (the default, or
     FORGE_ATTENTION_TRAIN unset at import): they keep torch's matmul - softmax - matmul. Returns the previous setting."""
-    global _attention_training
-    if not isinstance(flag, bool):
-        raise TypeError("set_attention_training takes True or False (got %r)" % (flag,))
-    prev, _attention_training = _attention_training, flag
-    return prev
+    return _attention_training.set(flag)
 
 
 def attention_training():
     """The current setting of set_attention_training()."""
-    return _attention_training
+    return _attention_training.on
 
 
 def _attention_train_domain(q, k, v):
-    """attention_applies' shape / dtype / device rules without its grad-mode clause, plus: a value table shared by the batch (v [1,Nk,64], B > 1)
-    is a constant - forge_attention_bwd does not sum a gradient over the batch for it."""
-    return (q.is_cuda and k.device == q.device and v.device == q.device
-            and q.dtype == torch.float32 and k.dtype == torch.float32 and v.dtype == torch.float32
-            and q.dim() == 3 and k.dim() == 3 and v.dim() == 3 and q.shape[-1] == 64 and k.shape[-1] == 64 and v.shape[-1] == 64
-            and q.shape[0] == k.shape[0] and v.shape[0] in (1, q.shape[0]) and v.shape[1] == k.shape[1]
-            and q.shape[1] % 64 == 0 and k.shape[1] % 64 == 0 and q.shape[1] > 0 and k.shape[1] > 0
-            and not (v.shape[0] == 1 and q.shape[0] > 1 and v.requires_grad))
+    """_attention_domain, plus: a value table shared by the batch (v [1,Nk,64], B > 1) is a constant - forge_attention_bwd does not sum a
+    gradient over the batch for it."""
+    return _attention_domain(q, k, v) and not (v.shape[0] == 1 and q.shape[0] > 1 and v.requires_grad)
 
 
 def attention_train_applies(q, k, v):
     """ops.attention_train's domain, and the switch (set_attention_training / FORGE_ATTENTION_TRAIN=1) is on."""
-    return _attention_training and _attention_train_domain(q, k, v)
+    return _attention_training.on and _attention_train_domain(q, k, v)
 
 
 class _AttentionTrain(torch.autograd.Function):
@@ -294,15 +330,8 @@ class _AttentionTrain(torch.autograd.Function):
     @staticmethod
     @_lib.on_tensor_device
     def forward(ctx, q, k, v):
-        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        B, Nq, d = q.shape
-        Nk = k.shape[1]
-        out = torch.empty(B, Nq, d, dtype=torch.float32, device=q.device)
-        lse = torch.empty(B, Nq, dtype=torch.float32, device=q.device)
-        ctx.v_rows = 0 if v.shape[0] == 1 and B > 1 else Nk
-        _lib.check(_lib.lib().forge_attention_fwd_lse(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), ctx.v_rows, _lib.ptr(out), _lib.ptr(lse), B, Nq, Nk, d,
-                                                      _lib.current_stream()), "forge_attention_fwd_lse")
-        ctx.save_for_backward(q, k, v, out, lse)
+        out, lse, qkv, ctx.v_rows = _sh_forward(q, k, v, True)
+        ctx.save_for_backward(*qkv, out, lse)
         return out
 
     @staticmethod
@@ -314,7 +343,7 @@ class _AttentionTrain(torch.autograd.Function):
         dout = dout.contiguous()
         dq, dk = torch.empty_like(q), torch.empty_like(k)                       # written in full by the kernels: no zero-fills
         dv = torch.empty_like(v) if ctx.needs_input_grad[2] and ctx.v_rows else None
-        delta = torch.empty(B, Nq, dtype=torch.float32, device=q.device)
+        delta = _empty_f32(q.device, B, Nq)
         _lib.check(_lib.lib().forge_attention_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), ctx.v_rows, _lib.ptr(out), _lib.ptr(lse), _lib.ptr(dout),
                                                   _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(delta), B, Nq, Nk, d, _lib.current_stream()),
                    "forge_attention_bwd")
@@ -336,23 +365,19 @@ def attention_train(q, k, v):
 # ---- multi-head attention (the 2-D pose estimator's six blocks), opt-in: forge_attention_mh_fwd / forge_attention_mh_bwd. Off by default - with
 # the switch off nothing in the package calls the two entry points and MultiHeadAttention runs torch's bmm - softmax - bmm, bit for bit as before.
 # Independent of set_attention_training (which keeps its meaning: the single-head attentions of the 3-D estimator inside an autograd graph).
-_multihead_attention = os.environ.get("FORGE_ATTENTION_MH", "0") == "1"            # read once, at import
+_multihead_attention = _Switch("FORGE_ATTENTION_MH", "set_multihead_attention")
 
 
 def set_multihead_attention(flag):
     """True: MultiHeadAttention (forge_amd/pose_estimator_2d.py) runs ops.attention_mh / ops.attention_mh_train where attention_mh_applies holds;
     False (the default, or FORGE_ATTENTION_MH unset at import): it keeps torch's head split - bmm - softmax - bmm - head merge. Returns the
     previous setting."""
-    global _multihead_attention
-    if not isinstance(flag, bool):
-        raise TypeError("set_multihead_attention takes True or False (got %r)" % (flag,))
-    prev, _multihead_attention = _multihead_attention, flag
-    return prev
+    return _multihead_attention.set(flag)
 
 
 def multihead_attention():
     """The current setting of set_multihead_attention()."""
-    return _multihead_attention
+    return _multihead_attention.on
 
 
 def _mh_strides(t):
@@ -378,25 +403,23 @@ def attention_mh_applies(q, k, v, num_heads, pad_mask=None, attn_mask=None, drop
     """The dispatch predicate of MultiHeadAttention: the switch (set_multihead_attention / FORGE_ATTENTION_MH=1) is on, q / k / v are in the
     kernels' domain (fp32 HIP tensors on one device, heads of 64 channels, token counts multiples of 64, float4-addressable strides), there is no
     key-padding mask and no attention mask, and dropout is inactive (p == 0, or the module is in eval mode)."""
-    return (_multihead_attention and pad_mask is None and attn_mask is None and (dropout_p == 0 or not training)
+    return (_multihead_attention.on and pad_mask is None and attn_mask is None and (dropout_p == 0 or not training)
             and _attention_mh_domain(q, k, v, num_heads))
 
 
 def _mh_check(what, q, k, v, num_heads, scale):
-    if (_attention_mh_domain(q, k, v, num_heads) and isinstance(scale, (int, float)) and not isinstance(scale, bool)
-            and math.isfinite(scale) and scale > 0):
+    if _attention_mh_domain(q, k, v, num_heads) and _finite_scalar(scale, 0, True):
         return
-    desc = lambda t: "%s %s strides %s %s" % (tuple(t.shape), str(t.dtype).replace("torch.", ""), tuple(t.stride()), t.device) if torch.is_tensor(t) else repr(t)
     raise RuntimeError("forge_amd: ops.%s needs fp32 q [B,Nq,H*64] and k, v [B,Nk,H*64] on the MI355X with heads of 64 channels, token counts that are "
                        "multiples of 64, channel stride 1, the other strides multiples of 4 floats, 16-byte aligned storage and a finite positive scale "
-                       "(got num_heads %r, scale %r, q %s, k %s, v %s)" % (what, num_heads, scale, desc(q), desc(k), desc(v)))
+                       "(got num_heads %r, scale %r, q %s, k %s, v %s)" % (what, num_heads, scale, _tensor_desc(q), _tensor_desc(k), _tensor_desc(v)))
 
 
 def _mh_forward(q, k, v, num_heads, scale, want_lse):
     B, Nq, C = q.shape
     Nk = k.shape[1]
-    out = torch.empty(B, Nq, C, dtype=torch.float32, device=q.device)
-    lse = torch.empty(B, num_heads, Nq, dtype=torch.float32, device=q.device) if want_lse else None
+    out = _empty_f32(q.device, B, Nq, C)
+    lse = _empty_f32(q.device, B, num_heads, Nq) if want_lse else None
     _lib.check(_lib.lib().forge_attention_mh_fwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(out), _lib.ptr(lse), B, num_heads, Nq, Nk, 64,
                                                  *_mh_strides(q), *_mh_strides(k), *_mh_strides(v), *_mh_strides(out), scale, _lib.current_stream()),
                "forge_attention_mh_fwd")
@@ -432,10 +455,9 @@ class _AttentionMHTrain(torch.autograd.Function):
         B, Nq, C = q.shape
         Nk, H = k.shape[1], ctx.num_heads
         dout = dout.contiguous()
-        mk = lambda n: torch.empty(B, n, C, dtype=torch.float32, device=q.device)     # dense, written in full by the kernels: no zero-fills
-        dq, dk = mk(Nq), mk(Nk)
-        dv = mk(Nk) if ctx.needs_input_grad[2] else None
-        delta = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
+        dq, dk = _empty_f32(q.device, B, Nq, C), _empty_f32(q.device, B, Nk, C)          # dense, written in full by the kernels: no zero-fills
+        dv = _empty_f32(q.device, B, Nk, C) if ctx.needs_input_grad[2] else None
+        delta = _empty_f32(q.device, B, H, Nq)
         _lib.check(_lib.lib().forge_attention_mh_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(out), _lib.ptr(lse), _lib.ptr(dout), _lib.ptr(dq),
                                                      _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(delta), B, H, Nq, Nk, 64, *_mh_strides(q), *_mh_strides(k),
                                                      *_mh_strides(v), *_mh_strides(out), ctx.scale, _lib.current_stream()), "forge_attention_mh_bwd")
@@ -453,22 +475,18 @@ def attention_mh_train(q, k, v, num_heads, scale):
 # ---- token-row layers (LayerNorm / Linear / GELU around the attention kernels of both pose estimators), opt-in: forge_token_linear_fwd / _bwd,
 # forge_layer_norm_fwd / _bwd (csrc/token.hip). Off by default - with the switch off nothing in the package calls the entry points and the blocks
 # run nn.LayerNorm / nn.Linear / nn.GELU, bit for bit as before. Independent of set_attention_training and set_multihead_attention.
-_token_layers = os.environ.get("FORGE_TOKEN_LAYERS", "0") == "1"                   # read once, at import
+_token_layers = _Switch("FORGE_TOKEN_LAYERS", "set_token_layers")
 
 
 def set_token_layers(flag):
     """True: the transformer blocks of both pose estimators run their LayerNorm / Linear / GELU chains on ops.token_linear / ops.layer_norm where
     token_layers_applies holds; False (the default, or FORGE_TOKEN_LAYERS unset at import): they keep torch's modules. Returns the previous setting."""
-    global _token_layers
-    if not isinstance(flag, bool):
-        raise TypeError("set_token_layers takes True or False (got %r)" % (flag,))
-    prev, _token_layers = _token_layers, flag
-    return prev
+    return _token_layers.set(flag)
 
 
 def token_layers():
     """The current setting of set_token_layers()."""
-    return _token_layers
+    return _token_layers.on
 
 
 TOKEN_MAX_CHANNELS, TOKEN_MAX_LN_CHANNELS = 1024, 256
@@ -498,7 +516,7 @@ def _layer_norm_domain(x, gamma, beta, eps):
         return False
     K = x.shape[-1]
     return (K % 64 == 0 and 64 <= K <= TOKEN_MAX_LN_CHANNELS and _token_vec(gamma, K, x.device) and _token_vec(beta, K, x.device)
-            and isinstance(eps, (int, float)) and not isinstance(eps, bool) and math.isfinite(eps) and eps >= 0)
+            and _finite_scalar(eps, 0, False))
 
 
 def _token_domain(x, weight, bias=None, ln=None, act=None, residual=None):
@@ -527,15 +545,11 @@ def token_layers_applies(x, weight=None, bias=None, ln=None, act=None, residual=
     """The dispatch predicate of the pose estimators' blocks: the switch (set_token_layers / FORGE_TOKEN_LAYERS=1) is on, dropout is inactive
     (p == 0, or the module is in eval mode) and the arguments are in the kernels' domain - of ops.token_linear, or with weight None of
     ops.layer_norm (ln = (gamma, beta, eps))."""
-    if not _token_layers or (dropout_p != 0 and training):
+    if not _token_layers.on or (dropout_p != 0 and training):
         return False
     if weight is None:
         return isinstance(ln, (tuple, list)) and len(ln) == 3 and _layer_norm_domain(x, *ln)
     return _token_domain(x, weight, bias, ln, act, residual)
-
-
-def _token_desc(t):
-    return "%s %s strides %s %s" % (tuple(t.shape), str(t.dtype).replace("torch.", ""), tuple(t.stride()), t.device) if torch.is_tensor(t) else repr(t)
 
 
 def _token_check(what, x, weight, bias, ln, act, residual):
@@ -544,8 +558,8 @@ def _token_check(what, x, weight, bias, ln, act, residual):
     raise RuntimeError("forge_amd: ops.%s needs fp32 x [...,K] and weight [N,K] on the MI355X with K and N multiples of 64 up to %d (K <= %d under a "
                        "LayerNorm (gamma, beta, eps)), channel stride 1, one row stride that is a multiple of 4 floats, 16-byte aligned storage, act None "
                        "or 'gelu', bias [N] and residual [...,N] (got act %r, x %s, weight %s, bias %s, ln %s, residual %s)"
-                       % (what, TOKEN_MAX_CHANNELS, TOKEN_MAX_LN_CHANNELS, act, _token_desc(x), _token_desc(weight), _token_desc(bias),
-                          "(%s)" % ", ".join(_token_desc(t) for t in ln) if isinstance(ln, (tuple, list)) else repr(ln), _token_desc(residual)))
+                       % (what, TOKEN_MAX_CHANNELS, TOKEN_MAX_LN_CHANNELS, act, _tensor_desc(x), _tensor_desc(weight), _tensor_desc(bias),
+                          "(%s)" % ", ".join(_tensor_desc(t) for t in ln) if isinstance(ln, (tuple, list)) else repr(ln), _tensor_desc(residual)))
 
 
 def _layer_norm_check(what, x, gamma, beta, eps):
@@ -553,7 +567,7 @@ def _layer_norm_check(what, x, gamma, beta, eps):
         return
     raise RuntimeError("forge_amd: ops.%s needs fp32 x [...,K] on the MI355X with K a multiple of 64 up to %d, channel stride 1, one row stride that is a "
                        "multiple of 4 floats, 16-byte aligned storage, gamma / beta [K] and a finite eps >= 0 (got x %s, gamma %s, beta %s, eps %r)"
-                       % (what, TOKEN_MAX_LN_CHANNELS, _token_desc(x), _token_desc(gamma), _token_desc(beta), eps))
+                       % (what, TOKEN_MAX_LN_CHANNELS, _tensor_desc(x), _tensor_desc(gamma), _tensor_desc(beta), eps))
 
 
 _TOKEN_ACT = {None: 0, "gelu": 1}
@@ -563,12 +577,12 @@ def _token_forward(x, weight, bias, ln, act, residual, out, want_saved):
     """One forge_token_linear_fwd launch. Returns (y, stats or None, pre or None); stats / pre only when want_saved (the autograd form)."""
     (xr, ldx), N = _token_rows(x), weight.shape[0]
     R, K = xr.shape
-    y = torch.empty(x.shape[:-1] + (N,), dtype=torch.float32, device=x.device) if out is None else out
+    y = _empty_f32(x.device, x.shape[:-1] + (N,)) if out is None else out
     yr, ldy = _token_rows(y)
     rr, ldr = _token_rows(residual) if residual is not None else (None, 0)
     gamma, beta, eps = ln if ln is not None else (None, None, 0.0)
-    stats = torch.empty(R, 2, dtype=torch.float32, device=x.device) if want_saved and ln is not None else None
-    pre = torch.empty(R, N, dtype=torch.float32, device=x.device) if want_saved and act is not None else None
+    stats = _empty_f32(x.device, R, 2) if want_saved and ln is not None else None
+    pre = _empty_f32(x.device, R, N) if want_saved and act is not None else None
     _lib.check(_lib.lib().forge_token_linear_fwd(_lib.ptr(xr), ldx, _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(gamma), _lib.ptr(beta), float(eps),
                                                  _lib.ptr(rr), ldr, _lib.ptr(yr), ldy, _lib.ptr(pre), _lib.ptr(stats), R, K, N, _TOKEN_ACT[act],
                                                  _lib.current_stream()), "forge_token_linear_fwd")
@@ -584,7 +598,7 @@ def token_linear(x, weight, bias=None, ln=None, act=None, residual=None, out=Non
     _token_check("token_linear", x, weight, bias, ln, act, residual)
     if out is not None and not (_token_rows(out) is not None and out.device == x.device and out.shape == x.shape[:-1] + (weight.shape[0],)):
         raise RuntimeError("forge_amd: ops.token_linear: out must be fp32 %s on x's device, addressed like x (got %s)"
-                           % (tuple(x.shape[:-1] + (weight.shape[0],)), _token_desc(out)))
+                           % (tuple(x.shape[:-1] + (weight.shape[0],)), _tensor_desc(out)))
     det = lambda t: None if t is None else t.detach()
     y = _token_forward(x.detach(), weight.detach(), det(bias), None if ln is None else (ln[0].detach(), ln[1].detach(), ln[2]), act, det(residual),
                        det(out), False)[0]
@@ -613,18 +627,16 @@ class _TokenLinearTrain(torch.autograd.Function):
         R = xr.shape[0]
         dy = dy.contiguous()
         dyr = dy.view(R, N)
-        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=x.device)         # written in full by the kernels: no zero-fills
-        dx = new(x.shape) if need[0] else None
-        dw = new(N, K) if need[1] or need[2] else None                                # dbias is a by-product of the dW pass
-        db = new(N) if need[2] else None
-        dg = new(K) if ctx.has_ln and need[3] else None
-        dbt = new(K) if ctx.has_ln and need[4] else None
-        L = _lib.lib()
-        nbytes = L.forge_token_linear_bwd_ws_bytes(R, K, N, int(ctx.has_ln))
-        ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=x.device)
-        _lib.check(L.forge_token_linear_bwd(_lib.ptr(dyr), N, _lib.ptr(xr), ldx, _lib.ptr(weight), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(stats),
-                                            _lib.ptr(pre), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(dg), _lib.ptr(dbt), _lib.ptr(ws), nbytes, R, K, N,
-                                            _TOKEN_ACT[ctx.act], _lib.current_stream()), "forge_token_linear_bwd")
+        dev = x.device
+        dx = _empty_f32(dev, x.shape) if need[0] else None
+        dw = _empty_f32(dev, N, K) if need[1] or need[2] else None                    # dbias is a by-product of the dW pass
+        db = _empty_f32(dev, N) if need[2] else None
+        dg = _empty_f32(dev, K) if ctx.has_ln and need[3] else None
+        dbt = _empty_f32(dev, K) if ctx.has_ln and need[4] else None
+        ws, nbytes = _bwd_workspace("forge_token_linear_bwd_ws_bytes", dev, R, K, N, int(ctx.has_ln))
+        _lib.check(_lib.lib().forge_token_linear_bwd(_lib.ptr(dyr), N, _lib.ptr(xr), ldx, _lib.ptr(weight), _lib.ptr(gamma), _lib.ptr(beta),
+                                                     _lib.ptr(stats), _lib.ptr(pre), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(dg), _lib.ptr(dbt),
+                                                     _lib.ptr(ws), nbytes, R, K, N, _TOKEN_ACT[ctx.act], _lib.current_stream()), "forge_token_linear_bwd")
         return dx, (dw if need[1] else None), db, dg, dbt, (dy if need[5] else None), None, None
 
 
@@ -640,8 +652,8 @@ def token_linear_train(x, weight, bias=None, ln=None, act=None, residual=None):
 def _layer_norm_forward(x, gamma, beta, eps, want_stats):
     xr, ldx = _token_rows(x)
     R, K = xr.shape
-    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-    stats = torch.empty(R, 2, dtype=torch.float32, device=x.device) if want_stats else None
+    y = _empty_f32(x.device, x.shape)
+    stats = _empty_f32(x.device, R, 2) if want_stats else None
     _lib.check(_lib.lib().forge_layer_norm_fwd(_lib.ptr(xr), ldx, _lib.ptr(gamma), _lib.ptr(beta), float(eps), _lib.ptr(y), K, _lib.ptr(stats), R, K,
                                                _lib.current_stream()), "forge_layer_norm_fwd")
     return y, stats
@@ -673,13 +685,11 @@ class _LayerNormTrain(torch.autograd.Function):
         xr, ldx = _token_rows(x)
         R, K = xr.shape
         dyr = dy.contiguous().view(R, K)
-        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=x.device)
-        dx, dg, dbt = (new(x.shape) if need[0] else None), (new(K) if need[1] else None), (new(K) if need[2] else None)
-        L = _lib.lib()
-        nbytes = L.forge_layer_norm_bwd_ws_bytes(R, K)
-        ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=x.device)
-        _lib.check(L.forge_layer_norm_bwd(_lib.ptr(dyr), K, _lib.ptr(xr), ldx, _lib.ptr(gamma), _lib.ptr(stats), _lib.ptr(dx), _lib.ptr(dg), _lib.ptr(dbt),
-                                          _lib.ptr(ws), nbytes, R, K, _lib.current_stream()), "forge_layer_norm_bwd")
+        dev = x.device
+        dx, dg, dbt = (_empty_f32(dev, x.shape) if need[0] else None), (_empty_f32(dev, K) if need[1] else None), (_empty_f32(dev, K) if need[2] else None)
+        ws, nbytes = _bwd_workspace("forge_layer_norm_bwd_ws_bytes", dev, R, K)
+        _lib.check(_lib.lib().forge_layer_norm_bwd(_lib.ptr(dyr), K, _lib.ptr(xr), ldx, _lib.ptr(gamma), _lib.ptr(stats), _lib.ptr(dx), _lib.ptr(dg),
+                                                   _lib.ptr(dbt), _lib.ptr(ws), nbytes, R, K, _lib.current_stream()), "forge_layer_norm_bwd")
         return dx, dg, dbt, None
 
 
@@ -692,7 +702,6 @@ def layer_norm_train(x, gamma, beta, eps=1e-5):
 
 def token_rows_plan(R, K, N):
     """(chunks, chunk_rows) of forge_token_linear_bwd's sums over rows (dW, dbias): host arithmetic on the shape alone (forge_token_rows_plan)."""
-    import ctypes
     c, r = ctypes.c_int(0), ctypes.c_int(0)
     _lib.check(_lib.lib().forge_token_rows_plan(int(R), int(K), int(N), ctypes.byref(c), ctypes.byref(r)), "forge_token_rows_plan")
     return c.value, r.value
@@ -717,7 +726,7 @@ def module_token_linear(x, weight, bias, norm=None, act=None, residual=None, dro
     """The modules' dispatch of one `residual + act(linear(norm(x)))` site: the fused launch (ops.token_linear_train inside an autograd graph, else
     ops.token_linear) when token_layers_applies holds, else None - the caller then runs its stock statements. norm: an nn.LayerNorm or None; act: an
     nn.GELU (exact erf) or None."""
-    if not _token_layers or site in TOKEN_SITES_ON_TORCH:
+    if not _token_layers.on or site in TOKEN_SITES_ON_TORCH:
         return None
     ln = None
     if norm is not None:
@@ -735,7 +744,7 @@ def module_token_linear(x, weight, bias, norm=None, act=None, residual=None, dro
 
 def module_layer_norm(x, norm, site=None):
     """The modules' dispatch of one stand-alone nn.LayerNorm site: ops.layer_norm(_train) when token_layers_applies holds, else None."""
-    if not _token_layers or site in TOKEN_SITES_ON_TORCH or not torch.is_tensor(x) or x.dim() < 1:
+    if not _token_layers.on or site in TOKEN_SITES_ON_TORCH or not torch.is_tensor(x) or x.dim() < 1:
         return None
     ln = _plain_layer_norm(norm, x.shape[-1])
     if ln is None or not token_layers_applies(x, ln=ln):
@@ -820,7 +829,6 @@ def mesh_case_table():
     tet_corner [6][4], tet_flip [6], tet_edge [6][2], case_ntri [16], case_tri [16][2][3] (include/forge_hip.h section g1)."""
     global _mesh_table
     if _mesh_table is None:
-        import ctypes
         buf = (ctypes.c_int * MESH_TABLE_INTS)()
         _lib.check(_lib.lib().forge_mesh_case_table(buf, MESH_TABLE_INTS), "forge_mesh_case_table")
         v = list(buf)
@@ -885,14 +893,6 @@ def _density_volume(fn, density, level=None):
     return n, D, H, W, level
 
 
-def _size_query(name, *args):
-    """A host-side size query of the library: a negative result is an error code, raised with the library's message."""
-    b = int(getattr(_lib.lib(), name)(*args))
-    if b < 0:
-        _lib.check(b, name)
-    return b
-
-
 def _row_lead(n, offsets):
     """Leading dimensions of mesh rows: [n, rows, ...] padded (offsets None), [rows, ...] packed."""
     return (n,) if offsets is None else ()
@@ -923,7 +923,7 @@ def mesh_count(density, level=0.5):
     per volume, workspace): the workspace goes to mesh_emit together with the same density and level. Nothing is read back."""
     n, D, H, W, level = _density_volume("mesh_count", density, level)
     _require_cuda(density)
-    nbytes = _size_query("forge_mesh_workspace_bytes", n, D, H, W)
+    nbytes = _lib.size_query("forge_mesh_workspace_bytes", n, D, H, W)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=density.device)
     counts = torch.empty(n, 2, dtype=torch.int32, device=density.device)
     _lib.check(_lib.lib().forge_mesh_count(_lib.ptr(density.detach()), n, D, H, W, level, _lib.ptr(ws), nbytes, _lib.ptr(counts), _lib.current_stream()),
@@ -944,7 +944,7 @@ def mesh_emit(density, workspace, counts, max_vertices, max_faces, level=0.5, vo
     max_vertices, max_faces = int(max_vertices), int(max_faces)
     if max_vertices < 0 or max_faces < 0:
         raise ValueError("mesh_emit: negative capacity (%d, %d)" % (max_vertices, max_faces))
-    nbytes = _size_query("forge_mesh_workspace_bytes", n, D, H, W)
+    nbytes = _lib.size_query("forge_mesh_workspace_bytes", n, D, H, W)
     dev = density.device
     _check_tensors("mesh_emit", [("workspace", workspace, nbytes, torch.uint8), ("counts", counts, (n, 2), torch.int32),
                                  ("offsets", offsets, (n, 2), torch.int32)], dev)
@@ -1044,7 +1044,7 @@ def surface_sample(vertices, faces, counts, n_samples, offsets=None):
     mv, mf = int(vertices.shape[-2]), int(faces.shape[-2])
     dev = _check_tensors("surface_sample", [("vertices", vertices, lead + (mv, 3), torch.float32), ("faces", faces, lead + (mf, 3), torch.int32),
                                          ("counts", counts, (n, 2), torch.int32), ("offsets", offsets, (n, 2), torch.int32)])
-    nbytes = _size_query("forge_surface_sample_workspace_bytes", n, mf, 0 if offsets is None else 1)
+    nbytes = _lib.size_query("forge_surface_sample_workspace_bytes", n, mf, 0 if offsets is None else 1)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     points = torch.empty(n, n_samples, 3, dtype=torch.float32, device=dev)
     normals = torch.empty(n, n_samples, 3, dtype=torch.float32, device=dev)
@@ -1086,7 +1086,6 @@ def geom_metrics(d2_ab, idx_ab, d2_ba, idx_ba, normals_a=None, normals_b=None, a
     float64. normals_a [B,Na,3] and normals_b [B,Nb,3]: both or neither; thresholds: up to GEOM_MAX_THRESHOLDS finite numbers (host). Returns
     (out [B,GEOM_OUT_DOUBLES] float64, laid out as GEOM_SCALARS and GEOM_PER_THRESHOLD say, status [B] int32 with GEOM_EMPTY for a pair with an empty
     side). Nothing is read back."""
-    import ctypes
     tensors = (d2_ab, idx_ab, d2_ba, idx_ba)
     if not all(torch.is_tensor(t) for t in tensors) or not all(t is None or torch.is_tensor(t) for t in (normals_a, normals_b, a_count, b_count)):
         raise TypeError("geom_metrics: d2 / idx of both directions (and normals, counts) must be tensors")
@@ -1103,7 +1102,7 @@ def geom_metrics(d2_ab, idx_ab, d2_ba, idx_ba, normals_a=None, normals_b=None, a
                                        ("d2_ba", d2_ba, (B, Nb), torch.float32), ("idx_ba", idx_ba, (B, Nb), torch.int32),
                                        ("normals_a", normals_a, (B, Na, 3), torch.float32), ("normals_b", normals_b, (B, Nb, 3), torch.float32),
                                        ("a_count", a_count, (B,), torch.int32), ("b_count", b_count, (B,), torch.int32)])
-    npart = _size_query("forge_geom_metrics_partial_doubles", B)
+    npart = _lib.size_query("forge_geom_metrics_partial_doubles", B)
     partial = torch.empty(npart, dtype=torch.float64, device=dev)
     out = torch.empty(B, GEOM_OUT_DOUBLES, dtype=torch.float64, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev)
@@ -1178,7 +1177,7 @@ def align_step(q, p, state, xf, status, idx=None, d2=None, q_count=None, p_count
     scalars = [float(v) for v in (reject, reject_floor, tol, rank_tol, clamp2)]
     if not all(math.isfinite(v) and v >= 0.0 for v in scalars[:3]) or not 0.0 <= scalars[3] < 1.0 or not scalars[4] >= 0.0:
         raise ValueError("align_step: reject, reject_floor, tol >= 0 and finite, rank_tol in [0, 1), clamp2 >= 0; got %r" % (scalars,))
-    npart = _size_query("forge_align_partial_doubles", B)
+    npart = _lib.size_query("forge_align_partial_doubles", B)
     partial = torch.empty(npart, dtype=torch.float64, device=dev)
     _lib.check(_lib.lib().forge_align_step(_lib.ptr(q.detach()), _lib.ptr(p.detach()), _lib.ptr(q_count), _lib.ptr(p_count), _lib.ptr(idx), _lib.ptr(d2),
                                            B, Nq, Np, 1 if with_scale else 0, 1 if update else 0, *scalars, _lib.ptr(partial), _lib.ptr(state),
@@ -1225,7 +1224,7 @@ def components_label(density, level=0.5, want_labels=True):
     components_select together with the same density. Nothing is read back."""
     n, D, H, W, level = _density_volume("components_label", density, level)
     _require_cuda(density)
-    nbytes = _size_query("forge_components_workspace_bytes", n, D, H, W)
+    nbytes = _lib.size_query("forge_components_workspace_bytes", n, D, H, W)
     dev = density.device
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     labels = torch.empty(n, D, H, W, dtype=torch.int32, device=dev) if want_labels else None
@@ -1244,7 +1243,7 @@ def components_stats(density, workspace, max_components):
     kmax = int(max_components)
     if kmax < 0:
         raise ValueError("components_stats: max_components=%d must not be negative" % kmax)
-    nbytes = _size_query("forge_components_workspace_bytes", n, D, H, W)
+    nbytes = _lib.size_query("forge_components_workspace_bytes", n, D, H, W)
     _check_tensors("components_stats", [("workspace", workspace, nbytes, torch.uint8)], density.device)
     _require_cuda(density, workspace)
     dev = density.device
@@ -1269,7 +1268,7 @@ def components_select(density, workspace, keep_largest=True, min_voxels=1, min_f
         raise ValueError("components_select: min_voxels=%d must be at least 1" % min_voxels)
     if not 0.0 <= min_fraction <= 1.0:
         raise ValueError("components_select: min_fraction=%r must lie in [0, 1]" % min_fraction)
-    nbytes = _size_query("forge_components_workspace_bytes", n, D, H, W)
+    nbytes = _lib.size_query("forge_components_workspace_bytes", n, D, H, W)
     _check_tensors("components_select", [("workspace", workspace, nbytes, torch.uint8)], density.device)
     _require_cuda(density, workspace)
     out = torch.empty_like(density)

@@ -1,6 +1,7 @@
 """CPU: the C-ABI library loads and exports every symbol include/forge_hip.h declares; argument
 validation returns the documented codes without touching a GPU; the Python surface keeps the
 reference's state_dict keys."""
+import ctypes
 import os
 import re
 
@@ -28,6 +29,129 @@ def test_header_symbols_exported(built_lib):
         assert hasattr(h, s), "libforge_hip.so does not export %s" % s
     # and the ctypes binding table covers exactly the header
     assert sorted(_lib.SIGNATURES) == syms
+
+
+_P, _I, _LL, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_double
+
+
+def declared_prototypes(src=None):
+    """{name: (result class, [argument classes])} of every declaration of include/forge_hip.h (or of `src`): the header's conventions restated
+    word by word, independently of forge_amd/_lib.py's parser. Anything with a `*` and forge_stream_t are pointers; long long, int, float and
+    double are themselves; results are int, long long or const char*. What the conventions do not name comes back as None."""
+    if src is None:
+        src = open(os.path.join(ROOT, "include", "forge_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
+    src = "\n".join(line.split("//")[0] for line in src.split("\n") if not line.lstrip().startswith("#"))
+    words = lambda text: text.replace("*", " * ").split()
+    scalars = {("long", "long"): _LL, ("int",): _I, ("float",): _F, ("double",): _D}
+    results = {("int",): _I, ("long", "long"): _LL, ("const", "char", "*"): ctypes.c_char_p}
+
+    def argument(w):
+        if "*" in w or w[0] == "forge_stream_t":
+            return _P
+        if len(w) > 1 and w[-1] not in ("int", "long", "float", "double", "unsigned", "char", "short"):
+            w = w[:-1]                                                             # the parameter's name
+        return scalars.get(tuple(w))
+
+    out = {}
+    for m in re.finditer(r"\b(forge_[a-z0-9_]+)\s*\(", src):
+        before = src[:m.start()]
+        result = words(before[max(before.rfind(c) for c in ";{}") + 1:])          # since the end of the previous statement
+        params = [words(a) for a in src[m.end():src.index(")", m.end())].split(",")]
+        if params in ([[]], [["void"]]):
+            params = []
+        out[m.group(1)] = (results.get(tuple(result)), [argument(w) for w in params])
+    return out
+
+
+def test_binding_types_are_the_headers_for_every_declaration(built_lib):
+    """Argument classes and result class of every declared symbol, by the independent restatement above, against the derived tables of
+    forge_amd/_lib.py and against what lib() put on the loaded functions."""
+    protos = declared_prototypes()
+    assert sorted(protos) == declared_symbols() and len(protos) >= 126
+    L = _lib.lib()
+    for name, (res, args) in protos.items():
+        assert res is not None and None not in args, name
+        assert _lib.SIGNATURES[name] == args, name
+        assert (res is _LL) == (name in _lib._LL_RESULTS), name
+        fn = getattr(L, name)
+        assert list(fn.argtypes) == args and fn.restype is res, name
+    assert len(_lib._LL_RESULTS) == len(set(_lib._LL_RESULTS)) and set(_lib._LL_RESULTS) <= set(protos)
+
+
+def test_binding_known_answers(built_lib):
+    """Declarations that exercise each rule of the header reading, written out: no parameters, const char* and long long results, doubles,
+    const unsigned char*, a declaration over four lines."""
+    L, S = _lib.lib(), _lib.SIGNATURES
+    assert S["forge_last_error"] == [] and L.forge_last_error.restype is ctypes.c_char_p
+    assert S["forge_version"] == [] and L.forge_version.restype is _I and "forge_version" not in _lib._LL_RESULTS
+    assert S["forge_psnr"] == [_P, _LL, _LL, _LL, _LL, _P, _LL, _LL, _LL, _LL, _I, _I, _I, _I, _D, _P, _P, _P]
+    assert S["forge_align_step"] == [_P] * 6 + [_I] * 5 + [_D] * 5 + [_P] * 5 and S["forge_align_step"].count(_D) == 5
+    assert S["forge_ingest_rgba8"] == [_P, _I, _I, _I, _I, _LL, _LL, _P, _I, _P, _I, _I, _I, _I, _P, _LL, _P, _P, _P, _P]
+    assert S["forge_mesh_bake"] == [_P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _F, _F, _F, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _F, _F, _I, _F, _F, _I,
+                                    _F, _P, _P, _P, _P] and len(S["forge_mesh_bake"]) == 34
+    assert S["forge_render_bwd_ws_bytes"] == [_I] * 6 and "forge_render_bwd_ws_bytes" in _lib._LL_RESULTS
+    assert L.forge_render_bwd_ws_bytes.restype is _LL and L.forge_render_bwd.restype is _I
+    assert _F is not _D and _I is not _LL                                          # the classes the table tells apart are distinct ctypes types
+
+
+@pytest.mark.parametrize("decl", ["int forge_bad(const float* x, unsigned n, forge_stream_t stream);", "size_t forge_bad(int n);",
+                                  "int forge_bad(forge_vec3 v, int n);", "int forge_bad(int (*callback)(int), int n);",
+                                  "int forge_bad(long n);", "struct forge_vec3 { float x, y, z; };"])
+def test_header_reading_refuses_what_it_cannot_class(decl):
+    """An unsigned parameter, a size_t result, a struct by value (and a function pointer, a plain long, a struct definition): never skipped, never
+    guessed - a RuntimeError that quotes the declaration. The declarations around it are fine."""
+    text = '#ifdef __cplusplus\nextern "C" {\n#endif\ntypedef void* forge_stream_t; /* a stream */\nint forge_good(void);\n%s\n}\n' % decl
+    with pytest.raises(RuntimeError) as e:
+        _lib.parse_header(text)
+    assert " ".join(decl.split(";")[0].split()) in str(e.value)
+    good = _lib.parse_header(text.replace(decl, "long long\nforge_fine(const unsigned char* src,   // bytes\n  double, forge_stream_t stream);\nconst char *forge_msg();"))
+    assert good == {"forge_good": (_I, []), "forge_fine": (_LL, [_P, _D, _P]), "forge_msg": (ctypes.c_char_p, [])}
+
+
+def test_header_reading_names_a_missing_header(tmp_path):
+    missing = str(tmp_path / "include" / "forge_hip.h")
+    with pytest.raises(RuntimeError) as e:
+        _lib.load_header(missing)
+    assert missing in str(e.value)
+    assert os.path.samefile(_lib.HEADER_PATH, os.path.join(ROOT, "include", "forge_hip.h"))
+
+
+def test_header_is_read_once_per_process(built_lib, monkeypatch):
+    """lib() binds from the tables made at import: it never opens the header again."""
+    monkeypatch.setattr(_lib, "load_header", lambda path: pytest.fail("the header was read again"))
+    monkeypatch.setattr(_lib, "parse_header", lambda text: pytest.fail("the header was parsed again"))
+    monkeypatch.setattr(_lib, "_lib", None)                                        # force a fresh load of the library
+    L = _lib.lib()
+    assert L.forge_version() >= 100 and L.forge_last_error.restype is ctypes.c_char_p
+
+
+SWITCHES = [("attention_training", "FORGE_ATTENTION_TRAIN"), ("multihead_attention", "FORGE_ATTENTION_MH"), ("token_layers", "FORGE_TOKEN_LAYERS")]
+
+
+@pytest.mark.parametrize("name,env", SWITCHES)
+def test_opt_in_switches_share_their_behaviour(name, env):
+    """The three opt-in switches of ops.py are one thing said three times: off unless the variable is "1" at import, set_* takes a bool and nothing
+    else (the documented message), returns the previous value, and moves no other switch."""
+    from forge_amd import ops
+    get, set_ = getattr(ops, name), getattr(ops, "set_" + name)
+    others = [getattr(ops, n) for n, _ in SWITCHES if n != name]
+    assert get() is (os.environ.get(env, "0") == "1")                              # the default (no test leaves a switch moved)
+    start, before = get(), [o() for o in others]
+    try:
+        assert set_(True) is start and get() is True
+        assert set_(True) is True and set_(False) is True and get() is False and set_(False) is False
+        for bad in (1, 0, None, "1", 1.0):
+            with pytest.raises(TypeError) as e:
+                set_(bad)
+            assert str(e.value) == "set_%s takes True or False (got %r)" % (name, bad)
+            assert get() is False                                                  # a refused value changes nothing
+        set_(True)
+        assert [o() for o in others] == before
+    finally:
+        set_(start)
+    assert get() is start and [o() for o in others] == before
+    assert get.__doc__ and set_.__doc__ and "previous setting" in set_.__doc__
 
 
 def test_c_host_program_compiles_against_the_header():

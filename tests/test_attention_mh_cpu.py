@@ -4,36 +4,20 @@ off by default and type-checked, and with the switch ON the attention modules of
 give with it off (host tensors, masks and float64 are outside the kernels' domain: the stock statements run)."""
 import ctypes
 import os
-import re
 
 import pytest
 import torch
 
 from forge_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("forge_attention_mh_fwd", "forge_attention_mh_bwd")
-_P, _I, _LL, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
-
-
-def prototype_argtypes(name):
-    """The ctypes argument list the header's prototype of `name` implies."""
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "forge_hip.h")).read(), flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, src)
-    assert m, "include/forge_hip.h does not declare %s" % name
-    out = []
-    for arg in m.group(1).split(","):
-        arg = " ".join(arg.split())
-        out.append(_P if "*" in arg or arg.startswith("forge_stream_t") else _LL if arg.startswith("long long") else _F if arg.startswith("float")
-                   else _I if arg.startswith("int") else None)
-    return out
 
 
 def test_library_exports_and_header_and_signatures_agree(built_lib):
     h = ctypes.CDLL(built_lib)
     for name in NEW:
         assert hasattr(h, name), "libforge_hip.so does not export %s" % name
-        assert name in _lib.SIGNATURES and _lib.SIGNATURES[name] == prototype_argtypes(name), name
+        assert name in _lib.SIGNATURES, name                                   # its types against the header: tests/test_abi_and_surface.py, for every symbol
     assert len(_lib.SIGNATURES["forge_attention_mh_fwd"]) == 20 and len(_lib.SIGNATURES["forge_attention_mh_bwd"]) == 25
 
 

@@ -15,30 +15,15 @@ from forge_amd import _lib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("forge_token_linear_fwd", "forge_layer_norm_fwd", "forge_token_rows_plan", "forge_token_linear_bwd_ws_bytes", "forge_token_linear_bwd",
        "forge_layer_norm_bwd_ws_bytes", "forge_layer_norm_bwd")
-_P, _I, _LL, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
 DET_SLAB_BYTES = 64 << 20                                                       # csrc/common.h
-
-
-def prototype(name):
-    """(result type, ctypes argument list) the header's prototype of `name` implies."""
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "forge_hip.h")).read(), flags=re.S)
-    m = re.search(r"\b(int|long long)\s+%s\s*\(([^)]*)\)\s*;" % name, src)
-    assert m, "include/forge_hip.h does not declare %s" % name
-    out = []
-    for arg in m.group(2).split(","):
-        arg = " ".join(arg.split())
-        out.append(_P if "*" in arg or arg.startswith("forge_stream_t") else _LL if arg.startswith("long long") else _F if arg.startswith("float")
-                   else _I if arg.startswith("int") else None)
-    return m.group(1), out
 
 
 def test_library_exports_and_header_and_signatures_agree(built_lib):
     h = ctypes.CDLL(built_lib)
     for name in NEW:
         assert hasattr(h, name), "libforge_hip.so does not export %s" % name
-        res, args = prototype(name)
-        assert name in _lib.SIGNATURES and _lib.SIGNATURES[name] == args, name
-        assert (res == "long long") == (name in _lib._LL_RESULTS), name
+        assert name in _lib.SIGNATURES, name                                   # its types against the header: tests/test_abi_and_surface.py, for every symbol
+        assert name.endswith("_ws_bytes") == (name in _lib._LL_RESULTS), name   # the two byte counts are long long, the other five results int
     assert len(_lib.SIGNATURES["forge_token_linear_fwd"]) == 18 and len(_lib.SIGNATURES["forge_token_linear_bwd"]) == 21
 
 
