@@ -73,6 +73,12 @@ def mesh_metrics(pred, gt, **kw):
     return _mm(pred, gt, **kw)
 
 
+def point_mesh_distance(points, meshes, **kw):
+    """Exact point-to-triangle distances from points to the surface of meshes, on the device (forge_amd/geometry.py)."""
+    from .geometry import point_mesh_distance as _pmd
+    return _pmd(points, meshes, **kw)
+
+
 def install_reference_aliases():
     """Make `from models.model import FORGE` (the import lines of kubric_train_*.py, demo.py,
     kubric_eval.py) and `from models.perceptual_loss import VGGPerceptualLoss` resolve to this package: registers forge_amd's modules under the reference's

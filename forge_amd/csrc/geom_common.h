@@ -1,6 +1,8 @@
-// geom_common.h — what mesh.hip, bake.hip, geomdist.hip, components.hip, align.hip and metrics.hip share, written once (header only: no translation unit).
+// geom_common.h — what mesh.hip, bake.hip, geomdist.hip, tridist.hip, components.hip, align.hip and metrics.hip share, written once (header only: no
+// translation unit).
 //   wave / block primitives   wave_inclusive_scan, wave_sum, waves_before, block_exclusive_scan_inplace (integer scans: any order gives the same bits)
 //   row spans                 row_span, mesh_spans: the rows of a padded or packed mesh array that one volume owns (forge_hip.h sections g1, g2, g3)
+//   mesh rows                 MeshRows, mesh_rows, face_area, face_normal, clamp_count, apply_xf: what geomdist.hip and tridist.hip read a mesh and a pair by
 //   fixed-tree reductions     block_reduce256 / block_sum256 / block_max256: float64, ONE tree, so every caller keeps its bits
 //   host side                 ws_align, ws_layout, volume_dims_ok, workspace_ok, level_ok: the argument checks of the workspace entry points
 #pragma once
@@ -84,6 +86,58 @@ __device__ __forceinline__ MeshSpans mesh_spans(const int* __restrict__ offsets,
     MeshSpans s = {row_span(offsets, vol, 0, max_vertices), row_span(offsets, vol, 1, max_faces)};
     if (s.v.row0 < 0 || s.f.row0 < 0) s.v.room = s.f.room = 0;
     return s;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------ mesh rows
+// The mesh arguments of forge_surface_sample and forge_nn_triangles (section g3), as the kernels take them.
+struct MeshRows {
+    const float* vertices;
+    const int* faces;
+    const int* counts;
+    const int* offsets;
+    int max_vertices, max_faces;                   // per mesh (offsets == nullptr) or in all (packed)
+};
+
+// rows of mesh v: first vertex / face row and how many of each are valid (a mesh that overflowed its capacity keeps the prefix that fitted)
+__device__ __forceinline__ void mesh_rows(const MeshRows& m, int v, long long& v0, long long& f0, int& nv, int& nf) {
+    const MeshSpans s = mesh_spans(m.offsets, v, m.max_vertices, m.max_faces);      // a negative offset of either array: the mesh is never followed
+    v0 = s.v.row0;
+    f0 = s.f.row0;
+    nv = (int)max(min((long long)m.counts[2 * v], s.v.room), 0ll);
+    nf = (int)max(min((long long)m.counts[2 * v + 1], s.f.room), 0ll);
+}
+
+// A_f in float64 from the fp32 corners: 0.5 |cross(b - a, c - a)|; 0 for a face with an index outside 0 .. nv - 1
+__device__ __forceinline__ double face_area(const float* __restrict__ vert, const int* __restrict__ face, int nv) {
+    const int ia = face[0], ib = face[1], ic = face[2];
+    if ((unsigned)ia >= (unsigned)nv || (unsigned)ib >= (unsigned)nv || (unsigned)ic >= (unsigned)nv) return 0.0;
+    const double ax = vert[3ll * ia], ay = vert[3ll * ia + 1], az = vert[3ll * ia + 2];
+    const double e1x = (double)vert[3ll * ib] - ax, e1y = (double)vert[3ll * ib + 1] - ay, e1z = (double)vert[3ll * ib + 2] - az;
+    const double e2x = (double)vert[3ll * ic] - ax, e2y = (double)vert[3ll * ic + 1] - ay, e2z = (double)vert[3ll * ic + 2] - az;
+    const double cx = e1y * e2z - e1z * e2y, cy = e1z * e2x - e1x * e2z, cz = e1x * e2y - e1y * e2x;
+    return 0.5 * sqrt(cx * cx + cy * cy + cz * cz);
+}
+
+// n = normalize(cross(e1, e2)) in fp32, e1 = b - a, e2 = c - a: the face normal along the winding; n is left as it is (zero) when the cross product is zero
+__device__ __forceinline__ void face_normal(float e1x, float e1y, float e1z, float e2x, float e2y, float e2z, float& nx, float& ny, float& nz) {
+    const float cx = fmaf(e1y, e2z, -(e1z * e2y)), cy = fmaf(e1z, e2x, -(e1x * e2z)), cz = fmaf(e1x, e2y, -(e1y * e2x));
+    const float len = sqrtf(fmaf(cz, cz, fmaf(cy, cy, cx * cx)));
+    if (len > 0.f) {
+        nx = cx / len;
+        ny = cy / len;
+        nz = cz / len;
+    }
+}
+
+// a valid-row count of a pair: count[b] clamped into 0 .. N, N without counts
+__device__ __forceinline__ int clamp_count(const int* __restrict__ count, int b, int N) { return count != nullptr ? min(max(count[b], 0), N) : N; }
+
+// row-major 3x4 (s R | t) applied to a point in place: the ONE fma chain of section g3's transforms
+__device__ __forceinline__ void apply_xf(const float* __restrict__ m, float& x, float& y, float& z) {
+    const float x0 = x, y0 = y, z0 = z;
+    x = fmaf(m[2], z0, fmaf(m[1], y0, fmaf(m[0], x0, m[3])));
+    y = fmaf(m[6], z0, fmaf(m[5], y0, fmaf(m[4], x0, m[7])));
+    z = fmaf(m[10], z0, fmaf(m[9], y0, fmaf(m[8], x0, m[11])));
 }
 
 // ------------------------------------------------------------------------------------------------------------------ fixed-tree reductions

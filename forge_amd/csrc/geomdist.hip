@@ -41,34 +41,6 @@ constexpr int GEOM_BLOCKS = 64;                    // per-(pair, direction) part
 constexpr int GEOM_PARTIAL = 8;                    // doubles per partial: sum d, sum d^2, max d, count(d < tau_k) x 4, sum |n.n|
 
 // ------------------------------------------------------------------------------------------------------------------------ surface sampling
-struct MeshRows {
-    const float* vertices;
-    const int* faces;
-    const int* counts;
-    const int* offsets;
-    int max_vertices, max_faces;                   // per mesh (offsets == nullptr) or in all (packed)
-};
-
-// rows of mesh v: first vertex / face row and how many of each are valid (a mesh that overflowed its capacity keeps the prefix that fitted)
-__device__ __forceinline__ void mesh_rows(const MeshRows& m, int v, long long& v0, long long& f0, int& nv, int& nf) {
-    const MeshSpans s = mesh_spans(m.offsets, v, m.max_vertices, m.max_faces);      // a negative offset of either array: the mesh is never followed
-    v0 = s.v.row0;
-    f0 = s.f.row0;
-    nv = (int)max(min((long long)m.counts[2 * v], s.v.room), 0ll);
-    nf = (int)max(min((long long)m.counts[2 * v + 1], s.f.room), 0ll);
-}
-
-// A_f in float64 from the fp32 corners: 0.5 |cross(b - a, c - a)|; 0 for a face with an index outside 0 .. nv - 1
-__device__ __forceinline__ double face_area(const float* __restrict__ vert, const int* __restrict__ face, int nv) {
-    const int ia = face[0], ib = face[1], ic = face[2];
-    if ((unsigned)ia >= (unsigned)nv || (unsigned)ib >= (unsigned)nv || (unsigned)ic >= (unsigned)nv) return 0.0;
-    const double ax = vert[3ll * ia], ay = vert[3ll * ia + 1], az = vert[3ll * ia + 2];
-    const double e1x = (double)vert[3ll * ib] - ax, e1y = (double)vert[3ll * ib + 1] - ay, e1z = (double)vert[3ll * ib + 2] - az;
-    const double e2x = (double)vert[3ll * ic] - ax, e2y = (double)vert[3ll * ic + 1] - ay, e2z = (double)vert[3ll * ic + 2] - az;
-    const double cx = e1y * e2z - e1z * e2y, cy = e1z * e2x - e1x * e2z, cz = e1x * e2y - e1y * e2x;
-    return 0.5 * sqrt(cx * cx + cy * cy + cz * cz);
-}
-
 // cum[f0 + f] = A_0 + ... + A_f, float64, in a FIXED order: thread t sums its chunk in increasing f, thread 0 adds the 256 chunk sums in increasing
 // t, then every thread rewrites its chunk as (sum of the chunks before it) + its own running sum. status[v] = FORGE_GEOM_EMPTY iff the total is 0
 // or not finite.
@@ -145,13 +117,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void surface_sample_kernel(MeshRows
             px = fmaf(r2, e2x, fmaf(r1, e1x, ax));
             py = fmaf(r2, e2y, fmaf(r1, e1y, ay));
             pz = fmaf(r2, e2z, fmaf(r1, e1z, az));
-            const float cx = fmaf(e1y, e2z, -(e1z * e2y)), cy = fmaf(e1z, e2x, -(e1x * e2z)), cz = fmaf(e1x, e2y, -(e1y * e2x));
-            const float len = sqrtf(fmaf(cz, cz, fmaf(cy, cy, cx * cx)));
-            if (len > 0.f) {
-                nx = cx / len;
-                ny = cy / len;
-                nz = cz / len;
-            }
+            face_normal(e1x, e1y, e1z, e2x, e2y, e2z, nx, ny, nz);
         } else {
             f = -1;
         }
@@ -166,8 +132,6 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void surface_sample_kernel(MeshRows
 }
 
 // ----------------------------------------------------------------------------------------------------------------------- nearest neighbours
-__device__ __forceinline__ int clamp_count(const int* __restrict__ count, int b, int N) { return count != nullptr ? min(max(count[b], 0), N) : N; }
-
 __global__ __launch_bounds__(NN_THREADS) void nn_points_kernel(const float* __restrict__ q, const float* __restrict__ p,
                                                                const int* __restrict__ q_count, const int* __restrict__ p_count,
                                                                const float* __restrict__ xf, int Nq, int Np, float* __restrict__ d2_out,
@@ -183,13 +147,7 @@ __global__ __launch_bounds__(NN_THREADS) void nn_points_kernel(const float* __re
     const int i = q0 + (int)threadIdx.x;           // this lane's query
     const int il = min(i, Nq - 1);                 // a lane past the end scores a copy of the last row and writes nothing
     float qx = qb[3ll * il], qy = qb[3ll * il + 1], qz = qb[3ll * il + 2];
-    if (xf != nullptr) {
-        const float* m = xf + 12 * b;
-        const float x = qx, y = qy, z = qz;
-        qx = fmaf(m[2], z, fmaf(m[1], y, fmaf(m[0], x, m[3])));
-        qy = fmaf(m[6], z, fmaf(m[5], y, fmaf(m[4], x, m[7])));
-        qz = fmaf(m[10], z, fmaf(m[9], y, fmaf(m[8], x, m[11])));
-    }
+    if (xf != nullptr) apply_xf(xf + 12 * b, qx, qy, qz);
     if (q_xf != nullptr && i < Nq) {               // the queries as they are scored: the references of the caller's opposite direction
         float* o = q_xf + 3ll * ((long long)b * Nq + i);
         o[0] = qx;
@@ -262,8 +220,10 @@ struct GeomTau {
 
 // grid (GEOM_BLOCKS, 2, B): direction 0 scores A -> B (rows of A, normals of B gathered through idx), direction 1 B -> A.
 // partial[((b 2 + dir) GEOM_BLOCKS + block) 8 + ..] = sum d | sum d^2 | max d | count(d < tau_k), k = 0..3 | sum |n_from . n_to[idx]|
+// hit_ab / hit_ba (forge_geom_metrics_hits; both or neither): the "to" normal of row i is hit[i], row-aligned with the queries, and idx is not read.
 __global__ __launch_bounds__(256) void geom_partial_kernel(const float* __restrict__ d2_ab, const int* __restrict__ idx_ab,
                                                            const float* __restrict__ d2_ba, const int* __restrict__ idx_ba,
+                                                           const float* __restrict__ hit_ab, const float* __restrict__ hit_ba,
                                                            const float* __restrict__ normals_a, const float* __restrict__ normals_b,
                                                            const int* __restrict__ a_count, const int* __restrict__ b_count, int Na, int Nb,
                                                            GeomTau tau, double* __restrict__ partial) {
@@ -271,9 +231,10 @@ __global__ __launch_bounds__(256) void geom_partial_kernel(const float* __restri
     const int N = dir == 0 ? Na : Nb, M = dir == 0 ? Nb : Na;
     const int n = clamp_count(dir == 0 ? a_count : b_count, b, N);
     const float* d2 = (dir == 0 ? d2_ab : d2_ba) + (long long)b * N;
-    const int* idx = (dir == 0 ? idx_ab : idx_ba) + (long long)b * N;
+    const bool aligned = hit_ab != nullptr;
+    const int* idx = aligned ? nullptr : (dir == 0 ? idx_ab : idx_ba) + (long long)b * N;
     const float* nf = normals_a == nullptr ? nullptr : (dir == 0 ? normals_a : normals_b) + 3ll * b * N;
-    const float* nt = normals_a == nullptr ? nullptr : (dir == 0 ? normals_b : normals_a) + 3ll * b * M;
+    const float* nt = normals_a == nullptr ? nullptr : aligned ? (dir == 0 ? hit_ab : hit_ba) + 3ll * b * N : (dir == 0 ? normals_b : normals_a) + 3ll * b * M;
     double sd = 0.0, sd2 = 0.0, md = 0.0, sn = 0.0, cnt[FORGE_GEOM_MAX_THRESHOLDS] = {0.0, 0.0, 0.0, 0.0};
     for (int i = blockIdx.x * 256 + (int)threadIdx.x; i < n; i += GEOM_BLOCKS * 256) {
         const double v = (double)d2[i];
@@ -283,8 +244,8 @@ __global__ __launch_bounds__(256) void geom_partial_kernel(const float* __restri
         md = fmax(md, d);
 #pragma unroll
         for (int k = 0; k < FORGE_GEOM_MAX_THRESHOLDS; ++k) cnt[k] += (k < tau.n && d < tau.tau[k]) ? 1.0 : 0.0;
-        const int j = idx[i];
-        if (nf != nullptr && (unsigned)j < (unsigned)M) {
+        const int j = nf == nullptr ? -1 : aligned ? i : idx[i];        // the row of the "to" normal; without normals idx is not read (it may be null)
+        if (nf != nullptr && (aligned || (unsigned)j < (unsigned)M)) {
             const double dot = fma((double)nf[3ll * i + 2], (double)nt[3ll * j + 2],
                                    fma((double)nf[3ll * i + 1], (double)nt[3ll * j + 1], (double)nf[3ll * i] * (double)nt[3ll * j]));
             sn += fabs(dot);
@@ -409,30 +370,47 @@ extern "C" long long forge_geom_metrics_partial_doubles(int B) {
     return (long long)B * 2 * GEOM_BLOCKS * GEOM_PARTIAL;
 }
 
-extern "C" int forge_geom_metrics(const float* d2_ab, const int* idx_ab, const float* d2_ba, const int* idx_ba, const float* normals_a,
-                                  const float* normals_b, const int* a_count, const int* b_count, int B, int Na, int Nb, const double* tau, int n_tau,
-                                  double* partial, double* out, int* status, forge_stream_t stream) {
+// the one launch sequence of forge_geom_metrics (idx_*: the "to" normals gathered) and forge_geom_metrics_hits (hit_*: row-aligned)
+static int geom_metrics_launch(const char* fn, const float* d2_ab, const int* idx_ab, const float* d2_ba, const int* idx_ba, const float* hit_ab,
+                               const float* hit_ba, const float* normals_a, const float* normals_b, const int* a_count, const int* b_count, int B, int Na,
+                               int Nb, const double* tau, int n_tau, double* partial, double* out, int* status, forge_stream_t stream) {
     using namespace forge;
-    FORGE_REQUIRE(B >= 1 && Na >= 1 && Nb >= 1, FORGE_EINVAL, "forge_geom_metrics: B=%d Na=%d Nb=%d must be at least 1", B, Na, Nb);
-    FORGE_REQUIRE(n_tau >= 0 && n_tau <= FORGE_GEOM_MAX_THRESHOLDS, FORGE_EINVAL, "forge_geom_metrics: %d thresholds (at most %d)", n_tau,
-                  FORGE_GEOM_MAX_THRESHOLDS);
-    FORGE_REQUIRE(tau != nullptr || n_tau == 0, FORGE_EINVAL, "forge_geom_metrics: null pointer (tau) with %d thresholds", n_tau);
+    FORGE_REQUIRE(B >= 1 && Na >= 1 && Nb >= 1, FORGE_EINVAL, "%s: B=%d Na=%d Nb=%d must be at least 1", fn, B, Na, Nb);
+    FORGE_REQUIRE(n_tau >= 0 && n_tau <= FORGE_GEOM_MAX_THRESHOLDS, FORGE_EINVAL, "%s: %d thresholds (at most %d)", fn, n_tau, FORGE_GEOM_MAX_THRESHOLDS);
+    FORGE_REQUIRE(tau != nullptr || n_tau == 0, FORGE_EINVAL, "%s: null pointer (tau) with %d thresholds", fn, n_tau);
     GeomTau t;
     t.n = n_tau;
     for (int k = 0; k < FORGE_GEOM_MAX_THRESHOLDS; ++k) {
         t.tau[k] = k < n_tau ? tau[k] : 0.0;
-        FORGE_REQUIRE(std::isfinite(t.tau[k]), FORGE_EINVAL, "forge_geom_metrics: threshold %d = %g is not finite", k, t.tau[k]);
+        FORGE_REQUIRE(std::isfinite(t.tau[k]), FORGE_EINVAL, "%s: threshold %d = %g is not finite", fn, k, t.tau[k]);
     }
-    FORGE_REQUIRE(d2_ab && idx_ab && d2_ba && idx_ba && partial && out && status, FORGE_EINVAL, "forge_geom_metrics: null pointer");
-    FORGE_REQUIRE((normals_a == nullptr) == (normals_b == nullptr), FORGE_EINVAL, "forge_geom_metrics: give the normals of both sides, or of neither");
+    FORGE_REQUIRE(d2_ab && d2_ba && partial && out && status, FORGE_EINVAL, "%s: null pointer", fn);
     FORGE_REQUIRE(((unsigned long long)partial & 7ull) == 0 && ((unsigned long long)out & 7ull) == 0, FORGE_EINVAL,
-                  "forge_geom_metrics: partial and out must be 8-byte aligned");
-    FORGE_REQUIRE(B <= 65535, FORGE_ESHAPE, "forge_geom_metrics: B=%d pairs in one call (at most 65535)", B);
-    hipLaunchKernelGGL(geom_partial_kernel, dim3(GEOM_BLOCKS, 2, (unsigned)B), dim3(256), 0, (hipStream_t)stream, d2_ab, idx_ab, d2_ba, idx_ba, normals_a,
-                       normals_b, a_count, b_count, Na, Nb, t, partial);
-    FORGE_LAUNCH_CHECK("forge_geom_metrics");
+                  "%s: partial and out must be 8-byte aligned", fn);
+    FORGE_REQUIRE(B <= 65535, FORGE_ESHAPE, "%s: B=%d pairs in one call (at most 65535)", fn, B);
+    hipLaunchKernelGGL(geom_partial_kernel, dim3(GEOM_BLOCKS, 2, (unsigned)B), dim3(256), 0, (hipStream_t)stream, d2_ab, idx_ab, d2_ba, idx_ba, hit_ab,
+                       hit_ba, normals_a, normals_b, a_count, b_count, Na, Nb, t, partial);
+    FORGE_LAUNCH_CHECK(fn);
     hipLaunchKernelGGL(geom_finalize_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, (const double*)partial, a_count, b_count,
                        B, Na, Nb, n_tau, normals_a != nullptr ? 1 : 0, out, status);
-    FORGE_LAUNCH_CHECK("forge_geom_metrics");
+    FORGE_LAUNCH_CHECK(fn);
     return 0;
+}
+
+extern "C" int forge_geom_metrics(const float* d2_ab, const int* idx_ab, const float* d2_ba, const int* idx_ba, const float* normals_a,
+                                  const float* normals_b, const int* a_count, const int* b_count, int B, int Na, int Nb, const double* tau, int n_tau,
+                                  double* partial, double* out, int* status, forge_stream_t stream) {
+    FORGE_REQUIRE(idx_ab && idx_ba, FORGE_EINVAL, "forge_geom_metrics: null pointer");
+    FORGE_REQUIRE((normals_a == nullptr) == (normals_b == nullptr), FORGE_EINVAL, "forge_geom_metrics: give the normals of both sides, or of neither");
+    return geom_metrics_launch("forge_geom_metrics", d2_ab, idx_ab, d2_ba, idx_ba, nullptr, nullptr, normals_a, normals_b, a_count, b_count, B, Na, Nb, tau,
+                               n_tau, partial, out, status, stream);
+}
+
+extern "C" int forge_geom_metrics_hits(const float* d2_ab, const float* hit_ab, const float* d2_ba, const float* hit_ba, const float* normals_a,
+                                       const float* normals_b, const int* a_count, const int* b_count, int B, int Na, int Nb, const double* tau,
+                                       int n_tau, double* partial, double* out, int* status, forge_stream_t stream) {
+    const int given = (hit_ab != nullptr) + (hit_ba != nullptr) + (normals_a != nullptr) + (normals_b != nullptr);
+    FORGE_REQUIRE(given == 0 || given == 4, FORGE_EINVAL, "forge_geom_metrics_hits: give the normals and the hit normals of both sides, or none of the four");
+    return geom_metrics_launch("forge_geom_metrics_hits", d2_ab, nullptr, d2_ba, nullptr, hit_ab, hit_ba, normals_a, normals_b, a_count, b_count, B, Na, Nb,
+                               tau, n_tau, partial, out, status, stream);
 }

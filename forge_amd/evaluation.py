@@ -264,6 +264,7 @@ def evaluate_geometry(pred_meshes, gt_meshes, transform=None, align=None, **kw):
     **kw) - accuracy, completeness, Chamfer, Hausdorff, F-score and normal consistency as float64 device tensors, one entry per mesh pair.
     transform maps the predictions (canonical frame of view 0) into the ground truth's frame; where nobody knows it (predicted poses, photographs,
     meshes in their own object frame), align="icp" or a dict of geometry.align_points keywords estimates it on the device first and returns it
-    under 'alignment'. Not part of evaluate_all, whose outputs are the reference's."""
+    under 'alignment'. surface="triangles" (passed through **kw) scores each side's samples against the other side's triangles, not its
+    samples: the distance to the surface, free of the sampling floor. Not part of evaluate_all, whose outputs are the reference's."""
     from . import geometry
     return geometry.mesh_metrics(pred_meshes, gt_meshes, transform=transform, align=align, **kw)

@@ -12,7 +12,9 @@ fused volume: heads, extract_mesh, nvs.render_360, one bake over photographs and
 
 mesh_metrics says how good that geometry is (csrc/geomdist.hip, section g3): both surfaces are sampled deterministically (sample_surface), nearest
 neighbours are searched exactly in both directions and reduced in float64 to accuracy, completeness, Chamfer distance, Hausdorff distance, F-score
-and normal consistency (point_metrics). Mesh.from_ply / Mesh.from_obj load the ground truth.
+and normal consistency (point_metrics). Mesh.from_ply / Mesh.from_obj load the ground truth. mesh_metrics(surface="triangles") scores each
+side's samples against the other side's TRIANGLES instead (point_mesh_distance, csrc/tridist.hip, section g3b): the distance to the surface,
+without the floor that the spacing of the other side's samples puts under every sample-to-sample distance.
 
 label_components and keep_components say which voxels belong to the object (csrc/components.hip, section g4): a few-view reconstruction emits the
 object plus small detached blobs - floaters - and every stage above pays for them (extra shells, volume, samples, occluders). Components are
@@ -596,12 +598,19 @@ def sample_surface(meshes, n):
     meshes: a list of Mesh (packed into one launch) or the MeshBatch of extract_mesh with capacities (no host synchronisation: counts stay
     on the device). Returns points [n_mesh,n,3], normals [n_mesh,n,3] (the face normal along the winding: outward for extracted meshes), face
     [n_mesh,n] int32, bary [n_mesh,n,2], status [n_mesh] int32 (ops.GEOM_EMPTY for a mesh without area: its points are zero, its faces -1)."""
+    vertices, faces, counts, offsets = _surface_rows(meshes, "sample_surface")
+    return ops.surface_sample(vertices, faces, counts, n, offsets=offsets)
+
+
+def _surface_rows(meshes, fn):
+    """(vertices, faces, counts, offsets) as ops.surface_sample and ops.nn_triangles take them: the padded rows of a MeshBatch (offsets None, no
+    host synchronisation) or the packed rows of a Mesh / a list of Mesh."""
     if isinstance(meshes, MeshBatch):
-        return ops.surface_sample(meshes.vertices, meshes.faces, meshes.counts, n)
+        return meshes.vertices, meshes.faces, meshes.counts, None
     if isinstance(meshes, Mesh):
         meshes = [meshes]
-    (vertices, faces), counts, offsets, _ = _pack_rows(meshes, "sample_surface", ("vertices", "faces"), cast=True)
-    return ops.surface_sample(vertices, faces, counts, n, offsets=offsets)
+    (vertices, faces), counts, offsets, _ = _pack_rows(meshes, fn, ("vertices", "faces"), cast=True)
+    return vertices, faces, counts, offsets
 
 
 def _as_batch(t, what):
@@ -624,6 +633,22 @@ def _pack_transform(transform, B, dev):
     return T[:, :3, :].reshape(B, 12).contiguous(), T[:, :3, :3]
 
 
+def _rotate_normals(normals, lin):
+    """a similarity's linear part is s R: rotate, then renormalise (a zero normal stays zero)"""
+    rot = normals @ lin.transpose(1, 2)
+    ln = rot.norm(dim=2, keepdim=True)
+    return torch.where(ln > 0, rot / ln.clamp_min(1e-30), torch.zeros_like(rot)).contiguous()
+
+
+def _metrics_dict(out, status, thresholds):
+    res = {name: out[:, k] for k, name in enumerate(ops.GEOM_SCALARS)}
+    for name, first in ops.GEOM_PER_THRESHOLD:
+        for k, t in enumerate(thresholds):
+            res["%s@%g" % (name, t)] = out[:, first + k]
+    res["status"] = status
+    return res
+
+
 def point_metrics(a, b, normals_a=None, normals_b=None, thresholds=(0.01, 0.02, 0.05), transform=None, counts_a=None, counts_b=None):
     """Surface metrics between point sets a [B,Na,3] (the prediction) and b [B,Nb,3] (the ground truth), [N,3] for one pair, on the device:
     exact nearest neighbours in both directions (ops.nn_points) reduced in float64 (ops.geom_metrics). Returns a dict of float64 device tensors
@@ -642,20 +667,13 @@ def point_metrics(a, b, normals_a=None, normals_b=None, thresholds=(0.01, 0.02, 
         xf, lin = _pack_transform(transform, B, dev)
     if normals_a is not None:
         normals_a, normals_b = _as_batch(normals_a, "normals_a"), _as_batch(normals_b, "normals_b")
-        if xf is not None:                         # a similarity's linear part is s R: rotate, then renormalise (a zero normal stays zero)
-            rot = normals_a @ lin.transpose(1, 2)
-            ln = rot.norm(dim=2, keepdim=True)
-            normals_a = torch.where(ln > 0, rot / ln.clamp_min(1e-30), torch.zeros_like(rot)).contiguous()
+        if xf is not None:
+            normals_a = _rotate_normals(normals_a, lin)
     d2_ab, idx_ab, a_in_b = ops.nn_points(a, b, counts_a, counts_b, xf, return_transformed=True)
     d2_ba, idx_ba = ops.nn_points(b, a_in_b, counts_b, counts_a)
     thresholds = tuple(float(t) for t in thresholds)
     out, status = ops.geom_metrics(d2_ab, idx_ab, d2_ba, idx_ba, normals_a, normals_b, counts_a, counts_b, thresholds)
-    res = {name: out[:, k] for k, name in enumerate(ops.GEOM_SCALARS)}
-    for name, first in ops.GEOM_PER_THRESHOLD:
-        for k, t in enumerate(thresholds):
-            res["%s@%g" % (name, t)] = out[:, first + k]
-    res["status"] = status
-    return res
+    return _metrics_dict(out, status, thresholds)
 
 
 def _sampled(side, n, what):
@@ -667,7 +685,61 @@ def _sampled(side, n, what):
     return points, normals, counts
 
 
-def mesh_metrics(pred, gt, n=100_000, thresholds=(0.01, 0.02, 0.05), transform=None, align=None):
+PointMeshDistance = namedtuple("PointMeshDistance", "distance face closest normal")
+PointMeshDistance.__doc__ = """point_mesh_distance, device tensors: distance [B,N] float32 (to the closest triangle; +inf for a mesh without a valid face, 0
+for rows past `counts`), face [B,N] int32 (that triangle, -1 without one), closest [B,N,3] (the closest point, in the meshes' frame), normal [B,N,3]
+(the unit normal of that triangle along its winding; zero without one)."""
+
+
+def point_mesh_distance(points, meshes, transform=None, counts=None):
+    """The distance from points [B,N,3] ([N,3] for one mesh) to the surface of meshes - a Mesh, a list of Mesh (packed rows) or a MeshBatch
+    (padded rows, no host synchronisation), one mesh per batch entry: exact point-to-triangle distances (ops.nn_triangles, include/forge_hip.h
+    section g3b; what PyTorch3D calls point_mesh_face_distance, unsquared). transform ([4,4] or [B,4,4], a similarity) maps the points into the
+    meshes' frame first; counts [B] int32 on the device limits the valid rows. Returns a PointMeshDistance. Nothing is read back."""
+    q = _as_batch(points, "points")
+    ops._require_cuda(q)
+    vertices, faces, mcounts, offsets = _surface_rows(meshes, "point_mesh_distance")
+    if mcounts.shape[0] != q.shape[0]:
+        raise ValueError("point_mesh_distance: %d point sets against %d meshes" % (q.shape[0], mcounts.shape[0]))
+    xf = None if transform is None else _pack_transform(transform, q.shape[0], q.device)[0]
+    d2, face, closest, normal = ops.nn_triangles(q, vertices, faces, mcounts, offsets=offsets, q_count=counts, xf_q=xf, want_closest=True, want_normal=True)
+    return PointMeshDistance(d2.sqrt(), face, closest, normal)
+
+
+def _triangle_metrics(pred, gt, n, thresholds, transform):
+    """mesh_metrics(surface="triangles"): n samples of each side scored against the other side's triangles."""
+    if torch.is_tensor(pred):
+        raise TypeError("mesh_metrics: surface='triangles' scores against the prediction's triangles: pred must be a Mesh, a list of Mesh or a MeshBatch")
+    rows_a = _surface_rows(pred, "mesh_metrics")
+    pa, na, _, _, sa = ops.surface_sample(*rows_a[:3], n, offsets=rows_a[3])
+    ca = torch.where((sa & ops.GEOM_EMPTY) != 0, torch.zeros_like(sa), torch.full_like(sa, int(n)))      # an empty mesh has no samples
+    B, dev = pa.shape[0], pa.device
+    xf = lin = None
+    if transform is not None:
+        xf, lin = _pack_transform(transform, B, dev)
+    thresholds = tuple(float(t) for t in thresholds)
+    if torch.is_tensor(gt):                        # a point cloud: nearest points as in point_metrics, triangles only towards the prediction
+        pb = _as_batch(gt, "gt")
+        if pb.shape[0] != B:
+            raise ValueError("mesh_metrics: %d predictions against %d ground truths" % (B, pb.shape[0]))
+        d2_ab, _ = ops.nn_points(pa, pb, ca, None, xf)
+        d2_ba, _, _, _ = ops.nn_triangles(pb, *rows_a[:3], offsets=rows_a[3], xf_mesh=xf)
+        out, status = ops.geom_metrics_hits(d2_ab, None, d2_ba, None, a_count=ca, thresholds=thresholds)
+        return _metrics_dict(out, status, thresholds)
+    rows_b = _surface_rows(gt, "mesh_metrics")
+    if rows_b[2].shape[0] != B:
+        raise ValueError("mesh_metrics: %d predictions against %d ground truths" % (B, rows_b[2].shape[0]))
+    pb, nb, _, _, sb = ops.surface_sample(*rows_b[:3], n, offsets=rows_b[3])
+    cb = torch.where((sb & ops.GEOM_EMPTY) != 0, torch.zeros_like(sb), torch.full_like(sb, int(n)))
+    if lin is not None:
+        na = _rotate_normals(na, lin)
+    d2_ab, _, _, hit_ab = ops.nn_triangles(pa, *rows_b[:3], offsets=rows_b[3], q_count=ca, xf_q=xf, want_normal=True)
+    d2_ba, _, _, hit_ba = ops.nn_triangles(pb, *rows_a[:3], offsets=rows_a[3], q_count=cb, xf_mesh=xf, want_normal=True)      # pred's mesh in gt's frame
+    out, status = ops.geom_metrics_hits(d2_ab, hit_ab, d2_ba, hit_ba, na, nb, ca, cb, thresholds)
+    return _metrics_dict(out, status, thresholds)
+
+
+def mesh_metrics(pred, gt, n=100_000, thresholds=(0.01, 0.02, 0.05), transform=None, align=None, surface="samples"):
     """Chamfer distance, F-score and the other entries of point_metrics between surfaces: n samples of each side (sample_surface), then
     point_metrics. pred / gt: a Mesh, a list of Mesh or a MeshBatch (one pair per mesh); gt may also be a point cloud [N,3] / [B,N,3], and then
     no normal consistency is computed. transform ([4,4] or [B,4,4], a similarity) maps pred into the frame of gt: extracted meshes live in the
@@ -676,7 +748,14 @@ def mesh_metrics(pred, gt, n=100_000, thresholds=(0.01, 0.02, 0.05), transform=N
     keywords (and 'n', the samples per side of the alignment, default 20 000): align_meshes runs first on its own smaller sample, started from
     `transform` (its `init`), the float32 of what it finds is the transform everything is measured under, and the Alignment is returned under
     'alignment'. With MeshBatch inputs there is no host synchronisation (an empty volume shows as ops.GEOM_EMPTY in 'status' and NaN means), so
-    the whole chain can sit in a captured graph."""
+    the whole chain can sit in a captured graph.
+    surface="samples" (the default) measures from each sample to the nearest SAMPLE of the other side, which puts a floor of about
+    0.5 sqrt(area / n) under every distance; surface="triangles" measures to the other side's TRIANGLES (ops.nn_triangles: exact
+    point-to-triangle distances; the prediction's mesh is brought into the ground truth's frame by `transform`), so a mesh scored against itself
+    gives 0 at any n, and normal consistency compares each sample's normal with the normal of the face it hit. A ground truth given as a point
+    cloud is still searched by nearest points (its points are scored against the prediction's triangles), without normal consistency."""
+    if surface not in ("samples", "triangles"):
+        raise ValueError("mesh_metrics: surface must be 'samples' or 'triangles', got %r" % (surface,))
     alignment = None
     if align is not None:
         if not (align == "icp" or isinstance(align, dict)):
@@ -686,13 +765,16 @@ def mesh_metrics(pred, gt, n=100_000, thresholds=(0.01, 0.02, 0.05), transform=N
             kw.setdefault("init", transform)
         alignment = align_meshes(pred, gt, **kw)
         transform = alignment.transform.to(torch.float32)
-    pa, na, ca = _sampled(pred, n, "pred")
-    pb, nb, cb = _sampled(gt, n, "gt")
-    if pa.shape[0] != pb.shape[0]:
-        raise ValueError("mesh_metrics: %d predictions against %d ground truths" % (pa.shape[0], pb.shape[0]))
-    if na is None or nb is None:
-        na = nb = None
-    res = point_metrics(pa, pb, na, nb, thresholds=thresholds, transform=transform, counts_a=ca, counts_b=cb)
+    if surface == "triangles":
+        res = _triangle_metrics(pred, gt, n, thresholds, transform)
+    else:
+        pa, na, ca = _sampled(pred, n, "pred")
+        pb, nb, cb = _sampled(gt, n, "gt")
+        if pa.shape[0] != pb.shape[0]:
+            raise ValueError("mesh_metrics: %d predictions against %d ground truths" % (pa.shape[0], pb.shape[0]))
+        if na is None or nb is None:
+            na = nb = None
+        res = point_metrics(pa, pb, na, nb, thresholds=thresholds, transform=transform, counts_a=ca, counts_b=cb)
     if alignment is not None:
         res["alignment"] = alignment
     return res

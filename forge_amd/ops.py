@@ -1115,6 +1115,87 @@ def geom_metrics(d2_ab, idx_ab, d2_ba, idx_ba, normals_a=None, normals_b=None, a
     return out, status
 
 
+def nn_tile_faces():
+    """Faces per LDS tile of forge_nn_triangles: host only, no device is touched."""
+    return int(_lib.lib().forge_nn_tile_faces())
+
+
+@_lib.on_tensor_device
+def nn_triangles(q, vertices, faces, counts, offsets=None, q_count=None, xf_q=None, xf_mesh=None, want_closest=False, want_normal=False,
+                 workspace=None):
+    """forge_nn_triangles (section g3b): for every query q [B,Nq,3] the closest triangle of mesh b, brute force and exact in fp32's closest-point
+    form. The mesh rows as surface_sample takes them: vertices [B,max_vertices,3] / faces [B,max_faces,3] int32 with counts [B,2] (offsets None)
+    or [max_vertices,3] / [max_faces,3] with offsets [B,2] (packed). q_count [B] int32 on the device (None: all rows); xf_q / xf_mesh [B,12],
+    row-major 3x4 (s R | t) applied to the queries / to every vertex on load. Returns (d2 [B,Nq] float32, face [B,Nq] int32, closest [B,Nq,3] or
+    None, normal [B,Nq,3] or None): ties go to the lowest face; rows past q_count get (0, -1); no candidate face: (+inf, -1); faces with a bad
+    index or without area are never candidates. workspace: a uint8 tensor of forge_nn_triangles_workspace_bytes to stage the faces in (None: a
+    fresh one). Nothing is read back."""
+    tensors = (q, vertices, faces, counts)
+    optional = (offsets, q_count, xf_q, xf_mesh, workspace)
+    if not all(torch.is_tensor(t) for t in tensors) or not all(t is None or torch.is_tensor(t) for t in optional):
+        raise TypeError("nn_triangles: q, vertices, faces, counts (and offsets, q_count, xf_q, xf_mesh, workspace) must be tensors")
+    _require_cuda(*tensors, *optional)
+    if q.dim() != 3 or q.shape[2] != 3 or min(q.shape[:2]) < 1:
+        raise ValueError("nn_triangles: q must be [B,Nq,3] with B, Nq >= 1, got %s" % (tuple(q.shape),))
+    B, Nq = int(q.shape[0]), int(q.shape[1])
+    lead = _row_lead(B, offsets)
+    if vertices.dim() != len(lead) + 2 or faces.dim() != len(lead) + 2:
+        raise ValueError("nn_triangles: vertices and faces must be %s, got %s and %s"
+                         % ("[%d,rows,3]" % B if offsets is None else "[rows,3] (packed: offsets given)", tuple(vertices.shape), tuple(faces.shape)))
+    mv, mf = int(vertices.shape[-2]), int(faces.shape[-2])
+    nbytes = _lib.size_query("forge_nn_triangles_workspace_bytes", B, mf, 0 if offsets is None else 1)
+    want = [("q", q, (B, Nq, 3), torch.float32), ("vertices", vertices, lead + (mv, 3), torch.float32), ("faces", faces, lead + (mf, 3), torch.int32),
+            ("counts", counts, (B, 2), torch.int32), ("offsets", offsets, (B, 2), torch.int32), ("q_count", q_count, (B,), torch.int32),
+            ("xf_q", xf_q, (B, 12), torch.float32), ("xf_mesh", xf_mesh, (B, 12), torch.float32)]
+    if workspace is not None:
+        want.append(("workspace", workspace, nbytes, torch.uint8))
+    dev = _check_tensors("nn_triangles", want)
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    rows3 = ((B, Nq, 3), torch.float32)
+    d2, face, closest, normal = _out_or_empty("nn_triangles", None, [((B, Nq), torch.float32), ((B, Nq), torch.int32), rows3 if want_closest else None,
+                                                                      rows3 if want_normal else None], dev)
+    _lib.check(_lib.lib().forge_nn_triangles(_lib.ptr(q.detach()), _lib.ptr(q_count), _lib.ptr(None if xf_q is None else xf_q.detach()),
+                                             _lib.ptr(vertices.detach()), _lib.ptr(faces), _lib.ptr(counts), _lib.ptr(offsets),
+                                             _lib.ptr(None if xf_mesh is None else xf_mesh.detach()), B, Nq, mv, mf, _lib.ptr(workspace),
+                                             int(workspace.numel()), _lib.ptr(d2), _lib.ptr(face), _lib.ptr(closest), _lib.ptr(normal),
+                                             _lib.current_stream()), "forge_nn_triangles")
+    return d2, face, closest, normal
+
+
+@_lib.on_tensor_device
+def geom_metrics_hits(d2_ab, hit_ab, d2_ba, hit_ba, normals_a=None, normals_b=None, a_count=None, b_count=None, thresholds=()):
+    """forge_geom_metrics_hits (section g3b): geom_metrics with row-aligned "to" normals - hit_ab [B,Na,3] and hit_ba [B,Nb,3], the `normal` of
+    nn_triangles, in place of idx_ab / idx_ba. normals_a, hit_ab, normals_b, hit_ba: all four or none (no normal consistency). Returns
+    (out [B,GEOM_OUT_DOUBLES] float64, status [B] int32), laid out as geom_metrics'. Nothing is read back."""
+    tensors = (d2_ab, d2_ba)
+    optional = (hit_ab, hit_ba, normals_a, normals_b, a_count, b_count)
+    if not all(torch.is_tensor(t) for t in tensors) or not all(t is None or torch.is_tensor(t) for t in optional):
+        raise TypeError("geom_metrics_hits: d2 of both directions (and hits, normals, counts) must be tensors")
+    _require_cuda(*tensors, *optional)
+    if d2_ab.dim() != 2 or d2_ba.dim() != 2 or d2_ab.shape[0] != d2_ba.shape[0] or min(tuple(d2_ab.shape) + tuple(d2_ba.shape)) < 1:
+        raise ValueError("geom_metrics_hits: d2_ab [B,Na] and d2_ba [B,Nb] with B, Na, Nb >= 1, got %s and %s" % (tuple(d2_ab.shape), tuple(d2_ba.shape)))
+    if sum(t is not None for t in (hit_ab, hit_ba, normals_a, normals_b)) not in (0, 4):
+        raise ValueError("geom_metrics_hits: give the normals and the hit normals of both sides, or none of the four")
+    thresholds = [float(t) for t in thresholds]
+    if len(thresholds) > GEOM_MAX_THRESHOLDS or not all(math.isfinite(t) for t in thresholds):
+        raise ValueError("geom_metrics_hits: at most %d finite thresholds, got %r" % (GEOM_MAX_THRESHOLDS, thresholds))
+    B, Na, Nb = int(d2_ab.shape[0]), int(d2_ab.shape[1]), int(d2_ba.shape[1])
+    dev = _check_tensors("geom_metrics_hits", [("d2_ab", d2_ab, (B, Na), torch.float32), ("hit_ab", hit_ab, (B, Na, 3), torch.float32),
+                                            ("d2_ba", d2_ba, (B, Nb), torch.float32), ("hit_ba", hit_ba, (B, Nb, 3), torch.float32),
+                                            ("normals_a", normals_a, (B, Na, 3), torch.float32), ("normals_b", normals_b, (B, Nb, 3), torch.float32),
+                                            ("a_count", a_count, (B,), torch.int32), ("b_count", b_count, (B,), torch.int32)])
+    npart = _lib.size_query("forge_geom_metrics_partial_doubles", B)
+    partial, out, status = _out_or_empty("geom_metrics_hits", None, [((npart,), torch.float64), ((B, GEOM_OUT_DOUBLES), torch.float64),
+                                                                     ((B,), torch.int32)], dev)
+    tau = (ctypes.c_double * GEOM_MAX_THRESHOLDS)(*thresholds)
+    det = lambda t: None if t is None else t.detach()                                                               # noqa: E731
+    _lib.check(_lib.lib().forge_geom_metrics_hits(_lib.ptr(d2_ab), _lib.ptr(det(hit_ab)), _lib.ptr(d2_ba), _lib.ptr(det(hit_ba)), _lib.ptr(det(normals_a)),
+                                                  _lib.ptr(det(normals_b)), _lib.ptr(a_count), _lib.ptr(b_count), B, Na, Nb, tau, len(thresholds),
+                                                  _lib.ptr(partial), _lib.ptr(out), _lib.ptr(status), _lib.current_stream()), "forge_geom_metrics_hits")
+    return out, status
+
+
 # ------------------------------------------------------------------------------------------------------------------------- alignment
 ALIGN_EMPTY, ALIGN_RANK, ALIGN_NONFINITE, ALIGN_CONVERGED = 1, 2, 4, 8      # status bits (FORGE_ALIGN_*)
 ALIGN_STATE_DOUBLES = 29

@@ -893,6 +893,64 @@ int forge_geom_metrics(const float* d2_ab, const int* idx_ab, const float* d2_ba
                        int* status, forge_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * g3b  Scoring samples against TRIANGLES (csrc/tridist.hip; the reduction in csrc/geomdist.hip): the distance from a point to a surface, not to
+ * a sampling of it. Between two samplings of n points of a surface of area A the nearest sample lies about 0.5 sqrt(A / n) away however good the
+ * reconstruction is; against the other side's triangles a mesh scored against itself gives 0 at any n. Brute force, as forge_nn_points.
+ *
+ * forge_nn_triangles  for each of B pairs and each query, the closest triangle of mesh b:
+ *   q [B][Nq][3] fp32; q_count [B] device int32, nullable (= Nq), clamped into 0 .. Nq; xf_q [B][12], nullable: applied to the QUERIES on load by
+ *             forge_nn_points' chain, x' = fma(m02, z, fma(m01, y, fma(m00, x, t0))) per row.
+ *   vertices, faces, counts [B][2], offsets [B][2] (nullable), max_vertices, max_faces  the arrays forge_surface_sample takes, in both layouts.
+ *   xf_mesh [B][12], nullable: applied to every VERTEX on load by the same chain - the mesh brought into the frame the queries are scored in.
+ *   candidates  every face of mesh b except: a face with an index outside 0 .. count_v - 1, and a face whose area A_f (forge_surface_sample's:
+ *             float64, from the fp32 corners BEFORE xf_mesh) is 0. Faces are taken in increasing index.
+ *   arithmetic  all fp32, in this order. A = a - q', B = b - q', C = c - q' per component (a, b, c the transformed corners); everything after
+ *             that is computed on A, B, C alone. ab = B - A, ac = C - A; with dot(u, v) = fma(uz, vz, fma(uy, vy, ux vx)):
+ *               n1 = dot(ab, A), n2 = dot(ac, A), n3 = dot(ab, B), n4 = dot(ac, B), n5 = dot(ab, C), n6 = dot(ac, C)
+ *               vc = fma(n1, n4, -(n3 n2)), vb = fma(n5, n2, -(n1 n6)), va = fma(n3, n6, -(n5 n4)), t34 = n3 - n4, t65 = n6 - n5
+ *             (n_k = -d_k of Ericson, Real-Time Collision Detection 5.1.5: the query is the origin). The Voronoi region of the triangle that
+ *             holds the query is the FIRST of these whose test holds, and it sets (vn, wn, den):
+ *               vertex A   n1 >= 0 and n2 >= 0                  (0, 0, 1)
+ *               vertex B   n3 <= 0 and n4 >= n3                 (1, 0, 1)
+ *               edge AB    vc <= 0 and n1 <= 0 and n3 >= 0      (n1, 0, n1 - n3)
+ *               vertex C   n6 <= 0 and n5 >= n6                 (0, 1, 1)
+ *               edge AC    vb <= 0 and n2 <= 0 and n6 >= 0      (0, n2, n2 - n6)
+ *               edge BC    va <= 0 and t34 >= 0 and t65 >= 0    (t65, t34, t34 + t65)
+ *               interior   otherwise                            (vb, vc, (va + vb) + vc)
+ *             r = 1 / den (ONE reciprocal on every path; the device's is within 1 ulp), v = vn r, w = wn r, and the closest point relative to
+ *             the query is P = fma(w, ac, fma(v, ab, A)) per component; d2_f = fma(Pz, Pz, fma(Py, Py, Px Px)). Evaluated with selects, no
+ *             branch; a NaN fails every test, takes the interior row and gives d2_f = NaN. No plane-distance formula and no |q|^2 + ...
+ *             expansion: the closest-point form keeps the error of the barycentrics second-order in the distance.
+ *   d2 [B][Nq] fp32 = min over the candidates of d2_f;  face [B][Nq] int32 = that f, relative to the mesh's first face row.
+ *   closest [B][Nq][3], nullable: q' + P of the winning face per component - the closest point, in the frame the queries were scored in.
+ *   normal [B][Nq][3], nullable: the unit normal of the winning face along its winding, forge_surface_sample's fp32 expression on the
+ *             (transformed) corners: without xf_mesh, bit for bit the normal sample_surface gives for that face.
+ *   A candidate wins only through `d2_f < best` (best starts at +inf): NaN never wins, ties go to the LOWEST face index. Rows at or past
+ *   q_count: d2 = 0, face = -1. A query with no winning face (no candidates, a NaN query): d2 = +inf, face = -1. closest and normal are zero
+ *   wherever face = -1.
+ *   workspace forge_nn_triangles_workspace_bytes(B, max_faces, packed = offsets != NULL) bytes, 16-byte aligned: one record of 12 floats per
+ *   face row (corners and normal; NaN for a face that is no candidate), written by a staging launch. Two launches: staging, then the search
+ *   with grid (query blocks of forge_nn_queries_per_block(), pairs), records walked in LDS tiles of forge_nn_tile_faces(); no split over the
+ *   faces, so no merge. FORGE_EINVAL: null q / counts / workspace / d2 / face (vertices / faces may be null with a zero capacity), B or Nq < 1,
+ *   a negative capacity, a workspace too small or unaligned. FORGE_ESHAPE: B > 65535, vertex or face rows beyond 2^31 - 1, Nq or max_faces
+ *   within a tile of 2^31.
+ *
+ * forge_geom_metrics_hits  forge_geom_metrics with ROW-ALIGNED "to" normals: hit_ab [B][Na][3] and hit_ba [B][Nb][3] (forge_nn_triangles'
+ *   `normal`) in place of idx_ab / idx_ba. The normal term of row i is |n_from[i] . hit[i]|, the same float64 fma chain z, y, x; a zero hit
+ *   adds 0. normals_a, hit_ab, normals_b, hit_ba: all four or none (NORMAL_CONSISTENCY is then NaN). Same outputs, partials, thresholds, status,
+ *   launches and errors as forge_geom_metrics; d2 of either direction may come from forge_nn_points or forge_nn_triangles.
+ * Nothing allocates, synchronises, reads the environment or uses atomics; every entry takes the stream; every output bit is reproducible.
+ */
+int forge_nn_tile_faces(void);
+long long forge_nn_triangles_workspace_bytes(int n_mesh, int max_faces, int packed);
+int forge_nn_triangles(const float* q, const int* q_count, const float* xf_q, const float* vertices, const int* faces, const int* counts,
+                       const int* offsets, const float* xf_mesh, int B, int Nq, int max_vertices, int max_faces, void* workspace,
+                       long long workspace_bytes, float* d2, int* face, float* closest, float* normal, forge_stream_t stream);
+int forge_geom_metrics_hits(const float* d2_ab, const float* hit_ab, const float* d2_ba, const float* hit_ba, const float* normals_a,
+                            const float* normals_b, const int* a_count, const int* b_count, int B, int Na, int Nb, const double* tau, int n_tau,
+                            double* partial, double* out, int* status, forge_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * g4  Connected components of density volumes, and dropping the floaters (csrc/components.hip): which voxels belong to the object. A few-view
  * reconstruction emits the object plus small detached blobs; every stage of g1 - g3 pays for them. The reference has no counterpart.
  *   density  [n][D][H][W] float32, as in g1;  level finite and > 0; a voxel is INSIDE iff d > level (strict, an fp32 compare - the one g1 makes):
