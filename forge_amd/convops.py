@@ -240,6 +240,7 @@ class _State:
     winograd = True                   # False: the direct implicit-GEMM kernel for every 3x3(x3) convolution
     wino_depth_nest = os.environ.get("FORGE_WINO_DEPTH_NEST", "1") != "0"     # False: the eval fusion's GRU launches stay on the four-point form
     wino_depth_nest4 = os.environ.get("FORGE_WINO_DEPTH_NEST4", "1") != "0"   # False: the nest stays on F(2, 3) (wino_depth_nest = False switches both off)
+    wino_w4 = os.environ.get("FORGE_WINO_W4", "1") != "0"                     # False: the F(4, 3) nest along H stays on F(2, 3) along W (tiles of 4 x 2, 24 points)
     wino_h4 = os.environ.get("FORGE_WINO_H4", "1") != "0"                     # False: the F(4, 3) nest stays on F(2, 3) along H (tiles of 2 x 2, 16 points)
     conv_fast_epilogue = os.environ.get("FORGE_CONV_FAST_EPILOGUE", "1") != "0"   # False: every launch of the wide kernel keeps the row-table epilogue
 
@@ -533,12 +534,12 @@ def wino_scene_chunk(b, D, H, W, C, views=1):
 
 
 def wino_fits(n, D, H, W, C, views=1, nest4=False, form=None):
-    """H, W even (H a multiple of the form's tile height), and every transformed operand ([n views D H/th W/2][C] floats per Winograd point, times the
+    """H, W even (multiples of the form's tile height and width), and every transformed operand ([n views D H/th W/tw][C] floats per Winograd point, times the
     operand rows per volume of `form`, a WinoForm - default: the plain transform's; nest4 = True names the F(4, 3) nest's) within the kernel's 32-bit
     buffer offsets."""
     form = form or WINO_FORMS["dn4" if nest4 else "points"]
-    rows = n * views * D * (H // form.th) * (W // 2) * form.rows
-    return H % form.th == 0 and W % 2 == 0 and rows * C * 4 <= MAX_OPERAND_BYTES
+    rows = n * views * D * (H // form.th) * (W // form.tw) * form.rows
+    return H % form.th == 0 and W % form.tw == 0 and rows * C * 4 <= MAX_OPERAND_BYTES
 
 
 @_lib.on_tensor_device
@@ -582,11 +583,24 @@ def wino_depth_nest4h_applies(R, D, Ht, Wt, Cout, Cin):
     return STATE.wino_h4 and wino_depth_nest4_applies(R, D, Ht, Wt, Cout, Cin)
 
 
+WINO_W4_MIN_C = 64    # four K-steps of 32 per loop: with fewer the point GEMM's short loops do not pay (why fusion_conv's K = C launches stay on F(2, 3))
+
+
+def wino_depth_nest4hw_applies(R, D, Ht, Wt, Cout, Cin):
+    """The launches that take the F(4, 3) nest with F(4, 3) along H AND W (WINO_DN4HW: 36 points on tiles of 4 x 4, 3/4 of WINO_DN4H's matrix-core work and
+    operand bytes): wino_depth_nest4h_applies on the form's OWN tile grid - Ht = H / 4, Wt = W / 4 (the caller has checked H % 4 == 0 and W % 4 == 0),
+    R = n D Ht Wt - with at least four K-steps per loop on the step's channel count C = Cin / 2 (the loops of a step run over [x | h], Cin = 2 C): C >=
+    WINO_W4_MIN_C. Unless switched off (STATE.wino_w4 / FORGE_WINO_W4=0, or any of the nests below it). The rules below it ask for the 64 x 128 tile of
+    forge_wino_gemm_tile, which a launch of Cout <= 64 columns does not get: a step's state launch has Cout = C, so through fusion._fuse_eval the floor is
+    in effect C > 64 (C = 64 is reached only with a forced tile)."""
+    return STATE.wino_w4 and Cin // 2 >= WINO_W4_MIN_C and wino_depth_nest4h_applies(R, D, Ht, Wt, Cout, Cin)
+
+
 # One immutable record per form. Everything that depends on the form reads it here: wino_fits, fusion._step_scratch, wino_pack, the weight and operand
 # checks of wino_form_gemm, flopmeter's counters, fusion._fuse_eval's choice.
 #   P        planes of point products the launch writes ([P][R][Cout]; wino_output reads the form from P)
 #   points   Winograd points = planes of the operand V and batched problems of the launch (16; 24 with F(4, 3) along H)
-#   th       output rows per tile: the tile grid is (H / th, W / 2) and R, Ht, rows and applies are in ITS tile rows (2; 4 with F(4, 3) along H)
+#   th, tw   output rows and columns per tile: the tile grid is (H / th, W / tw) and R, Ht, Wt, rows and applies are in ITS tile rows (2; 4 with F(4, 3) along H / W)
 #   gemm     the forge_wino_gemm* entry
 #   weights  the weight entry, ushape(kd, Cout, Cin) the shape of its tensor
 #   input    the input-transform entry, rows its operand rows per volume as a ratio to D Ht Wt
@@ -599,7 +613,7 @@ def wino_depth_nest4h_applies(R, D, Ht, Wt, Cout, Cin):
 # at call time (wino_calls) - the nest's [16][2][2][Cout][Cin] weight shape exists for exactly that meter, dimension 1 being its K loops per plane; (2) the
 # F(4, 3) launches and their input transform do NOT go through them (wino_form_gemm / wino_form_input directly): the recorder would count them 4 x too
 # high (U.shape[1] = 6 for 3/2 loops per plane), so that it does not see them is the lesser evil. That is the `metered` column.
-WinoForm = collections.namedtuple("WinoForm", "name P gemm weights ushape input rows kloops applies tile metered points th", defaults=(16, 2))
+WinoForm = collections.namedtuple("WinoForm", "name P gemm weights ushape input rows kloops applies tile metered points th tw", defaults=(16, 2, 2))
 _U4 = lambda kd, co_, ci_: (16, kd, co_, ci_)
 WINO_FORMS = {f.name: f for f in (
     WinoForm("points", 16, "forge_wino_gemm", "forge_wino_weights", _U4, "forge_wino_input", 1, None, lambda R, D, Ht, Wt, Cout, Cin: True,
@@ -616,6 +630,11 @@ WINO_FORMS = {f.name: f for f in (
 # Unmetered like "dn4"; its inverse transform is forge_wino_output_dn4h (wino_output reads P = 24).
 WINO_DN4H = WinoForm("dn4h", 24, "forge_wino_gemm_dn4h", "forge_wino_weights_dn4h", lambda kd, co_, ci_: (24, 6, co_, ci_), "forge_wino_input_dn4h",
                      Fraction(3, 2), Fraction(3, 2), lambda *a: wino_depth_nest4h_applies(*a), False, False, 24, 4)
+
+# And along W: 36 points on tiles of 4 x 4 (forge_wino_output_dn4hw; wino_output reads P = 36).
+WINO_DN4HW = WinoForm("dn4hw", 36, "forge_wino_gemm_dn4hw", "forge_wino_weights_dn4hw", lambda kd, co_, ci_: (36, 6, co_, ci_), "forge_wino_input_dn4hw",
+                      Fraction(3, 2), Fraction(3, 2), lambda *a: wino_depth_nest4hw_applies(*a), False, False, 36, 4, 4)
+_WINO_OUT = {f.P: f for f in (WINO_DN4H, WINO_DN4HW)}     # the forms with an inverse transform of their own, by their planes
 
 
 def wino_calls(form):
@@ -646,11 +665,11 @@ def wino_pack(form, wp, transpose=False):
 
 @_lib.on_tensor_device
 def wino_form_input(form, x, C, ld, n, D, H, W, bs=0, out=None, nsum=1, sum_stride=0):
-    """V [form.points][rows][C], rows = n D H/th W/2 x form.rows: the input transform of `form` (form.input) of the channels-last rows x ([n][D][H][W] x ld floats,
+    """V [form.points][rows][C], rows = n D H/th W/tw x form.rows: the input transform of `form` (form.input) of the channels-last rows x ([n][D][H][W] x ld floats,
     batch stride bs rows). The plain transform is B^T d B per tile; forge_wino_input_dn4 puts the depth stage of the F(4, 3) nest in front - position k of
     group g of four planes is plane 6 g + k of the batch element. nsum > 1: d is the mean of nsum such tensors sum_stride rows apart (the view mean feeding
     fusion_conv, models/encoder.py:62). out: a buffer of that shape."""
-    rows = int(n * D * (H // form.th) * (W // 2) * form.rows)
+    rows = int(n * D * (H // form.th) * (W // form.tw) * form.rows)
     V = out if out is not None else torch.empty(form.points, rows, C, dtype=torch.float32, device=x.device)
     if form.rows != 1 and (V.shape != (form.points, rows, C) or not V.is_contiguous()):
         raise ValueError("depth-nest operand buffer %s is not [%d][%d][%d]" % (tuple(V.shape), form.points, rows, C))
@@ -729,19 +748,23 @@ def wino_gemm_tile(R, Cout, Cin):
 def wino_output(Mm, bias, scale, shift, slope, residual, aux_h, aux_z, out, out2, out3, n, D, H, W, Cout, ldo, epilogue, Mm2=None, view=0, views=1):
     """out = epilogue(A^T (Mm + Mm2) A): the element-wise tails of conv_igemm (EPI_*) on the inverse-transformed tiles. Mm: the point products
     wino_gemm returned, [P][n D H/2 W/2][Cout]; their form is P - 16 points, or 8 planes whose row stage the GEMM epilogue has applied
-    (forge_wino_output_half then runs the column stage), or the 24 points of WINO_DN4H over n D H/4 W/2 rows (forge_wino_output_dn4h). Mm2 (optional) [P][n views D H/2 W/2][Cout], the same form: point products of the input
+    (forge_wino_output_half then runs the column stage), or the 24 points of WINO_DN4H over n D H/4 W/2 rows (forge_wino_output_dn4h), or the 36 points of
+    WINO_DN4HW over n D H/4 W/4 rows (forge_wino_output_dn4hw). Mm2 (optional) [P][n views D H/2 W/2][Cout], the same form: point products of the input
     half for `views` views per batch element; this call adds view `view`. Any other shape raises ValueError."""
     P = Mm.shape[0] if Mm.dim() == 3 else 0
-    vol = D * (H // (WINO_DN4H.th if P == WINO_DN4H.P else 2)) * (W // 2)
-    if P not in (8, 16, WINO_DN4H.P) or Mm.shape[1:] != (n * vol, Cout) or not Mm.is_contiguous():
-        raise ValueError("point products %s do not match [8 | 16][%d][%d] (or the 24 points' rows)" % (tuple(Mm.shape), n * vol, Cout))
-    if P == WINO_DN4H.P:
-        # the 24 points of F(4, 3) along H: the GRU tails of the eval fusion's full steps only
-        if Mm2 is not None or residual is not None or H % 4 or epilogue not in (EPI_GRU_GATES, EPI_GRU_OUT):
-            raise ValueError("24-point products take the GRU tails only, without a second addend or a residual, on H %% 4 == 0 (H=%d epilogue=%d)" % (H, epilogue))
-        _lib.check(_lib.lib().forge_wino_output_dn4h(_lib.ptr(Mm), _lib.ptr(bias), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(aux_h), _lib.ptr(aux_z),
-                                                     _lib.ptr(out), _lib.ptr(out2), _lib.ptr(out3), n, D, H, W, Cout, ldo, epilogue, _lib.current_stream()),
-                   "forge_wino_output_dn4h")
+    own = _WINO_OUT.get(P)
+    th, tw = (own.th, own.tw) if own else (2, 2)
+    vol = D * (H // th) * (W // tw)
+    if P not in (8, 16, *_WINO_OUT) or Mm.shape[1:] != (n * vol, Cout) or not Mm.is_contiguous():
+        raise ValueError("point products %s do not match [8 | 16][%d][%d] (or the 24 / 36 points' rows)" % (tuple(Mm.shape), n * vol, Cout))
+    if own:
+        # the 24 / 36 points of F(4, 3) along H (and W): the GRU tails of the eval fusion's full steps only
+        if Mm2 is not None or residual is not None or H % th or W % tw or epilogue not in (EPI_GRU_GATES, EPI_GRU_OUT):
+            raise ValueError("%d-point products take the GRU tails only, without a second addend or a residual, on H %% %d == 0, W %% %d == 0 (H=%d W=%d epilogue=%d)"
+                             % (P, th, tw, H, W, epilogue))
+        name = "forge_wino_output_" + own.name
+        _lib.check(getattr(_lib.lib(), name)(_lib.ptr(Mm), _lib.ptr(bias), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(aux_h), _lib.ptr(aux_z),
+                                             _lib.ptr(out), _lib.ptr(out2), _lib.ptr(out3), n, D, H, W, Cout, ldo, epilogue, _lib.current_stream()), name)
         return out
     if Mm2 is not None and (Mm2.shape != (P, n * views * vol, Cout) or not Mm2.is_contiguous()):
         raise ValueError("second addend %s does not match [%d][%d][%d] (the form of Mm)" % (tuple(Mm2.shape), P, n * views * vol, Cout))

@@ -1420,9 +1420,9 @@ extern "C" int forge_wino_gemm_tile(long long R, int Cout, int Cin) {
 static int wino_gemm_impl(const float* V1, int C1, int ld1, long long bs1, long long pt1, const float* V2, int C2, int ld2, long long bs2,
                           long long pt2, const float* U, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, int tile, int form, forge_stream_t stream) {
     // form: 0 = 16 points, 1 = the four-point row stage, 2 = the depth nest, 3 = its F(4, 3) form, 4 = that form on the 24 points of F(4, 3) along H (the same launch
-    // with 24 batched problems on the grid of 4 x 2 tiles)
-    const bool half = form == 1, dn = form == 2, dn4h = form == 4, dn4 = form == 3 || dn4h;
-    const char* const name4 = dn4h ? "forge_wino_gemm_dn4h" : "forge_wino_gemm_dn4";
+    // with 24 batched problems on the grid of 4 x 2 tiles), 5 = on the 36 points of F(4, 3) along H and W (36 problems on the grid of 4 x 4 tiles)
+    const bool half = form == 1, dn = form == 2, dn4hw = form == 5, dn4h = form == 4 || dn4hw, dn4 = form == 3 || dn4h;
+    const char* const name4 = dn4hw ? "forge_wino_gemm_dn4hw" : dn4h ? "forge_wino_gemm_dn4h" : "forge_wino_gemm_dn4";
     FORGE_REQUIRE(tile == 0 || (tile >= 'A' && tile <= 'E'), FORGE_EINVAL, "forge_wino_gemm: tile must be 0 (default rule) or 'A'..'E'");
     FORGE_REQUIRE(V1 && U && Mm && (kd == 1 || kd == 3), FORGE_EINVAL, "forge_wino_gemm: null pointer argument / kd not 1 or 3");
     FORGE_REQUIRE(n > 0 && D > 0 && Ht > 0 && Wt > 0 && Cout > 16, FORGE_EINVAL, "forge_wino_gemm: bad dims n=%d D=%d Ht=%d Wt=%d Cout=%d (Cout > 16)", n,
@@ -1434,7 +1434,7 @@ static int wino_gemm_impl(const float* V1, int C1, int ld1, long long bs1, long 
                   "forge_wino_gemm_dn: needs three depth taps, an even D and Ht Wt %% 64 == 0 (kd=%d D=%d Ht=%d Wt=%d)", kd, D, Ht, Wt);
     FORGE_REQUIRE(!dn4 || (kd == 3 && D % 4 == 0 && ((long long)Ht * Wt) % 64 == 0), FORGE_EINVAL,
                   "%s: needs three depth taps, D %% 4 == 0 and Ht Wt %% 64 == 0 (kd=%d D=%d Ht=%d Wt=%d)", name4, kd, D, Ht, Wt);
-    FORGE_REQUIRE(!dn4h || D >= 8, FORGE_EINVAL, "forge_wino_gemm_dn4h: D=%d must be at least 8", D);
+    FORGE_REQUIRE(!dn4h || D >= 8, FORGE_EINVAL, "%s: D=%d must be at least 8", name4, D);
     ConvArgs a;
     memset(&a, 0, sizeof(a));
     // operand rows per batch element and K loops per tile: vol rows and the kd depth taps; depth nest: U' [16][4][Cout][Cin], the four depth positions
@@ -1455,7 +1455,7 @@ static int wino_gemm_impl(const float* V1, int C1, int ld1, long long bs1, long 
     }
     a.wp = U; a.slope = 1.f; a.out = Mm; a.n = n; a.D = D; a.H = Ht; a.W = Wt; a.is = 1; a.Di = D; a.Hi = Ht; a.Wi = Wt;
     a.Cout = Cout; a.ldo = Cout; a.ldr = Cout; a.ntaps = a.tpp = npos; a.os = 1; a.Do = D; a.Ho = Ht; a.Wo = Wt; a.nphase = 1; a.epi = EPI_BIAS;
-    a.ksplit = 1; a.nbat = half ? 4 : dn4h ? 24 : 16;
+    a.ksplit = 1; a.nbat = half ? 4 : dn4hw ? 36 : dn4h ? 24 : 16;
     a.pt1 = pt1 > 0 ? pt1 : (long long)n * rows * ld1; a.pt2 = V2 ? (pt2 > 0 ? pt2 : (long long)n * rows * ld2) : 0;   // 0 = dense planes, as forge_wino_wgrad reads it
     a.ptw = (long long)npos * Cout * Cin; a.pto = R * Cout;
     if (form == 0 || half) {
@@ -1511,4 +1511,13 @@ extern "C" int forge_wino_gemm_dn4h(const float* V1, int C1, int ld1, long long 
                                     long long pt2, const float* Ud, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, forge_stream_t stream) {
     FORGE_REQUIRE(C1 > 0 && C1 % BK == 0 && C2 >= 0 && C2 % BK == 0, FORGE_EINVAL, "forge_wino_gemm_dn4h: C1=%d / C2=%d must be multiples of %d", C1, C2, BK);
     return wino_gemm_impl(V1, C1, ld1, bs1, pt1, V2, C2, ld2, bs2, pt2, Ud, Mm, n, D, Ht, Wt, Cout, kd, 'B', 4, stream);
+}
+
+// forge_wino_gemm_dn4h on the 36 points of F(4, 3) along H AND W (the same kernel, 36 batched problems): the point products Mm [36][R][Cout], R = n D Ht Wt tile
+// rows of the grid of 4 x 4 tiles (Ht = H / 4, Wt = W / 4), from the operands V [36][n][D/4][6][Ht Wt][C] (forge_wino_input_dn4hw) against Ud [36][6][Cout][C1 + C2]
+// (forge_wino_weights_dn4hw); forge_wino_output_dn4hw inverts them. forge_wino_gemm_dn4h's preconditions on this grid.
+extern "C" int forge_wino_gemm_dn4hw(const float* V1, int C1, int ld1, long long bs1, long long pt1, const float* V2, int C2, int ld2, long long bs2,
+                                     long long pt2, const float* Ud, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, forge_stream_t stream) {
+    FORGE_REQUIRE(C1 > 0 && C1 % BK == 0 && C2 >= 0 && C2 % BK == 0, FORGE_EINVAL, "forge_wino_gemm_dn4hw: C1=%d / C2=%d must be multiples of %d", C1, C2, BK);
+    return wino_gemm_impl(V1, C1, ld1, bs1, pt1, V2, C2, ld2, bs2, pt2, Ud, Mm, n, D, Ht, Wt, Cout, kd, 'B', 5, stream);
 }

@@ -107,14 +107,22 @@ __device__ __forceinline__ double depth_row_f43(int k, double w0, double w1, dou
 }
 
 // U[4i + j] = (float)(G_H d G^T)[i][j] of one 3 x 3 kernel slice d in float64, rounded once; point p at up + p pt. G_H = the NH rows HROW of the form along H
-// (F(2, 3): 4 rows, 16 points; F(4, 3): 6 rows, 24 points), G = F(2, 3) along W.
-template <int NH = 4, double (*HROW)(int, double, double, double) = depth_row_f23>
+// (F(2, 3): 4 rows, 16 points; F(4, 3): 6 rows, 24 points), G = F(2, 3) along W. NW = 6: F(4, 3) along W as well, point 6 i + j = depth_row_f43(j, .) of the three
+// W taps of row i (36 points).
+template <int NH = 4, double (*HROW)(int, double, double, double) = depth_row_f23, int NW = 4>
 __device__ __forceinline__ void g_d_gt_store(const double (&d)[3][3], float* up, long long pt) {
     double g[NH][3];                                 // G_H d
 #pragma unroll
     for (int b = 0; b < 3; ++b)
 #pragma unroll
         for (int i = 0; i < NH; ++i) g[i][b] = HROW(i, d[0][b], d[1][b], d[2][b]);
+    if constexpr (NW == 6) {
+#pragma unroll
+        for (int i = 0; i < NH; ++i)
+#pragma unroll
+            for (int j = 0; j < 6; ++j) up[(6 * i + j) * pt] = (float)depth_row_f43(j, g[i][0], g[i][1], g[i][2]);
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < NH; ++i) {                   // (G_H d) G^T
         up[(4 * i + 0) * pt] = (float)g[i][0];
@@ -249,6 +257,93 @@ __global__ __launch_bounds__(256) void wino_input_dn4_kernel(const WinoInArgs a)
     }
 }
 
+// The input transform of the F(4, 3) nest on depth, H AND W (forge_wino_input_dn4hw): tiles of 4 x 4 output pixels, Ht = H / 4, Wt = W / 4; the patch of tile
+// (th, tw) of group g is the planes 4 g - 1 .. 4 g + 4 x the rows 4 th - 1 .. 4 th + 4 x the columns 4 tw - 1 .. 4 tw + 4 (zero outside the batch element's grid).
+// Three stages, in this order, all f43_six_lines:
+//   depth   q_k[i][j]   over the six planes of the group, per patch element
+//   rows    w_k[i'][j]  over the six patch rows i of q_k, per depth position k and patch column j
+//   cols    V[6 i' + j'] over the six patch columns j of w_k[i'], per depth position and point row
+// Output V [36][n][D/4][6][Ht Wt][C], point p = 6 i' + j'. A tile's 6 x 6 x 6 values per channel do not fit one thread: a tile and channel is split over the THREE
+// waves of a 192-thread workgroup by depth-position pairs - (0, 5), (1, 2), (3, 4): the lines 0 and 5 read three planes each, the other four the same four
+// planes, so the three waves load 14 planes per patch element (168 loads per wave; the sibling waves' repeats are L1 hits: the same addresses from the same
+// workgroup). A wave keeps its two positions: 72 values live, 72 stores. It reads and writes 64 channels = 256 contiguous bytes per instruction. KP is the
+// wave's index, uniform, so each wave runs one instantiation of the body.
+// Every load is unconditional - the coordinates are clamped into the element's grid and the value is masked to zero outside it - so that the loads issue back
+// to back instead of one branch and one wait each (with the loads under their conditions the launch took 34 us where this form takes 27, at one scene).
+// MEAN: the view-mean path (nsum > 1), a kernel instantiation of its own.
+// Code object (hipcc -O3, gfx950): MEAN = false 165 VGPRs, no scratch = 3 waves per SIMD; MEAN = true 252 VGPRs, no scratch = 2 waves per SIMD.
+template <int KP, bool MEAN>
+__device__ __forceinline__ void wino_input_dn4hw_body(const WinoInArgs& a, long long idx) {
+    const int Ht = a.H >> 2, Wt = a.W >> 2, Dg = a.D >> 2;
+    unsigned r, t;
+    int c, tw, th;
+    tile_decode(idx, a.C, 0, Ht, Wt, r, c, tw, th, t);
+    const unsigned q = t; t = q / (unsigned)Dg;
+    const int g = (int)(q - t * (unsigned)Dg);                      // t = batch element
+    const float* base = a.in + (long long)t * a.bs * a.ld + c;
+    const float inv = 1.f / (float)a.nsum;                           // ATen divides by a scalar as a multiplication by its fp32 reciprocal
+    constexpr int K0 = KP == 0 ? 0 : 2 * KP - 1, K1 = KP == 0 ? 5 : 2 * KP;      // the pairs (0, 5), (1, 2), (3, 4): lines 0 and 5 read three planes each, the others
+    const int kpos[2] = {K0, K1};                                    // the same four - 14 loads per patch element over the three waves instead of 18
+    float d[2][6][6];                                                // [depth position kpos[k]][patch row i][patch column j]
+    // offsets of the six planes, rows and columns inside the batch element, in floats (32 bits: the entry refuses elements of 2^31 floats), clamped into its grid
+    unsigned oz[6], oy[6], ox[6];
+#pragma unroll
+    for (int e = 0; e < 6; ++e) {
+        oz[e] = (unsigned)min(max(4 * g - 1 + e, 0), a.D - 1) * (unsigned)(a.H * a.W) * (unsigned)a.ld;
+        oy[e] = (unsigned)min(max(4 * th - 1 + e, 0), a.H - 1) * (unsigned)a.W * (unsigned)a.ld;
+        ox[e] = (unsigned)min(max(4 * tw - 1 + e, 0), a.W - 1) * (unsigned)a.ld;
+    }
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {                                    // one patch column at a time: its loads, depth lines and row lines
+        const int x = 4 * tw - 1 + j;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const int y = 4 * th - 1 + i;
+            const bool ok = (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
+            float p[6], o[6];
+#pragma unroll
+            for (int e = 0; e < 6; ++e) {
+                const int z = 4 * g - 1 + e;
+                const float* s = base + (oz[e] + oy[i] + ox[j]);
+                float v = *s;
+                if constexpr (MEAN) {
+                    for (int k = 1; k < a.nsum; ++k) v += s[(long long)k * a.ss * a.ld];
+                    v *= inv;
+                }
+                p[e] = __int_as_float(__float_as_int(v) & (ok && (unsigned)z < (unsigned)a.D ? -1 : 0));    // (a mask, not a select: a select of a load becomes a branch again)
+            }
+            f43_six_lines(p[0], p[1], p[2], p[3], p[4], p[5], o[0], o[1], o[2], o[3], o[4], o[5]);
+            d[0][i][j] = o[K0];
+            d[1][i][j] = o[K1];
+        }
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            f43_six_lines(d[k][0][j], d[k][1][j], d[k][2][j], d[k][3][j], d[k][4][j], d[k][5][j], d[k][0][j], d[k][1][j], d[k][2][j], d[k][3][j], d[k][4][j], d[k][5][j]);
+    }
+    const long long HWt = (long long)Ht * Wt;
+    float* vp = a.V + ((((long long)t * Dg + g) * 6) * HWt + (long long)th * Wt + tw) * a.ldv + c;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            float v[6];
+            f43_six_lines(d[k][i][0], d[k][i][1], d[k][i][2], d[k][i][3], d[k][i][4], d[k][i][5], v[0], v[1], v[2], v[3], v[4], v[5]);
+#pragma unroll
+            for (int j = 0; j < 6; ++j) vp[kpos[k] * HWt * a.ldv + (6 * i + j) * a.ptv] = v[j];
+        }
+    }
+}
+
+template <bool MEAN>
+__global__ __launch_bounds__(192) void wino_input_dn4hw_kernel(const WinoInArgs a) {
+    const long long idx = (long long)xcd_remap(blockIdx.x, gridDim.x) * 64 + (threadIdx.x & 63);
+    if (idx >= (long long)a.n * (a.D >> 2) * (a.H >> 2) * (a.W >> 2) * a.C) return;
+    const int kp = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (kp == 0) wino_input_dn4hw_body<0, MEAN>(a, idx);
+    else if (kp == 1) wino_input_dn4hw_body<1, MEAN>(a, idx);
+    else wino_input_dn4hw_body<2, MEAN>(a, idx);
+}
+
 // U[4i+j][kd][o][c] = (G w[kd] G^T)[i][j] from packed weights wp[(kd 3 + a) 3 + b][co][ci]: one thread per (kd, o, c). Evaluated in float64
 // (exact: at most 9 fp32 terms with coefficients 1, 1/2, 1/4) and rounded once. transpose: the weights of the DATA GRADIENT - the
 // correlation of dy with the flipped kernel and swapped channel roles: w'[kd][a][b][o = ci][c = co] = wp[(2-kd, 2-a, 2-b)][co][ci].
@@ -277,8 +372,10 @@ __global__ __launch_bounds__(256) void wino_weight_kernel(const float* __restric
 //           result is depth_row_f43's float64 evaluation, correctly rounded to within one float64 rounding per operation)
 //   F(4, 3) on depth AND on H (forge_wino_gemm_dn4h, NH = 6, HROW = the F(4, 3) rows): U''' [24][6][Cout][Cin] = G4(depth) (x) G4(H) (x) G2(W), point p = 4 i + j with
 //           i = 0..5 the H point: the depth rows on every element, then the H rows, then the W rows, all in float64, rounded once
+//   F(4, 3) on depth, H AND W (forge_wino_weights_dn4hw, NW = 6): U [36][6][Cout][Cin] = G4(depth) (x) G4(H) (x) G4(W), point p = 6 i + j: the depth rows on every
+//           element, then the H rows, then the same six rows over the W taps, all in float64, rounded once
 // (the rows: depth_row_f23 / depth_row_f43 above g_d_gt_store)
-template <int K, double (*ROW)(int, double, double, double), int NH = 4, double (*HROW)(int, double, double, double) = depth_row_f23>
+template <int K, double (*ROW)(int, double, double, double), int NH = 4, double (*HROW)(int, double, double, double) = depth_row_f23, int NW = 4>
 __global__ __launch_bounds__(256) void wino_weight_nest_kernel(const float* __restrict__ wp, float* __restrict__ U, int Cout, int Cin) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, per = (long long)Cout * Cin;
     if (idx >= per) return;
@@ -292,7 +389,7 @@ __global__ __launch_bounds__(256) void wino_weight_nest_kernel(const float* __re
         for (int a = 0; a < 3; ++a)
 #pragma unroll
             for (int b = 0; b < 3; ++b) d[a][b] = ROW(k, w[0][a][b], w[1][a][b], w[2][a][b]);
-        g_d_gt_store<NH, HROW>(d, U + k * per + idx, K * per);
+        g_d_gt_store<NH, HROW, NW>(d, U + k * per + idx, K * per);
     }
 }
 
@@ -434,6 +531,106 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const WinoOutArgs a) {
         }
 }
 
+// A deliberate second copy of wino_output_kernel's GRU tails: with that kernel calling this function its existing instantiations compile to other code (another
+// instruction order and register allocation, e.g. <W_GRU_OUT, false, 4> 2559 -> 2581 lines, 168 -> 160 VGPRs), and the steps that do not take the 36-point form
+// would no longer run the code they were measured with. A change to either tail is made in both.
+// The GRU tails of wino_output_kernel (the same operations in the same order) on the NI x NJ voxels y of one tile and four channels c .. c + 3: voxel (i, j) is
+// row y0 + i, column x0 + j of plane t = (n, z). EPI: W_GRU_GATES (z | h r | optional r) or W_GRU_OUT (lerp, optional tanh(c), fusion_norm-folded second output).
+template <int EPI, int NI, int NJ>
+__device__ __forceinline__ void wino_tail(const WinoOutArgs& a, const float4 (&y)[NI][NJ], unsigned t, int y0, int x0, int c) {
+    float4 bias = make_float4(0.f, 0.f, 0.f, 0.f), sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = bias;
+    if (a.bias) bias = *reinterpret_cast<const float4*>(a.bias + c);
+    if (EPI == W_GRU_OUT && a.out2 && a.scale) {
+        sc = *reinterpret_cast<const float4*>(a.scale + c);
+        sh = *reinterpret_cast<const float4*>(a.shift + c);
+    }
+    const int Ch = a.Cout >> 1;
+    const long long plane = (long long)t * a.H * a.W;               // first output row of plane (n, z)
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const long long orow = plane + (long long)(y0 + i) * a.W + (x0 + j);
+            float v[4] = {y[i][j].x + bias.x, y[i][j].y + bias.y, y[i][j].z + bias.z, y[i][j].w + bias.w};
+            const float scv[4] = {sc.x, sc.y, sc.z, sc.w}, shv[4] = {sh.x, sh.y, sh.z, sh.w};
+            if constexpr (EPI == W_GRU_GATES) {
+                float g[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) g[k] = 1.f / (1.f + expf(-v[k]));      // full-precision exponential, as torch.sigmoid
+                if (c < Ch) {
+                    *reinterpret_cast<float4*>(a.out + orow * Ch + c) = make_float4(g[0], g[1], g[2], g[3]);
+                } else {
+                    const float4 h = *reinterpret_cast<const float4*>(a.aux_h + orow * Ch + (c - Ch));
+                    *reinterpret_cast<float4*>(a.out2 + orow * Ch + (c - Ch)) = make_float4(h.x * g[0], h.y * g[1], h.z * g[2], h.w * g[3]);
+                    if (a.out3) *reinterpret_cast<float4*>(a.out3 + orow * Ch + (c - Ch)) = make_float4(g[0], g[1], g[2], g[3]);
+                }
+            } else {   // W_GRU_OUT
+                const float4 z4 = *reinterpret_cast<const float4*>(a.aux_z + orow * a.Cout + c);
+                const float4 h4 = *reinterpret_cast<const float4*>(a.aux_h + orow * a.Cout + c);
+                const float zv[4] = {z4.x, z4.y, z4.z, z4.w}, hv[4] = {h4.x, h4.y, h4.z, h4.w};
+                float cand[4], hn[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    cand[k] = tanhf(v[k]);
+                    hn[k] = hv[k] * (1.f - zv[k]) + cand[k] * zv[k];
+                }
+                *reinterpret_cast<float4*>(a.out + orow * a.ldo + c) = make_float4(hn[0], hn[1], hn[2], hn[3]);
+                if (a.out2)
+                    *reinterpret_cast<float4*>(a.out2 + orow * a.ldo + c) =
+                        make_float4(fmaf(hn[0], scv[0], shv[0]), fmaf(hn[1], scv[1], shv[1]), fmaf(hn[2], scv[2], shv[2]), fmaf(hn[3], scv[3], shv[3]));
+                if (a.out3) *reinterpret_cast<float4*>(a.out3 + orow * a.ldo + c) = make_float4(cand[0], cand[1], cand[2], cand[3]);
+            }
+        }
+}
+
+// The inverse transform of forge_wino_gemm_dn4hw's 36 point products (forge_wino_output_dn4hw): tiles of 4 x 4 voxels, Ht = H / 4, Wt = W / 4, point p = 6 i + j
+// (i the H point, j the W point). A^T of F(4, 3) over the H points, per W point j - the four lines of wino_output_kernel<., false, 4> - then THE SAME four lines
+// over the six W points of each output row, then the GRU tails. A tile and four channels is split over two threads by output-row pairs: the waves 0, 1 of a
+// workgroup run the rows 0, 1 and the waves 2, 3 the rows 2, 3 of the same 128 (tile, channel quad) items, so RH is uniform per wave. A thread loads 30 of the
+// 36 planes (rows 0, 1 need no m5, rows 2, 3 no m0; the sibling waves' repeats are L1 hits), keeps 12 row sums and writes 2 x 4 voxels.
+template <int EPI, int RH>
+__device__ __forceinline__ void wino_output_dn4hw_body(const WinoOutArgs& a, long long idx) {
+    const int C4 = a.Cout >> 2, Ht = a.H >> 2, Wt = a.W >> 2;
+    unsigned r, t;                                   // t = (n, z) plane index
+    int c, tw, th;
+    tile_decode(idx, C4, 2, Ht, Wt, r, c, tw, th, t);
+    const float* mp = a.Mm + (long long)r * a.Cout + c;
+    float4 s[2][6];                                  // rows 2 RH, 2 RH + 1 of A^T m
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        float4 m[6];
+#pragma unroll
+        for (int i = RH; i < 5 + RH; ++i) m[i] = *reinterpret_cast<const float4*>(mp + (6 * i + j) * a.ptm);
+        const float4 sl = add(m[1], m[2]), dl = sub(m[1], m[2]), Sl = add(m[3], m[4]), Dl = sub(m[3], m[4]);
+        if constexpr (RH == 0) {
+            s[0][j] = add(add(sl, Sl), m[0]);
+            s[1][j] = fma4(2.f, Dl, dl);
+        } else {
+            s[0][j] = fma4(4.f, Sl, sl);
+            s[1][j] = add(fma4(8.f, Dl, dl), m[5]);
+        }
+    }
+    float4 y[2][4];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const float4 sl = add(s[i][1], s[i][2]), dl = sub(s[i][1], s[i][2]), Sl = add(s[i][3], s[i][4]), Dl = sub(s[i][3], s[i][4]);
+        y[i][0] = add(add(sl, Sl), s[i][0]);
+        y[i][1] = fma4(2.f, Dl, dl);
+        y[i][2] = fma4(4.f, Sl, sl);
+        y[i][3] = add(fma4(8.f, Dl, dl), s[i][5]);
+    }
+    wino_tail<EPI>(a, y, t, 4 * th + 2 * RH, 4 * tw, c);
+}
+
+// Code object (hipcc -O3, gfx950): gates 182 VGPRs, state 196 VGPRs, no scratch = 2 waves per SIMD (wino_output_kernel<., false, 4>: 153 / 168, 2 waves).
+template <int EPI>
+__global__ __launch_bounds__(256) void wino_output_dn4hw_kernel(const WinoOutArgs a) {
+    const long long idx = (long long)blockIdx.x * 128 + (threadIdx.x & 127);
+    if (idx >= (long long)a.n * a.D * (a.H >> 2) * (a.W >> 2) * (a.Cout >> 2)) return;
+    if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 7)) == 0) wino_output_dn4hw_body<EPI, 0>(a, idx);
+    else wino_output_dn4hw_body<EPI, 1>(a, idx);
+}
+
 // ---- weight gradient in the Winograd domain: dL/dU[p][kd] = sum_r dMm[p][r] (x) V[p][r + kd plane] (forge_wino_wgrad: conv_wgrad_kernel
 // on 16 batched problems), with dMm = A dy A^T the adjoint of the inverse transform, then dL/dw[kd] = G^T dU[kd] G.
 struct WinoDyArgs {
@@ -544,19 +741,27 @@ extern "C" int forge_wino_weights_dn4h(const float* wp, float* Ud, int Cout, int
     return wino_weights_launch("forge_wino_weights_dn4h", wino_weight_nest_kernel<6, depth_row_f43, 6, depth_row_f43>, (long long)Cout * Cin, stream, wp, Ud, Cout, Cin);
 }
 
-// The four input entries. IN_DN4: the depth stage of the F(4, 3) nest in front (wino_input_dn4_kernel: one thread per tile of a GROUP of four planes and channel,
+extern "C" int forge_wino_weights_dn4hw(const float* wp, float* Ud, int Cout, int Cin, forge_stream_t stream) {
+    FORGE_REQUIRE(wp && Ud && Cout > 0 && Cin > 0, FORGE_EINVAL, "forge_wino_weights_dn4hw: bad argument");
+    return wino_weights_launch("forge_wino_weights_dn4hw", wino_weight_nest_kernel<6, depth_row_f43, 6, depth_row_f43, 6>, (long long)Cout * Cin, stream, wp, Ud, Cout, Cin);
+}
+
+// The five input entries. IN_DN4: the depth stage of the F(4, 3) nest in front (wino_input_dn4_kernel: one thread per tile of a GROUP of four planes and channel,
 // six operand rows per group tile); IN_DN4H: that with F(4, 3) along H as well (wino_input_dn4_kernel<4>: tiles of 4 x 2 pixels, H % 4 == 0);
+// IN_DN4HW: and along W (wino_input_dn4hw_kernel: tiles of 4 x 4 pixels, W % 4 == 0, three waves per 64 tile-channels);
 // IN_DY: also dM = A y A^T (wino_input_kernel<true>; dense operands, no view mean).
-enum WinoInKind { IN_PLAIN, IN_DN4, IN_DY, IN_DN4H };
+enum WinoInKind { IN_PLAIN, IN_DN4, IN_DY, IN_DN4H, IN_DN4HW };
 
 static int wino_input_impl(const char* name, WinoInKind kind, const float* in, int ld, long long bs, float* V, int ldv, long long ptv, float* dM, int n, int D, int H,
                            int W, int C, int nsum, long long sum_stride, forge_stream_t stream) {
-    const bool dn4 = kind == IN_DN4 || kind == IN_DN4H;                 // six operand rows per tile of a group of four planes
-    const int th = kind == IN_DN4H ? 4 : 2;                             // output rows per tile
+    const bool h4 = kind == IN_DN4H || kind == IN_DN4HW, dn4 = kind == IN_DN4 || h4;       // six operand rows per tile of a group of four planes
+    const int th = h4 ? 4 : 2, tw = kind == IN_DN4HW ? 4 : 2;          // output rows and columns per tile
     FORGE_REQUIRE(in && V && (kind != IN_DY || dM), FORGE_EINVAL, "%s: null pointer argument", name);
     FORGE_REQUIRE(nsum >= 1 && (nsum == 1 || sum_stride > 0), FORGE_EINVAL, "%s: nsum >= 1, and a positive sum_stride (rows) with nsum > 1", name);
     FORGE_REQUIRE(!dn4 || (D > 0 && D % 4 == 0), FORGE_EINVAL, "%s: D=%d must be a multiple of 4", name, D);
-    FORGE_REQUIRE(kind != IN_DN4H || (D >= 8 && H > 0 && H % 4 == 0), FORGE_EINVAL, "%s: D=%d H=%d (D >= 8; H a multiple of 4)", name, D, H);
+    FORGE_REQUIRE(!h4 || (D >= 8 && H > 0 && H % 4 == 0), FORGE_EINVAL, "%s: D=%d H=%d (D >= 8; H a multiple of 4)", name, D, H);
+    FORGE_REQUIRE(kind != IN_DN4HW || (W > 0 && W % 4 == 0), FORGE_EINVAL, "%s: W=%d must be a multiple of 4", name, W);
+    FORGE_REQUIRE(kind != IN_DN4HW || (long long)D * H * W * ld < (1ll << 31), FORGE_EINVAL, "%s: a batch element of 2^31 floats or more (32-bit offsets inside it)", name);
     const bool ok = n > 0 && D > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C > 0 && C % 4 == 0 && ld >= C && ld % 4 == 0 && ldv >= C && ldv % 4 == 0;
     if (kind == IN_DY)                                // (this entry takes no ldv: its operands are dense)
         FORGE_REQUIRE(ok, FORGE_ESHAPE, "%s: n=%d D=%d H=%d W=%d C=%d ld=%d (H, W even; C, ld multiples of 4)", name, n, D, H, W, C, ld);
@@ -564,14 +769,17 @@ static int wino_input_impl(const char* name, WinoInKind kind, const float* in, i
     WinoInArgs a;
     a.in = in; a.ld = ld; a.bs = bs > 0 ? bs : (long long)D * H * W; a.V = V; a.ldv = ldv; a.n = n; a.D = D; a.H = H; a.W = W; a.C = C;
     a.nsum = nsum; a.ss = sum_stride;
-    const long long R = (long long)n * (dn4 ? D / 4 : D) * (H / th) * (W / 2), rows = dn4 ? 6 * R : R;     // thread tiles; operand rows per point
+    const long long R = (long long)n * (dn4 ? D / 4 : D) * (H / th) * (W / tw), rows = dn4 ? 6 * R : R;    // thread tiles; operand rows per point
     a.ptv = ptv > 0 ? ptv : rows * ldv;
     a.dM = dM; a.ptm = dM ? R * C : 0;
     FORGE_REQUIRE(rows < (1ll << 31), FORGE_ESHAPE, dn4 ? "%s: more than 2^31 operand rows; split the batch" : "%s: more than 2^31 tiles; split the batch", name);
-    const long long total = R * (dn4 ? C : C / 4), grid = (total + 255) / 256;
+    const int per = kind == IN_DN4HW ? 64 : 256;                        // tile-channels per workgroup (IN_DN4HW: three waves each)
+    const long long total = R * (dn4 ? C : C / 4), grid = (total + per - 1) / per;
     FORGE_REQUIRE(grid < (1ll << 31), FORGE_ESHAPE, "%s: grid too large", name);
     const dim3 g((unsigned)grid), b(256);
-    if (kind == IN_DN4H) hipLaunchKernelGGL(wino_input_dn4_kernel<4>, g, b, 0, (hipStream_t)stream, a);
+    if (kind == IN_DN4HW && nsum > 1) hipLaunchKernelGGL(wino_input_dn4hw_kernel<true>, g, dim3(192), 0, (hipStream_t)stream, a);
+    else if (kind == IN_DN4HW) hipLaunchKernelGGL(wino_input_dn4hw_kernel<false>, g, dim3(192), 0, (hipStream_t)stream, a);
+    else if (kind == IN_DN4H) hipLaunchKernelGGL(wino_input_dn4_kernel<4>, g, b, 0, (hipStream_t)stream, a);
     else if (dn4) hipLaunchKernelGGL(wino_input_dn4_kernel<2>, g, b, 0, (hipStream_t)stream, a);
     else if (kind == IN_DY) hipLaunchKernelGGL(wino_input_kernel<true>, g, b, 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(wino_input_kernel<false>, g, b, 0, (hipStream_t)stream, a);
@@ -596,6 +804,13 @@ extern "C" int forge_wino_input_dn4(const float* in, int ld, long long bs, float
 extern "C" int forge_wino_input_dn4h(const float* in, int ld, long long bs, float* V, int ldv, long long ptv, int n, int D, int H, int W, int C,
                                      int nsum, long long sum_stride, forge_stream_t stream) {
     return wino_input_impl("forge_wino_input_dn4h", IN_DN4H, in, ld, bs, V, ldv, ptv, nullptr, n, D, H, W, C, nsum, sum_stride, stream);
+}
+
+// forge_wino_input_dn4h with F(4, 3) along W as well (wino_input_dn4hw_kernel): V [36][n][D/4][6][H/4 W/4][C], the operand of forge_wino_gemm_dn4hw.
+// ptv: floats between points (0 = dense, n (D/4) 6 (H/4)(W/4) ldv). FORGE_EINVAL unless D % 4 == 0, D >= 8, H % 4 == 0 and W % 4 == 0.
+extern "C" int forge_wino_input_dn4hw(const float* in, int ld, long long bs, float* V, int ldv, long long ptv, int n, int D, int H, int W, int C,
+                                      int nsum, long long sum_stride, forge_stream_t stream) {
+    return wino_input_impl("forge_wino_input_dn4hw", IN_DN4HW, in, ld, bs, V, ldv, ptv, nullptr, n, D, H, W, C, nsum, sum_stride, stream);
 }
 
 extern "C" int forge_wino_input_dy(const float* dy, int ld, float* V, float* dM, int n, int D, int H, int W, int C, forge_stream_t stream) {
@@ -683,5 +898,32 @@ extern "C" int forge_wino_output_dn4h(const float* Mm, const float* bias, const 
     if (epilogue == W_GRU_GATES) hipLaunchKernelGGL((wino_output_kernel<W_GRU_GATES, false, 4>), g, b, 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((wino_output_kernel<W_GRU_OUT, false, 4>), g, b, 0, (hipStream_t)stream, a);
     FORGE_LAUNCH_CHECK("forge_wino_output_dn4h");
+    return 0;
+}
+
+// The inverse transform of forge_wino_gemm_dn4hw's point products Mm [36][n D H/4 W/4][Cout] with the GRU tails of forge_wino_output_dn4h (epilogue 2: gates, ldo ==
+// Cout / 2; 3: state; no second addend, no residual, as that entry): wino_output_dn4hw_kernel. FORGE_EINVAL unless H % 4 == 0 and W % 4 == 0.
+extern "C" int forge_wino_output_dn4hw(const float* Mm, const float* bias, const float* scale, const float* shift, const float* aux_h, const float* aux_z, float* out,
+                                       float* out2, float* out3, int n, int D, int H, int W, int Cout, int ldo, int epilogue, forge_stream_t stream) {
+    FORGE_REQUIRE(Mm && out && aux_h, FORGE_EINVAL, "forge_wino_output_dn4hw: null pointer argument");
+    FORGE_REQUIRE(n > 0 && D > 0 && H > 0 && W > 0 && H % 4 == 0 && W % 4 == 0, FORGE_EINVAL, "forge_wino_output_dn4hw: n=%d D=%d H=%d W=%d (H, W multiples of 4)", n, D, H, W);
+    FORGE_REQUIRE(Cout > 0 && Cout % 8 == 0 && ldo % 4 == 0, FORGE_ESHAPE, "forge_wino_output_dn4hw: Cout=%d ldo=%d (Cout multiple of 8; ldo of 4)", Cout, ldo);
+    FORGE_REQUIRE(epilogue == W_GRU_GATES || epilogue == W_GRU_OUT, FORGE_EINVAL, "forge_wino_output_dn4hw: epilogue %d is not a GRU tail (2, 3)", epilogue);
+    FORGE_REQUIRE(epilogue == W_GRU_GATES ? ldo == Cout / 2 : ldo >= Cout, FORGE_ESHAPE,
+                  "forge_wino_output_dn4hw: ldo=%d (epilogue 3: ldo >= Cout=%d; epilogue 2: ldo == Cout / 2)", ldo, Cout);
+    FORGE_REQUIRE(epilogue != W_GRU_GATES || out2, FORGE_EINVAL, "forge_wino_output_dn4hw: GRU gate epilogue needs out2");
+    FORGE_REQUIRE(epilogue != W_GRU_OUT || (aux_z && (!out2 || (scale && shift))), FORGE_EINVAL,
+                  "forge_wino_output_dn4hw: GRU out epilogue needs aux_z (and scale/shift with out2)");
+    WinoOutArgs a;
+    const long long R = (long long)n * D * (H / 4) * (W / 4);
+    a.Mm = Mm; a.ptm = R * Cout; a.Mm2 = nullptr; a.bs2 = 0; a.ptm2 = 0; a.bias = bias; a.scale = scale; a.shift = shift; a.slope = 1.f; a.residual = nullptr;
+    a.aux_h = aux_h; a.aux_z = aux_z; a.out = out; a.out2 = out2; a.out3 = out3; a.ldo = ldo; a.n = n; a.D = D; a.H = H; a.W = W; a.Cout = Cout; a.epi = epilogue;
+    FORGE_REQUIRE(R < (1ll << 31), FORGE_ESHAPE, "forge_wino_output_dn4hw: more than 2^31 tiles; split the batch");
+    const long long total = R * (Cout / 4), grid = (total + 127) / 128;              // 128 (tile, channel quad) items per workgroup, two threads each
+    FORGE_REQUIRE(grid < (1ll << 31), FORGE_ESHAPE, "forge_wino_output_dn4hw: grid too large");
+    const dim3 g((unsigned)grid), b(256);
+    if (epilogue == W_GRU_GATES) hipLaunchKernelGGL(wino_output_dn4hw_kernel<W_GRU_GATES>, g, b, 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(wino_output_dn4hw_kernel<W_GRU_OUT>, g, b, 0, (hipStream_t)stream, a);
+    FORGE_LAUNCH_CHECK("forge_wino_output_dn4hw");
     return 0;
 }

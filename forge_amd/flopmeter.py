@@ -1,6 +1,6 @@
 """Executed-FLOP meter for the matrix-core launches of libforge_hip.so (measurement aid for bench.py / tools; not on the product path).
 
-`with FlopMeter() as m: step()` wraps the ctypes entry points whose work runs on the fp32 MFMA pipe - forge_conv_igemm, forge_wino_gemm (_half, _dn, _dn4, _dn4h),
+`with FlopMeter() as m: step()` wraps the ctypes entry points whose work runs on the fp32 MFMA pipe - forge_conv_igemm, forge_wino_gemm (_half, _dn, _dn4, _dn4h, _dn4hw),
 forge_conv_wgrad, forge_wino_wgrad, forge_attention_fwd / _fwd_lse / _bwd / _mh_fwd / _mh_bwd, forge_token_linear_fwd / _bwd - for the duration of the block and sums the FLOPs each launch EXECUTES, computed from the call's own
 arguments (2 M N taps Cin for a direct / data-gradient / weight-gradient convolution, 2 x 16 R N kd Cin for the 16 Winograd point problems).
 Only eager launches made by this process are seen (a hipGraph replay makes no Python calls): meter one eager pass, time the replay.
@@ -8,7 +8,7 @@ Only eager launches made by this process are seen (a hipGraph replay makes no Py
 import torch
 
 from . import _lib
-from .convops import WINO_DN4H, WINO_FORMS
+from .convops import WINO_DN4H, WINO_DN4HW, WINO_FORMS
 
 
 def _v(a):
@@ -23,7 +23,7 @@ def _igemm(a):          # forge_conv_igemm(in1,C1,ld1,bs1,in2,C2,ld2,bs2,wp,bias
 
 def _wino_counter(form):    # forge_wino_gemm* (V1,C1,ld1,bs1,pt1,V2,C2,ld2,bs2,pt2,U,Mm,n,D,Ht,Wt,Cout,kd,[tile,]stream): 16 points x R rows x Cout x the form's
     def count(a):           # K loops of Cin per output plane (convops.WINO_FORMS: kd, 2 - four positions per PAIR of planes - or 3/2 - six per FOUR planes);
-        loops = _v(a[17]) if form.kloops is None else form.kloops           # WINO_DN4H: 24 points on ITS tile rows = 24 x 6 x Cin per four planes
+        loops = _v(a[17]) if form.kloops is None else form.kloops           # WINO_DN4H / WINO_DN4HW: 24 / 36 points on THEIR tile rows = 24 | 36 x 6 x Cin per four planes
         return float(2 * form.points * _v(a[12]) * _v(a[13]) * _v(a[14]) * _v(a[15]) * _v(a[16]) * loops * (_v(a[1]) + _v(a[6])))
     return count
 
@@ -66,7 +66,7 @@ def _token_bwd(a):      # forge_token_linear_bwd(dy,lddy,x,ldx,w,gamma,beta,stat
     return 2.0 * _v(a[16]) * _v(a[17]) * _v(a[18]) * ((1 if dxn else 0) + (1 if _v(a[10]) else 0))
 
 
-_ENTRIES = {"forge_conv_igemm": _igemm, **{f.gemm: _wino_counter(f) for f in (*WINO_FORMS.values(), WINO_DN4H)}, "forge_conv_wgrad": _wgrad, "forge_wino_wgrad": _wino_wgrad,
+_ENTRIES = {"forge_conv_igemm": _igemm, **{f.gemm: _wino_counter(f) for f in (*WINO_FORMS.values(), WINO_DN4H, WINO_DN4HW)}, "forge_conv_wgrad": _wgrad, "forge_wino_wgrad": _wino_wgrad,
             "forge_attention_fwd": _attention, "forge_attention_fwd_lse": _attention_lse, "forge_attention_bwd": _attention_bwd,
             "forge_attention_mh_fwd": _attention_mh, "forge_attention_mh_bwd": _attention_mh_bwd,
             "forge_token_linear_fwd": _token_fwd, "forge_token_linear_bwd": _token_bwd}

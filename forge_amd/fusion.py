@@ -240,11 +240,11 @@ def bn_act_rows(bn, rows, slope=1.0, residual=None, stats=None):
 def _step_scratch(R, C, dev, form=None, conv0=None):
     """One buffer for the point products of a GRU step's 2C-column (gates) and C-column (state, fusion_conv) launches over R tile rows of 2 x 2 voxels, sized
     for the larger of their forms: convops.wino_gemm returns each launch's products as a view of its front. form: the convops.WinoForm of the step's
-    launches (None: each launch's own choice between the points and their half form), P planes over its own tile rows (R x 2 / th); conv0: that of
+    launches (None: each launch's own choice between the points and their half form), P planes over its own tile rows (R x 4 / (th tw)); conv0: that of
     fusion_conv's C-column launches, when it is another."""
     F = co.WINO_FORMS
     P2, P1 = ((form or F["half" if co.wino_half_applies(R, c, C) else "points"]) for c in (2 * C, C))
-    need = [f.P * (R * 2 // f.th) * c for f, c in ((P2, 2 * C), (P1, C))]
+    need = [f.P * (R * 4 // (f.th * f.tw)) * c for f, c in ((P2, 2 * C), (P1, C))]
     if form is not None:
         need.append((conv0 or F["half" if co.wino_half_applies(R, C, C) else "points"]).P * R * C)
     return torch.empty(max(need), dtype=torch.float32, device=dev)
@@ -451,7 +451,7 @@ def _h0_direct(p, xr, grp, t0, h):
                   epilogue=co.EPI_AFFINE_ACT)
 
 
-def _wino_step(geo, x, view, views, wg, wo, V, Mm, h, z, hr, hn, out=None, r=None, cand=None, calls=None, th=2):
+def _wino_step(geo, x, view, views, wg, wo, V, Mm, h, z, hr, hn, out=None, r=None, cand=None, calls=None, th=2, tw=2):
     """One ConvGRU step on the Winograd launches over geo = (b, D, H, W): transform h, point GEMMs, inverse transform fused with the gate tail
     (z, hr = h r; r into `r`); transform hr, point GEMMs, inverse transform fused with tanh / lerp (hn; tanh(c) into `cand`, the fusion_norm
     folded output into `out`). (Fusing each inverse transform with the next input transform through LDS was built and measured slower -
@@ -461,7 +461,7 @@ def _wino_step(geo, x, view, views, wg, wo, V, Mm, h, z, hr, hn, out=None, r=Non
              hidden-half weights; the inverse transforms add view `view`'s products
     wg = (U, bias), wo = (U, bias, scale, shift). V: the buffer of both transforms, or None for a new one each (returned: the training node
     keeps them for the weight gradient). Mm: the point-product scratch (_step_scratch). calls = (input transform, point GEMM) of the form that x, V
-    and the weights are in (convops.wino_calls; default: convops.wino_input / wino_gemm, which read the form from the weights), th its tile height."""
+    and the weights are in (convops.wino_calls; default: convops.wino_input / wino_gemm, which read the form from the weights), th, tw its tile height and width."""
     b, D, H, W = geo
     C = h.shape[-1]
     transform, gemm = calls or co.wino_calls(co.WINO_FORMS["points"])
@@ -469,8 +469,8 @@ def _wino_step(geo, x, view, views, wg, wo, V, Mm, h, z, hr, hn, out=None, r=Non
     def conv(src, U, Cout, i):
         Vs = transform(src, C, C, b, D, H, W, out=V)
         if isinstance(x, tuple):                      # split adds Mm2, full does not
-            return Vs, gemm(Vs, C, None, 0, U, Mm, b, D, H // th, W // 2, Cout), dict(Mm2=x[i], view=view, views=views)
-        return Vs, gemm(x, C, Vs, C, U, Mm, b, D, H // th, W // 2, Cout, view=view, views=views), {}
+            return Vs, gemm(Vs, C, None, 0, U, Mm, b, D, H // th, W // tw, Cout), dict(Mm2=x[i], view=view, views=views)
+        return Vs, gemm(x, C, Vs, C, U, Mm, b, D, H // th, W // tw, Cout, view=view, views=views), {}
 
     Vh, G, add = conv(h, wg[0], 2 * C, 0)
     co.wino_output(G, wg[1], None, None, 1.0, None, h, None, z, hr, r, *geo, 2 * C, C, co.EPI_GRU_GATES, **add)
@@ -496,9 +496,9 @@ def _direct_step(grid, x, wg, wo, h, z, hr, hn, out=None, r=None, cand=None, bs=
 
 
 # form -> key suffix of its weights in ConvGRU_3D's pack cache
-_WKEY = {None: "_U", co.WINO_FORMS["dn"]: "_Ud", co.WINO_FORMS["dn4"]: "_Ud4", co.WINO_DN4H: "_Ud4h"}
+_WKEY = {None: "_U", co.WINO_FORMS["dn"]: "_Ud", co.WINO_FORMS["dn4"]: "_Ud4", co.WINO_DN4H: "_Ud4h", co.WINO_DN4HW: "_Ud4hw"}
 _PACKS = ((None, ("gate", "out", "fc0", "fc3")), (co.WINO_FORMS["dn"], ("gate", "out", "fc0", "fc3")), (co.WINO_FORMS["dn4"], ("gate", "out")),
-          (co.WINO_DN4H, ("gate", "out")))
+          (co.WINO_DN4H, ("gate", "out")), (co.WINO_DN4HW, ("gate", "out")))
 
 
 def _fuse_eval(gru, xr, groups, wino, split, h0=None, keep=None, const0=None):
@@ -519,8 +519,9 @@ def _fuse_eval(gru, xr, groups, wino, split, h0=None, keep=None, const0=None):
     if wino:
         R = b * D * (H // 2) * (W // 2)
         F = co.WINO_FORMS
-        # a form's rule on ITS tile grid (H / th, W / 2), for both launches of a step
-        both = lambda form: H % form.th == 0 and all(form.applies(R * 2 // form.th, D, H // form.th, W // 2, c, 2 * C) for c in (2 * C, C))
+        # a form's rule on ITS tile grid (H / th, W / tw), for both launches of a step
+        both = lambda form: H % form.th == 0 and W % form.tw == 0 and all(
+            form.applies(R * 4 // (form.th * form.tw), D, H // form.th, W // form.tw, c, 2 * C) for c in (2 * C, C))
         fits = lambda form: co.wino_fits(b, D, H, W, C, views=t, form=form)
         # the full steps of the plain eval fusion take the depth nest where both of their launches qualify (K = 2C per depth position)
         if not split and keep is None and const0 is None and both(F["dn"]):
@@ -530,6 +531,9 @@ def _fuse_eval(gru, xr, groups, wino, split, h0=None, keep=None, const0=None):
             # and F(4, 3) along H as well (24 points on tiles of 4 x 2: 3/4 of the K loops, operand and point-product bytes) where that form's rule holds
             if step is F["dn4"] and both(co.WINO_DN4H) and fits(co.WINO_DN4H):
                 step = co.WINO_DN4H
+            # and along W (36 points on tiles of 4 x 4: again 3/4 of the K loops and bytes) where that form's rule holds: at least 64 channels
+            if step is co.WINO_DN4H and both(co.WINO_DN4HW) and fits(co.WINO_DN4HW):
+                step = co.WINO_DN4HW
             # fusion_conv's two launches (K = C per position) follow where the rule holds for them (tools/wino_dn_probe.py: 0.90 of the four-point
             # pair) and stay on F(2, 3) (four K-steps per loop)
             conv0 = F["dn"] if F["dn"].applies(R, D, H // 2, W // 2, C, C) else None
@@ -544,9 +548,11 @@ def _fuse_eval(gru, xr, groups, wino, split, h0=None, keep=None, const0=None):
         if split:
             X = (_input_products(X, p["gate_Ux"], b * t, geo, 2 * C), _input_products(X, p["out_Ux"], b * t, geo, C))
         # one buffer for the transforms of h and h r in the steps' form; fusion_conv's plain transforms (and const0's step) alias its front - the
-        # F(4, 3) operands have 1.5 x the rows (24 points x 3/4 of them with F(4, 3) along H: 18 R C >= 16 R C)
-        Vs = torch.empty(step.points, int(R * 2 // step.th * step.rows), C, dtype=torch.float32, device=dev) if step else torch.empty(16, R, C, dtype=torch.float32, device=dev)
-        V = Vs.reshape(-1)[:16 * R * C].view(16, R, C)
+        # F(4, 3) operands have 1.5 x the rows (24 points x 3/4 of them with F(4, 3) along H: 18 R C >= 16 R C; 36 points x 3/8 along W as well: 13.5 R C)
+        srows = int(R * 4 // (step.th * step.tw) * step.rows) if step else R
+        buf = torch.empty(max(step.points * srows if step else 0, 16 * R) * C, dtype=torch.float32, device=dev)
+        V = buf[:16 * R * C].view(16, R, C)
+        Vs = buf[:step.points * srows * C].view(step.points, srows, C) if step else V
         Mm = _step_scratch(R, C, dev, step, conv0)
     elif split:                                                            # the input halves once per view (no bias: added with the hidden half)
         X = {}
@@ -583,7 +589,7 @@ def _fuse_eval(gru, xr, groups, wino, split, h0=None, keep=None, const0=None):
             elif const0 is not None and k == 0:
                 _wino_step(geo, (const0["MXg0"], const0["MXc0"]), 0, 1, *weights("h"), V, Mm, h, z, hr, hn, last, r, cand)
             else:
-                _wino_step(geo, X, ti, t, wg, wo, Vs, Mm, h, z, hr, hn, last, r, cand, calls=calls, th=step.th if step else 2)
+                _wino_step(geo, X, ti, t, wg, wo, Vs, Mm, h, z, hr, hn, last, r, cand, calls=calls, th=step.th if step else 2, tw=step.tw if step else 2)
             if keep is not None:
                 keep += [h, z, r, cand]
             h, hn = hn, h

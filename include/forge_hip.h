@@ -355,6 +355,29 @@ int forge_wino_gemm_dn4h(const float* V1, int C1, int ld1, long long bs1, long l
                          long long pt2, const float* Ud, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, forge_stream_t stream);
 int forge_wino_output_dn4h(const float* Mm, const float* bias, const float* scale, const float* shift, const float* aux_h, const float* aux_z, float* out,
                            float* out2, float* out3, int n, int D, int H, int W, int Cout, int ldo, int epilogue, forge_stream_t stream);
+/* The F(4, 3) depth nest with F(4, 3) along H AND W ("dn4hw"): tiles of 4 x 4 output voxels, Ht = H / 4, Wt = W / 4, 36 points p = 6 i + j (i = 0..5 the H point,
+ * j = 0..5 the W point) - 2.25 multiplies per output against dn4h's 3, operands and point products at 3/4 of its bytes. Four entries:
+ * forge_wino_input_dn4hw: V [36][n][D/4][6][Ht Wt][C] (arguments as forge_wino_input_dn4h: bs, nsum / sum_stride, ldv, ptv). Per tile (th, tw) of group g the patch is
+ *   the six planes 4 g - 1 .. 4 g + 4 x the six rows 4 th - 1 .. 4 th + 4 x the six columns 4 tw - 1 .. 4 tw + 4 (zero outside the element's grid, never the
+ *   neighbouring element). Three stages, in this order, each forge_wino_input_dn4's six lines q0 .. q5: (1) depth, per patch element, on the planes; (2) rows, per
+ *   position k and patch column, on the six patch rows of q_k; (3) columns, per position and point row i, on the six patch columns: V[6 i + j] = line j. Every
+ *   multiplier is a power of two: a float32 evaluation in this order reproduces the bits. FORGE_EINVAL unless D % 4 == 0, D >= 8, H % 4 == 0, W % 4 == 0.
+ * forge_wino_weights_dn4hw: Ud [36][6][Cout][Cin] = G4(depth) (x) G4(H) (x) G4(W) from wp [27][Cout][Cin]: forge_wino_weights_dn4's six depth rows on every element,
+ *   then the same six rows over the kernel's H taps, then the same six rows over its W taps; float64 throughout, rounded once.
+ * forge_wino_gemm_dn4hw: forge_wino_gemm_dn4h's launch with 36 batched problems on the grid (n, D, Ht, Wt): Mm [36][n D Ht Wt][Cout]; V1 | V2 along K, view strides as
+ *   there. FORGE_EINVAL, before any launch, unless kd == 3, D % 4 == 0, D >= 8, Ht Wt % 64 == 0, C1 and C2 are multiples of 32 and every operand and output plane
+ *   stays within 32-bit offsets.
+ * forge_wino_output_dn4hw: the inverse transform with the GRU tails of forge_wino_output_dn4h (epilogue 2: gates, ldo == Cout / 2; 3: state; no second addend, no
+ *   residual, as that entry). Over the six H points, per W point: s = m1 + m2, d = m1 - m2, S = m3 + m4, D = m3 - m4, rows (s + S) + m0 | d + 2 D | s + 4 S |
+ *   (d + 8 D) + m5 (the scalings fused, exact); then THE SAME four lines over the six W points of each row; the tails run on the 4 x 4 voxels.
+ *   FORGE_EINVAL unless H % 4 == 0 and W % 4 == 0; FORGE_ESHAPE unless Cout % 8 == 0. */
+int forge_wino_input_dn4hw(const float* in, int ld, long long bs, float* V, int ldv, long long ptv, int n, int D, int H, int W, int C,
+                           int nsum, long long sum_stride, forge_stream_t stream);
+int forge_wino_weights_dn4hw(const float* wp, float* Ud, int Cout, int Cin, forge_stream_t stream);
+int forge_wino_gemm_dn4hw(const float* V1, int C1, int ld1, long long bs1, long long pt1, const float* V2, int C2, int ld2, long long bs2,
+                          long long pt2, const float* Ud, float* Mm, int n, int D, int Ht, int Wt, int Cout, int kd, forge_stream_t stream);
+int forge_wino_output_dn4hw(const float* Mm, const float* bias, const float* scale, const float* shift, const float* aux_h, const float* aux_z, float* out,
+                            float* out2, float* out3, int n, int D, int H, int W, int Cout, int ldo, int epilogue, forge_stream_t stream);
 int forge_wino_gemm_tile(long long R, int Cout, int Cin);   /* the workgroup tile letter ('A'..'E', see forge_conv_igemm_plan) forge_wino_gemm uses for R tile rows per point, Cin = C1 + C2 */
 int forge_wino_output(const float* Mm, const float* Mm2, long long bs2, long long pt2, const float* bias, const float* scale, const float* shift, float slope, const float* residual,
                       const float* aux_h, const float* aux_z, float* out, float* out2, float* out3, int n, int D, int H, int W, int Cout,

@@ -6,7 +6,8 @@
         ITERS launches, best of 3, and the largest difference of the two results; then the F(4, 3) form: its operand transform of the hidden-state
         operand (forge_wino_input_dn4 against forge_wino_input), its GEMM (forge_wino_gemm_dn4) and the transform + GEMM + inverse pair against both
         the F(2, 3) nest's and the four-point form's; then, for gates and state with their GRU tails, the 24-point form (F(4, 3) along H as well,
-        convops.WINO_DN4H) against the F(4, 3) nest launch by launch: transform, GEMM, inverse.  -> DIR/<--tag>_launch.txt
+        convops.WINO_DN4H) against the F(4, 3) nest, and the 36-point form (along W as well, convops.WINO_DN4HW) against the 24-point form, launch by
+        launch: transform, GEMM, inverse.  -> DIR/<--tag>_launch.txt
     python tools/wino_dn_probe.py ab --parent-root DIR0 [--pairs 3] [--out DIR] [-- bench arguments]
         End to end: `python bench.py <bench arguments>` of a built checkout of the parent commit (DIR0) and of this tree, alternated --pairs times in
         fresh processes; one JSON line per run and the pair rule (new value_min above the parent's value_max in EVERY pair) with the median ratio.
@@ -91,19 +92,20 @@ def launch(args):
                          name, t4, tf(t4, 1.5), t_in6, t_in, p4, p2, p1, p4 / p2, p4 / p1))
     # the 24-point form (F(4, 3) along H as well, convops.WINO_DN4H) against the F(4, 3) nest, launch by launch, with the GRU tails of the steps
     lines.append("per launch, us: transform of the hidden-state operand | point GEMM | inverse transform with the GRU tail | sum")
-    F4, FH = co.WINO_FORMS["dn4"], co.WINO_DN4H
+    F4, FH, FHW = co.WINO_FORMS["dn4"], co.WINO_DN4H, co.WINO_DN4HW
     for name, Cout, epi in (("gates", 2 * C, co.EPI_GRU_GATES), ("state", C, co.EPI_GRU_OUT)):
         wp = rn(27, Cout, 2 * C) / (27 * 2 * C) ** 0.5
         x, h, z = rn(M, C), rn(M, C), torch.rand(M, C, generator=g).to(dev)
         o1, o2 = torch.empty(M, C, device=dev), torch.empty(M, C, device=dev)
         row = []
-        for f in (F4, FH):
-            Rf, rows = b * D * (H // f.th) * Wt, int(b * D * (H // f.th) * Wt * f.rows)
+        for f in (F4, FH, FHW):
+            Wf = W // f.tw
+            Rf, rows = b * D * (H // f.th) * Wf, int(b * D * (H // f.th) * Wf * f.rows)
             U = co.wino_pack(f, wp)
             Vx, Vh = rn(f.points, rows, C), torch.empty(f.points, rows, C, device=dev)
             Mm = torch.empty(f.P * Rf * Cout, device=dev)
             t_in = timed(lambda: co.wino_form_input(f, x, C, C, b, D, H, W, out=Vh))
-            gemm = lambda: co.wino_form_gemm(f, Vx, C, Vh, C, U, Mm, b, D, H // f.th, Wt, Cout)
+            gemm = lambda: co.wino_form_gemm(f, Vx, C, Vh, C, U, Mm, b, D, H // f.th, Wf, Cout)
             t_g = timed(gemm)
             P = gemm()
             inv = ((lambda: co.wino_output(P, None, None, None, 1.0, None, h, None, o1, o2, None, b, D, H, W, Cout, C, epi)) if epi == co.EPI_GRU_GATES else
@@ -111,9 +113,9 @@ def launch(args):
             t_o = timed(inv)
             wgs = (Rf // 256) * ((Cout + 127) // 128) * f.points
             row.append((f.name, t_in, t_g, t_o, wgs))
-        (n4, i4, g4, o4, w4), (nh, ih, gh, oh, wh) = row
-        lines.append("%-6s %-5s %6.1f | %7.1f (%4d workgroups) | %6.1f | %7.1f    %-5s %6.1f | %7.1f (%4d workgroups) | %6.1f | %7.1f    ratios %.3f %.3f %.3f | %.3f" % (
-            name, n4, i4, g4, w4, o4, i4 + g4 + o4, nh, ih, gh, wh, oh, ih + gh + oh, ih / i4, gh / g4, oh / o4, (ih + gh + oh) / (i4 + g4 + o4)))
+        for (n4, i4, g4, o4, w4), (nh, ih, gh, oh, wh) in zip(row, row[1:]):
+            lines.append("%-6s %-5s %6.1f | %7.1f (%4d workgroups) | %6.1f | %7.1f    %-5s %6.1f | %7.1f (%4d workgroups) | %6.1f | %7.1f    ratios %.3f %.3f %.3f | %.3f" % (
+                name, n4, i4, g4, w4, o4, i4 + g4 + o4, nh, ih, gh, wh, oh, ih + gh + oh, ih / i4, gh / g4, oh / o4, (ih + gh + oh) / (i4 + g4 + o4)))
     text = "\n".join(lines)
     print(text)
     os.makedirs(args.out, exist_ok=True)
