@@ -1,8 +1,9 @@
-// geom_common.h — what mesh.hip, bake.hip, geomdist.hip, tridist.hip, components.hip, align.hip and metrics.hip share, written once (header only: no
-// translation unit).
+// geom_common.h — what mesh.hip, bake.hip, geomdist.hip, tridist.hip, winding.hip, components.hip, align.hip and metrics.hip share, written once
+// (header only: no translation unit; the one function it merely declares, stage_triangles, lives beside its kernel in tridist.hip).
 //   wave / block primitives   wave_inclusive_scan, wave_sum, waves_before, block_exclusive_scan_inplace (integer scans: any order gives the same bits)
 //   row spans                 row_span, mesh_spans: the rows of a padded or packed mesh array that one volume owns (forge_hip.h sections g1, g2, g3)
 //   mesh rows                 MeshRows, mesh_rows, face_area, face_normal, clamp_count, apply_xf: what geomdist.hip and tridist.hip read a mesh and a pair by
+//   triangle records          TRI_REC, TRI_TILE, stage_triangles: the staged face records tridist.hip and winding.hip search (defined in tridist.hip)
 //   fixed-tree reductions     block_reduce256 / block_sum256 / block_max256: float64, ONE tree, so every caller keeps its bits
 //   host side                 ws_align, ws_layout, volume_dims_ok, workspace_ok, level_ok: the argument checks of the workspace entry points
 #pragma once
@@ -139,6 +140,16 @@ __device__ __forceinline__ void apply_xf(const float* __restrict__ m, float& x, 
     y = fmaf(m[6], z0, fmaf(m[5], y0, fmaf(m[4], x0, m[7])));
     z = fmaf(m[10], z0, fmaf(m[9], y0, fmaf(m[8], x0, m[11])));
 }
+
+// ------------------------------------------------------------------------------------------------------------------------ triangle records
+// What tridist.hip stages and tridist.hip and winding.hip search (section g3b: the workspace): one record of TRI_REC floats per face row,
+// ax ay az bx | by bz cx cy | cz nx ny nz (three float4), all NaN for a face that is no candidate; walked in LDS tiles of TRI_TILE records.
+constexpr int TRI_REC = 12;
+constexpr int TRI_TILE = 256;                      // forge_nn_tile_faces()
+
+// tridist.hip's staging launch (tri_stage_kernel) on `stream`: the records of every face row of the B meshes of m into rec, xf_mesh (nullable)
+// applied to the corners. No launch without face rows. Returns 0 or the launch's error, reported under the entry's name fn.
+int stage_triangles(const MeshRows& m, const float* xf_mesh, float4* rec, int B, hipStream_t stream, const char* fn);
 
 // ------------------------------------------------------------------------------------------------------------------ fixed-tree reductions
 // One double per thread of a 256-thread workgroup, combined by the fixed tree red[t] = op(red[t], red[t + s]), s = 128 .. 1; valid in thread 0.

@@ -25,9 +25,8 @@ namespace forge {
 
 constexpr int NT_THREADS = 256;
 constexpr int NT_Q = NT_THREADS;                   // queries per workgroup: one per lane, as nn_points_kernel measured to be right
-constexpr int NT_T = 256;                          // faces per LDS tile (one per thread)
+constexpr int NT_T = TRI_TILE;                     // faces per LDS tile (one per thread)
 constexpr int NT_G = 8;                            // faces per group: the minimum is tracked per group, its face found afterwards
-constexpr int TRI_REC = 12;                        // floats per record: ax ay az bx | by bz cx cy | cz nx ny nz (three float4)
 static_assert(NT_T == NT_THREADS && NT_T % NT_G == 0, "thread t stages record t of a tile; a tile is whole groups");
 
 struct TriRec {
@@ -66,6 +65,16 @@ __global__ __launch_bounds__(NT_THREADS) void tri_stage_kernel(MeshRows m, const
     o[0] = r0;
     o[1] = r1;
     o[2] = r2;
+}
+
+// The staging launch, for every entry that searches the records (geom_common.h declares it): one record per face row of every mesh into rec.
+int stage_triangles(const MeshRows& m, const float* xf_mesh, float4* rec, int B, hipStream_t stream, const char* fn) {
+    if (m.max_faces > 0) {
+        hipLaunchKernelGGL(tri_stage_kernel, dim3((unsigned)((m.max_faces + NT_THREADS - 1) / NT_THREADS), (unsigned)B), dim3(NT_THREADS), 0, stream, m,
+                           xf_mesh, rec);
+        FORGE_LAUNCH_CHECK(fn);
+    }
+    return 0;
 }
 
 __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) { return fmaf(az, bz, fmaf(ay, by, ax * bx)); }
@@ -247,11 +256,8 @@ extern "C" int forge_nn_triangles(const float* q, const int* q_count, const floa
     m.vertices = vertices; m.faces = faces; m.counts = counts; m.offsets = offsets;
     m.max_vertices = max_vertices; m.max_faces = max_faces;
     float4* rec = (float4*)workspace;
-    if (max_faces > 0) {
-        hipLaunchKernelGGL(tri_stage_kernel, dim3((unsigned)((max_faces + NT_THREADS - 1) / NT_THREADS), (unsigned)B), dim3(NT_THREADS), 0,
-                           (hipStream_t)stream, m, xf_mesh, rec);
-        FORGE_LAUNCH_CHECK("forge_nn_triangles");
-    }
+    const int rs = stage_triangles(m, xf_mesh, rec, B, (hipStream_t)stream, "forge_nn_triangles");
+    if (rs != 0) return rs;
     hipLaunchKernelGGL(nn_triangles_kernel, dim3((unsigned)((Nq + NT_Q - 1) / NT_Q), (unsigned)B), dim3(NT_THREADS), 0, (hipStream_t)stream, q, q_count,
                        xf_q, m, (const float4*)rec, Nq, d2, face, closest, normal);
     FORGE_LAUNCH_CHECK("forge_nn_triangles");

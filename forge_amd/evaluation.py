@@ -259,12 +259,22 @@ def sync_pose(return_dict, best_canonical_id, device=None, rank_tol=1e-6):
     return torch.where(status.reshape(1, 1) != 0, keep, synced), status
 
 
-def evaluate_geometry(pred_meshes, gt_meshes, transform=None, align=None, **kw):
+def evaluate_geometry(pred_meshes, gt_meshes, transform=None, align=None, iou=False, **kw):
     """The surface metrics beside the image and pose metrics above: geometry.mesh_metrics(pred_meshes, gt_meshes, transform=transform, align=align,
     **kw) - accuracy, completeness, Chamfer, Hausdorff, F-score and normal consistency as float64 device tensors, one entry per mesh pair.
     transform maps the predictions (canonical frame of view 0) into the ground truth's frame; where nobody knows it (predicted poses, photographs,
     meshes in their own object frame), align="icp" or a dict of geometry.align_points keywords estimates it on the device first and returns it
     under 'alignment'. surface="triangles" (passed through **kw) scores each side's samples against the other side's triangles, not its
-    samples: the distance to the surface, free of the sampling floor. Not part of evaluate_all, whose outputs are the reference's."""
+    samples: the distance to the surface, free of the sampling floor. iou=True, or a dict of geometry.volume_iou keywords (n, absolute), adds
+    the volumetric intersection over union under the same transform - the one align= found, when it found one: 'iou', 'volume_pred', 'volume_gt'
+    and 'iou_status' (volume_iou's 'status'); both sides must then be meshes. Not part of evaluate_all, whose outputs are the reference's."""
     from . import geometry
-    return geometry.mesh_metrics(pred_meshes, gt_meshes, transform=transform, align=align, **kw)
+    res = geometry.mesh_metrics(pred_meshes, gt_meshes, transform=transform, align=align, **kw)
+    if iou is not False and iou is not None:
+        if not (iou is True or isinstance(iou, dict)):
+            raise ValueError("evaluate_geometry: iou must be False, True or a dict of volume_iou keywords, got %r" % (iou,))
+        if "alignment" in res:
+            transform = res["alignment"].transform.to(torch.float32)
+        vol = geometry.volume_iou(pred_meshes, gt_meshes, transform=transform, **(iou if isinstance(iou, dict) else {}))
+        res.update({"iou": vol["iou"], "volume_pred": vol["volume_pred"], "volume_gt": vol["volume_gt"], "iou_status": vol["status"]})
+    return res

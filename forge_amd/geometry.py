@@ -24,7 +24,12 @@ first.
 
 align_points, align_meshes and fit_similarity find the similarity between a prediction and its ground truth when nobody knows it (csrc/align.hip,
 section g5): ICP on the exact nearest-neighbour search above with a closed-form float64 update per iteration, several starts in one batch,
-nothing read back; mesh_metrics(align="icp") scores under what they find."""
+nothing read back; mesh_metrics(align="icp") scores under what they find.
+
+winding_number says whether a point is inside (csrc/winding.hip, section g3c): the generalized winding number, defined for any triangle soup, so
+ground-truth scans with holes have an answer where ray parity has none. contains thresholds it, signed_distance gives point_mesh_distance its
+sign, voxelize evaluates it on extract_mesh's own lattice (occupancy targets from a mesh; voxelize(extract_mesh(d)) is d > level), and
+volume_iou is the volumetric intersection over union of two meshes on deterministic quasi-random points."""
 import math
 from collections import namedtuple
 
@@ -704,6 +709,148 @@ def point_mesh_distance(points, meshes, transform=None, counts=None):
     xf = None if transform is None else _pack_transform(transform, q.shape[0], q.device)[0]
     d2, face, closest, normal = ops.nn_triangles(q, vertices, faces, mcounts, offsets=offsets, q_count=counts, xf_q=xf, want_closest=True, want_normal=True)
     return PointMeshDistance(d2.sqrt(), face, closest, normal)
+
+
+# ------------------------------------------------------------------------------------------------------------------ inside or outside
+def _winding(fn, points, meshes, transform=None, counts=None, mesh_transform=None):
+    """ops.winding_number of points [B,N,3] ([N,3]: one mesh) against meshes (a Mesh, a list of Mesh or a MeshBatch): transform maps the points
+    into the meshes' frame, mesh_transform the meshes into the points' frame -> (w [B,N], the queries as a batch)."""
+    q = _as_batch(points, "points")
+    ops._require_cuda(q)
+    vertices, faces, mcounts, offsets = _surface_rows(meshes, fn)
+    B = q.shape[0]
+    if mcounts.shape[0] != B:
+        raise ValueError("%s: %d point sets against %d meshes" % (fn, B, mcounts.shape[0]))
+    xf_q = None if transform is None else _pack_transform(transform, B, q.device)[0]
+    xf_mesh = None if mesh_transform is None else _pack_transform(mesh_transform, B, q.device)[0]
+    return ops.winding_number(q, vertices, faces, mcounts, offsets=offsets, q_count=counts, xf_q=xf_q, xf_mesh=xf_mesh), q
+
+
+def _inside(w, threshold, absolute):
+    return (w.abs() if absolute else w) > float(threshold)
+
+
+def winding_number(points, meshes, transform=None, counts=None):
+    """The generalized winding number of points [B,N,3] ([N,3] for one mesh) with respect to meshes - a Mesh, a list of Mesh (packed rows) or a
+    MeshBatch (padded rows, no host synchronisation), one mesh per batch entry (ops.winding_number, include/forge_hip.h section g3c): the signed
+    solid angles of the triangles seen from the point, summed, over 4 pi. For a closed mesh wound as extract_mesh winds it: 1 inside, 0 outside,
+    exactly up to rounding. It is defined for any triangle soup: a scan with holes gives values near 1 inside and near 0 outside that cross the
+    holes smoothly - which ray parity cannot do. transform ([4,4] or [B,4,4], a similarity) maps the points into the meshes' frame first; counts
+    [B] int32 on the device limits the valid rows (rows past it get 0). Returns w [B,N] float32. Nothing is read back."""
+    return _winding("winding_number", points, meshes, transform, counts)[0]
+
+
+def contains(points, meshes, threshold=0.5, absolute=False, transform=None, counts=None):
+    """Which of points [B,N,3] lie inside meshes: winding_number(points, meshes, transform, counts) > threshold - a strict fp32 compare on the
+    float32 winding number. absolute=True compares |w|, for meshes whose orientation is unknown (an inward-wound closed mesh has w = -1
+    inside). Returns bool [B,N]; rows past counts are outside. Nothing is read back."""
+    return _inside(_winding("contains", points, meshes, transform, counts)[0], threshold, absolute)
+
+
+SignedDistance = namedtuple("SignedDistance", "distance face closest normal w")
+SignedDistance.__doc__ = """signed_distance, device tensors: PointMeshDistance's fields with distance [B,N] float32 NEGATIVE inside (the sign bit is set exactly
+where `contains` holds; the magnitude is point_mesh_distance's, bit for bit), and w [B,N] float32, the winding number the sign was taken from."""
+
+
+def signed_distance(points, meshes, threshold=0.5, absolute=False, transform=None, counts=None):
+    """point_mesh_distance with a sign: negative where contains(points, meshes, threshold, absolute, transform, counts). The sign comes from the
+    winding number, not from the normal of the closest face - that one is wrong near edges and vertices and means nothing on a mesh with holes.
+    Returns a SignedDistance. The faces are staged twice (once per search). Nothing is read back."""
+    hit = point_mesh_distance(points, meshes, transform=transform, counts=counts)
+    w, _ = _winding("signed_distance", points, meshes, transform, counts)
+    return SignedDistance(torch.where(_inside(w, threshold, absolute), -hit.distance, hit.distance), hit.face, hit.closest, hit.normal, w)
+
+
+_LATTICES = {}
+
+
+def _lattice(shape, volume_size, device):
+    """The grid points of extract_mesh's lattice (section g1) as [D H W,3] float32 rows (x, y, z) <-> (W, H, D), z slowest: index i of an axis of N
+    lies at ((2 i) / (N - 1) - 1) e, e = 0.5 (N - 1) volume_size / N, evaluated as (i - 0.5 (N - 1)) (volume_size / N) in float64 and rounded
+    once. Built with torch, once per (shape, volume_size, device)."""
+    key = (tuple(shape), float(volume_size), torch.device(device))
+    if key not in _LATTICES:
+        D, H, W = key[0]
+        axis = lambda N: ((torch.arange(N, dtype=torch.float64, device=device) - 0.5 * (N - 1)) * (key[1] / N)).to(torch.float32)      # noqa: E731
+        Z, Y, X = torch.meshgrid(axis(D), axis(H), axis(W), indexing="ij")
+        _LATTICES[key] = torch.stack([X, Y, Z], dim=-1).reshape(D * H * W, 3).contiguous()
+    return _LATTICES[key]
+
+
+def voxelize(meshes, shape, volume_size=1.0, transform=None, threshold=0.5, absolute=False):
+    """Occupancy of meshes (a Mesh, a list of Mesh or a MeshBatch) on the lattice extract_mesh marches over: bool [B,D,H,W] for shape = (D, H, W),
+    True where the grid point - index i of an axis of N at ((2 i) / (N - 1) - 1) e, e = 0.5 (N - 1) volume_size / N, (x, y, z) <-> (W, H, D) -
+    lies inside (contains). voxelize(extract_mesh(d, level), d.shape[2:]) is `d > level` at every grid point: ground-truth occupancy for the
+    density head from a mesh, and a mesh-side check of extract_mesh and keep_components. transform ([4,4] or [B,4,4]) maps the grid points into
+    the meshes' frame. Nothing is read back."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError("voxelize: shape must be (D, H, W) with positive extents, got %r" % (shape,))
+    rows = _surface_rows(meshes, "voxelize")
+    B, dev = int(rows[2].shape[0]), rows[0].device
+    q = _lattice(shape, volume_size, dev)[None].expand(B, -1, 3).contiguous()
+    xf = None if transform is None else _pack_transform(transform, B, dev)[0]
+    w = ops.winding_number(q, *rows[:3], offsets=rows[3], xf_q=xf)
+    return _inside(w, threshold, absolute).reshape(B, *shape)
+
+
+R3 = (3518319155, 2882110345, 2360945575)          # round(2^32 / g^k), k = 1, 2, 3, g the real root of g^4 = g + 1
+
+
+def r3_points(n, device=None):
+    """The first n points of volume_iou's sequence in the unit cube, [n,3] float32: integers only - coordinate k of point i is
+    (uint32(i R3[k] + 2^31) >> 8) 2^-24, the R3 low-discrepancy sequence (additive recurrence on the powers of 1 / g, g^4 = g + 1) in 32-bit
+    wrap-around arithmetic, started at the centre of the cube. Exact in fp32, in [0, 1), the same bits everywhere."""
+    i = torch.arange(int(n), dtype=torch.int64, device=device)
+    k = torch.stack([((i * c + 0x80000000) & 0xFFFFFFFF) >> 8 for c in R3], dim=-1)
+    return k.to(torch.float32) * (2.0 ** -24)
+
+
+def _bounding_box(rows, lin=None, shift=None):
+    """Per mesh the box of its valid vertex rows (past the counts, before the offsets: masked), after x -> lin x + shift when given ->
+    (lo [B,3], hi [B,3]) float32; a mesh without vertices gives (+inf, -inf), the neutral element of the union."""
+    vertices, _, counts, offsets = rows
+    v = vertices if vertices.dim() == 3 else vertices[None]
+    r = torch.arange(v.shape[1], device=v.device)[None]
+    start = 0 if offsets is None else offsets[:, 0:1]
+    mask = ((r >= start) & (r < start + counts[:, 0:1]))[..., None]
+    if lin is not None:
+        v = v @ lin.transpose(1, 2) + shift[:, None, :]
+    inf = torch.full((), math.inf, device=v.device)
+    if v.shape[1] == 0:                            # no vertex rows at all: amin of nothing
+        return inf.expand(counts.shape[0], 3), (-inf).expand(counts.shape[0], 3)
+    return torch.where(mask, v, inf).amin(dim=1), torch.where(mask, v, -inf).amax(dim=1)
+
+
+def volume_iou(pred, gt, n=100_000, transform=None, absolute=True):
+    """Volumetric intersection over union of meshes pred and gt (each a Mesh, a list of Mesh or a MeshBatch; one pair per mesh) - the standard
+    shape metric beside Chamfer distance and F-score. n deterministic quasi-random points (r3_points: the R3 sequence with the 32-bit constants
+    R3 = (3518319155, 2882110345, 2360945575), started at the centre) are spread over the union bounding box of the two meshes' valid vertices
+    (computed on the device), pred under transform ([4,4] or [B,4,4], a similarity into gt's frame); both sides classify them by `contains`
+    (absolute=True by default: ground-truth meshes come wound either way). Returns a dict of float64 device tensors [B]: 'iou' (points inside
+    both over points inside either; NaN when there are none), 'volume_pred' and 'volume_gt' (the inside share times the box volume, in gt's
+    frame), and 'status' [B] int32 with ops.GEOM_EMPTY for a pair with a side that has no faces, whose iou is NaN. The Monte-Carlo error of
+    the shares is below 1 / sqrt(n). With MeshBatch inputs nothing synchronises with the host."""
+    rows_p, rows_g = _surface_rows(pred, "volume_iou"), _surface_rows(gt, "volume_iou")
+    B, dev = int(rows_p[2].shape[0]), rows_p[0].device
+    if rows_g[2].shape[0] != B:
+        raise ValueError("volume_iou: %d predictions against %d ground truths" % (B, rows_g[2].shape[0]))
+    xf = lin = shift = None
+    if transform is not None:
+        xf, lin = _pack_transform(transform, B, dev)
+        shift = xf.reshape(B, 3, 4)[:, :, 3]
+    lo_p, hi_p = _bounding_box(rows_p, lin, shift)
+    lo_g, hi_g = _bounding_box(rows_g)
+    lo, hi = torch.minimum(lo_p, lo_g), torch.maximum(hi_p, hi_g)
+    q = (lo[:, None, :] + r3_points(n, dev)[None] * (hi - lo)[:, None, :]).contiguous()
+    in_p = _inside(ops.winding_number(q, *rows_p[:3], offsets=rows_p[3], xf_mesh=xf), 0.5, absolute)
+    in_g = _inside(ops.winding_number(q, *rows_g[:3], offsets=rows_g[3]), 0.5, absolute)
+    count = lambda m: m.sum(dim=1).to(torch.float64)          # noqa: E731
+    box = (hi - lo).to(torch.float64).prod(dim=1)
+    empty = (rows_p[2][:, 1] <= 0) | (rows_g[2][:, 1] <= 0)
+    iou = torch.where(empty, torch.full((), math.nan, dtype=torch.float64, device=dev), count(in_p & in_g) / count(in_p | in_g))
+    return {"iou": iou, "volume_pred": count(in_p) / float(n) * box, "volume_gt": count(in_g) / float(n) * box,
+            "status": torch.where(empty, ops.GEOM_EMPTY, 0).to(torch.int32)}
 
 
 def _triangle_metrics(pred, gt, n, thresholds, transform):

@@ -1164,6 +1164,42 @@ def nn_triangles(q, vertices, faces, counts, offsets=None, q_count=None, xf_q=No
 
 
 @_lib.on_tensor_device
+def winding_number(q, vertices, faces, counts, offsets=None, q_count=None, xf_q=None, xf_mesh=None, workspace=None):
+    """forge_winding_number (section g3c): for every query q [B,Nq,3] the generalized winding number of mesh b - the signed solid angles of its
+    triangles summed, over 4 pi: 1 inside a closed mesh wound as mesh_emit winds it, 0 outside, and defined for meshes with holes. The mesh rows,
+    q_count, xf_q, xf_mesh and workspace (forge_winding_workspace_bytes) as nn_triangles takes them; faces with a bad index or without area add
+    nothing. Returns w [B,Nq] float32; rows past q_count and meshes without a valid face get 0. Nothing is read back."""
+    tensors = (q, vertices, faces, counts)
+    optional = (offsets, q_count, xf_q, xf_mesh, workspace)
+    if not all(torch.is_tensor(t) for t in tensors) or not all(t is None or torch.is_tensor(t) for t in optional):
+        raise TypeError("winding_number: q, vertices, faces, counts (and offsets, q_count, xf_q, xf_mesh, workspace) must be tensors")
+    _require_cuda(*tensors, *optional)
+    if q.dim() != 3 or q.shape[2] != 3 or min(q.shape[:2]) < 1:
+        raise ValueError("winding_number: q must be [B,Nq,3] with B, Nq >= 1, got %s" % (tuple(q.shape),))
+    B, Nq = int(q.shape[0]), int(q.shape[1])
+    lead = _row_lead(B, offsets)
+    if vertices.dim() != len(lead) + 2 or faces.dim() != len(lead) + 2:
+        raise ValueError("winding_number: vertices and faces must be %s, got %s and %s"
+                         % ("[%d,rows,3]" % B if offsets is None else "[rows,3] (packed: offsets given)", tuple(vertices.shape), tuple(faces.shape)))
+    mv, mf = int(vertices.shape[-2]), int(faces.shape[-2])
+    nbytes = _lib.size_query("forge_winding_workspace_bytes", B, mf, 0 if offsets is None else 1)
+    want = [("q", q, (B, Nq, 3), torch.float32), ("vertices", vertices, lead + (mv, 3), torch.float32), ("faces", faces, lead + (mf, 3), torch.int32),
+            ("counts", counts, (B, 2), torch.int32), ("offsets", offsets, (B, 2), torch.int32), ("q_count", q_count, (B,), torch.int32),
+            ("xf_q", xf_q, (B, 12), torch.float32), ("xf_mesh", xf_mesh, (B, 12), torch.float32)]
+    if workspace is not None:
+        want.append(("workspace", workspace, nbytes, torch.uint8))
+    dev = _check_tensors("winding_number", want)
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    w = torch.empty(B, Nq, dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().forge_winding_number(_lib.ptr(q.detach()), _lib.ptr(q_count), _lib.ptr(None if xf_q is None else xf_q.detach()),
+                                               _lib.ptr(vertices.detach()), _lib.ptr(faces), _lib.ptr(counts), _lib.ptr(offsets),
+                                               _lib.ptr(None if xf_mesh is None else xf_mesh.detach()), B, Nq, mv, mf, _lib.ptr(workspace),
+                                               int(workspace.numel()), _lib.ptr(w), _lib.current_stream()), "forge_winding_number")
+    return w
+
+
+@_lib.on_tensor_device
 def geom_metrics_hits(d2_ab, hit_ab, d2_ba, hit_ba, normals_a=None, normals_b=None, a_count=None, b_count=None, thresholds=()):
     """forge_geom_metrics_hits (section g3b): geom_metrics with row-aligned "to" normals - hit_ab [B,Na,3] and hit_ba [B,Nb,3], the `normal` of
     nn_triangles, in place of idx_ab / idx_ba. normals_a, hit_ab, normals_b, hit_ba: all four or none (no normal consistency). Returns

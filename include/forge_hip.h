@@ -974,6 +974,48 @@ int forge_geom_metrics_hits(const float* d2_ab, const float* hit_ab, const float
                             double* partial, double* out, int* status, forge_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * g3c  Inside or outside (csrc/winding.hip): the generalized winding number of a point with respect to a triangle mesh - the sum of the signed
+ * solid angles of its triangles over 4 pi. For a closed mesh wound as g1 winds it, it is 1 inside and 0 outside; for a mesh with holes, or any
+ * triangle soup, it stays near 1 inside and near 0 outside and crosses the holes smoothly, where ray parity has no answer. Brute force over
+ * (query, face) pairs, as forge_nn_triangles.
+ *
+ * forge_winding_number  for each of B pairs and each query, w of mesh b:
+ *   q, q_count, xf_q, vertices, faces, counts, offsets, xf_mesh, B, Nq, max_vertices, max_faces, workspace  forge_nn_triangles' arguments, word for
+ *             word: both row layouts, q_count clamped into 0 .. Nq, xf_q applied to the queries and xf_mesh to every vertex on load by the chain
+ *             x' = fma(m02, z, fma(m01, y, fma(m00, x, t0))), and the same candidates - every face of mesh b except a face with an index outside
+ *             0 .. count_v - 1 and a face whose float64 area A_f of the fp32 corners BEFORE xf_mesh is 0. A face that is no candidate adds exactly 0.
+ *   arithmetic  fp32, in this order. A = a - q', B = b - q', C = c - q' per component (a, b, c the transformed corners); with
+ *             dot(u, v) = fma(uz, vz, fma(uy, vy, ux vx)) and sqrt the device's (v_sqrt_f32, within 1 ulp):
+ *               la = sqrt(dot(A, A)), lb = sqrt(dot(B, B)), lc = sqrt(dot(C, C))
+ *               n = B x C: nx = fma(By, Cz, -(Bz Cy)), ny = fma(Bz, Cx, -(Bx Cz)), nz = fma(Bx, Cy, -(By Cx));  num = dot(A, n)
+ *               ab = dot(A, B), bc = dot(B, C), ca = dot(C, A);  den = fma(ca, lb, fma(bc, la, fma(ab, lc, (la lb) lc)))
+ *               theta_f = atan2(num, den)       (Van Oosterom and Strackee: half the signed solid angle of the triangle seen from q')
+ *             atan2(y, x) is written out, not a library's: ax = |x|, ay = |y|, mx = max(ax, ay), mn = min(ax, ay), t = mn (1 / mx) (ONE reciprocal,
+ *             the device's, within 1 ulp), s = t t,
+ *               p = 2.920691855e-03; p = fma(p, s, c) for c = -1.636792719e-02, 4.321185872e-02, -7.552213967e-02, 1.066600457e-01,
+ *               -1.421105564e-01, 1.999377310e-01, -3.333315253e-01 in turn;  r = fma(p s, t, t)      (within 1.1 ulp of atan(t) on [0, 1])
+ *               r = 1.57079637 - r if ay > ax;  r = 3.14159274 - r if x < 0;  atan2 = r with the sign of y.      Selects, no branch.
+ *   terms that drop  a theta_f that is NaN adds 0 (one compare, one select): the NaN record of a face that is no candidate, a NaN corner, and a
+ *             query ON a vertex, where num = den = 0 and t = 0 (1 / 0) = NaN - so atan2(0, 0) counts as 0. A NaN query gives w = 0.
+ *   sum       faces in increasing index, in GROUPS of 8 consecutive faces counted from the mesh's first face: the 8 terms of a group are added
+ *             in fp32, in order, starting from 0.f; each group total is widened and added to a float64 sum, in increasing group index;
+ *             w = (float)(sum (1 / (2 pi))), the product in float64 with 1 / (2 pi) = 0.15915494309189535. The grouping is by face index, not by
+ *             LDS tile. One running fp32 sum would grow its error with the face count; this keeps it at that of 8 terms.
+ *   w [B][Nq] fp32: positive inside a mesh wound as g1 winds it (counter-clockwise seen from outside). Rows at or past q_count: 0. A mesh without
+ *             candidates: 0.
+ *   workspace forge_winding_workspace_bytes(B, max_faces, packed = offsets != NULL) bytes, 16-byte aligned: forge_nn_triangles' records, written by
+ *   the same staging launch. Two launches: staging, then the sum with grid (query blocks of forge_nn_queries_per_block(), pairs), records walked
+ *   in LDS tiles of forge_nn_tile_faces(); no split over the faces, no atomics, nothing read back. Every output bit is reproducible and independent
+ *   of the pair's position in the batch and of padded versus packed rows. FORGE_EINVAL: null q / counts / workspace / w (vertices / faces may be
+ *   null with a zero capacity), B or Nq < 1, a negative capacity, a workspace too small or unaligned. FORGE_ESHAPE: B > 65535, vertex or face rows
+ *   beyond 2^31 - 1, Nq or max_faces within a tile of 2^31.
+ */
+long long forge_winding_workspace_bytes(int n_mesh, int max_faces, int packed);
+int forge_winding_number(const float* q, const int* q_count, const float* xf_q, const float* vertices, const int* faces, const int* counts,
+                         const int* offsets, const float* xf_mesh, int B, int Nq, int max_vertices, int max_faces, void* workspace,
+                         long long workspace_bytes, float* w, forge_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * g4  Connected components of density volumes, and dropping the floaters (csrc/components.hip): which voxels belong to the object. A few-view
  * reconstruction emits the object plus small detached blobs; every stage of g1 - g3 pays for them. The reference has no counterpart.
  *   density  [n][D][H][W] float32, as in g1;  level finite and > 0; a voxel is INSIDE iff d > level (strict, an fp32 compare - the one g1 makes):
